@@ -18,12 +18,18 @@ quoted on, profile.sh / main.py:210-264).  A "step" is one recurrent frame
 K-frame clip per GPU run through FRNet.infer_sequence (true recurrence; FNet of
 frame t+1 overlapped with SRNet of frame t on a second HIP stream), uniform
 random LR frames resident in HBM, random-init weights (seeded), fp32 end to end.
-The reference's own profile protocol (independent random frames through step(),
-sync per frame) is reported beside it as fps_step_protocol_*.
 Clips are independent, so N GPUs run N clips with no data-path collective
-(weak scaling); value = N*K frames / max-over-ranks wall time.
+(weak scaling); value = N*K frames / max-over-ranks wall time.  The timed region
+is exactly K steps (--clips R repeats it R times and reports the median region).
 
-Extra objects on the same line:
+A plain run does only what `value` needs: set-up, W warm-up steps, the timed
+steps and, with --dump-outputs DIR, the timed path's result of its last timed
+region written as DIR/*.npy (float32; see dump_outputs()).  Everything else is
+measured only with --full, as extra objects on the same line:
+  fps_*         the reference's own profile protocol (independent random frames
+                through step(), sync per frame), single stream, with host I/O,
+                2 / 4 / 8 clips in lockstep.
+  config5_2xBI, train_ddp, parity_check, roofline*, kernels, aten_gpu_baseline.
   roofline      dominant kernel class (fp32-MFMA conv3x3): algorithmic FLOPs of
                 its launches in one frame / their summed duration measured with
                 HIP events around a masked replay of exactly those launches.
@@ -54,8 +60,14 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=60)
     ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--clips', type=int, default=10,
+    ap.add_argument('--clips', type=int, default=1,
                     help='how many times the K-step timed region is repeated (median reported)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure the secondary protocols, configs[4], the training leg, the parity check, '
+                         'the roofline / kernel table and the ATen and CPU baselines (the --no-* options below '
+                         'and --cpu-frames / --aten-frames select among them)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the timed path's output of the last timed region as DIR/<name>.npy (float32)")
     ap.add_argument('--no-train-leg', action='store_true',
                     help='skip the data-parallel TecoGAN training leg (BASELINE configs[2]/[3])')
     ap.add_argument('--train-steps', type=int, default=10)
@@ -649,6 +661,23 @@ def parity_check(dev, c, h, w, s, deg):
     return out
 
 
+def dump_outputs(out_dir, hr_u8, max_values=1 << 21):
+    """--dump-outputs: what the caller of the timed path receives -- the (K, s*h, s*w, c) uint8 HR frames of the last
+    timed region (rank 0's clip) -- as float32 .npy files, so two builds can be compared output for output:
+      hr_uint8_last_frame.npy  the last step's frame;
+      hr_uint8_clip.npy        every frame of the region.
+    An array of more than `max_values` values is replaced by a fixed, seeded sample of that many (numpy seed 0,
+    sorted flat indices, written beside it as <name>_index.npy in float64): at most 48 MB in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (('hr_uint8_last_frame', hr_u8[-1]), ('hr_uint8_clip', hr_u8)):
+        if t.numel() > max_values:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), max_values, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            np.save(os.path.join(out_dir, name + '_index.npy'), idx.astype(np.float64))
+        np.save(os.path.join(out_dir, name + '.npy'), t.float().cpu().numpy())
+
+
 def _barrier(dist, local_rank):
     if dist.get_backend() == 'nccl':
         dist.barrier(device_ids=[local_rank])
@@ -868,7 +897,8 @@ def main():
     torch.manual_seed(0)                      # same random-init weights on every rank
     net = FRNet(c, c, 64, 10, deg, s).to(dev).eval()
 
-    # per-rank clip data (base_utils.py:46: seed + rank)
+    # per-rank clip data (base_utils.py:46: seed + rank); the step-protocol pool is drawn in every
+    # run, --full or not, so that the timed clip drawn after it is the same in both
     gen = torch.Generator(device='cpu').manual_seed(1234 + rank)
     pool = []
     for _ in range(4):
@@ -891,31 +921,34 @@ def main():
         pipe = not args.no_pipeline
         net.infer_sequence(wclip, dev, pipeline=pipe, return_device_tensor=True)     # W warm-up steps
         torch.cuda.synchronize()
-        # plus two untimed clips of the timed shape: the first clips of a process also pay for the
-        # allocator, the event ring and the runtime's stream -> hardware-queue assignment
-        # (DESIGN.md section 9); steady state is reached from the second clip on
-        for _ in range(2):
-            net.infer_sequence(clip, dev, pipeline=pipe, return_device_tensor=True)
-            torch.cuda.synchronize()
+        # plus one untimed clip of the timed shape: the first clip of a given length also pays for
+        # its buffers, its event ring and its flow-pass plans (~1 ms in all on MI355X: +8 % on a
+        # 20-frame clip); the next clip of that length is in steady state
+        net.infer_sequence(clip, dev, pipeline=pipe, return_device_tensor=True)
+        torch.cuda.synchronize()
         # The timed region is EXACTLY K steps (one K-frame clip) between barrier + synchronize
-        # brackets; it is repeated `--clips` times (default 10) and the MEDIAN region is the
-        # reported one (min / max beside it): a single 20-60 ms region is at the mercy of one
-        # scheduling hiccup, and box-to-box spread was already 2 % in round 1.
+        # brackets; `--clips R` repeats it R times (default 1) and the MEDIAN region is the
+        # reported one (min / max beside it).
         times = []
         for _ in range(max(1, args.clips)):
+            hr_u8 = None                             # the previous region's frames go back to the allocator first
             barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            net.infer_sequence(clip, dev, pipeline=pipe, return_device_tensor=True)  # exactly K steps
+            hr_u8 = net.infer_sequence(clip, dev, pipeline=pipe, return_device_tensor=True)  # exactly K steps
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t0)   # this rank's K steps; MAX over ranks below
             net.check_faults()                       # fail-safe of chained launches (a host read, after the sync)
             barrier()                                # closing bracket (its own latency is not a step)
             torch.cuda.synchronize()
 
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, hr_u8)
+        del hr_u8
+
         # ---- secondary protocols (rank-local, not part of `value`) -----------------------
         sec = {}
-        if not args.no_pipeline and not args.no_secondary:
+        if args.full and not args.no_pipeline and not args.no_secondary:
             net.infer_sequence(wclip, dev, pipeline=False, return_device_tensor=True)
             torch.cuda.synchronize()
             t1 = time.perf_counter()
@@ -1007,7 +1040,7 @@ def main():
     # ---- BASELINE configs[4]: 2x BI at 3x268x640 (the other up-sampler, warp stride 2, and the shape
     # whose SRNet runs as ONE chained Winograd launch), under the same clock as the headline ------
     cfg5 = None
-    if rank == 0 and not args.no_secondary and (s, deg, (c, h, w)) == (4, 'BD', (3, 134, 320)):
+    if rank == 0 and args.full and not args.no_secondary and (s, deg, (c, h, w)) == (4, 'BD', (3, 134, 320)):
         try:
             cfg5 = config5_leg(dev, gen, min(args.steps, 60))
         except Exception as e:          # a context leg: never lose the headline line to it
@@ -1019,7 +1052,7 @@ def main():
     elapsed = sorted(times)[len(times) // 2] if len(times) % 2 else \
         0.5 * (sorted(times)[len(times) // 2 - 1] + sorted(times)[len(times) // 2])
     train_leg = None
-    if not args.no_train_leg:
+    if args.full and not args.no_train_leg:
         try:
             train_leg = ddp_train_leg(args, dev, rank, world, local_rank, dist_on)
         except Exception as e:          # a context leg: never lose the headline line to it
@@ -1057,7 +1090,7 @@ def main():
                                    'not a baseline for vs_baseline',
         }
         result.update(sec)
-        if not args.no_parity_check:
+        if args.full and not args.no_parity_check:
             pc = parity_check(dev, c, h, w, s, deg)
             result['parity_check'] = 'ok' if pc.get('ok') else 'FAILED'
             result['parity_check_detail'] = pc
@@ -1065,7 +1098,7 @@ def main():
             result['train_ddp'] = train_leg
         if cfg5 is not None:
             result['config5_2xBI'] = cfg5
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             with torch.no_grad():
                 rows = kernel_table(net, plan, (*pool[0], outs[0]))
             dom = max(rows, key=lambda r: r['ms_per_frame'])
@@ -1163,7 +1196,7 @@ def main():
             result['slowest_kernel_class'] = dom['kernel']
         # context baselines only in a plain process (MIOpen's find segfaults next to an RCCL process
         # group on this stack; the driver's N = 1 run is a plain process)
-        if world == 1 and not dist_on and args.aten_frames > 0:
+        if args.full and world == 1 and not dist_on and args.aten_frames > 0:
             sd_dev = {k: v.detach() for k, v in net.state_dict().items()}
             # the reference's profile mode sets cudnn.benchmark = True (main.py:216), which
             # on ROCm is MIOpen's exhaustive find; report the better of both settings
@@ -1179,7 +1212,7 @@ def main():
             if 'value' in result['aten_gpu_baseline'] and 'fps_step_protocol_sync_every_frame' in result:
                 result['vs_aten_gpu'] = (result['fps_step_protocol_sync_every_frame'] /
                                          result['aten_gpu_baseline']['value'])
-        if world == 1 and args.cpu_frames > 0:
+        if args.full and world == 1 and args.cpu_frames > 0:
             sd = {k: v.detach().cpu() for k, v in net.state_dict().items()}
             result['cpu_baseline'] = cpu_baseline(sd, s, deg, c, h, w, args.cpu_frames,
                                                   args.cpu_seconds)

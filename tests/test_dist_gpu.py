@@ -189,7 +189,7 @@ def test_plain_bench_invocation_brings_up_two_ranks():
     import json
     env = _bench_env() if torch.cuda.device_count() >= 2 else _bench_env(TG_BENCH_REHEARSAL='1')
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2',
-                        '--clips', '2', '--train-steps', '2', '--cpu-frames', '0', '--no-roofline', '--no-secondary',
+                        '--full', '--clips', '2', '--train-steps', '2', '--cpu-frames', '0', '--no-roofline', '--no-secondary',
                         '--no-parity-check'], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     js = [ln for ln in r.stdout.splitlines() if ln.lstrip().startswith('{')]

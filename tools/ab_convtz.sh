@@ -6,7 +6,7 @@ TG_LAB_BUILD=1 OUT=$REPO/tools/_lab_libs/ztest bash tecogan-pytorch_amd/csrc/bui
 export TECOGAN_HIP_LIB=$REPO/tools/_lab_libs/ztest/libtecogan_lab.so
 for rep in 1 2; do
 for f in 0 1 2; do
-  TG_CONVTZ_FORM=$f timeout 200 python bench.py --steps 40 --warmup 5 --clips 7 --no-train-leg --cpu-frames 0 --aten-frames 0 --no-live-pmc --no-parity-check 2>/dev/null | python -c "
+  TG_CONVTZ_FORM=$f timeout 200 python bench.py --full --steps 40 --warmup 5 --clips 7 --no-train-leg --cpu-frames 0 --aten-frames 0 --no-live-pmc --no-parity-check 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 z = [r for r in d['kernels'] if 'convt3x3s2' in r['kernel']]

@@ -7,7 +7,7 @@ echo "== smoke"; timeout 300 python __graft_entry__.py smoke 2>&1 | tail -1
 echo "== bench at the driver's flags"; timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench_driver_flags.json 2>/dev/null; cut -c1-330 $OUT/${TAG}_bench_driver_flags.json
 for n in 2 4; do
   echo "== python bench.py --gpus $n (TG_BENCH_REHEARSAL=1: $n ranks on this ONE GPU over gloo; the numbers mean nothing)"
-  TG_BENCH_REHEARSAL=1 timeout 600 python bench.py --gpus $n --steps 10 --warmup 3 --clips 3 --train-steps 3 --cpu-frames 0 --no-roofline --no-secondary > $OUT/${TAG}_rehearsal_${n}ranks_one_gpu_selfspawn.json 2> $OUT/${TAG}_rehearsal_${n}ranks.err
+  TG_BENCH_REHEARSAL=1 timeout 600 python bench.py --gpus $n --full --steps 10 --warmup 3 --clips 3 --train-steps 3 --cpu-frames 0 --no-roofline --no-secondary > $OUT/${TAG}_rehearsal_${n}ranks_one_gpu_selfspawn.json 2> $OUT/${TAG}_rehearsal_${n}ranks.err
   echo "rc=$?"; python -c "
 import json,sys
 d=json.load(open('$OUT/${TAG}_rehearsal_${n}ranks_one_gpu_selfspawn.json'))

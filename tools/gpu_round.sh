@@ -16,8 +16,8 @@ echo "== PMC passes"; bash tools/gpu_pmc.sh $TAG 2>&1 | grep "^pass"
 # summarise on the box (the raw per-dispatch tables are too large to travel back)
 python tools/summarize_pmc.py $TAG $TAG $OUT && rm -rf $OUT/pmc_${TAG}_*
 cp $OUT/pmc_traffic.json $REPO/profiles/pmc_traffic.json 2>/dev/null
-echo "== bench (default flags)"; timeout 900 python bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; tail -2 $OUT/${TAG}_bench.err; cut -c1-600 $OUT/${TAG}_bench.json
-echo "== bench 2xBI (configs[4]) as its own run"; timeout 600 python bench.py --lr-size 3x268x640 --scale 2 --degradation BI --no-train-leg --cpu-frames 0 --aten-frames 0 --clips 5 > $OUT/${TAG}_bench_config5_2xBI.json 2>/dev/null; cut -c1-300 $OUT/${TAG}_bench_config5_2xBI.json
+echo "== bench (default flags)"; timeout 900 python bench.py --full --clips 10 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; tail -2 $OUT/${TAG}_bench.err; cut -c1-600 $OUT/${TAG}_bench.json
+echo "== bench 2xBI (configs[4]) as its own run"; timeout 600 python bench.py --full --lr-size 3x268x640 --scale 2 --degradation BI --no-train-leg --cpu-frames 0 --aten-frames 0 --clips 5 > $OUT/${TAG}_bench_config5_2xBI.json 2>/dev/null; cut -c1-300 $OUT/${TAG}_bench_config5_2xBI.json
 echo "== rocprofv3 kernel stats: pipelined / single stream / training"
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o kt -- python $REPO/bench.py --steps 30 --warmup 5 --clips 3 --no-roofline --no-secondary --no-parity-check --no-train-leg --cpu-frames 0 --aten-frames 0 > $OUT/prof_$TAG.log 2>&1

@@ -5,4 +5,4 @@
 N=${1:-2}
 export TG_BENCH_REHEARSAL=1 HSA_ENABLE_IPC_MODE_LEGACY=0
 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-  --master-port 29533 bench.py --gpus $N --steps 10 --warmup 3 --clips 3 --train-steps 3 --cpu-seconds 2 2>&1 | tail -3
+  --master-port 29533 bench.py --gpus $N --full --steps 10 --warmup 3 --clips 3 --train-steps 3 --cpu-seconds 2 2>&1 | tail -3

@@ -502,6 +502,27 @@ int tg_psnr_sse_u8(const uint8_t* true_hwc, const uint8_t* pred_hwc, uint64_t* s
  * conversion can be checked exhaustively against numpy. */
 int tg_luma_u8(const uint8_t* rgb, uint8_t* y, int64_t n, tg_stream_t stream);
 
+/* LPIPS v0.1, alex / net-lin, spatial=False (codes/metrics/LPIPS/models/networks_basic.py:25-99,
+ * pretrained_networks.py:57-95): the AlexNet layers that have no kernel elsewhere, and the head.
+ * tg_lpips_conv_fwd: Conv2d(cin, cout, ks, stride, pad) + bias + ReLU as an fp32-MFMA implicit GEMM,
+ * y (n, cout, oh, ow).  Weights wt are (cin*ks*ks, cout): the Conv2d weight reshaped to (cout, K)
+ * and transposed.  Images [0, n0) are read from x0, [n0, n) from x1 (x1 = NULL: all from x0).  Two
+ * forms: ks 11 / stride 4 with lut != NULL reads uint8 HWC RGB images (cin 3) through the (256, 3)
+ * fp32 table lut[v*3 + c] (the [-1,1] scaling and ScalingLayer); ks 5 / stride 1 with lut == NULL
+ * reads fp32 NCHW.  Out-of-image taps are zero (padding of the normalised input). */
+int tg_lpips_conv_fwd(const void* x0, const void* x1, int n0, const float* lut, const float* wt,
+                      const float* bias, float* y, int n, int cin, int h, int w, int cout, int ks,
+                      int stride, int pad, tg_stream_t stream);
+/* nn.MaxPool2d(3, 2), floor mode: y (nc, (h-3)/2+1, (w-3)/2+1) */
+int tg_maxpool3s2_fwd(const float* x, float* y, int nc, int h, int w, tg_stream_t stream);
+/* workspace of tg_lpips_head for `frames` frames of an h x w map, bytes (-1: bad arguments) */
+int64_t tg_lpips_head_workspace_bytes(int frames, int h, int w);
+/* One LPIPS layer: feat_true / feat_pred (frames, c, h, w) -> res[f*5 + layer] = spatial mean of
+ * sum_c lin[c] (a/(|a|+1e-10) - b/(|b|+1e-10))^2.  Deterministic (fixed-order partial sums, no
+ * atomics).  total != NULL (layer 4 only): total[f] = res[f*5+0] + ... + res[f*5+4], in that order. */
+int tg_lpips_head(const float* feat_true, const float* feat_pred, const float* lin, int frames, int c,
+                  int h, int w, void* ws, float* res, int layer, float* total, tg_stream_t stream);
+
 /* ========================================================================
  * Training side: backward kernels.
  * Conv data gradients reuse tg_conv3x3_fwd with weights packed by

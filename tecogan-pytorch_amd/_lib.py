@@ -92,6 +92,10 @@ SIGNATURES = {
     'tg_dequantize_u8_hwc': (I, [P, P, I, I, I, I, P]),
     'tg_psnr_sse_u8': (I, [P, P, P, I, I, I, I, P]),
     'tg_luma_u8': (I, [P, P, I64, P]),
+    'tg_lpips_conv_fwd': (I, [P, P, I, P, P, P, P, I, I, I, I, I, I, I, I, P]),
+    'tg_maxpool3s2_fwd': (I, [P, P, I, I, I, P]),
+    'tg_lpips_head_workspace_bytes': (I64, [I, I, I]),
+    'tg_lpips_head': (I, [P, P, P, I, I, I, I, P, P, I, P, P]),
     'tg_wgrad3x3_workspace_floats': (SZ, [I, I, I, I, I]),
     'tg_wgrad3x3': (I, [P, I64, P, I64, P, P, I, I, I, I, I, I, I, I, P]),
     'tg_wgrad3x3_multi': (I, [P, P, I, I64, I64, P, P, I, I, I, I, I, I, I, I, P]),

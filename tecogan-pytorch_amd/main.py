@@ -3,10 +3,11 @@ codes/utils/base_utils.py:14-30): train | test | profile.
 
 `train` reads the reference's LMDB training sets when `dataset.train.seq_dir` names one
 (tecogan_pytorch_amd/data: the decoded frames live in HBM, batches are cut out by a HIP
-kernel with the reference's augmentation); without it, and for `test` (PNG folders are out of
-scope), clips come from a synthetic source that honours the loader's output contract
-(unpaired_lmdb_dataset.py:89-93, paired_folder_dataset.py:57-63); any iterable of such dicts
-can be passed to `train()` / `test()`.
+kernel with the reference's augmentation).  `test` reads the reference's PNG folders when the
+yml's `dataset.test*` entries name an existing `gt_seq_dir` (and `lr_seq_dir`, or BD degradation
+of the GT) and evaluates with the yml's `metric` section (PSNR, LPIPS).  Otherwise clips come from
+a synthetic source that honours the loader's output contract (unpaired_lmdb_dataset.py:89-93,
+paired_folder_dataset.py:57-63); any iterable of such dicts can be passed to `train()` / `test()`.
 
   python -m tecogan_pytorch_amd.main --mode profile --lr_size 3x134x320 --test_speed
   python -m tecogan_pytorch_amd.main --mode train --opt my_train.yml --gpu_ids 0
@@ -21,7 +22,7 @@ import numpy as np
 import torch
 import yaml
 
-from .metrics.psnr import compute_psnr, compute_psnr_device
+from .metrics.psnr import compute_psnr, compute_psnr_device  # noqa: F401
 from .models import define_model
 from .models.networks import define_generator
 from .utils import dist_utils
@@ -148,9 +149,13 @@ def train(opt, batches, start_iter=0):
     return model
 
 
-def test(opt, sequences):
+def test(opt, sequences, model_idx=None, ds_name=None):
     """codes/main.py:132-207: sequences sharded round-robin over ranks, PSNR-Y per sequence.
-    `sequences`: list of {'gt': thwc uint8, 'lr': thwc float32, 'seq_idx': str}."""
+    `sequences`: list of {'gt': thwc uint8, 'lr': thwc float32, 'seq_idx': str}.
+    With a `metric` section in opt the sequences are evaluated by MetricCalculator instead
+    (evaluate(); it is returned)."""
+    if opt.get('metric'):
+        return evaluate(opt, sequences, model_idx or 'G_iter0', ds_name or 'test')
     model = define_model(opt)
     rank, world = dist_utils.get_dist_info()
     vals = [0.0] * len(sequences)
@@ -168,6 +173,52 @@ def test(opt, sequences):
         for d, v in zip(sequences, red.tolist()):
             print(f"{d['seq_idx']}: PSNR-Y {v:.3f} dB")
     return red
+
+
+def evaluate(opt, sequences, model_idx, ds_name):
+    """One model on one test set, as codes/main.py:158-205: infer each sequence (sharded over ranks),
+    optionally save the frames (test.save_res / res_dir), compute the yml's metrics, gather them on
+    rank 0 and write `{json_dir}/{ds_name}_avg.json` (test.save_json) or print them."""
+    from .metrics.metric_calculator import MetricCalculator
+    from .utils.data_utils import save_sequence
+    model = define_model(opt)
+    mc = MetricCalculator(opt)
+    topt = opt.get('test', {})
+    for idx in dist_utils.shard_indices(len(sequences)):
+        data = sequences[idx]
+        model.prepare_inference_data(data)
+        hr_seq = model.infer(device_output=True).contiguous()
+        mc.compute_sequence_metrics(data['seq_idx'], data['gt'], hr_seq)
+        model.net_G.check_faults()
+        if topt.get('save_res'):
+            res_dir = topt.get('res_dir') or os.path.join(opt.get('exp_dir', '.'), 'test', 'results')
+            save_sequence(os.path.join(res_dir, ds_name, model_idx, data['seq_idx']), hr_seq.cpu().numpy(),
+                          data.get('frm_idx'))
+    seq_ids = getattr(sequences, 'keys', None) or [d['seq_idx'] for d in sequences]
+    mc.gather(list(seq_ids))
+    if topt.get('save_json'):
+        json_dir = topt.get('json_dir') or os.path.join(opt.get('exp_dir', '.'), 'test', 'metrics')
+        os.makedirs(json_dir, exist_ok=True)
+        mc.save(model_idx, os.path.join(json_dir, f'{ds_name}_avg.json'), override=True)
+    else:
+        mc.display()
+    return mc
+
+
+def folder_test_sets(opt):
+    """[(name, FolderDataset)] of the yml's `dataset.test*` entries whose gt_seq_dir exists (sorted by
+    entry name, as codes/main.py:154-158)."""
+    from .data.folder_dataset import FolderDataset
+    out = []
+    deg = opt['dataset'].get('degradation', {}).get('type', 'BD')
+    for key in sorted(opt.get('dataset', {})):
+        d = opt['dataset'][key]
+        if 'test' not in key or not isinstance(d, dict) or not d.get('gt_seq_dir'):
+            continue
+        if not os.path.isdir(d['gt_seq_dir']):
+            continue
+        out.append((d.get('name', key), FolderDataset(d, degradation=deg)))
+    return out
 
 
 def profile(opt, lr_size, test_speed=False):
@@ -227,6 +278,12 @@ def main(argv=None):
         train(opt, synthetic_train_batches(opt, 20 if args.iters is None else args.iters,
                                            100 + opt['rank'] + 7919 * args.resume),
               start_iter=args.resume)
+    elif args.mode == 'test' and folder_test_sets(opt):
+        opt['exp_dir'] = args.exp_dir
+        gen = opt['model']['generator']
+        model_idx = os.path.splitext(os.path.basename(gen['load_path']))[0] if gen.get('load_path') else 'G_iter0'
+        for ds_name, seqs in folder_test_sets(opt):
+            test(opt, seqs, model_idx=model_idx, ds_name=ds_name)
     elif args.mode == 'test':
         g = torch.Generator().manual_seed(7)
         seqs = []

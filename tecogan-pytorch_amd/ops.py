@@ -442,6 +442,72 @@ def luma_u8(rgb):
     return out
 
 
+def lpips_conv(x0, wt, bias, cout, ks, stride, pad, x1=None, lut=None, out=None):
+    """tg_lpips_conv_fwd: relu(Conv2d(cin, cout, ks, stride, pad)(cat[x0, x1]) + bias).
+    lut given: x0 / x1 are (n,h,w,3) uint8 images read through the (256,3) table; else (n,cin,h,w) fp32.
+    wt: (cin*ks*ks, cout), the Conv2d weight reshaped to (cout, K) and transposed."""
+    _chk(wt, 'wt'); _chk(bias, 'bias')
+    if lut is not None:
+        _chk(lut, 'lut'); _chk_u8(x0, 'x0')
+        if x1 is not None:
+            _chk_u8(x1, 'x1')
+        n0, h, w, cin = x0.shape
+    else:
+        _chk(x0, 'x0')
+        if x1 is not None:
+            _chk(x1, 'x1')
+        n0, cin, h, w = x0.shape
+    if x1 is not None and tuple(x1.shape[1:]) != tuple(x0.shape[1:]):
+        raise L.TecoganHipError(f'lpips_conv: x0 {tuple(x0.shape)} x1 {tuple(x1.shape)}')
+    if tuple(wt.shape) != (cin * ks * ks, cout) or tuple(bias.shape) != (cout,):
+        raise L.TecoganHipError(f'lpips_conv: wt {tuple(wt.shape)} bias {tuple(bias.shape)} for cin {cin} '
+                                f'cout {cout} k{ks}')
+    n = n0 + (0 if x1 is None else x1.shape[0])
+    oh, ow = (h + 2 * pad - ks) // stride + 1, (w + 2 * pad - ks) // stride + 1
+    if out is None:
+        out = torch.empty(n, cout, oh, ow, dtype=torch.float32, device=x0.device)
+    _chk(out, 'out')
+    if tuple(out.shape) != (n, cout, oh, ow):
+        raise L.TecoganHipError(f'lpips_conv: out {tuple(out.shape)}, expected {(n, cout, oh, ow)}')
+    L.check(L.lib().tg_lpips_conv_fwd(x0.data_ptr(), _ptr(x1), n0, _ptr(lut), wt.data_ptr(), bias.data_ptr(),
+                                      out.data_ptr(), n, cin, h, w, cout, ks, stride, pad, _stream()),
+            'tg_lpips_conv_fwd')
+    return out
+
+
+def maxpool3s2(x, out=None):
+    """nn.MaxPool2d(3, 2) (floor mode) of (n,c,h,w) fp32."""
+    _chk(x, 'x')
+    n, c, h, w = x.shape
+    oh, ow = (h - 3) // 2 + 1, (w - 3) // 2 + 1
+    if out is None:
+        out = torch.empty(n, c, oh, ow, dtype=torch.float32, device=x.device)
+    _chk(out, 'out')
+    if tuple(out.shape) != (n, c, oh, ow):
+        raise L.TecoganHipError(f'maxpool3s2: out {tuple(out.shape)}, expected {(n, c, oh, ow)}')
+    L.check(L.lib().tg_maxpool3s2_fwd(x.data_ptr(), out.data_ptr(), n * c, h, w, _stream()), 'tg_maxpool3s2_fwd')
+    return out
+
+
+def lpips_head(feat_true, feat_pred, lin, res, layer, total=None):
+    """tg_lpips_head: one LPIPS layer of (t,c,h,w) feature maps into column `layer` of res (t,5);
+    with total (t,) (layer 4 only): the sum of the five columns in order."""
+    _chk(feat_true, 'feat_true'); _chk(feat_pred, 'feat_pred'); _chk(lin, 'lin'); _chk(res, 'res')
+    t, c, h, w = feat_true.shape
+    if feat_pred.shape != feat_true.shape or lin.numel() != c or tuple(res.shape) != (t, 5):
+        raise L.TecoganHipError(f'lpips_head: feats {tuple(feat_true.shape)} / {tuple(feat_pred.shape)}, '
+                                f'lin {tuple(lin.shape)}, res {tuple(res.shape)}')
+    if total is not None:
+        _chk(total, 'total')
+        if tuple(total.shape) != (t,):
+            raise L.TecoganHipError(f'lpips_head: total {tuple(total.shape)}')
+    nbytes = L.lib().tg_lpips_head_workspace_bytes(t, h, w)
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=feat_true.device)
+    L.check(L.lib().tg_lpips_head(feat_true.data_ptr(), feat_pred.data_ptr(), lin.data_ptr(), t, c, h, w,
+                                  ws.data_ptr(), res.data_ptr(), layer, _ptr(total), _stream()), 'tg_lpips_head')
+    return res
+
+
 # ---------------------------------------------------------------------------
 # training-side wrappers (backward kernels, losses, optimiser)
 # ---------------------------------------------------------------------------

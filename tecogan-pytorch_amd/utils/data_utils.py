@@ -16,3 +16,16 @@ def gaussian_kernel2d(sigma, ksize=None):
     g1 = np.exp(-0.5 * (xs / sigma) ** 2)
     g2 = np.outer(g1, g1)
     return np.float32(g2 / g2.sum())
+
+
+def save_sequence(seq_dir, seq_data, frm_idx_lst=None):
+    """data_utils.py:90-113: each frame of a thwc | rgb | uint8 sequence as a PNG in seq_dir
+    (named by frm_idx_lst, default 0000.png, ...); written with Pillow from RGB."""
+    import os
+    from PIL import Image
+    tot_frm = len(seq_data)
+    if frm_idx_lst is None:
+        frm_idx_lst = ['{:04d}.png'.format(i) for i in range(tot_frm)]
+    os.makedirs(seq_dir, exist_ok=True)
+    for i in range(tot_frm):
+        Image.fromarray(np.ascontiguousarray(seq_data[i])).save(os.path.join(seq_dir, frm_idx_lst[i]))

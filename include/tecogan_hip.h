@@ -388,6 +388,20 @@ int tg_convt3x3s2_z_fwd_form(const float* x, int64_t x_nstride, const float* w_p
                              const float* bias, const float* wz, int cz, float* z,
                              int64_t z_nstride, int n, int cin, int cout, int h, int w, int act,
                              int form, tg_stream_t stream);
+/* The Z mode of a 64 -> 64 channel ConvTranspose2d in the Winograd domain: the same quantity as
+ * tg_convt3x3s2_z_fwd_form (the 9*cz tap planes of the output conv over act(convT(x) + bias), in the same
+ * (n, 32, 2h, 2w) buffer), with F(2,2) along x and y over 2x2 input tiles -- 25 products per tile instead of 36 --
+ * on 16x16x4 fp32 MFMAs.  Not bit-identical to the direct form (different summation order; within 1e-5 of the fp64
+ * composition like it).  w_wino: tg_convt_pack_wino of the direct form's packed weights (tg_conv3x3_pack(transposed=1),
+ * TG_CONVT_WINO_FLOATS floats out); wz: tg_convt_pack_wz.  cin, cout <= 64 (zero-padded to 64), cz <= 3.
+ * split: -1 the library's rule, 0 one launch, 1 whole rounds of resident workgroups (two per CU) + a remainder launch
+ * whenever one image has a whole round; every form gives the same planes bit for bit, and so do n = 2 and two n = 1
+ * calls.  The frame plan uses it for its Z-mode layer when nf = 64 (TG_CONVTZ_WINO=0 in lab builds: the direct form). */
+#define TG_CONVT_WINO_FLOATS (16 * 64 * 64)
+int tg_convt_pack_wino(const float* w_packed, float* w_wino, int cin, int cout, tg_stream_t stream);
+int tg_convt3x3s2_z_wino_fwd(const float* x, int64_t x_nstride, const float* w_wino, const float* bias,
+                             const float* wz, int cz, float* z, int64_t z_nstride, int n, int cin, int cout,
+                             int h, int w, int act, int split, tg_stream_t stream);
 int tg_convout_tail(const float* z, int64_t z_nstride, int cz, const float* bias,
                     const float* up_src, int up_mode, int up_scale, float* y,
                     int64_t y_nstride, uint8_t* u8_out, int n, int h, int w,

@@ -44,6 +44,8 @@ struct tg_frnet_plan {
   float *FA, *FB, *FPART, *FLOW2;   // FNet's own buffers (phase 1 may overlap phase 2 of the previous frame)
   float* WZ;                        // packed output-conv weights for the fused HR stage
   bool wz_ready;
+  float* WA;                        // Winograd-domain weights of the Z-mode layer (tg_convt_pack_wino)
+  bool wa_ready;
   int32_t* CHAINF;                  // per-tile flags of the chained SRNet launch (tg_conv3x3_wino_chain)
   bool chain_ready;                 // flags zeroed
   unsigned epoch;                   // one per chained launch
@@ -155,7 +157,7 @@ static void carve(const tg_frnet_cfg* c, size_t off[15]) {
   off[8] = o; o += align64(n * 64 * hw);                       // FB   (FNet pong)
   off[9] = o; o += align64(fnet_partial_floats(c));            // FPART (split-K partial sums, FNet)
   off[10] = o; o += align64(n * 2 * hw);                       // FLOW2 (second flow slot)
-  off[11] = o; o += sr * 2048;                                 // WZ (A operand of the fused output-conv contraction)
+  off[11] = o; o += sr * (2048 + TG_CONVT_WINO_FLOATS);       // WZ (A operand of the fused output-conv contraction), WA (Winograd-domain weights of the last up-sampling layer)
   off[12] = o;                                                 // CHAINF (int32 flags: 24 layers x 16-tile workgroups + error counter)
   o += sr * align64((size_t)CHAIN_MAX_LAYERS * n * ((c->h + 1) / 2) * ((c->w + 31) / 32) + 16);
   off[13] = o;                                                 // RESWS (tg_conv3x3_wino_res.hip: exchange buffer + flags; n == 1 only)
@@ -198,6 +200,7 @@ extern "C" int tg_frnet_plan_create(const tg_frnet_cfg* cfg, const tg_layer_weig
   size_t off[15];
   carve(cfg, off);
   p->WZ = workspace + off[11]; p->wz_ready = false;
+  p->WA = p->WZ + 2048; p->wa_ready = false;
   p->RESWS = workspace + off[13]; p->res_ready = false;
   p->CHAINF = reinterpret_cast<int32_t*>(workspace + off[12]); p->chain_ready = false; p->epoch = 0; p->chain_layers = 0;
   p->chain_err = nullptr; p->chain_disabled = false; p->chain_faults = 0; p->chain_poll_limit = tg::TG_CHAIN_POLL_LIMIT_DEFAULT;
@@ -267,6 +270,12 @@ enum {
 // kernel shift-adds them.  TG_HR_FUSE=0 selects the unfused launches (lab / A-B).
 static bool hr_fuse_enabled() {
   static const int v = TG_LAB_ENV("TG_HR_FUSE", 1);
+  return v != 0;
+}
+// The Z-mode layer in the Winograd domain (tg_convt3x3s2_wino.hip: 25 products per 2x2 input tile instead of 36) where
+// it applies (cin = cout = 64); TG_CONVTZ_WINO=0 selects the direct Z form (lab / A-B).
+static bool convtz_wino_enabled() {
+  static const int v = TG_LAB_ENV("TG_CONVTZ_WINO", 1);
   return v != 0;
 }
 // SRNet's 1 + 2*nb full-resolution layers as one chained launch (tg_conv3x3_wino_chain) when a layer
@@ -521,9 +530,19 @@ static int step_impl(tg_frnet_plan* p, const float* lr_curr, const float* lr_pre
       zin = p->U1;
     }
     const tg_layer_weights lw_last = s == 4 ? lw_up2 : lw_up1;
-    if (dry && tg::convt_z_split_rule(n, zh, zw, -1)) p->st_launch[K_CONVT_Z] += 1;   // (two launches: split tail, round 6)
+    // the Winograd form where it applies; its weights are derived once per plan, like WZ (same kind, same algorithmic flops)
+    const bool wino = convtz_wino_enabled() && nf == 64;
+    if (wino && !dry && !p->wa_ready && (phases & 2) && rc == TG_OK) {
+      rc = tg_convt_pack_wino(lw_last.w, p->WA, nf, nf, st);
+      p->wa_ready = rc == TG_OK;
+    }
+    if (dry && (wino ? tg::convt_z_wino_split_rule(n, zh, zw, -1) : tg::convt_z_split_rule(n, zh, zw, -1)))
+      p->st_launch[K_CONVT_Z] += 1;                // (two launches: whole rounds + a remainder)
     go(K_CONVT_Z, 2.0 * nf * 9 * nf * n * zh * zw + 2.0 * nf * 9 * c.out_nc * hpx,
        4.0 * n * zh * zw * nf + 4.0 * hpx * 9 * c.out_nc, [&] {
+         if (wino)
+           return tg_convt3x3s2_z_wino_fwd(zin, (int64_t)nf * zh * zw, p->WA, lw_last.b, p->WZ, c.out_nc, zbuf,
+                                           (int64_t)32 * s * s * hw, n, nf, nf, zh, zw, TG_ACT_RELU, -1, st);
          return tg_convt3x3s2_z_fwd(zin, (int64_t)nf * zh * zw, lw_last.w, lw_last.b, p->WZ, c.out_nc, zbuf,
                                     (int64_t)32 * s * s * hw, n, nf, nf, zh, zw, TG_ACT_RELU, st);
        });

@@ -255,6 +255,29 @@ def convt3x3s2_z(x, wpk, bias, wz, cz, cout, act=ACT_NONE, form=-1, out=None):
     return out
 
 
+def convt_pack_wino(wpk, cin, cout):
+    """tg_convt_pack_wino: the 16 Winograd-domain weight matrices of tg_convt3x3s2_z_wino_fwd from the direct form's
+    packed ConvTranspose2d weights (pack_conv3x3(weight, transposed=True)[0])."""
+    _chk(wpk, 'wpk')
+    wa = torch.empty(16 * 64 * 64, dtype=torch.float32, device=wpk.device)
+    L.check(L.lib().tg_convt_pack_wino(wpk.data_ptr(), wa.data_ptr(), cin, cout, _stream()), 'tg_convt_pack_wino')
+    return wa
+
+
+def convt3x3s2_z_wino(x, wa, bias, wz, cz, cout, act=ACT_NONE, split=-1, out=None):
+    """tg_convt3x3s2_z_wino_fwd: the tap planes of convt3x3s2_z computed in the Winograd domain (F(2,2) along x and y,
+    25 products per 2x2 input tile instead of 36).  wa: convt_pack_wino.  split: -1 the library's rule, 0 one launch,
+    1 whole rounds of workgroups + a remainder launch (bit-identical)."""
+    _chk(x, 'x')
+    n, cin, h, w = x.shape
+    if out is None:
+        out = torch.empty(n, 32, 2 * h, 2 * w, dtype=torch.float32, device=x.device)
+    L.check(L.lib().tg_convt3x3s2_z_wino_fwd(x.data_ptr(), cin * h * w, wa.data_ptr(), _ptr(bias), wz.data_ptr(), cz,
+                                             out.data_ptr(), 32 * 4 * h * w, n, cin, cout, h, w, act, split, _stream()),
+            'tg_convt3x3s2_z_wino_fwd')
+    return out
+
+
 def convout_tail(z, cz, bias, up_src=None, up_mode=UP_NONE, up_scale=1, want_u8=False, form=-1):
     """tg_convout_tail_form: out[o] = bias[o] + sum_tap z[tap * cz + o] shifted by the tap (zero padding) [+ the
     up-sampled residual of up_src] -> fp32 (n, cz, h, w) [and the uint8 (n, h, w, cz) frame].  z: (n, 32, h, w) planes

@@ -537,6 +537,32 @@ int64_t tg_lpips_head_workspace_bytes(int frames, int h, int w);
 int tg_lpips_head(const float* feat_true, const float* feat_pred, const float* lin, int frames, int c,
                   int h, int w, void* ws, float* res, int layer, float* total, tg_stream_t stream);
 
+/* The official evaluation protocol's frame metrics (codes/official_metrics/metrics.py:60-73) on uint8 HWC
+ * frames resident on the device.  Both work on the UNROUNDED luma Y = 16 + y'/255000 with the integer
+ * y' = 65481 R + 128553 G + 24966 B, on a window of h x w pixels whose origin (y0, x0) is the same in the true
+ * frames (frames, true_h, true_w, 3) and the predicted frames (frames, pred_h, pred_w, 3), so that neither the
+ * protocol's top-left size-matching crop nor its crop_8x8 needs a copy.  The window must lie inside both.
+ *
+ * tg_ssim_y_u8: ssim[f] = mean SSIM of frame f as skimage.measure.compare_ssim computes it with its defaults
+ * and data_range = max - min of the PREDICTED frame's Y over the window: 7x7 uniform window, sample
+ * covariance (49/48), K1 0.01, K2 0.03, mean over the (h-6) x (w-6) positions whose window lies inside.
+ * Window sums are exact integers, the formula is fp64, the mean comes from fixed-order fp64 partials: results
+ * are bit-identical from run to run, for any batch split, and for a window vs a contiguous copy of it.  A
+ * constant predicted frame (data_range 0) gives NaN, as numpy's 0/0 does.  h, w >= 7.
+ * workspace: tg_ssim_workspace_bytes(frames, h, w) bytes (-1: bad arguments). */
+int64_t tg_ssim_workspace_bytes(int frames, int h, int w);
+int tg_ssim_y_u8(const uint8_t* true_hwc, const uint8_t* pred_hwc, int frames, int true_h, int true_w,
+                 int pred_h, int pred_w, int y0, int x0, int h, int w, double* ssim, void* workspace,
+                 size_t workspace_bytes, tg_stream_t stream);
+/* tg_psnr_yfloat_sse_u8: partials[f * nb + i] = exact sum of (y'_true - y'_pred)^2 over pixels
+ * [4096 i, 4096 (i+1)) of frame f's window in row-major order, nb = tg_psnr_yfloat_partials(h, w) (-1: bad
+ * arguments).  A whole frame does not fit 64 bits; the caller adds the partials (wider integers or fp64):
+ * PSNR = 20 log10(255 / sqrt(sum / 255000^2 / (h w))). */
+int64_t tg_psnr_yfloat_partials(int h, int w);
+int tg_psnr_yfloat_sse_u8(const uint8_t* true_hwc, const uint8_t* pred_hwc, int frames, int true_h, int true_w,
+                          int pred_h, int pred_w, int y0, int x0, int h, int w, uint64_t* partials,
+                          tg_stream_t stream);
+
 /* ========================================================================
  * Training side: backward kernels.
  * Conv data gradients reuse tg_conv3x3_fwd with weights packed by

@@ -98,6 +98,10 @@ SIGNATURES = {
     'tg_maxpool3s2_fwd': (I, [P, P, I, I, I, P]),
     'tg_lpips_head_workspace_bytes': (I64, [I, I, I]),
     'tg_lpips_head': (I, [P, P, P, I, I, I, I, P, P, I, P, P]),
+    'tg_ssim_workspace_bytes': (I64, [I, I, I]),
+    'tg_ssim_y_u8': (I, [P, P, I, I, I, I, I, I, I, I, I, P, P, SZ, P]),
+    'tg_psnr_yfloat_partials': (I64, [I, I]),
+    'tg_psnr_yfloat_sse_u8': (I, [P, P, I, I, I, I, I, I, I, I, I, P, P]),
     'tg_wgrad3x3_workspace_floats': (SZ, [I, I, I, I, I]),
     'tg_wgrad3x3': (I, [P, I64, P, I64, P, P, I, I, I, I, I, I, I, I, P]),
     'tg_wgrad3x3_multi': (I, [P, P, I, I64, I64, P, P, I, I, I, I, I, I, I, I, P]),

@@ -184,11 +184,15 @@ def evaluate(opt, sequences, model_idx, ds_name):
     model = define_model(opt)
     mc = MetricCalculator(opt)
     topt = opt.get('test', {})
+    official = _official_metrics(opt) if topt.get('official_metrics') else None
+    official_res = {}
     for idx in dist_utils.shard_indices(len(sequences)):
         data = sequences[idx]
         model.prepare_inference_data(data)
         hr_seq = model.infer(device_output=True).contiguous()
         mc.compute_sequence_metrics(data['seq_idx'], data['gt'], hr_seq)
+        if official is not None:
+            official_res[data['seq_idx']] = official.compute_sequence(data['gt'], hr_seq)
         model.net_G.check_faults()
         if topt.get('save_res'):
             res_dir = topt.get('res_dir') or os.path.join(opt.get('exp_dir', '.'), 'test', 'results')
@@ -202,7 +206,49 @@ def evaluate(opt, sequences, model_idx, ds_name):
         mc.save(model_idx, os.path.join(json_dir, f'{ds_name}_avg.json'), override=True)
     else:
         mc.display()
+    if official is not None:
+        _save_official(opt, official, official_res, list(seq_ids), model_idx, ds_name)
     return mc
+
+
+def _official_metrics(opt):
+    """test.official_metrics: the official protocol (metrics/official.py) next to the in-loop metrics.  Its LPIPS
+    is a second instance WITH ScalingLayer, built from the weight paths of the metric section."""
+    from .metrics.lpips import LPIPS
+    from .metrics.official import OfficialMetrics
+    device = opt.get('device', 'cuda')
+    cfg = dict((opt.get('metric') or {}).get('LPIPS') or {})
+    return OfficialMetrics(LPIPS.from_config(cfg, device=device, scaling=True), device=device)
+
+
+def _save_official(opt, official, per_seq, seq_ids, model_idx, ds_name):
+    """Ranks exchange per-sequence sums and counts; rank 0 writes `{json_dir}/{ds_name}_official.json`: the three
+    aggregates, frame counts, crop windows, "skipped"; per-frame lists in the single-process case only."""
+    import json
+    from .metrics.official import reduce_and_aggregate, summary_lines
+    rank, world = dist_utils.get_dist_info()
+    dev = official.device if (opt.get('dist') and official.device.type == 'cuda') else 'cpu'
+    agg = reduce_and_aggregate(per_seq, seq_ids, official.keys, device=dev)
+    # windows and frame counts of the other ranks' sequences: 6 integers per sequence through the same reduction
+    info = []
+    for sid in seq_ids:
+        r = per_seq.get(sid)
+        info += ([r['frames'], r['evaluated']] + list(r['window'] or [0, 0, 0, 0])) if r else [0] * 6
+    info = dist_utils.reduce_sum_to_master(info, device=dev).cpu().numpy().astype(np.int64).reshape(-1, 6)
+    if rank != 0:
+        return
+    doc = {'model': model_idx, 'keys': list(official.keys), 'skipped': official.skipped, 'cutfr': official.cutfr,
+           'sequences': list(seq_ids), 'frames': info[:, 0].tolist(), 'evaluated': info[:, 1].tolist(),
+           'windows': info[:, 2:].tolist()}
+    doc.update(agg)
+    if world == 1:
+        doc['per_frame'] = {sid: {k: per_seq[sid][k] for k in official.keys} for sid in seq_ids}
+    topt = opt.get('test', {})
+    json_dir = topt.get('json_dir') or os.path.join(opt.get('exp_dir', '.'), 'test', 'metrics')
+    os.makedirs(json_dir, exist_ok=True)
+    with open(os.path.join(json_dir, f'{ds_name}_official.json'), 'w') as f:
+        json.dump(doc, f, indent=2)
+    print('\n'.join(summary_lines(agg, official.keys)))
 
 
 def folder_test_sets(opt):

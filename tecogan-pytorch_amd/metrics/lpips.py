@@ -200,6 +200,36 @@ class LPIPS:
             y = out
         return feats
 
+    def features_of(self, seq_u8):
+        """relu1..relu5 of every frame of a (t,h,w,3) uint8 device clip: list of five (t,c,h,w) fp32 tensors,
+        computed in chunks of _chunk frames.  A frame's taps do not depend on the chunking or on the other
+        frames (see features), so distance() on them gives forward()'s values bit for bit; a metric that needs
+        one frame in several pairs (tLP) runs the backbone once per frame."""
+        self._device_weights()
+        if not (torch.is_tensor(seq_u8) and seq_u8.is_cuda and seq_u8.dtype == torch.uint8 and seq_u8.dim() == 4
+                and seq_u8.shape[3] == 3):
+            raise TecoganHipError(f'LPIPS: frames must be a (t,h,w,3) uint8 device tensor, got '
+                                  f'{getattr(seq_u8, "dtype", type(seq_u8))} {tuple(getattr(seq_u8, "shape", ()))}')
+        t, h, w, _ = seq_u8.shape
+        alexnet_out_sizes(h, w)
+        seq_u8 = seq_u8.contiguous()
+        step = 2 * self._chunk(t, h, w)          # forward() holds the two sides of a chunk at once
+        chunks = [self.features(seq_u8[f0:min(t, f0 + step)]) for f0 in range(0, t, step)]
+        return chunks[0] if len(chunks) == 1 else [torch.cat(c) for c in zip(*chunks)]
+
+    def distance(self, feats_a, feats_b, per_layer=False):
+        """The head on two lists of taps (features_of, or equally long slices of them along the frames):
+        (n,) fp32 LPIPS on the device ((n,5) per layer), what forward() gives for the same frame pairs."""
+        _, lin, _ = self._device_weights()
+        if len(feats_a) != 5 or len(feats_b) != 5:
+            raise ValueError('LPIPS.distance: five taps per side')
+        n = feats_a[0].shape[0]
+        res = torch.zeros(n, 5, dtype=torch.float32, device=feats_a[0].device)
+        total = torch.zeros(n, dtype=torch.float32, device=feats_a[0].device)
+        for k, (a, b) in enumerate(zip(feats_a, feats_b)):
+            ops.lpips_head(a, b, lin[k], res, k, total if k == 4 else None)
+        return res if per_layer else total
+
     def forward(self, true_u8, pred_u8, per_layer=False):
         """(t,h,w,3) uint8 device frames -> (t,) fp32 LPIPS on the device ((t,5) per layer)."""
         _, lin, _ = self._device_weights()

@@ -531,6 +531,52 @@ def lpips_head(feat_true, feat_pred, lin, res, layer, total=None):
     return res
 
 
+def _window_args(true_hwc, pred_hwc, window, what):
+    """Checks of the windowed frame metrics: (t,h,w,3) uint8 device frames, a window inside both."""
+    _chk_u8(true_hwc, 'true'); _chk_u8(pred_hwc, 'pred')
+    if true_hwc.dim() != 4 or pred_hwc.dim() != 4 or true_hwc.shape[3] != 3 or pred_hwc.shape[3] != 3 or \
+            true_hwc.shape[0] != pred_hwc.shape[0] or true_hwc.shape[0] < 1:
+        raise L.TecoganHipError(f'{what}: shapes {tuple(true_hwc.shape)} / {tuple(pred_hwc.shape)}')
+    t, th, tw, _ = true_hwc.shape
+    _, ph, pw, _ = pred_hwc.shape
+    if window is None:
+        if (th, tw) != (ph, pw):
+            raise L.TecoganHipError(f'{what}: frames of {th}x{tw} and {ph}x{pw} need a window')
+        window = (0, 0, th, tw)
+    y0, x0, h, w = (int(v) for v in window)
+    return t, th, tw, ph, pw, y0, x0, h, w
+
+
+def ssim_y_u8(true_hwc, pred_hwc, window=None):
+    """tg_ssim_y_u8: per-frame mean SSIM of the unrounded Y planes (7x7 uniform window, data_range of the
+    predicted frame) of (t,h,w,3) uint8 device frames on window = (y0, x0, h, w), the same origin in both
+    (None: the whole, equally sized frames) -> float64 (t,) on the device."""
+    t, th, tw, ph, pw, y0, x0, h, w = _window_args(true_hwc, pred_hwc, window, 'ssim_y_u8')
+    nbytes = L.lib().tg_ssim_workspace_bytes(t, h, w)
+    if nbytes < 0:
+        raise L.TecoganHipError(f'ssim_y_u8: no workspace for frames={t} window {h}x{w} (at least 7x7)')
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=true_hwc.device)
+    out = torch.empty(t, dtype=torch.float64, device=true_hwc.device)
+    L.check(L.lib().tg_ssim_y_u8(true_hwc.data_ptr(), pred_hwc.data_ptr(), t, th, tw, ph, pw, y0, x0, h, w,
+                                 out.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()), 'tg_ssim_y_u8')
+    return out
+
+
+def psnr_yfloat_sse_u8(true_hwc, pred_hwc, window=None):
+    """tg_psnr_yfloat_sse_u8: exact per-frame sums of (y'_true - y'_pred)^2 over the window, with the integer
+    luma y' = 65481 R + 128553 G + 24966 B (Y = 16 + y' / 255000) -> list of t Python integers (a frame's sum
+    does not fit 64 bits; the kernel's per-block partials are added here)."""
+    t, th, tw, ph, pw, y0, x0, h, w = _window_args(true_hwc, pred_hwc, window, 'psnr_yfloat_sse_u8')
+    nb = L.lib().tg_psnr_yfloat_partials(h, w)
+    if nb < 0:
+        raise L.TecoganHipError(f'psnr_yfloat_sse_u8: window {h}x{w}')
+    part = torch.empty(t, nb, dtype=torch.int64, device=true_hwc.device)
+    L.check(L.lib().tg_psnr_yfloat_sse_u8(true_hwc.data_ptr(), pred_hwc.data_ptr(), t, th, tw, ph, pw, y0, x0, h, w,
+                                          part.data_ptr(), _stream()), 'tg_psnr_yfloat_sse_u8')
+    # the partials are unsigned 64-bit (up to 4096 * 3.12e15 > 2^63): undo int64's wrap
+    return [sum(v + (1 << 64) if v < 0 else v for v in row) for row in part.tolist()]
+
+
 # ---------------------------------------------------------------------------
 # training-side wrappers (backward kernels, losses, optimiser)
 # ---------------------------------------------------------------------------

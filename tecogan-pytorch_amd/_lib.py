@@ -7,7 +7,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# TECOGAN_HIP_LIB: measurement builds of the same sources (tools/build_lab_libs.sh); never a fallback
+# TECOGAN_HIP_LIB: measurement builds of the same sources (tools/build_var.sh, or csrc/build.sh with TG_LAB_BUILD=1); never a fallback
 LIB_PATH = os.environ.get('TECOGAN_HIP_LIB') or os.path.join(_HERE, 'libtecogan_hip.so')
 
 TG_OK = 0

@@ -3,7 +3,7 @@
 #
 # The in-tree library (../libtecogan_hip.so, the one the package loads) is ALWAYS built with exactly the flags below:
 # EXTRA_FLAGS / lab switches are refused for it.  A lab build (ablation / A-B variants, timing only) is
-#   TG_LAB_BUILD=1 OUT=/some/dir EXTRA_FLAGS="-DWR_RDFORM=1" bash build.sh
+#   TG_LAB_BUILD=1 OUT=/some/dir EXTRA_FLAGS="-DWR_UASM=0" bash build.sh
 # which compiles with -DTG_LAB=1 into OUT (objects and libtecogan_lab.so), never into the package; load it with
 # TECOGAN_HIP_LIB.  tg_build_info() of either library says which one it is (tests/test_abi_cpu.py asserts lab=0).
 set -euo pipefail

@@ -158,23 +158,21 @@ __device__ __forceinline__ void chunk_taps_sel(int ry, int rx, const float* si, 
 // ABL: ablation bits for tools/conv_lab.hip only (0 in the product):
 //   1 = no re-staging inside the chunk loop, 2 = no barrier in the loop,
 //   4 = no epilogue stores, 8 = no LDS operand reads.
-// OPT bits (tuning switches, selected by the launcher): 1 = epilogue through LDS with
-// 16-byte stores (needs a.vec_ok), 2 = weight chunks staged by LDS-DMA (global_load_lds).
+// The weight chunks are staged by LDS-DMA (global_load_lds) and, where a.vec_ok, the epilogue goes through LDS
+// with 16-byte stores: together measured +2 % on the frame against staging through registers + 4-byte stores.
 // KS = 2: the workgroup's waves are also split over K -- wave group wk takes every KS-th
 // channel chunk (both chunks of a pair are staged together), the partial accumulators are
 // added through LDS in a fixed order.  For problems with fewer 32x32 tiles than SIMDs
 // (training: 2 x 64 x 64 LR frames) this doubles the busy SIMDs without a second launch.
-template <int WM, int WN, int NT, bool DUAL, int ABL = 0, int OPT = 0, int STAGGER = 12, int KS = 1>
+template <int WM, int WN, int NT, bool DUAL, int ABL = 0, int KS = 1>
 __global__ __launch_bounds__(WM* WN* KS * 64) void conv3x3_mfma_kernel(Conv3x3Args a) {
-  static_assert(KS == 1 || (KS == 2 && (OPT & 2)), "the K-split variant stages weights by LDS-DMA");
+  static_assert(KS == 1 || KS == 2, "wave groups over K: one or two");
   constexpr int NTHREADS = WM * WN * KS * 64;
   constexpr int OCB = WN * NT * 32;
   constexpr int PH = WM + 2;
   constexpr int IN_ITEMS = PH * 2 * PW;            // 16-byte items (pixel x 4 channels) per chunk
   constexpr int IN_FLOATS = PH * 2 * RS * 4;
   constexpr int W_FLOATS = 9 * CK * OCB;
-  constexpr int W_VEC4 = W_FLOATS / 4;
-  constexpr int W_PER_T = (W_VEC4 + NTHREADS - 1) / NTHREADS;
   constexpr int I_PER_T = (IN_ITEMS + NTHREADS - 1) / NTHREADS;
 
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -233,7 +231,6 @@ __global__ __launch_bounds__(WM* WN* KS * 64) void conv3x3_mfma_kernel(Conv3x3Ar
       reinterpret_cast<const f32x4*>(a.wpk + (size_t)ocg * a.nchunk * W_FLOATS);
 
   f32x4 rin[KS][I_PER_T];
-  f32x4 rw[W_PER_T];
 
   auto load_chunk = [&](int ch) {
     if (!((ABL & 32) && ch != ch_begin))      // lab: skip input re-staging
@@ -253,32 +250,23 @@ __global__ __launch_bounds__(WM* WN* KS * 64) void conv3x3_mfma_kernel(Conv3x3Ar
         }
       }
     }
-    const f32x4* ws = wsrc + (size_t)ch * W_VEC4;
     if ((ABL & 64) && ch != ch_begin) return;   // lab: skip weight re-staging
-    if constexpr (OPT & 2) {
-      // LDS-DMA: each wave instruction moves 1 KiB (64 lanes x 16 B) of the packed chunk
-      // straight into the other weight buffer; no VGPR round trip, no ds_write.
-      constexpr int PIECES = W_FLOATS * 4 / 1024;
-      constexpr int NWAVES = NTHREADS / 64;
-      // chunk ch + k lives in slot bufof(ch) * KS + k; the packed chunks of a pair are
-      // contiguous in global memory and in LDS, so the pair is one run of KS * PIECES pieces
-      const char* src = reinterpret_cast<const char*>(ws) + lane * 16;
-      char* dst = reinterpret_cast<char*>(s_w + bufof(ch) * KS * W_FLOATS);
-      const int valid = (ch_end - ch < KS ? ch_end - ch : KS) * PIECES;   // never read past the last chunk
+    // LDS-DMA: each wave instruction moves 1 KiB (64 lanes x 16 B) of the packed chunk
+    // straight into the other weight buffer; no VGPR round trip, no ds_write.
+    constexpr int PIECES = W_FLOATS * 4 / 1024;
+    constexpr int NWAVES = NTHREADS / 64;
+    // chunk ch + k lives in slot bufof(ch) * KS + k; the packed chunks of a pair are
+    // contiguous in global memory and in LDS, so the pair is one run of KS * PIECES pieces
+    const char* src = reinterpret_cast<const char*>(wsrc + (size_t)ch * (W_FLOATS / 4)) + lane * 16;
+    char* dst = reinterpret_cast<char*>(s_w + bufof(ch) * KS * W_FLOATS);
+    const int valid = (ch_end - ch < KS ? ch_end - ch : KS) * PIECES;   // never read past the last chunk
 #pragma unroll
-      for (int i = 0; i < (KS * PIECES + NWAVES - 1) / NWAVES; ++i) {
-        int piece = wave + i * NWAVES;
-        if (piece < valid)
-          __builtin_amdgcn_global_load_lds(
-              (const __attribute__((address_space(1))) void*)(src + piece * 1024),
-              (__attribute__((address_space(3))) void*)(dst + piece * 1024), 16, 0, 0);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < W_PER_T; ++i) {
-        int idx = tid + i * NTHREADS;
-        rw[i] = ws[idx < W_VEC4 ? idx : W_VEC4 - 1];
-      }
+    for (int i = 0; i < (KS * PIECES + NWAVES - 1) / NWAVES; ++i) {
+      int piece = wave + i * NWAVES;
+      if (piece < valid)
+        __builtin_amdgcn_global_load_lds(
+            (const __attribute__((address_space(1))) void*)(src + piece * 1024),
+            (__attribute__((address_space(3))) void*)(dst + piece * 1024), 16, 0, 0);
     }
   };
   auto store_chunk = [&](int buf) {
@@ -288,14 +276,6 @@ __global__ __launch_bounds__(WM* WN* KS * 64) void conv3x3_mfma_kernel(Conv3x3Ar
 #pragma unroll
       for (int i = 0; i < I_PER_T; ++i)
         if (lds_item[i] >= 0) *reinterpret_cast<f32x4*>(si + lds_item[i]) = rin[k][i];
-    }
-    if constexpr (!(OPT & 2)) {
-      f32x4* sw = reinterpret_cast<f32x4*>(s_w + buf * W_FLOATS);
-#pragma unroll
-      for (int i = 0; i < W_PER_T; ++i) {
-        int idx = tid + i * NTHREADS;
-        if (idx < W_VEC4) sw[idx] = rw[i];
-      }
     }
   };
 
@@ -310,13 +290,6 @@ __global__ __launch_bounds__(WM* WN* KS * 64) void conv3x3_mfma_kernel(Conv3x3Ar
   const int b_off = ((wm * 2 + lh) * RS + ll) * 4;
   const int a_off = (lh * OCB + wn * (NT * 32) + ll) * 4;
 
-  if constexpr (OPT & 4) {
-    // De-synchronise the workgroups that share a CU: they run the same instruction stream
-    // and would otherwise hit their staging / barrier points at the same moments, leaving the
-    // MFMA pipe idle.  Offset each residency "layer" by a fraction of a chunk period.
-    const int layer = (blockIdx.x / 256) % 3;
-    for (int i = 0; i < layer; ++i) __builtin_amdgcn_s_sleep(STAGGER);
-  }
   long long tk0 = 0, tk1 = 0, t_mfma = 0, t_sync = 0, t_issue = 0;
   if constexpr (ABL & 16) tk0 = clock64();
   load_chunk(ch_begin);
@@ -426,48 +399,46 @@ __global__ __launch_bounds__(WM* WN* KS * 64) void conv3x3_mfma_kernel(Conv3x3Ar
     return;
   }
   const float slope = act_slope(a.act);
-  if constexpr (OPT & 1) {
-    if (a.vec_ok) {      // wave-uniform
-      // accumulators -> LDS [oc][32 px] (stride 36) -> each lane re-reads 4 consecutive
-      // pixels of one channel and issues 16-byte stores: 4x fewer store instructions.
-      constexpr int ES = 36;
-      float* ep = smem + (wave % (WM * WN)) * (NT * 32 * ES);
-      if (do_ep) {
+  if (a.vec_ok) {      // wave-uniform
+    // accumulators -> LDS [oc][32 px] (stride 36) -> each lane re-reads 4 consecutive
+    // pixels of one channel and issues 16-byte stores: 4x fewer store instructions.
+    constexpr int ES = 36;
+    float* ep = smem + (wave % (WM * WN)) * (NT * 32 * ES);
+    if (do_ep) {
 #pragma unroll
-        for (int t = 0; t < NT; ++t)
+      for (int t = 0; t < NT; ++t)
 #pragma unroll
-          for (int r = 0; r < 16; ++r)
-            ep[(t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * ES + ll] = acc[t][r];
-      }
-      __syncthreads();
-      const int ocw = ocg * OCB + wn * (NT * 32);
-      if (do_ep && py < a.h) {
+        for (int r = 0; r < 16; ++r)
+          ep[(t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * ES + ll] = acc[t][r];
+    }
+    __syncthreads();
+    const int ocw = ocg * OCB + wn * (NT * 32);
+    if (do_ep && py < a.h) {
 #pragma unroll
-        for (int j = 0; j < NT * 4; ++j) {
-          int idx4 = j * 64 + lane;
-          int ol = idx4 >> 3, p4 = (idx4 & 7) * 4;
-          int oc = ocw + ol;
-          int gx = x0 + p4;
-          if (oc < a.cout && gx < a.w) {
-            f32x4 v = *reinterpret_cast<const f32x4*>(ep + ol * ES + p4);
-            float bb = a.bias ? a.bias[oc] : 0.f;
-            long long off = (long long)oc * hw + (long long)py * a.w + gx;
-            f32x4 rr = {0.f, 0.f, 0.f, 0.f};
-            if (a.res) rr = *reinterpret_cast<const f32x4*>(a.res + (long long)n * a.res_ns + off);
-            f32x4 mm = {1.f, 1.f, 1.f, 1.f};
-            if (a.mask) mm = *reinterpret_cast<const f32x4*>(a.mask + (long long)n * a.mask_ns + off);
+      for (int j = 0; j < NT * 4; ++j) {
+        int idx4 = j * 64 + lane;
+        int ol = idx4 >> 3, p4 = (idx4 & 7) * 4;
+        int oc = ocw + ol;
+        int gx = x0 + p4;
+        if (oc < a.cout && gx < a.w) {
+          f32x4 v = *reinterpret_cast<const f32x4*>(ep + ol * ES + p4);
+          float bb = a.bias ? a.bias[oc] : 0.f;
+          long long off = (long long)oc * hw + (long long)py * a.w + gx;
+          f32x4 rr = {0.f, 0.f, 0.f, 0.f};
+          if (a.res) rr = *reinterpret_cast<const f32x4*>(a.res + (long long)n * a.res_ns + off);
+          f32x4 mm = {1.f, 1.f, 1.f, 1.f};
+          if (a.mask) mm = *reinterpret_cast<const f32x4*>(a.mask + (long long)n * a.mask_ns + off);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              float q = v[e] + bb;
-              q = (q >= 0.f ? q : q * slope + 0.f) + rr[e];
-              v[e] = mm[e] > 0.f ? q : 0.f;
-            }
-            *reinterpret_cast<f32x4*>(a.y + (long long)n * a.y_ns + off) = v;
+          for (int e = 0; e < 4; ++e) {
+            float q = v[e] + bb;
+            q = (q >= 0.f ? q : q * slope + 0.f) + rr[e];
+            v[e] = mm[e] > 0.f ? q : 0.f;
           }
+          *reinterpret_cast<f32x4*>(a.y + (long long)n * a.y_ns + off) = v;
         }
       }
-      return;
     }
+    return;
   }
   if (!do_ep) return;        // no barrier below
   float bv[NT][16], rv[NT][16];
@@ -785,11 +756,6 @@ __global__ __launch_bounds__(512) void conv3x3s2_oneshot_kernel(Conv3x3Args a) {
   }
 }
 
-// 3 = LDS-transposed 16-byte epilogue + LDS-DMA weight staging (measured +2 % on the frame,
-// parity suite green); bit 4 (start-up stagger of co-resident workgroups) measured null.
-#ifndef TG_CONV_OPT
-#define TG_CONV_OPT 3
-#endif
 
 template <int WM, int WN, int NT, int KS = 1>
 static int launch_conv(const Conv3x3Args& a0, int n, hipStream_t stream) {
@@ -809,10 +775,10 @@ static int launch_conv(const Conv3x3Args& a0, int n, hipStream_t stream) {
     static bool attr_set = false;
     if (!attr_set) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(
-                              conv3x3_mfma_kernel<WM, WN, NT, true, 0, TG_CONV_OPT, 12, KS>),
+                              conv3x3_mfma_kernel<WM, WN, NT, true, 0, KS>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(
-                              conv3x3_mfma_kernel<WM, WN, NT, false, 0, TG_CONV_OPT, 12, KS>),
+                              conv3x3_mfma_kernel<WM, WN, NT, false, 0, KS>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       attr_set = true;
     }
@@ -825,10 +791,10 @@ static int launch_conv(const Conv3x3Args& a0, int n, hipStream_t stream) {
   a.nblocks = xcd ? (int)blocks : 0;
   const unsigned grid = xcd ? (unsigned)(8 * ((blocks + 7) / 8)) : (unsigned)blocks;
   if (a.x2)
-    hipLaunchKernelGGL((conv3x3_mfma_kernel<WM, WN, NT, true, 0, TG_CONV_OPT, 12, KS>),
+    hipLaunchKernelGGL((conv3x3_mfma_kernel<WM, WN, NT, true, 0, KS>),
                        dim3(grid), dim3(WM * WN * KS * 64), lds, stream, a);
   else
-    hipLaunchKernelGGL((conv3x3_mfma_kernel<WM, WN, NT, false, 0, TG_CONV_OPT, 12, KS>),
+    hipLaunchKernelGGL((conv3x3_mfma_kernel<WM, WN, NT, false, 0, KS>),
                        dim3(grid), dim3(WM * WN * KS * 64), lds, stream, a);
   return check_launch("conv3x3_mfma");
 }

@@ -29,17 +29,6 @@
 
 #include "tg_common.h"
 
-#ifndef TG_CHAIN_FENCES
-#define TG_CHAIN_FENCES 0   // 1: release / acquire fences around the flag of the chained launch (measurement build)
-#endif
-#ifndef TG_WINO_LAB
-#define TG_WINO_LAB 0   // 1: ablation switches of tools/wino_abl.sh (TG_WINO_ABL) compiled in
-#endif
-#define WABL(bit) (TG_WINO_LAB && (a.abl & (bit)))
-#if !TG_LAB && TG_WINO_LAB
-#error "tg_conv3x3_wino.hip: TG_WINO_LAB needs -DTG_LAB=1 (lab builds only; csrc/build.sh refuses it for the in-tree library)"
-#endif
-
 namespace tg {
 
 struct WinoArgs {
@@ -55,12 +44,8 @@ struct WinoArgs {
   int tiles_x, tiles_y, nstage, nocg, nocb;
   int nblocks;         // > 0: XCD-banded block order
   int vec_ok;          // float2 stores allowed (w even, 8-byte aligned planes)
-  int abl;             // lab builds only (TG_WINO_LAB, env TG_WINO_ABL): 1 no weight loads, 2 no input loads, 4 no stores, 16 no MFMA, 32 weights from L1, 64 empty launch, 128 no main loop
 };
 
-#ifndef W_BRANCHY_U
-#define W_BRANCHY_U 0   // 1: the round 2-4 form of the weight prefetch, for A/B
-#endif
 constexpr int W_ICS = 16;             // input channels per stage
 constexpr int W_RS = 40;              // LDS row stride of the raw patch (floats); 4 rows = 160 = 32 mod 64 banks
 constexpr int W_ICSTR = 4 * W_RS;
@@ -184,7 +169,6 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
       a.x2 ? (unsigned)(a.cin - a.c1) * hw * 4u : 0u, 0x00020000);
   const bool dual = a.x2 != nullptr;
   auto load_raw = [&](int s, float (&reg)[RAW_PER_T]) {
-    if (WABL(2) && s > 0) return;
     const unsigned so = (unsigned)(s * W_ICS) * hw * 4u;
 #pragma unroll
     for (int k = 0; k < RAW_PER_T; ++k) {
@@ -210,17 +194,11 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
   const int ktotal = 4 * a.nstage;
   // one half (positions 8*half .. 8*half+7) of the weights of K step `kstep`
   auto load_uh = [&](int kstep, int half, f32x4 (&u)[4]) {
-#if W_BRANCHY_U
-    if (kstep >= ktotal || (WABL(1) && kstep > 1)) return;
-#else
     // BRANCH-FREE (round 5): behind `if (kstep < ktotal)` the compiler's s_waitcnt insertion merges both paths at the
     // join assuming the FEWER loads in flight, and every K step waited `vmcnt(1) / vmcnt(0)` -- for the half-block
     // requested a moment ago as well as for its own.  Past the last K step the last block is requested again (an L1
     // hit, never used); the waits then carry the exact counts (vmcnt(7) .. (4) in the ISA).
-    if (WABL(1) && kstep > 1) return;
     kstep = kstep < ktotal ? kstep : ktotal - 1;
-#endif
-    if (WABL(32)) kstep &= 1;
     const f32x4* p = ug + (size_t)kstep * ustep + half * 128;
     u[2 * half] = p[0];
     u[2 * half + 1] = p[64];
@@ -241,7 +219,6 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
     f32x4 bq[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) bq[j] = bv[buf * VBUF4 + ks * (4 * 16 * W_VS / 4) + 2 * half + j];
-    if (WABL(16)) { acc[ks][0] += bq[0][0] + bq[1][1] + u[2 * half][0] + u[2 * half + 1][0]; return; }
 #pragma unroll
     for (int p = 0; p < 8; ++p)
       acc[8 * half + p] = __builtin_amdgcn_mfma_f32_16x16x4f32(u[2 * half + (p >> 2)][p & 3], bq[p >> 2][p & 3],
@@ -306,7 +283,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
   // scheduling fences keep the compiler from hoisting all operand reads to the top, which
   // would cost the third wave per SIMD.)
   auto nothing = [] {};
-  for (int s = 0; s < (WABL(128) ? 0 : last); ++s) {
+  for (int s = 0; s < last; ++s) {
     const int cur = s & 1, nxt = cur ^ 1;
     kstep(4 * s + 0, u0, cur, nothing);
     __syncthreads();                         // patch of stage s+1 visible
@@ -349,7 +326,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
       sr[0][j] = (acc[0 + j][r] + acc[4 + j][r]) + acc[8 + j][r];
       sr[1][j] = (acc[4 + j][r] - acc[8 + j][r]) - acc[12 + j][r];
     }
-    if (oc >= a.cout || ox >= a.w || (WABL(4) && sr[0][0] != 123.f)) continue;
+    if (oc >= a.cout || ox >= a.w) continue;
     const float bz = a.bias ? a.bias[oc] : 0.f;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -380,7 +357,6 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
 
 template <int TR>
 __global__ __launch_bounds__(256, 3) void conv3x3_wino_kernel(WinoArgs a) {
-  if (WABL(64)) return;                      // empty launch
   int b = blockIdx.x;
   if (a.nblocks > 0) {      // XCD x gets the contiguous band of tiles [x*per, (x+1)*per)
     const int per = (a.nblocks + 7) >> 3;
@@ -455,7 +431,7 @@ __global__ __launch_bounds__(256, 3) void conv3x3_wino_chain_kernel(WinoChainArg
   a.x_ns = L.x_ns; a.x2_ns = L.x2_ns; a.res_ns = L.res_ns; a.mask_ns = 0; a.y_ns = L.y_ns;
   a.c1 = L.c1; a.cin = L.cin; a.cout = c.cout; a.h = c.h; a.w = c.w; a.act = L.act;
   a.tiles_x = c.tiles_x; a.tiles_y = c.tiles_y; a.nstage = L.nstage; a.nocg = 1; a.nocb = 4;
-  a.nblocks = 0; a.vec_ok = c.vec_ok; a.abl = 0;
+  a.nblocks = 0; a.vec_ok = c.vec_ok;
   if (layer > 0) {                            // wait for the producers of the 3x3 neighbourhood
     const int t = threadIdx.x;
     if (t < 9) {
@@ -470,9 +446,6 @@ __global__ __launch_bounds__(256, 3) void conv3x3_wino_chain_kernel(WinoChainArg
         }
         if (fault) __hip_atomic_fetch_add(c.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
-#if TG_CHAIN_FENCES
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // measured variant, see the note below
-#endif
     }
     __syncthreads();
   }
@@ -485,16 +458,10 @@ __global__ __launch_bounds__(256, 3) void conv3x3_wino_chain_kernel(WinoChainArg
   // On gfx950 the release fence is `buffer_wbl2 sc1; s_waitcnt vmcnt(0)` and the acquire fence `buffer_inv sc1`
   // (MI355X_MICROARCH.md): with agent-scope (sc1, write-through) data stores that were waited for there is
   // nothing left to write back, and with sc1 data loads there is no L1 line to invalidate -- the fences
-  // add nothing but their cost.  Built with -DTG_CHAIN_FENCES=1 the launch measured +X % (tools/chain_fence_lab.sh;
-  // DESIGN.md section 10c has the number), so the shipped form keeps sc1 stores + acknowledged waitcnt +
+  // add nothing but their cost.  Built with both fences the launch measured +80 % (128.3 vs 71.4 us per layer at
+  // 4 clips of 134x320, EXPERIMENTS.md), so the shipped form keeps sc1 stores + acknowledged waitcnt +
   // relaxed agent-scope flag, and the property is held by tests/test_hip_soak.py (200 launches per production
   // shape on fresh data under a concurrent memory stream, bit-compared with per-layer launches).
-#if TG_CHAIN_FENCES
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-#endif
   if (threadIdx.x == 0)
     __hip_atomic_store(reinterpret_cast<unsigned*>(c.flags) + (size_t)layer * c.ntile + tile, c.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -562,8 +529,6 @@ int conv3x3_wino_launch(const float* x, int64_t x_ns, int c1, const float* x2, i
   auto al8 = [](const void* p, int64_t ns) { return ((uintptr_t)p % 8) == 0 && ns % 2 == 0; };
   a.vec_ok = (w % 2 == 0) && ((int64_t)h * w) % 2 == 0 && al8(y, y_ns) && (!res || al8(res, res_ns)) &&
              (!mask || al8(mask, mask_ns));
-  static const int abl_env = TG_LAB_ENV("TG_WINO_ABL", 0);
-  a.abl = abl_env;
   const long long blocks = (long long)a.tiles_x * a.tiles_y * a.nocg * n;
   static const int xcd_env = TG_LAB_ENV("TG_WINO_XCD", -1);   // lab
   const bool xcd = xcd_env >= 0 ? xcd_env != 0 : blocks >= 512;
@@ -590,26 +555,6 @@ extern "C" int tg_conv3x3_wino_fwd(const float* x, int64_t x_nstride, int c1, co
   return conv3x3_wino_launch(x, x_nstride, c1, x2, x2_nstride, u_packed, bias, res, res_nstride, relu_mask,
                              mask_nstride, y, y_nstride, n, cin, cout, h, w, act, stream);
 }
-
-#if TG_WINO_LAB
-// lab only (tools/wino_split_probe.py): `layers` dependent 64->64 layers on ONE stream, or the same
-// on two independent half-height chains whose launches alternate between two streams (all enqueued
-// from C so that the host is not the bottleneck)
-extern "C" int tg_lab_wino_chains(float* a0, float* c0, float* a1, float* c1, const float* u, const float* bias,
-                                  int layers, int h, int w, tg_stream_t s0, tg_stream_t s1, int two) {
-  float *pa[2] = {a0, a1}, *pc[2] = {c0, c1};
-  tg_stream_t st[2] = {s0, s1};
-  const int64_t ns = (int64_t)64 * h * w;
-  for (int l = 0; l < layers; ++l)
-    for (int k = 0; k < (two ? 2 : 1); ++k) {
-      int rc = conv3x3_wino_launch(pa[k], ns, 64, nullptr, 0, u, bias, nullptr, 0, nullptr, 0, pc[k], ns, 1, 64, 64, h, w,
-                                   TG_ACT_RELU, st[k]);
-      if (rc != TG_OK) return rc;
-      float* t = pa[k]; pa[k] = pc[k]; pc[k] = t;
-    }
-  return TG_OK;
-}
-#endif
 
 extern "C" int64_t tg_conv3x3_wino_chain_flag_ints(int n_layers, int n, int h, int w) {
   if (n_layers <= 0 || n_layers > W_MAX_CHAIN || n <= 0 || h <= 0 || w <= 0) return -1;

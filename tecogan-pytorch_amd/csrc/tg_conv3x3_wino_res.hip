@@ -34,61 +34,22 @@
 
 #include "tg_common.h"
 
-// ---- lab switches (A/B and ablation builds, tools/build_lab_libs.sh).  Every one of them needs -DTG_LAB=1, which
-// csrc/build.sh refuses for the in-tree library: the shipped translation unit is the DEFAULT column below and nothing
-// else (WR_FAKEBANK computes wrong results by design, timing only). ----
-#ifndef WR_POLL_SLEEP
-#define WR_POLL_SLEEP 2   // s_sleep units (64 cycles) between two polls of the ring
-#endif
-#ifndef WR_PRIO_I
-#define WR_PRIO_I 0     // s_setprio of the interior waves
-#endif
-#ifndef WR_PRIO_B
-#define WR_PRIO_B 0     // s_setprio of the boundary waves (the interior waves stay at 0)
-#endif
-#ifndef WR_USETS
-#define WR_USETS 2      // weight blocks (K steps) in flight per wave: 2 or 3
-#endif
-#ifndef TG_WRES_LAB
-#define TG_WRES_LAB 0   // 1: ablation switches (env TG_WRES_ABL) compiled in -- tools/build_lab_libs.sh, timing only
-#endif
-#define RABL(bit) (TG_WRES_LAB && (a.abl & (bit)))
-#ifndef WR_FAKEBANK
-#define WR_FAKEBANK 0   // lab, TIMING ONLY (wrong results): window origins spread over distinct bank pairs -- the ceiling of any layout fix
-#endif
-#ifndef WR_RDFORM
-#define WR_RDFORM 0     // 0: the compiler's window reads (it merges them into ds_read2_b64); 1: eight ds_read_b64 (inline asm)
-#endif
-#ifndef WR_PREF
-#define WR_PREF 1       // 1: K step ks + 1's window is requested before K step ks's MFMAs (second register set)
-#endif
-#ifndef WR_PK
-#define WR_PK 0         // 1: the input transform on v_pk_add_f32 (measured)
-#endif
+// ---- the one build switch.  WR_UASM = 1 is what ships: hand-written weight requests + exact vmcnt waits (round 5).
+// WR_UASM = 0 is the round-4 form of the same kernel -- compiler-visible weight loads behind a branch, the compiler's own
+// waits -- and exists as the reference the hand-written waits are checked against: tests/test_hip_soak.py rebuilds this
+// file with it and requires bit-identical results.  It needs -DTG_LAB=1, which csrc/build.sh refuses for the in-tree
+// library.  (The variants that lost their A/B -- wave priorities, three weight blocks in flight, inline-asm window reads,
+// the packed input transform, the ablation bits -- are written up in EXPERIMENTS.md and live in git history.) ----
 #ifndef WR_UASM
-#define WR_UASM 1       // hand-written weight requests + exact vmcnt waits (round 5); 0: compiler-visible loads, for A/B
+#define WR_UASM 1
 #endif
-#ifndef WR_BRANCHY_U
-#define WR_BRANCHY_U 0
-#endif
-#define WR_LAB_BITS ((TG_WRES_LAB ? 1 : 0) | (WR_FAKEBANK ? 2 : 0) | (WR_RDFORM ? 4 : 0) | (WR_PREF != 1 ? 8 : 0) | \
-                     (WR_PK ? 16 : 0) | (WR_UASM != 1 ? 32 : 0) | (WR_BRANCHY_U ? 64 : 0) | (WR_USETS != 2 ? 128 : 0) | \
-                     (WR_PRIO_I || WR_PRIO_B ? 256 : 0) | (WR_POLL_SLEEP != 2 ? 512 : 0))
-#if !TG_LAB && WR_LAB_BITS
+#if !TG_LAB && WR_UASM != 1
 #error "tg_conv3x3_wino_res.hip: a lab switch is set without -DTG_LAB=1 (the in-tree library ships the defaults only)"
-#endif
-#if WR_UASM && WR_PK
-#error "WR_PK's K step never waits for the hand-requested weight block (wait_u): -DWR_PK=1 needs -DWR_UASM=0"
-#endif
-#if WR_UASM && WR_USETS != 2
-#error "the hand-written waits assume two weight blocks in flight"
 #endif
 
 namespace tg {
 
-int wres_lab_bits() { return WR_LAB_BITS | (TG_LAB ? 1024 : 0); }    // tg_build_info(): 0 in the shipped library
-
-typedef float v2f __attribute__((ext_vector_type(2)));
+int wres_lab_bits() { return (WR_UASM != 1 ? 32 : 0) | (TG_LAB ? 1024 : 0); }    // tg_build_info(): 0 in the shipped library
 
 constexpr int WR_TH = 4, WR_TW = 12;             // Winograd tiles per block
 constexpr int WR_BH = 2 * WR_TH, WR_BW = 2 * WR_TW;   // 8 x 24 pixels
@@ -100,6 +61,7 @@ constexpr int WR_THREADS = 768;                   // 12 waves: 3 per SIMD
 constexpr int WR_MAXL = 24;
 constexpr int WR_SLOTS = 64;                      // published ring pixels of a block: top 24, bottom 24, left 8, right 8
 constexpr int WR_SC1 = 16;                        // agent-scope cache policy bit of the buffer instructions
+constexpr int WR_POLL_SLEEP = 2;                  // s_sleep units (64 cycles) between two polls of the ring
 constexpr int WR_ACT_FLOATS = 2 * WR_NC * WR_CS;   // the two activation buffers: 147 456 bytes
 constexpr int WR_BIAS_OFF = WR_ACT_FLOATS;          // [layer][64] biases (read once per launch)
 constexpr int WR_SYNC_OFF = WR_BIAS_OFF + WR_MAXL * WR_NC;   // 16 bytes: arrival counter of the boundary waves
@@ -115,14 +77,6 @@ __constant__ unsigned char WR_TILE[48] = {
     17, 18, 19, 20, 21, 22, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34};
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-#if TG_WRES_LAB
-// lab: s_memtime stamps of every wave of workgroup 100, 8 per layer (tools/wino_res_lab.py --stamps)
-__device__ long long g_wres_dbg[12 * 24 * 8];
-#define RSTAMP(k) do { if (blockIdx.x == 100 && l == 0) g_wres_dbg[(wv * 24 + L) * 8 + (k)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define RSTAMP(k) do { } while (0)
-#endif
 
 struct WResLayer {
   const float* u;      // tg_pack_conv3x3_wino form
@@ -148,7 +102,6 @@ struct WResArgs {
   const float* ct_bias;
   float* ct_y;         // (64, 2h, 2w)
   int ct_act;
-  int abl;             // lab builds only: 1 no flag wait / ring loads, 2 no MFMA, 4 no weight loads, 8 no ring stores, 16 no window reads, 32 no hand-over at all, 64 no input transform, 128 weights from L1, 256 half the weight bytes, 512 half the window bytes
 };
 
 __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WResArgs a) {
@@ -211,14 +164,8 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
   const int T = WR_TILE[16 * g + (l & 15)];   // tile of the block (row-major 4 x 12)
   const int ty = T / WR_TW, tx = T - ty * WR_TW;
   const bool interior = g == 2;               // wave-uniform
-  if (WR_PRIO_B > 0 && !interior) __builtin_amdgcn_s_setprio(WR_PRIO_B);
-  if (WR_PRIO_I > 0 && interior) __builtin_amdgcn_s_setprio(WR_PRIO_I);
   const int kk = l >> 4;                      // K index inside a K step (B operand) / output-channel quad (D)
-#if WR_FAKEBANK
-  const int rb = kk * WR_CS + 2 * (l & 15);
-#else
   const int rb = kk * WR_CS + (2 * ty) * WR_RS + 2 * tx;        // window origin in the resident block (floats)
-#endif
   const int oc_base = 16 * q + 4 * kk;
   const int wb = oc_base * WR_CS + (2 * ty + 1) * WR_RS + 2 * tx + 1;   // own 2x2 pixels, channel oc_base
   const int gy0 = Y0 + 2 * ty, gx0 = X0 + 2 * tx;               // image position of the tile
@@ -242,62 +189,48 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
   // stronger than needed as well.  The stream of blocks runs ACROSS the layers: the last two K steps of a layer
   // request the first two blocks of the next one (they arrive under the epilogue and the hand-over), so exactly two
   // blocks are in flight at every point of the launch and the epilogue issues no request of its own.
-  // (WR_UASM = 0: compiler-visible loads, the round-4 form with -DWR_BRANCHY_U=1; lab builds only.  Because the compiler
-  // cannot see these loads, csrc/build.sh FAILS the build if this kernel ever reports scratch or spilled registers.)
-  const f32x4* un = nullptr;                   // WR_UASM: the next layer's blocks (the K loop runs on into them)
-  auto load_u = [&](const f32x4* ub, int ks, int nks, f32x4 (&u)[4]) {
-#if WR_BRANCHY_U
-    if (ks >= nks || (RABL(4) && ks > 1)) return;
-#elif WR_UASM
-    if (RABL(4) && ks > 1) return;
-    if (ks >= nks) { ub = un; ks -= nks; }      // uniform: a scalar select, no branch
-#else
-    if (RABL(4) && ks > 1) return;
-    ks = ks < nks ? ks : nks - 1;
-#endif
-    const f32x4* p = ub + (size_t)(RABL(128) ? (ks & 1) : ks) * USTEP;     // lab 128: always the same two blocks (L1 hits)
+  // Because the compiler cannot see these loads, csrc/build.sh FAILS the build if this kernel ever reports scratch or
+  // spilled registers.
+  [[maybe_unused]] const f32x4* un = nullptr;   // the next layer's blocks (the K loop runs on into them; WR_UASM only)
 #if WR_UASM
+  auto load_u = [&](const f32x4* ub, int ks, int nks, f32x4 (&u)[4]) {
+    if (ks >= nks) { ub = un; ks -= nks; }      // uniform: a scalar select, no branch
+    const f32x4* p = ub + (size_t)ks * USTEP;
     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(u[0]) : "v"(p));
     asm volatile("global_load_dwordx4 %0, %1, off offset:1024" : "=v"(u[1]) : "v"(p));
     asm volatile("global_load_dwordx4 %0, %1, off offset:2048" : "=v"(u[2]) : "v"(p));
     asm volatile("global_load_dwordx4 %0, %1, off offset:3072" : "=v"(u[3]) : "v"(p));
-#else
-    u[0] = p[0]; u[1] = p[64];
-    if (RABL(256)) return;                     // lab 256: half the weight bytes
-    u[2] = p[128]; u[3] = p[192];
-#endif
-  };
-  // Behind the K loop two blocks nobody uses are still in flight (the clamped requests of the last two K steps): the
-  // compiler takes their registers for dead and would hand them to the next instruction -- a landing load then
-  // overwrites, say, the address of the epilogue's first request (a memory fault, found on the GPU).  The drain keeps
-  // the eight registers allocated until every load has landed.
-  auto drain_u = [&](f32x4 (&ua)[4], f32x4 (&ub_)[4]) {
-#if WR_UASM
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(ua[0]), "+v"(ua[1]), "+v"(ua[2]), "+v"(ua[3]),
-                                        "+v"(ub_[0]), "+v"(ub_[1]), "+v"(ub_[2]), "+v"(ub_[3]));
-#endif
   };
   // the block `u` was requested one block ago (see above): release it quarter by quarter
   auto wait_u = [&](f32x4 (&u)[4]) {
-#if WR_UASM
     asm volatile("s_waitcnt vmcnt(7)" : "+v"(u[0]));
     asm volatile("s_waitcnt vmcnt(6)" : "+v"(u[1]));
     asm volatile("s_waitcnt vmcnt(5)" : "+v"(u[2]));
     asm volatile("s_waitcnt vmcnt(4)" : "+v"(u[3]));
-#endif
   };
+  // Behind the K loop two blocks nobody uses are still in flight (the requests of the last two K steps): the
+  // compiler takes their registers for dead and would hand them to the next instruction -- a landing load then
+  // overwrites, say, the address of the epilogue's first request (a memory fault, found on the GPU).  The drain keeps
+  // the eight registers allocated until every load has landed.
+  auto drain_u = [&](f32x4 (&ua)[4], f32x4 (&ub_)[4]) {
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(ua[0]), "+v"(ua[1]), "+v"(ua[2]), "+v"(ua[3]),
+                                        "+v"(ub_[0]), "+v"(ub_[1]), "+v"(ub_[2]), "+v"(ub_[3]));
+  };
+#else   // the cross-check form: plain loads, nothing requested past a layer's last K step, the compiler's waits
+  auto load_u = [&](const f32x4* ub, int ks, int nks, f32x4 (&u)[4]) {
+    if (ks >= nks) return;
+    const f32x4* p = ub + (size_t)ks * USTEP;
+    u[0] = p[0]; u[1] = p[64]; u[2] = p[128]; u[3] = p[192];
+  };
+  auto wait_u = [&](f32x4 (&)[4]) {};
+  auto drain_u = [&](f32x4 (&)[4], f32x4 (&)[4]) {};
+#endif
 
   f32x4 u0[4], u1[4];
-#if WR_USETS == 3
-  f32x4 u2[4];
-#endif
   {
     const f32x4* ub = reinterpret_cast<const f32x4*>(a.L[0].u) + ulane;
     load_u(ub, 0, a.L[0].nks, u0);
     load_u(ub, 1, a.L[0].nks, u1);
-#if WR_USETS == 3
-    load_u(ub, 2, a.L[0].nks, u2);
-#endif
   }
 
   const bool fold = a.ct_u != nullptr;        // launch-uniform
@@ -310,42 +243,19 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
     // (behind the last layer its own first blocks are requested once more; drain_u retires them)
     un = reinterpret_cast<const f32x4*>(a.L[L + 1 < a.nlayer ? L + 1 : L].u) + ulane;
 
-    RSTAMP(0);
     f32x4 acc[16];
 #pragma unroll
     for (int p = 0; p < 16; ++p) acc[p] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // one K step: window of channel 4 ks + kk -> B^T d B in registers -> 16 MFMAs.  (fp32 MFMAs and VALU
-    // instructions of the waves of a SIMD do NOT overlap on gfx950 -- tools/valu_lab.hip: 16 MFMAs + 32
-    // adds take exactly the sum of both -- so the order inside a step matters little; a burst form with
-    // the next window prefetched measured slower: 24.4 vs 21.5 us per layer, it costs registers.)
-    // the 4 x 4 window of channel 4 ks + kk at this lane's tile
+    // the 4 x 4 window of channel 4 ks + kk at this lane's tile (the compiler merges the reads into ds_read2_b64)
     auto win_load = [&](int ks, float (&d)[4][4]) {
-      const float* sp = src + rb + (RABL(16) ? 0 : ks * (4 * WR_CS));
-#if WR_RDFORM == 1
-      // eight ds_read_b64 (2 x 32 lanes, 256 B/clk) instead of the four ds_read2_b64 the compiler merges them into
-      // (4 x 16 lanes per access, 128 B/clk -- MI355X_MICROARCH.md section LDS)
-      const unsigned ad = (unsigned)(uintptr_t)sp;      // LDS byte address = low 32 bits of the generic pointer
-      v2f p[8];
-#define WR_DSR(i, off) asm volatile("ds_read_b64 %0, %1 offset:" #off : "=v"(p[i]) : "v"(ad))
-      WR_DSR(0, 0); WR_DSR(1, 8); WR_DSR(2, 112); WR_DSR(3, 120); WR_DSR(4, 224); WR_DSR(5, 232); WR_DSR(6, 336); WR_DSR(7, 344);
-#undef WR_DSR
-      static_assert(WR_RS == 28, "the byte offsets above are rows of 28 floats");
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]), "+v"(p[4]), "+v"(p[5]), "+v"(p[6]), "+v"(p[7]));
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { d[r][0] = p[2 * r].x; d[r][1] = p[2 * r].y; d[r][2] = p[2 * r + 1].x; d[r][3] = p[2 * r + 1].y; }
-#else
+      const float* sp = src + rb + ks * (4 * WR_CS);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        if (RABL(512) && r >= 2) {             // lab 512: half the window bytes
-          d[r][0] = d[r - 2][1]; d[r][1] = d[r - 2][0]; d[r][2] = d[r - 2][3]; d[r][3] = d[r - 2][2];
-          continue;
-        }
         const float2 p0 = *reinterpret_cast<const float2*>(sp + r * WR_RS);
         const float2 p1 = *reinterpret_cast<const float2*>(sp + r * WR_RS + 2);
         d[r][0] = p0.x; d[r][1] = p0.y; d[r][2] = p1.x; d[r][3] = p1.y;
       }
-#endif
     };
     // one K step: window -> B^T d B in registers -> 16 MFMAs.  (fp32 MFMAs and VALU
     // instructions of the waves of a SIMD do NOT overlap on gfx950 -- tools/valu_lab.hip: 16 MFMAs + 32
@@ -354,67 +264,20 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
     auto kcompute = [&](const float (&d)[4][4], f32x4 (&u)[4]) {
       wait_u(u);
       f32x4 bq[4];
-      if (RABL(64)) {                          // lab: no input transform (wrong results; what the 32 adds cost)
+      float qa[4], qb[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) bq[r] = f32x4{d[r][0], d[r][1], d[r][2], d[r][3]};
-      } else {
-        float qa[4], qb[4];
+      for (int c = 0; c < 4; ++c) { qa[c] = d[0][c] - d[2][c]; qb[c] = d[1][c] + d[2][c]; }
+      bq[0] = f32x4{qa[0] - qa[2], qa[1] + qa[2], qa[2] - qa[1], qa[1] - qa[3]};
+      bq[1] = f32x4{qb[0] - qb[2], qb[1] + qb[2], qb[2] - qb[1], qb[1] - qb[3]};
 #pragma unroll
-        for (int c = 0; c < 4; ++c) { qa[c] = d[0][c] - d[2][c]; qb[c] = d[1][c] + d[2][c]; }
-        bq[0] = f32x4{qa[0] - qa[2], qa[1] + qa[2], qa[2] - qa[1], qa[1] - qa[3]};
-        bq[1] = f32x4{qb[0] - qb[2], qb[1] + qb[2], qb[2] - qb[1], qb[1] - qb[3]};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { qa[c] = d[2][c] - d[1][c]; qb[c] = d[1][c] - d[3][c]; }
-        bq[2] = f32x4{qa[0] - qa[2], qa[1] + qa[2], qa[2] - qa[1], qa[1] - qa[3]};
-        bq[3] = f32x4{qb[0] - qb[2], qb[1] + qb[2], qb[2] - qb[1], qb[1] - qb[3]};
-      }
-      if (RABL(2)) { acc[0] += bq[0] + bq[1] + bq[2] + bq[3] + u[0] + u[1] + u[2] + u[3]; return; }
+      for (int c = 0; c < 4; ++c) { qa[c] = d[2][c] - d[1][c]; qb[c] = d[1][c] - d[3][c]; }
+      bq[2] = f32x4{qa[0] - qa[2], qa[1] + qa[2], qa[2] - qa[1], qa[1] - qa[3]};
+      bq[3] = f32x4{qb[0] - qb[2], qb[1] + qb[2], qb[2] - qb[1], qb[1] - qb[3]};
 #pragma unroll
       for (int p = 0; p < 16; ++p)
         acc[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(u[p >> 2][p & 3], bq[p >> 2][p & 3], acc[p], 0, 0, 0);
     };
-#if WR_PK
-    auto kstep = [&](int ks, const f32x4 (&u)[4]) {
-      const float* sp = src + rb + (RABL(16) ? 0 : ks * (4 * WR_CS));
-      // B^T d B on packed fp32 (v_pk_add_f32: the two columns of an 8-byte LDS read are one operand): 8 packed
-      // row combinations, then per combination {q0 - q2, q1 - q3} (packed) and {q1 + q2, q2 - q1} -- ONE
-      // v_pk_add_f32 with op_sel / neg_hi picking the halves (the compiler needs three instructions for that
-      // shuffle, hence the asm).  16 VALU instructions per window instead of 32, the same fp32 sums bit for bit
-      // (q2 - q1 is evaluated as -q1 + q2).  The s_nop closes the VALU-write -> MFMA-read distance (2 wait
-      // states on gfx950) that the compiler cannot see through the asm.
-      v2f lo[4], hi[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        lo[r] = *reinterpret_cast<const v2f*>(sp + r * WR_RS);
-        hi[r] = *reinterpret_cast<const v2f*>(sp + r * WR_RS + 2);
-      }
-      f32x4 bq[4];
-      auto cols = [&](const v2f ql0, const v2f qh0, const v2f ql1, const v2f qh1, f32x4& b0, f32x4& b1) {
-        const v2f e0 = ql0 - qh0, e1 = ql1 - qh1;
-        v2f f0, f1;
-        asm("v_pk_add_f32 %0, %2, %3 op_sel:[1,0] op_sel_hi:[1,0] neg_hi:[1,0]\n\t"
-            "v_pk_add_f32 %1, %4, %5 op_sel:[1,0] op_sel_hi:[1,0] neg_hi:[1,0]\n\t"
-            "s_nop 1"
-            : "=&v"(f0), "=&v"(f1) : "v"(ql0), "v"(qh0), "v"(ql1), "v"(qh1));
-        b0 = f32x4{e0.x, f0.x, f0.y, e0.y};
-        b1 = f32x4{e1.x, f1.x, f1.y, e1.y};
-      };
-      cols(lo[0] - lo[2], hi[0] - hi[2], lo[1] + lo[2], hi[1] + hi[2], bq[0], bq[1]);
-      cols(lo[2] - lo[1], hi[2] - hi[1], lo[1] - lo[3], hi[1] - hi[3], bq[2], bq[3]);
-      if (RABL(2)) { acc[0] += bq[0] + bq[1] + bq[2] + bq[3] + u[0] + u[1] + u[2] + u[3]; return; }
-#pragma unroll
-      for (int p = 0; p < 16; ++p)
-        acc[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(u[p >> 2][p & 3], bq[p >> 2][p & 3], acc[p], 0, 0, 0);
-    };
-#else
-    auto kstep = [&](int ks, f32x4 (&u)[4]) {
-      float d[4][4];
-      win_load(ks, d);
-      kcompute(d, u);
-    };
-#endif
 
-#if WR_PREF
     {   // window of K step ks + 1 in flight under the MFMAs of K step ks (the LDS latency of a K step is otherwise
         // exposed at its head: a wave that is alone on its SIMD -- the interior waves during the hand-over -- idles there)
       float dA[4][4], dB[4][4];
@@ -433,37 +296,6 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-#elif WR_USETS == 3
-    {   // three weight blocks in flight (two K steps of distance): a wave that runs alone on its SIMD -- the
-        // interior waves during the hand-over -- otherwise waits for L2 every K step
-      int ks = 0;
-      for (; ks + 3 <= nks; ks += 3) {
-        kstep(ks, u0);
-        __builtin_amdgcn_sched_barrier(0);
-        load_u(ub, ks + 3, nks, u0);
-        kstep(ks + 1, u1);
-        __builtin_amdgcn_sched_barrier(0);
-        load_u(ub, ks + 4, nks, u1);
-        kstep(ks + 2, u2);
-        __builtin_amdgcn_sched_barrier(0);
-        load_u(ub, ks + 5, nks, u2);
-      }
-      if (ks < nks) kstep(ks, u0);
-      if (ks + 1 < nks) kstep(ks + 1, u1);
-    }
-#else
-    for (int ks = 0; ks < nks; ks += 2) {
-      kstep(ks, u0);
-      __builtin_amdgcn_sched_barrier(0);
-      load_u(ub, ks + 2, nks, u0);
-      __builtin_amdgcn_sched_barrier(0);        // (straight-line code now: without it the scheduler sinks the loads into the next K step)
-      kstep(ks + 1, u1);
-      __builtin_amdgcn_sched_barrier(0);
-      load_u(ub, ks + 3, nks, u1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#endif
-    RSTAMP(1);
     // ---- inverse transform A^T m A, bias / activation / residual -----------------------------
     const bool last = L + 1 == a.nlayer && !fold;   // with the transposed-conv tail the last layer hands over like any other
     const float slope = act_slope(lay.act);
@@ -471,14 +303,13 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
 #pragma unroll
     for (int r = 0; r < 4; ++r) bz[r] = s_act[WR_BIAS_OFF + L * WR_NC + oc_base + r];
     float v[4][2][2];                         // [channel r][row i][column j]
-    // ACTK (round 6): 0 = no activation (conv2 of a residual block: nothing to do), 2 = the generic form, 2 VALU per
-    // output: max(x, slope * x) = x >= 0 ? x : x * slope for every slope in [0, 1] (ReLU 0, LeakyReLU 0.2, none 1) -- the
-    // round-4 form max(x, 0) + slope * min(x, 0) was 3; on this SIMD VALU time adds to the matrix time.  (Further
-    // instantiations -- ReLU as one v_max, nothing at all for act none -- spill: 165 of 168 registers are taken, and this
-    // kernel must not spill: csrc/build.sh.)
-    auto epilogue = [&](auto has_res, auto act_k) {
+    // The activation is the generic form, 2 VALU per output (round 6): max(x, slope * x) = x >= 0 ? x : x * slope for
+    // every slope in [0, 1] (ReLU 0, LeakyReLU 0.2, none 1), without a conditional move (v_cndmask_b32: ~23 cycles per
+    // wave instruction on gfx950, tools/valu_lab.hip) -- the round-4 form max(x, 0) + slope * min(x, 0) was 3; on this
+    // SIMD VALU time adds to the matrix time.  (Instantiations per activation -- ReLU as one v_max, nothing at all for
+    // act none -- spill: 165 of 168 registers are taken, and this kernel must not spill: csrc/build.sh.)
+    auto epilogue = [&](auto has_res) {
       constexpr bool RES = decltype(has_res)::value;
-      constexpr int ACTK = decltype(act_k)::value;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float sr[2][4];
@@ -491,12 +322,8 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
         for (int i = 0; i < 2; ++i) {
           float v0 = ((sr[i][0] + sr[i][1]) + sr[i][2]) + bz[r];
           float v1 = ((sr[i][1] - sr[i][2]) - sr[i][3]) + bz[r];
-          // x >= 0 ? x : x * slope without a conditional move (v_cndmask_b32: ~23 cycles per wave instruction
-          // on gfx950, tools/valu_lab.hip): max(x, 0) + slope * min(x, 0) -- same value for every finite x
-          if constexpr (ACTK == 2) {
-            v0 = __builtin_fmaxf(v0, slope * v0);
-            v1 = __builtin_fmaxf(v1, slope * v1);
-          }
+          v0 = __builtin_fmaxf(v0, slope * v0);
+          v1 = __builtin_fmaxf(v1, slope * v1);
           if constexpr (RES) {                // the residual input: what the destination buffer still holds
             v0 += dst[wb + r * WR_CS + i * WR_RS];
             v1 += dst[wb + r * WR_CS + i * WR_RS + 1];
@@ -505,22 +332,13 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
         }
       }
     };
-    {
-      using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-      (void)sizeof(I1);
-      (void)sizeof(I0);
-      if (lay.res) epilogue(std::true_type{}, I2{}); else epilogue(std::false_type{}, I2{});      // layer-uniform
-    }
-    // the next layer's first weights travel under the hand-over
+    if (lay.res) epilogue(std::true_type{}); else epilogue(std::false_type{});      // layer-uniform
 #if !WR_UASM
-    {   // (branch-free for the same reason as load_u: behind the last layer the last layer's blocks are requested again)
+    {   // the next layer's first weights travel under the hand-over (WR_UASM: the K loop has requested them already)
       const int Ln = L + 1 < a.nlayer ? L + 1 : L;
       const f32x4* un2 = reinterpret_cast<const f32x4*>(a.L[Ln].u) + ulane;
       load_u(un2, 0, a.L[Ln].nks, u0);
       load_u(un2, 1, a.L[Ln].nks, u1);
-#if WR_USETS == 3
-      load_u(un2, 2, a.L[Ln].nks, u2);
-#endif
     }
 #endif
     if (live) {
@@ -546,7 +364,10 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
         const unsigned tag = a.base + (unsigned)(L + 1);
         const unsigned pb = ((unsigned)((L & 1) * nwg + wg) * WR_SLOTS * (WR_NC / 2) + (unsigned)(oc_base >> 1)) * 16u;
         auto pub = [&](int slot, int i, int j) {
-          if (RABL(8)) return;
+          // (names the argument block so that [&] captures it: with no closure holding its address the compiler reads the
+          // arguments in another order and commutes some thirty integer operands of the loader and of the ring geometry --
+          // same results, but not the instruction stream every number in EXPERIMENTS.md was measured on)
+          (void)a;
           const u32x4 d0 = {__builtin_bit_cast(unsigned, v[0][i][j]), tag, __builtin_bit_cast(unsigned, v[1][i][j]), tag};
           const u32x4 d1 = {__builtin_bit_cast(unsigned, v[2][i][j]), tag, __builtin_bit_cast(unsigned, v[3][i][j]), tag};
           const unsigned o = pb + (unsigned)slot * (WR_NC / 2 * 16u);
@@ -559,9 +380,7 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
         if (e_rgt) { pub(2 * WR_BW + WR_BH + 2 * ty, 0, 1); pub(2 * WR_BW + WR_BH + 2 * ty + 1, 1, 1); }
       }
     }
-    RSTAMP(2);
     if (last) { drain_u(u0, u1); break; }
-    if (RABL(32)) { __syncthreads(); continue; }
 
     // ---- hand-over -------------------------------------------------------------------------------
     // Every wave: the workgroup barrier (all of dst's own pixels are written, all reads of src are
@@ -570,9 +389,7 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
     // agent-scope load per item, re-issued until both tags of the item carry this layer's value --
     // store it into dst and meet at an LDS arrival counter, while the interior waves already keep the
     // matrix pipe busy.
-    RSTAMP(3);
     __syncthreads();
-    RSTAMP(4);
     if (interior) continue;
     {
       constexpr int NRING = 2 * (WR_BW + 2) + 2 * WR_BH;           // 68
@@ -596,7 +413,7 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
         else { ry = pi - 2 * (WR_BW + 2) - WR_BH + 1; rx = WR_BW + 1; }
         const int gy = Y0 - 1 + ry, gx = X0 - 1 + rx;
         off[k] = 0u; ho[k] = 0;
-        if (item < ITEMS && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w && !RABL(1)) {
+        if (item < ITEMS && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w) {
           const int sby = gy / WR_BH, sbx = gx / WR_BW;
           const int ly = gy - sby * WR_BH, lx = gx - sbx * WR_BW;
           // which of the owner's published rows / columns holds the pixel
@@ -642,7 +459,6 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
       }
       if (fault && pend != 0u) __hip_atomic_fetch_add(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    RSTAMP(6);
     // arrival counter of the eight boundary waves (monotonic over the launch): a wave's LDS stores are
     // ordered before its increment, so whoever reads the full count sees every ring pixel
     if (l == 0) __hip_atomic_fetch_add(s_cnt, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -651,7 +467,6 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
       while ((int)(__hip_atomic_load(s_cnt, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) - want) < 0)
         __builtin_amdgcn_s_sleep(1);
     }
-    RSTAMP(7);
   }
   if (!fold) return;
   drain_u(u0, u1);                            // (the requests behind the last layer's epilogue)
@@ -684,24 +499,33 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
     constexpr size_t CSTEP = (size_t)4 * 3 * 64;
     constexpr int CT_NKS = WR_NC / 4;
     // (weights: the same hand-written request / wait pairs as the layers' -- see load_u; three 16-byte loads per block)
-    auto load_w = [&](int ks, f32x4 (&w)[3]) {
 #if WR_UASM
+    auto load_w = [&](int ks, f32x4 (&w)[3]) {
       const f32x4* pw = cu + (size_t)(ks < CT_NKS ? ks : CT_NKS - 1) * CSTEP;
       asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(w[0]) : "v"(pw));
       asm volatile("global_load_dwordx4 %0, %1, off offset:1024" : "=v"(w[1]) : "v"(pw));
       asm volatile("global_load_dwordx4 %0, %1, off offset:2048" : "=v"(w[2]) : "v"(pw));
-#else
-      if (ks >= CT_NKS) return;
-      const f32x4* pw = cu + (size_t)ks * CSTEP;
-      w[0] = pw[0]; w[1] = pw[64]; w[2] = pw[128];
-#endif
     };
-    auto cstep = [&](int ks, f32x4 (&w)[3]) {
-#if WR_UASM
+    auto wait_w = [&](f32x4 (&w)[3]) {
       asm volatile("s_waitcnt vmcnt(5)" : "+v"(w[0]));
       asm volatile("s_waitcnt vmcnt(4)" : "+v"(w[1]));
       asm volatile("s_waitcnt vmcnt(3)" : "+v"(w[2]));
+    };
+    // (the last two requests are never used: keep their registers until they have landed -- see drain_u)
+    auto drain_w = [&](f32x4 (&wa)[3], f32x4 (&wb_)[3]) {
+      asm volatile("s_waitcnt vmcnt(0)" : "+v"(wa[0]), "+v"(wa[1]), "+v"(wa[2]), "+v"(wb_[0]), "+v"(wb_[1]), "+v"(wb_[2]));
+    };
+#else
+    auto load_w = [&](int ks, f32x4 (&w)[3]) {
+      if (ks >= CT_NKS) return;
+      const f32x4* pw = cu + (size_t)ks * CSTEP;
+      w[0] = pw[0]; w[1] = pw[64]; w[2] = pw[128];
+    };
+    auto wait_w = [&](f32x4 (&)[3]) {};
+    auto drain_w = [&](f32x4 (&)[3], f32x4 (&)[3]) {};
 #endif
+    auto cstep = [&](int ks, f32x4 (&w)[3]) {
+      wait_w(w);
       const float* sp = src + cb + ks * (4 * WR_CS);
       float d[3][3];
 #pragma unroll
@@ -740,10 +564,7 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
       load_w(ks + 3, w1);
       __builtin_amdgcn_sched_barrier(0);
     }
-#if WR_UASM
-    // (the last two requests are never used: keep their registers until they have landed -- see drain_u)
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(w0[0]), "+v"(w0[1]), "+v"(w0[2]), "+v"(w1[0]), "+v"(w1[1]), "+v"(w1[2]));
-#endif
+    drain_w(w0, w1);
     if (live) {
       const float cslope = act_slope(a.ct_act);
       const size_t ohw = (size_t)4 * hw;
@@ -859,9 +680,6 @@ int conv3x3_wino_resident_launch(const tg_wino_layer* layers, int n_layers, int 
     TG_REQUIRE(n_layers + 1 < 32 && ((uintptr_t)ct->y % 16) == 0, TG_E_ARG, "conv3x3_wino_resident: transposed-conv tail: layers / alignment");
     a.ct_u = ct->u_packed; a.ct_bias = ct->bias; a.ct_y = ct->y; a.ct_act = ct->act;
   }
-#if TG_WRES_LAB
-  { static const int abl = [] { const char* e = getenv("TG_WRES_ABL"); return e ? atoi(e) : 0; }(); a.abl = abl; }
-#endif
   hipLaunchKernelGGL(conv3x3_wino_resident_kernel, dim3((unsigned)nb), dim3(WR_THREADS), WR_LDS_BYTES,
                      (hipStream_t)stream, a);
   return check_launch("conv3x3_wino_resident");
@@ -870,12 +688,6 @@ int conv3x3_wino_resident_launch(const tg_wino_layer* layers, int n_layers, int 
 }  // namespace tg
 
 using namespace tg;
-
-#if TG_WRES_LAB
-extern "C" int tg_lab_wres_stamps(long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wres_dbg), sizeof(long long) * 12 * 24 * 8) == hipSuccess ? 0 : -1;
-}
-#endif
 
 extern "C" int tg_conv3x3_wino_resident_supported(int n, int cout, int h, int w) {
   return conv3x3_wino_resident_ok(n, cout, h, w) ? 1 : 0;

@@ -438,12 +438,6 @@ __global__ __launch_bounds__(512) void convt3x3s2_oneshot_kernel(ConvTArgs a) {
 //     contraction sums added in its order: results are BIT-IDENTICAL to convt3x3s2_mfma_kernel<.,.,true>.
 // The counter pair {next item, finished waves} lives in a device-global slot the host rotates per launch; the last wave
 // to finish puts the slot back to zero.
-#ifndef ZS_ABL
-#define ZS_ABL 0     // lab builds (TG_LAB), timing only: 1 no B loads after an item's first chunk, 2 no contraction / stores, 4 no A reads after the first tap
-#endif
-#if !TG_LAB && ZS_ABL
-#error "tg_convt3x3s2_mfma.hip: ZS_ABL needs -DTG_LAB=1 (lab builds only; the ablated kernel computes wrong results)"
-#endif
 constexpr int ZS_WAVES = 12;
 constexpr int ZS_THREADS = ZS_WAVES * 64;
 constexpr int ZS_W_FLOATS = 9 * 64 * 64;                  // the packed weights, verbatim: [chunk 8][tap 9][half 2][oc 64][4]
@@ -527,22 +521,20 @@ __device__ __forceinline__ void zs_item(const ConvTArgs& a, const float* s_w, in
     const float* sw = sa + ch * (9 * CK * TOCB);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      if (ZS_ABL & 4) { if (ch == 0 && t == 0) lda(sw, TT[1], ab[1]); }
-      else if (t + 1 < NT) lda(sw, TT[t + 1], ab[(PAR + t + 1) & 1]);
+      if (t + 1 < NT) lda(sw, TT[t + 1], ab[(PAR + t + 1) & 1]);
       else if (!last) lda(sw + 9 * CK * TOCB, TT[0], ab[(PAR + t + 1) & 1]);      // the next chunk's first tap
       mm(TQ[t], ab[(PAR + t) & 1], b[TB[t]]);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
   // The K loop, fully unrolled over the (at most 8) chunks with compile-time register sets; the B operand is requested
-  // one chunk ahead (two chunks ahead -- three register sets -- measured +-0 and spilled: tools/abl_convtz.sh, round 6).
+  // one chunk ahead (two chunks ahead -- three register sets -- measured +-0 and spilled, round 6).
   load_b(0, bq[0]);
-  if ((ZS_ABL & 1)) load_b(1, bq[1]);
   lda(sa, TT[0], ab[0]);
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     if (c < a.nchunk) {
-      if (c + 1 < a.nchunk && !(ZS_ABL & 1)) load_b(c + 1, bq[(c + 1) % 2]);
+      if (c + 1 < a.nchunk) load_b(c + 1, bq[(c + 1) % 2]);
       fix_edge(bq[c % 2]);
       if ((c * NT) & 1) chunk(c, bq[c % 2], c + 1 >= a.nchunk, std::integral_constant<int, 1>{});
       else chunk(c, bq[c % 2], c + 1 >= a.nchunk, std::integral_constant<int, 0>{});
@@ -558,7 +550,7 @@ __device__ __forceinline__ void zs_item(const ConvTArgs& a, const float* s_w, in
   const int ohw = 4 * hw;
   // One contraction chain per (phase, channel half) -- the halves added in the tiled kernel's order, wn 0 + wn 1 -- with
   // the two chains of a phase interleaved (a chain's MFMAs depend on each other) and the operands of four MFMAs
-  // prepared ahead of them (VALU -> MFMA hazard distance).  Round-6 anatomy (tools/abl_convtz.sh): this epilogue cost
+  // prepared ahead of them (VALU -> MFMA hazard distance).  Round-6 anatomy (ablation builds, EXPERIMENTS.md): this epilogue cost
   // 29 us of the launch's 145 for 18 us of MFMA work in its first form (one chain at a time, 4 VALU per element,
   // sixteen divergent branches around the stores).
   const bool relu = slope == 0.f;                          // launch-uniform

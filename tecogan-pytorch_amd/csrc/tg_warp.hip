@@ -111,18 +111,8 @@ __device__ __forceinline__ float warp_coord_c(int i, int n, float flow, float st
 // zero flow and slower as soon as the flow varies inside a block; XCD-banded block order
 // +4 %; nontemporal stores +-0; nontemporal gathers +30 %.
 // All offsets are 32-bit against block-uniform buffer resources.
-#ifndef TG_WARP_ABL
-#define TG_WARP_ABL 0   // lab only (tools/warp_lab.py): 1 no stores, 2 one tap row instead of two, 4 no flow loads
-#endif
-#if !TG_LAB && TG_WARP_ABL
-#error "tg_warp.hip: TG_WARP_ABL needs -DTG_LAB=1 (lab builds only; the ablated kernels compute wrong results)"
-#endif
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-#ifndef TG_WARP_PF
-#define TG_WARP_PF 0    // 1: speculative touch of the previous frame under the flow loads for one-frame launches (see PF below);
-                        // measured +-0 on MI355X (6.3 - 7.8 us per launch with and without, round 5): off
-#endif
-template <int S, int C, int R, int RPT, int PF = 0>
+template <int S, int C, int R, int RPT>
 __global__ __launch_bounds__(128 * (R / RPT)) void flowup_warp_s2d_kernel(FusedArgs a) {
   constexpr int SEG = 256;
   constexpr int NT = 128 * (R / RPT);      // threads: 128 pixel pairs x R/RPT row groups
@@ -165,23 +155,6 @@ __global__ __launch_bounds__(128 * (R / RPT)) void flowup_warp_s2d_kernel(FusedA
   const bool bicubic = a.up_mode == TG_UP_BICUBIC;
   const bool vec_out = (a.w & 3) == 0 && a.out_aligned;   // dwordx4 stores need 16-byte rows
 
-  // PF (round 5, one-frame launches: every block is resident at once and the kernel's duration is ONE block's chain
-  // of dependent round trips -- flow patch, gathers, stores).  The gathers cannot start before the flow is known, but
-  // the flow only moves a sample by a few pixels: the 16 bytes at the thread's OWN position are requested at once, so
-  // the previous frame's lines travel towards this CU's L2 / L1 while the flow patch is in flight and the real gathers
-  // find them there.  The values are never used (the asm at the end only keeps the loads alive).
-  // (requested BEHIND the flow loads: vmcnt retires in order, so the flow patch must not queue behind them)
-  f32x4 pf[C];
-  auto issue_pf = [&]() {
-    if constexpr (PF != 0) {
-      const int ptp = t & 127, pr = (t >> 7) * RPT;
-      const unsigned po = ((unsigned)(hy0 + pr) * (unsigned)WW + (unsigned)(x0 + 2 * ptp)) * 4u;
-#pragma unroll
-      for (int ch = 0; ch < C; ++ch)
-        pf[ch] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ri, (int)po, (int)(ch * hrhw * 4u), 0));
-    }
-  };
-
   // ---- 1. LR-flow terms
   if (bicubic) {
     {   // every load of the patch is issued before the first LDS store: a loop of load -> store
@@ -194,9 +167,8 @@ __global__ __launch_bounds__(128 * (R / RPT)) void flowup_warp_s2d_kernel(FusedA
         const int k = it % NV, p = (it / NV) & 3, ch = it / (4 * NV);
         const unsigned cc = (unsigned)reflect_src(clampi(jbase + k, 0, a.w - 1), a.fw);
         const unsigned o = ((unsigned)reflect_src(clampi(oy - 1 + p, 0, a.h - 1), a.fh) * a.fw + cc) * 4u;
-        fv[i] = (it < 2 * 4 * NV && !(TG_WARP_ABL & 4)) ? bload(rf, o, (ch & 1) * fhw * 4u) : 0.01f;
+        fv[i] = it < 2 * 4 * NV ? bload(rf, o, (ch & 1) * fhw * 4u) : 0.01f;
       }
-      issue_pf();
 #pragma unroll
       for (int i = 0; i < FPT; ++i) {
         const int it = t + i * NT;
@@ -237,7 +209,6 @@ __global__ __launch_bounds__(128 * (R / RPT)) void flowup_warp_s2d_kernel(FusedA
         b1[i] = make_float2(bload(rf, o1, 0), bload(rf, o1, fhw * 4u));
       }
     }
-    issue_pf();
 #pragma unroll
     for (int i = 0; i < BPT; ++i) {
       const int it = t + i * NT;
@@ -336,7 +307,7 @@ __global__ __launch_bounds__(128 * (R / RPT)) void flowup_warp_s2d_kernel(FusedA
       for (int ch = 0; ch < C; ++ch) {
         const unsigned pl = ch * hrhw * 4u;
         const f32x4 t4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ri, (int)o0[0], (int)pl, 0));
-        const f32x4 b4 = (TG_WARP_ABL & 2) ? t4 : __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ri, (int)o1[0], (int)pl, 0));
+        const f32x4 b4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ri, (int)o1[0], (int)pl, 0));
         va[ch] = ((t4[0] * w00[0] + t4[1] * w01[0]) + b4[0] * w10[0]) + b4[1] * w11[0];
         const float t0 = pick(t4[0], t4[1], t4[2]);
         const float t1 = pick(t4[1], t4[2], t4[3]);
@@ -363,10 +334,6 @@ __global__ __launch_bounds__(128 * (R / RPT)) void flowup_warp_s2d_kernel(FusedA
     }
   }
   __syncthreads();
-  if constexpr (PF != 0) {
-#pragma unroll
-    for (int ch = 0; ch < C; ++ch) asm volatile("" ::"v"(pf[ch]));
-  }
 
   // ---- 3. space_to_depth: staged as s_out[(r, sx, ch)][ox]
   if (vec_out) {
@@ -380,7 +347,6 @@ __global__ __launch_bounds__(128 * (R / RPT)) void flowup_warp_s2d_kernel(FusedA
         const int r = pl / (S * C), rem = pl - r * (S * C);   // rem = sx * C + ch
         const f32x4 v = *reinterpret_cast<const f32x4*>(&s_out[pl * PS + 4 * q]);
         const unsigned o = ((unsigned)((sy0 + r) * S * C + rem) * lrhw + (unsigned)oy * a.w + ox) * 4u;
-        if ((TG_WARP_ABL & 1) && v[0] != 12345.678f) continue;
         __builtin_amdgcn_raw_buffer_store_b128(
             __builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(int)))) int, v), rout, (int)o, 0, 0);
       }
@@ -683,7 +649,6 @@ extern "C" int tg_flowup_warp_s2d_fwd(const float* lr_flow, int fh, int fw, cons
   const int rpt = rpt_env ? rpt_env : (tiles <= 2048 ? 1 : 2);
   if (scale == 4) {
     if (rpt == 2) hipLaunchKernelGGL((flowup_warp_s2d_kernel<4, 3, 4, 2>), dim3(tiles), dim3(256), 0, s, a);
-    else if (TG_WARP_PF) hipLaunchKernelGGL((flowup_warp_s2d_kernel<4, 3, 4, 1, 1>), dim3(tiles), dim3(512), 0, s, a);
     else hipLaunchKernelGGL((flowup_warp_s2d_kernel<4, 3, 4, 1>), dim3(tiles), dim3(512), 0, s, a);
   } else {
     hipLaunchKernelGGL((flowup_warp_s2d_kernel<2, 3, 2, 1>), dim3(tiles), dim3(256), 0, s, a);

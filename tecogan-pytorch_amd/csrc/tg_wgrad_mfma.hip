@@ -45,8 +45,6 @@ struct WgradArgs {
   int ca, cb, cb_total, cb_off;   // G is written at columns [cb_off, cb_off+cb) of a cb_total-wide matrix
   int n, h, w;
   int tiles_x, tiles_y, ntiles, nsplit, nab, nbb;
-  // (ablation builds, -DWG_ABL=bits: 1 no global loads after the first tile, 2 no LDS stores after the
-  //  first, 4 no MFMAs, 8 no LDS operand reads)
   // phase-restricted taps (see tg_conv3x3_mfma.hip): the b channels come in 4 sub-pixel phases
   // of cphase channels; phase coordinate v along an axis uses tap set rowsets[v].  Taps outside
   // the set are not computed (their gradient entries are written as 0; the embedding drops them).
@@ -309,55 +307,37 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a) {
     store_tile(0);
   }
   __syncthreads();
-#ifndef WG_ABL
-#define WG_ABL 0      // compile-time ablation bits (tools/build_lab_libs.sh builds one library per value)
-#endif
-#define WGABL(bit) ((WG_ABL & (bit)) != 0)
-#if !TG_LAB && WG_ABL
-#error "tg_wgrad_mfma.hip: WG_ABL needs -DTG_LAB=1 (lab builds only; the ablated kernels compute wrong results)"
-#endif
   constexpr int NBV = G::S2 ? 9 : 6;         // shifted Q values one (row, group of 4 pixels) needs per tap row
   constexpr int QS = G::S2 ? 2 : 1;          // Q step per P pixel
   for (; tile < a.ntiles; tile += a.nsplit, ++it) {
     const int buf = it & 1;
     const bool more = tile + a.nsplit < a.ntiles;
-    if (more && !WGABL(1)) load_tile(tile + a.nsplit);
+    if (more) load_tile(tile + a.nsplit);
     const float* pa = sA + buf * G::A_FLOATS + a_rd;
     const float* pb = sB + buf * G::B_FLOATS + b_rd;
 #pragma unroll
     for (int r = 0; r < G::R; ++r) {
 #pragma unroll
       for (int g = 0; g < G::TW / 8; g += KS) {     // (K split: this wave's groups are kid, kid + KS, ...)
-        f32x4 av = {1.f, 2.f, 3.f, 4.f};
+        const f32x4 av = *reinterpret_cast<const f32x4*>(pa + r * G::TW + 8 * g);
         float bv[3][NBV];
-        if (!WGABL(8)) {
-          av = *reinterpret_cast<const f32x4*>(pa + r * G::TW + 8 * g);
 #pragma unroll
-          for (int ky = 0; ky < 3; ++ky)
+        for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-            for (int c6 = 0; c6 < NBV; ++c6) bv[ky][c6] = pb[(QS * r + ky) * G::RSB + QS * 8 * g + c6];
-        } else {
-#pragma unroll
-          for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-            for (int c6 = 0; c6 < NBV; ++c6) bv[ky][c6] = (float)(ky + c6 + r + g);
-        }
+          for (int c6 = 0; c6 < NBV; ++c6) bv[ky][c6] = pb[(QS * r + ky) * G::RSB + QS * 8 * g + c6];
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
           for (int kx = 0; kx < 3; ++kx)
             if (wtap_on(RY, ky) && wtap_on(RX, kx)) {
 #pragma unroll
-              for (int kk = 0; kk < 4; ++kk) {
-                if (WGABL(4)) acc[ky * 3 + kx][kk] += av[kk] * bv[ky][QS * kk + kx];
-                else
+              for (int kk = 0; kk < 4; ++kk)
                 acc[ky * 3 + kx] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[kk], bv[ky][QS * kk + kx],
                                                                         acc[ky * 3 + kx], 0, 0, 0);
-              }
             }
       }
     }
-    if (more && !WGABL(2)) store_tile(buf ^ 1);
+    if (more) store_tile(buf ^ 1);
     __syncthreads();
   }
 

@@ -156,7 +156,7 @@ def test_soak_row_chain_training_frames_under_memory_pressure(ops):
 def test_resident_launch_cross_check_with_compiler_visible_weight_loads(tmp_path):
     """the shipped resident kernel requests its weights in inline asm the compiler cannot see (WR_UASM = 1,
     hand-written `vmcnt` waits).  Cross-check on every GPU run: the SAME source built with compiler-visible loads
-    (`-DWR_UASM=0 -DWR_BRANCHY_U=1`, the round-4 form; a lab build: -DTG_LAB=1) must pass the bit-identity test of the
+    (`-DWR_UASM=0`, the round-4 form: plain loads behind a branch; a lab build: -DTG_LAB=1) must pass the bit-identity test of the
     resident launch against the per-layer launches -- which the product passes too, so the two forms are bit-identical
     to each other.  Needs hipcc and the product's objects next to the sources (they travel with the snapshot)."""
     import glob
@@ -173,7 +173,7 @@ def test_resident_launch_cross_check_with_compiler_visible_weight_loads(tmp_path
     file_flags = [ln.split(':', 1)[1].split() for ln in open(src) if ln.startswith('// TG_FILE_FLAGS:')][0]
     obj, lib = str(tmp_path / 'wres_visible.o'), str(tmp_path / 'libtecogan_wres_visible.so')
     base = [hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-fast-math', '-ffp-contract=on']
-    r = subprocess.run(base + file_flags + ['-DTG_LAB=1', '-DWR_UASM=0', '-DWR_BRANCHY_U=1', '-c', src, '-o', obj],
+    r = subprocess.run(base + file_flags + ['-DTG_LAB=1', '-DWR_UASM=0', '-c', src, '-o', obj],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     r = subprocess.run([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', lib] + objs + [obj, '-ldl'],

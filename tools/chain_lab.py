@@ -1,5 +1,6 @@
 """Where does a layer of the chained training body spend its time?  Lab library only
-(TECOGAN_HIP_LIB=tools/_lab_libs/libtecogan_lab.so, built with -DTG_LAB=1): workgroup 37 stamps
+(TG_LAB_BUILD=1 OUT=tools/_lab_libs/lab bash tecogan-pytorch_amd/csrc/build.sh, then
+TECOGAN_HIP_LIB=tools/_lab_libs/lab/libtecogan_lab.so): workgroup 37 stamps
 s_memtime (100 MHz) at 7 points of every layer: 0 top (weights requested) 1 flags seen 2 patch in LDS
 3 MFMAs done 4 stores issued 5 stores acknowledged 6 barrier passed (flag store follows)."""
 import os, sys, ctypes, torch

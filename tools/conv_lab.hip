@@ -7,7 +7,7 @@
 namespace tg { void set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fputc('\n', stderr);} }
 using namespace tg;
 
-template <int WM, int WN, int NT, int ABL, int OPT = 0, int STG = 12>
+template <int WM, int WN, int NT, int ABL>
 static float run(const char* name, Conv3x3Args a, int n, int reps, double gflop) {
   a.vec_ok = (a.w % 4 == 0);
   a.ksplit = 1;
@@ -17,10 +17,10 @@ static float run(const char* name, Conv3x3Args a, int n, int reps, double gflop)
   unsigned blocks = a.tiles_x * a.tiles_y * a.nocg * n;
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   for (int i = 0; i < 3; ++i)
-    hipLaunchKernelGGL((conv3x3_mfma_kernel<WM, WN, NT, false, ABL, OPT, STG>), dim3(blocks), dim3(WM * WN * 64), lds, 0, a);
+    hipLaunchKernelGGL((conv3x3_mfma_kernel<WM, WN, NT, false, ABL>), dim3(blocks), dim3(WM * WN * 64), lds, 0, a);
   hipEventRecord(e0, 0);
   for (int i = 0; i < reps; ++i)
-    hipLaunchKernelGGL((conv3x3_mfma_kernel<WM, WN, NT, false, ABL, OPT, STG>), dim3(blocks), dim3(WM * WN * 64), lds, 0, a);
+    hipLaunchKernelGGL((conv3x3_mfma_kernel<WM, WN, NT, false, ABL>), dim3(blocks), dim3(WM * WN * 64), lds, 0, a);
   hipEventRecord(e1, 0); hipEventSynchronize(e1);
   float ms; hipEventElapsedTime(&ms, e0, e1);
   float us = 1e3f * ms / reps;
@@ -54,22 +54,21 @@ int main(int argc, char** argv) {
   {
     int nb = 0;
     size_t lds = 2 * (size_t)((2 + 2) * 2 * RS * 4 + 9 * CK * 64) * sizeof(float);
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)conv3x3_mfma_kernel<2, 2, 1, false, 0, 3>, 256, lds);
-    hipFuncAttributes fa; hipFuncGetAttributes(&fa, (const void*)conv3x3_mfma_kernel<2, 2, 1, false, 0, 3>);
-    printf("occupancy API: %d blocks/CU for <2,2,1> OPT3 (dyn LDS %zu B, numRegs %d, static LDS %zu)\n", nb, lds, fa.numRegs, (size_t)fa.sharedSizeBytes);
+    hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)conv3x3_mfma_kernel<2, 2, 1, false, 0>, 256, lds);
+    hipFuncAttributes fa; hipFuncGetAttributes(&fa, (const void*)conv3x3_mfma_kernel<2, 2, 1, false, 0>);
+    printf("occupancy API: %d blocks/CU for <2,2,1> (dyn LDS %zu B, numRegs %d, static LDS %zu)\n", nb, lds, fa.numRegs, (size_t)fa.sharedSizeBytes);
     for (size_t l = 16384; l <= 65536; l += 8192) {
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)conv3x3_mfma_kernel<2, 2, 1, false, 0, 3>, 256, l);
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)conv3x3_mfma_kernel<2, 2, 1, false, 0>, 256, l);
       printf("   dyn LDS %6zu -> %d blocks/CU\n", l, nb);
     }
   }
   const int R = 50;
-  run<2, 2, 1, 0>("<2,2,1> base", a, n, R, gflop);
-  auto anatomy = [&](auto tag, const char* name) {
-    constexpr int OPTV = decltype(tag)::value;
+  run<2, 2, 1, 0>("<2,2,1>", a, n, R, gflop);
+  {   // anatomy of a workgroup (ABL 16: clock stamps)
     long long* dbg; unsigned nb = 670;
     hipMalloc(&dbg, nb * 8 * sizeof(long long)); hipMemset(dbg, 0, nb * 8 * sizeof(long long));
     Conv3x3Args ad = a; ad.dbg = dbg;
-    run<2, 2, 1, 16, OPTV>(name, ad, n, 5, gflop);
+    run<2, 2, 1, 16>("<2,2,1> instrumented", ad, n, 5, gflop);
     std::vector<long long> h(nb * 8);
     hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost);
     double pro = 0, iss = 0, mf = 0, sy = 0, life = 0;
@@ -89,55 +88,30 @@ int main(int argc, char** argv) {
       if (cnt) printf("   XCD %d: %3d WGs  span %6lld  avg lifetime %6.0f  last start +%lld  first end +%lld\n", x, cnt, hi - lo, lf / cnt, last_start - lo, first_end - lo);
     }
     hipFree(dbg);
-  };
-  run<3, 2, 1, 0, 3>("<3,2,1> OPT3 (6 waves)", a, n, R, gflop);
-  run<2, 2, 1, 0, 3>("<2,2,1> OPT3", a, n, R, gflop);
-  run<3, 2, 1, 0, 3>("<3,2,1> OPT3 (6 waves)", a, n, R, gflop);
-  run<2, 2, 1, 0, 3>("<2,2,1> OPT3", a, n, R, gflop);
-  run<3, 2, 1, 0, 3>("<3,2,1> OPT3 (6 waves)", a, n, R, gflop);
-  run<5, 2, 1, 0, 3>("<5,2,1> OPT3 (10 waves)", a, n, R, gflop);
-  run<2, 2, 1, 32, 3>("<2,2,1> OPT3 no input restage", a, n, R, gflop);
-  run<2, 2, 1, 64, 3>("<2,2,1> OPT3 no weight restage", a, n, R, gflop);
-  run<2, 2, 1, 96, 3>("<2,2,1> OPT3 neither", a, n, R, gflop);
-  run<2, 2, 1, 0, 3>("<2,2,1> OPT3 full", a, n, R, gflop);
-  run<3, 2, 1, 0, 3>("<3,2,1> OPT3 (6 waves)", a, n, R, gflop);
-  run<2, 2, 1, 0, 3>("<2,2,1> OPT3", a, n, R, gflop);
-  run<3, 2, 1, 0, 3>("<3,2,1> OPT3 (6 waves)", a, n, R, gflop);
-  run<2, 2, 1, 0, 3>("<2,2,1> OPT3", a, n, R, gflop);
-  run<3, 2, 1, 0, 3>("<3,2,1> OPT3 (6 waves)", a, n, R, gflop);
-  run<5, 2, 1, 0, 3>("<5,2,1> OPT3 (10 waves)", a, n, R, gflop);
-  run<2, 2, 1, 32, 3>("<2,2,1> OPT3 no input restage", a, n, R, gflop);
-  run<2, 2, 1, 64, 3>("<2,2,1> OPT3 no weight restage", a, n, R, gflop);
-  run<2, 2, 1, 0, 3>("<2,2,1> OPT3 full", a, n, R, gflop);
-  anatomy(std::integral_constant<int, 0>{}, "<2,2,1> OPT0 instrumented");
-  anatomy(std::integral_constant<int, 1>{}, "<2,2,1> OPT1 instrumented");
-  anatomy(std::integral_constant<int, 3>{}, "<2,2,1> OPT3 instrumented");
-  run<2, 2, 1, 0, 3>("<2,2,1> OPT3", a, n, R, gflop);
-  run<2, 2, 1, 0, 7, 6>("<2,2,1> OPT7 stagger 6", a, n, R, gflop);
-  run<2, 2, 1, 0, 7, 12>("<2,2,1> OPT7 stagger 12", a, n, R, gflop);
-  run<2, 2, 1, 0, 7, 24>("<2,2,1> OPT7 stagger 24", a, n, R, gflop);
-  run<2, 2, 1, 0, 7, 48>("<2,2,1> OPT7 stagger 48", a, n, R, gflop);
-  run<2, 2, 1, 0, 3>("<2,2,1> OPT3 again", a, n, R, gflop);
-  run<2, 2, 1, 0, 7, 12>("<2,2,1> OPT7 stagger 12 again", a, n, R, gflop);
-  run<2, 2, 1, 0, 1>("<2,2,1> OPT1 lds-epilogue", a, n, R, gflop);
-  run<2, 2, 1, 0, 2>("<2,2,1> OPT2 dma-weights", a, n, R, gflop);
-  run<2, 2, 1, 0, 3>("<2,2,1> OPT3 both", a, n, R, gflop);
-  run<2, 2, 1, 0, 0>("<2,2,1> base (again)", a, n, R, gflop);
-  run<2, 2, 1, 0, 3>("<2,2,1> OPT3 both (again)", a, n, R, gflop);
-  run<4, 1, 2, 0, 3>("<4,1,2> OPT3 both", a, n, R, gflop);
+  }
+  // tile shapes (each twice: the first run of a shape also pays its code load)
+  for (int rep = 0; rep < 2; ++rep) {
+    run<2, 2, 1, 0>("<2,2,1>", a, n, R, gflop);
+    run<3, 2, 1, 0>("<3,2,1> (6 waves)", a, n, R, gflop);
+    run<5, 2, 1, 0>("<5,2,1> (10 waves)", a, n, R, gflop);
+    run<4, 1, 2, 0>("<4,1,2>", a, n, R, gflop);
+    run<4, 2, 1, 0>("<4,2,1> (8 waves)", a, n, R, gflop);
+    run<2, 1, 2, 0>("<2,1,2> (2 waves)", a, n, R, gflop);
+    run<1, 2, 1, 0>("<1,2,1> (2 waves)", a, n, R, gflop);
+    run<1, 1, 2, 0>("<1,1,2> (1 wave)", a, n, R, gflop);
+  }
+  // ablations (wrong results, timing only)
+  run<2, 2, 1, 32>("<2,2,1> no input restage", a, n, R, gflop);
+  run<2, 2, 1, 64>("<2,2,1> no weight restage", a, n, R, gflop);
+  run<2, 2, 1, 96>("<2,2,1> neither", a, n, R, gflop);
   run<2, 2, 1, 1>("<2,2,1> no-restage", a, n, R, gflop);
   run<2, 2, 1, 3>("<2,2,1> no-restage no-bar", a, n, R, gflop);
   run<2, 2, 1, 4>("<2,2,1> no-epilogue-store", a, n, R, gflop);
   run<2, 2, 1, 7>("<2,2,1> mfma+lds only", a, n, R, gflop);
   run<2, 2, 1, 15>("<2,2,1> mfma only", a, n, R, gflop);
-  run<4, 1, 2, 0>("<4,1,2> base", a, n, R, gflop);
   run<4, 1, 2, 7>("<4,1,2> mfma+lds only", a, n, R, gflop);
-  run<4, 2, 1, 0>("<4,2,1> base (8 waves)", a, n, R, gflop);
   run<4, 2, 1, 7>("<4,2,1> mfma+lds only", a, n, R, gflop);
-  run<2, 1, 2, 0>("<2,1,2> base (2 waves)", a, n, R, gflop);
-  run<1, 2, 1, 0>("<1,2,1> base (2 waves)", a, n, R, gflop);
-  run<1, 1, 2, 0>("<1,1,2> base (1 wave)", a, n, R, gflop);
-  run<2, 2, 1, 0>("<2,2,1> base again", a, n, R, gflop);
+  run<2, 2, 1, 0>("<2,2,1> again", a, n, R, gflop);
   a.wpk = wp32;
   run<4, 1, 1, 0>("<4,1,1> ocb32", a, n, R, gflop);
   run<2, 1, 1, 0>("<2,1,1> ocb32 (2 waves)", a, n, R, gflop);

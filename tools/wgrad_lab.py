@@ -1,7 +1,6 @@
 """wgrad3x3 on the batched SRNet layer of the training step (19 frames x 2 x 64 x 64 x 64ch, or 32x32),
-timed alone.  With the lab library (TECOGAN_HIP_LIB=tools/_lab_libs/libtecogan_lab.so): TG_WGRAD_ABL
-bits 1 no global loads after the first tile, 2 no LDS stores, 4 no MFMAs, 8 no LDS operand reads;
-TG_WGRAD_MAXWG caps the K split."""
+timed alone.  With a lab library (TG_LAB_BUILD=1 OUT=<dir> bash tecogan-pytorch_amd/csrc/build.sh, then
+TECOGAN_HIP_LIB=<dir>/libtecogan_lab.so): TG_WGRAD_MAXWG caps the K split, TG_WGRAD_NOVEC=1 forces the scalar staging."""
 import os, sys, torch
 sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
 from tecogan_pytorch_amd import ops
@@ -20,4 +19,4 @@ for _ in range(R):
 e1.record(); torch.cuda.synchronize()
 us = e0.elapsed_time(e1) / R * 1e3
 fl = 2.0 * 64 * 64 * 9 * frames * 2 * hw * hw
-print(f'hw={hw} ABL={os.environ.get("TG_WGRAD_ABL", "0")} MAXWG={os.environ.get("TG_WGRAD_MAXWG", "-")}: wgrad + reduce {us:.1f} us  ({fl / us / 1e6:.1f} TFLOP/s)')
+print(f'hw={hw} MAXWG={os.environ.get("TG_WGRAD_MAXWG", "-")}: wgrad + reduce {us:.1f} us  ({fl / us / 1e6:.1f} TFLOP/s)')

@@ -937,6 +937,51 @@ int tg_frnet_step_masked(tg_frnet_plan* plan, const float* lr_curr, const float*
                          const float* hr_prev, float* hr_out, uint8_t* u8_out,
                          unsigned kind_mask, tg_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * fp16 inference body of SRNet (tg_conv3x3_f16.hip): 64 -> 64 channel 3x3 layers on the
+ * f16 matrix cores, fp32 accumulation, fp32 bias.  fp16 tensors are passed as uint16_t* (IEEE binary16 bits),
+ * activations channels-last (n, h, w, 64), 16-byte aligned.  Every conversion rounds to nearest even.
+ *   tg_conv3x3_f16_supported      1 if the two layer kernels take the shape (cin = cout = 64, n, h, w >= 1)
+ *   tg_conv3x3_f16_packed_halves  fp16 elements of one packed weight tensor (0: cin / cout outside 1..64)
+ *   tg_conv3x3_f16_act_halves     fp16 elements of one activation tensor (-1: bad shape)
+ *   tg_conv3x3_f16_pack_weights   fp32 OIHW (transposed = 0) or IOHW (transposed = 1, ConvTranspose2d) -> packed
+ *                                 fp16, cin and cout zero padded to 64; run once per weight tensor
+ *   tg_conv3x3_f16_pack_input     channels [0, c1) of x1 and [0, c2) of x2 (fp32 NCHW) -> fp16 channels-last,
+ *                                 c1 + c2 <= 64, the remaining channels zero
+ *   tg_conv3x3_f16_fwd            y = round16(act(conv3x3(x) + bias) + res); res optional, y may alias res, not x
+ *   tg_convt3x3s2_f16_fwd         y (fp32 NCHW, n x 64 x 2h x 2w, NOT rounded) = act(ConvTranspose2d(3, 2, 1, 1)(x) + bias)
+ * act: TG_ACT_NONE | TG_ACT_RELU. */
+int tg_conv3x3_f16_supported(int n, int cin, int cout, int h, int w);
+size_t tg_conv3x3_f16_packed_halves(int cin, int cout);
+int64_t tg_conv3x3_f16_act_halves(int n, int h, int w);
+int tg_conv3x3_f16_pack_weights(const float* w, int cin, int cout, int transposed, uint16_t* out, tg_stream_t stream);
+int tg_conv3x3_f16_pack_input(const float* x1, int64_t x1_nstride, int c1, const float* x2, int64_t x2_nstride,
+                              int c2, uint16_t* y, int n, int h, int w, tg_stream_t stream);
+int tg_conv3x3_f16_fwd(const uint16_t* x, const uint16_t* w_packed, const float* bias, const uint16_t* res,
+                       uint16_t* y, int n, int cin, int cout, int h, int w, int act, tg_stream_t stream);
+int tg_convt3x3s2_f16_fwd(const uint16_t* x, const uint16_t* w_packed, const float* bias, float* y,
+                          int64_t y_nstride, int n, int cin, int cout, int h, int w, int act, tg_stream_t stream);
+
+/* Precision of a frame plan's SRNet body.  TG_PREC_F32 (what tg_frnet_plan_create gives): every launch as before.
+ * TG_PREC_F16: phase 2 packs SRNet's input to fp16 and runs conv_in, the residual blocks and the first
+ * up-sampling layer through the kernels above, one launch per layer (no workgroup waits for another one:
+ * tg_frnet_plan_chain_status reports chain_active = 0); FNet, the warp and everything behind the first
+ * up-sampling layer stay the fp32 launches.
+ *   plain      the PLAIN fp32 weights (`w`) and biases (`b`) of those layers, 2 + 2 * nb entries: conv_in (OIHW),
+ *              the block convs (OIHW), the first up-sampling layer (IOHW); `u` is not read.  The plan packs them
+ *              to fp16 once, in stream order, in front of the first fp16 frame; they must outlive the plan.
+ *   workspace  tg_frnet_f16_workspace_bytes(cfg) bytes, 16-byte aligned, caller-owned like the fp32 workspace
+ *              (0: the cfg has no fp16 form -- nf != 64, FNet-only, or not a valid cfg).
+ * With TG_PREC_F32 `plain` and `workspace` are ignored and the fp32 launch list is restored exactly.  At scale 2
+ * the fp16 body ends in the unfused output conv, so a uint8 output then needs n == 1 (TG_E_ARG otherwise, as for
+ * the unfused fp32 HR stage): the plan never computes a frame in another precision than the one it was set to. */
+#define TG_PREC_F32 0
+#define TG_PREC_F16 1
+size_t tg_frnet_f16_workspace_bytes(const tg_frnet_cfg* cfg);
+int tg_frnet_plan_set_precision(tg_frnet_plan* plan, int precision, const tg_layer_weights* plain, int n_plain,
+                                void* workspace);
+int tg_frnet_plan_precision(const tg_frnet_plan* plan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ TG_OK = 0
 ABI_MAJOR = 2            # include/tecogan_hip.h TG_ABI_MAJOR
 ACT_NONE, ACT_RELU, ACT_LRELU02, ACT_TANH24 = 0, 1, 2, 3
 UP_NONE, UP_BICUBIC, UP_BILINEAR = 0, 1, 2
+PREC_F32, PREC_F16 = 0, 1
 
 P, I, I64, F, SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 
@@ -211,6 +212,16 @@ SIGNATURES = {
                                      C.POINTER(C.c_double)]),
     'tg_frnet_replay': (I, [P, P, P, P, P, C.c_uint, I, P]),
     'tg_frnet_step_masked': (I, [P, P, P, P, P, P, C.c_uint, P]),
+    'tg_conv3x3_f16_supported': (I, [I, I, I, I, I]),
+    'tg_conv3x3_f16_packed_halves': (SZ, [I, I]),
+    'tg_conv3x3_f16_act_halves': (I64, [I, I, I]),
+    'tg_conv3x3_f16_pack_weights': (I, [P, I, I, I, P, P]),
+    'tg_conv3x3_f16_pack_input': (I, [P, I64, I, P, I64, I, P, I, I, I, P]),
+    'tg_conv3x3_f16_fwd': (I, [P, P, P, P, P, I, I, I, I, I, I, P]),
+    'tg_convt3x3s2_f16_fwd': (I, [P, P, P, P, I64, I, I, I, I, I, I, P]),
+    'tg_frnet_f16_workspace_bytes': (SZ, [C.POINTER(FrnetCfg)]),
+    'tg_frnet_plan_set_precision': (I, [P, I, C.POINTER(LayerWeights), I, P]),
+    'tg_frnet_plan_precision': (I, [P]),
 }
 
 _lib = None

@@ -65,6 +65,11 @@ struct tg_frnet_plan {
   int rearm_first, rearm_wait, clean_frames, rearms;
   hipEvent_t rearm_fence;           // recorded behind the first per-layer frame after a report: the re-arm waits until the
   bool fence_set;                   // GPU has passed it, so a late fault of a PRE-report launch is never blamed on the re-armed body
+  // fp16 body (tg_frnet_plan_set_precision): packed fp16 weights and two channels-last activation buffers in a
+  // caller-owned workspace; the plain fp32 weights they are packed from, once, in stream order
+  bool f16, f16_ready;
+  std::vector<tg_layer_weights> HL;
+  uint16_t *HWT, *HA, *HB;
   int fh, fw, launches;
   int st_launch[24];
   double st_flops[24], st_bytes[24];
@@ -141,6 +146,18 @@ static size_t fnet_partial_floats(const tg_frnet_cfg* c) {
   return best;
 }
 
+// dry run: per-kernel-class launch counts, algorithmic flops and bytes of one frame
+// (dummy non-null pointers; nothing is dereferenced or launched)
+static void account(tg_frnet_plan* p) {
+  for (int k = 0; k < 24; ++k) { p->st_launch[k] = 0; p->st_flops[k] = 0; p->st_bytes[k] = 0; }
+  p->chain_layers = 0;
+  static float dummy;
+  step_impl(p, &dummy, &dummy, &dummy, &dummy, nullptr, nullptr, 0, true);
+  p->launches = 0;
+  for (int k = 0; k < 24; ++k) p->launches += p->st_launch[k];
+  p->launches -= p->st_launch[8];  // quantise only runs when a u8 output is requested
+}
+
 static const int CHAIN_MAX_LAYERS = 24;
 static void carve(const tg_frnet_cfg* c, size_t off[15]) {
   size_t hw = (size_t)c->h * c->w, n = c->n;
@@ -199,6 +216,7 @@ extern "C" int tg_frnet_plan_create(const tg_frnet_cfg* cfg, const tg_layer_weig
   p->L.assign(layers, layers + n_layers);
   size_t off[15];
   carve(cfg, off);
+  p->f16 = false; p->f16_ready = false; p->HWT = p->HA = p->HB = nullptr;
   p->WZ = workspace + off[11]; p->wz_ready = false;
   p->WA = p->WZ + 2048; p->wa_ready = false;
   p->RESWS = workspace + off[13]; p->res_ready = false;
@@ -221,14 +239,7 @@ extern "C" int tg_frnet_plan_create(const tg_frnet_cfg* cfg, const tg_layer_weig
   p->S2D = workspace + off[3]; p->U1 = workspace + off[4];
   p->U2 = cfg->scale == 4 ? workspace + off[5] : nullptr;
   p->fh = cfg->h / 8 * 8; p->fw = cfg->w / 8 * 8;
-  for (int k = 0; k < 24; ++k) { p->st_launch[k] = 0; p->st_flops[k] = 0; p->st_bytes[k] = 0; }
-  // dry run: per-kernel-class launch counts, algorithmic flops and bytes of one frame
-  // (dummy non-null pointers; nothing is dereferenced or launched)
-  static float dummy;
-  step_impl(p, &dummy, &dummy, &dummy, &dummy, nullptr, nullptr, 0, true);
-  p->launches = 0;
-  for (int k = 0; k < 24; ++k) p->launches += p->st_launch[k];
-  p->launches -= p->st_launch[8];  // quantise only runs when a u8 output is requested
+  account(p);
   *out = p;
   return TG_OK;
 }
@@ -262,7 +273,10 @@ enum {
   K_CONV_WINO = 14,     // conv3x3_wino_kernel: Winograd F(2x2,3x3) form of the large 64-channel-group layers
   K_WINO_CHAIN = 15,    // conv3x3_wino_chain_kernel: SRNet's conv_in + residual blocks as ONE launch
   K_WINO_RES = 16,      // conv3x3_wino_resident_kernel: the same layers on persistent, LDS-resident workgroups (one 134x320-class frame)
-  K_COUNT = 17
+  K_F16_PACK = 17,      // pack_input_f16_kernel: SRNet's two fp32 sources -> fp16 channels-last (fp16 body only)
+  K_F16_CONV = 18,      // conv3x3_f16_kernel<false>: conv_in and the residual-block convs of the fp16 body
+  K_F16_CONVT = 19,     // conv3x3_f16_kernel<true>: the first up-sampling layer of the fp16 body (fp32 out)
+  K_COUNT = 20
 };
 
 // The HR stage as two launches instead of three and without the 64-channel HR tensor: the last
@@ -297,6 +311,7 @@ static bool resident_wanted(bool layer_prefers_wino) {
 }
 // the fused tail writes (n, H, W, c) uint8 frames for any n; the unfused quantise pass only n == 1
 static bool plan_u8_ok(const tg_frnet_plan* p) {
+  if (p->f16 && p->cfg.scale == 2) return p->cfg.n == 1;      // (the fp16 body ends in the unfused HR stage at 2x)
   return p->cfg.n == 1 || (hr_fuse_enabled() && p->cfg.out_nc <= 3 && p->cfg.nf <= 64);
 }
 
@@ -442,7 +457,39 @@ static int step_impl(tg_frnet_plan* p, const float* lr_curr, const float* lr_pre
   for (int i = skip; i < 1 + 2 * c.nb && resident; ++i) resident = p->L[li + i].u != nullptr && p->L[li + i].b != nullptr;
   if (resident) chain = true;
   bool ct_fold = false;
-  if (chain) {
+  if (p->f16) {
+    // fp16 body: one launch per layer, the first up-sampling layer included (its fp32 result lands in U1)
+    const int nbody = 1 + 2 * c.nb;
+    const size_t wstep = tg_conv3x3_f16_packed_halves(64, 64);
+    if (!dry && !p->f16_ready && (phases & 2)) {
+      for (int k = 0; k <= nbody && rc == TG_OK; ++k)
+        rc = tg_conv3x3_f16_pack_weights(p->HL[k].w, k == 0 ? c.in_nc + s2dc : nf, nf, k == nbody ? 1 : 0,
+                                         p->HWT + k * wstep, st);
+      p->f16_ready = rc == TG_OK;
+    }
+    const double px = (double)n * h * w;
+    const double lfl = 2.0 * nf * 9 * nf * px, lby = 2.0 * px * 2 * nf + 2.0 * 9 * nf * nf;
+    uint16_t *HA = p->HA, *HB = p->HB;
+    go(K_F16_PACK, 0, px * (4.0 * (c.in_nc + s2dc) + 2.0 * 64), [&] {
+      return tg_conv3x3_f16_pack_input(lr_curr, c.in_nc * hw, c.in_nc, p->S2D, s2dc * hw, s2dc, HB, n, h, w, st);
+    });
+    auto hconv = [&](int k, const uint16_t* xin, const uint16_t* res, uint16_t* y, int act) {
+      go(K_F16_CONV, lfl, lby + (res ? 2.0 * px * nf : 0), [&] {
+        return tg_conv3x3_f16_fwd(xin, p->HWT + k * wstep, p->HL[k].b, res, y, n, 64, 64, h, w, act, st);
+      });
+    };
+    hconv(0, HB, nullptr, HA, TG_ACT_RELU);
+    for (int b = 0; b < c.nb; ++b) {
+      hconv(1 + 2 * b, HA, nullptr, HB, TG_ACT_RELU);
+      hconv(2 + 2 * b, HB, HA, HA, TG_ACT_NONE);
+    }
+    go(K_F16_CONVT, lfl, 2.0 * px * nf + 4.0 * px * nf * 4 + 2.0 * 9 * nf * nf, [&] {
+      return tg_convt3x3s2_f16_fwd(HA, p->HWT + nbody * wstep, p->HL[nbody].b, p->U1, (int64_t)nf * 4 * hw, n, 64, 64,
+                                   h, w, TG_ACT_RELU, st);
+    });
+    li += nbody;
+    ct_fold = true;                      // (the HR stage below starts behind the first up-sampling layer)
+  } else if (chain) {
     if (skip)
       conv(lr_curr, c.in_nc * hw, c.in_nc, p->S2D, s2dc * hw, c.in_nc + s2dc, nf, h, w, TG_ACT_RELU,
            nullptr, 0, A, nf * hw);
@@ -506,7 +553,8 @@ static int step_impl(tg_frnet_plan* p, const float* lr_curr, const float* lr_pre
       conv(B, nf * hw, nf, nullptr, 0, nf, nf, h, w, TG_ACT_NONE, A, nf * hw, A, nf * hw);
     }
   }
-  const bool fuse = hr_fuse_enabled() && c.out_nc <= 3 && nf <= 64;
+  // (at 2x the fused HR stage IS the first up-sampling layer: the fp16 body then ends in the unfused output conv)
+  const bool fuse = hr_fuse_enabled() && c.out_nc <= 3 && nf <= 64 && !(p->f16 && s == 2);
   const tg_layer_weights lw_up1 = p->L[li++];
   const tg_layer_weights lw_up2 = s == 4 ? p->L[li++] : tg_layer_weights{nullptr, nullptr, nullptr};
   const tg_layer_weights lw_out = p->L[li++];
@@ -675,6 +723,47 @@ extern "C" int tg_frnet_plan_chain_rearms(const tg_frnet_plan* p, int* rearms, i
   return TG_OK;
 }
 
+extern "C" size_t tg_frnet_f16_workspace_bytes(const tg_frnet_cfg* cfg) {
+  if (!cfg_ok(cfg) || cfg->fnet_only || cfg->nf != 64) return 0;
+  const size_t wbytes = (size_t)(2 + 2 * cfg->nb) * tg_conv3x3_f16_packed_halves(64, 64) * 2;
+  const size_t abytes = (size_t)tg_conv3x3_f16_act_halves(cfg->n, cfg->h, cfg->w) * 2;
+  return align64(wbytes) + 2 * align64(abytes);
+}
+
+extern "C" int tg_frnet_plan_set_precision(tg_frnet_plan* p, int precision, const tg_layer_weights* plain,
+                                           int n_plain, void* workspace) {
+  TG_REQUIRE(p, TG_E_ARG, "frnet_plan_set_precision: null plan");
+  TG_REQUIRE(precision == TG_PREC_F32 || precision == TG_PREC_F16, TG_E_ARG,
+             "frnet_plan_set_precision: precision %d (TG_PREC_F32 | TG_PREC_F16)", precision);
+  if (precision == TG_PREC_F16) {
+    const tg_frnet_cfg& c = p->cfg;
+    TG_REQUIRE(!c.fnet_only, TG_E_ARG, "frnet_plan_set_precision: an FNet-only plan has no SRNet body");
+    TG_REQUIRE(c.nf == 64 && tg_conv3x3_f16_supported(c.n, 64, 64, c.h, c.w), TG_E_ARG,
+               "frnet_plan_set_precision: the fp16 body needs nf = 64 (nf = %d)", c.nf);
+    TG_REQUIRE(plain && n_plain == 2 + 2 * c.nb, TG_E_ARG, "frnet_plan_set_precision: %d plain layers given, %d expected",
+               n_plain, 2 + 2 * c.nb);
+    for (int i = 0; i < n_plain; ++i)
+      TG_REQUIRE(plain[i].w && plain[i].b, TG_E_ARG, "frnet_plan_set_precision: plain layer %d null", i);
+    TG_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, TG_E_ARG,
+               "frnet_plan_set_precision: workspace null or not 16-byte aligned");
+    p->HL.assign(plain, plain + n_plain);
+    const size_t wbytes = align64((size_t)n_plain * tg_conv3x3_f16_packed_halves(64, 64) * 2);
+    const size_t abytes = align64((size_t)tg_conv3x3_f16_act_halves(c.n, c.h, c.w) * 2);
+    unsigned char* base = static_cast<unsigned char*>(workspace);
+    p->HWT = reinterpret_cast<uint16_t*>(base);
+    p->HA = reinterpret_cast<uint16_t*>(base + wbytes);
+    p->HB = reinterpret_cast<uint16_t*>(base + wbytes + abytes);
+    p->f16_ready = false;
+  }
+  p->f16 = precision == TG_PREC_F16;
+  // back in fp32 the one-launch bodies start from zeroed flags / exchange buffers, as after plan_create
+  p->res_ready = false; p->chain_ready = false;
+  account(p);
+  return TG_OK;
+}
+
+extern "C" int tg_frnet_plan_precision(const tg_frnet_plan* p) { return p && p->f16 ? TG_PREC_F16 : TG_PREC_F32; }
+
 extern "C" int tg_frnet_plan_kinds(void) { return K_COUNT; }
 
 extern "C" const char* tg_frnet_kind_name(int kind) {
@@ -684,7 +773,8 @@ extern "C" const char* tg_frnet_kind_name(int kind) {
       "maxpool2_kernel",             "upsample_kernel",            "quantize_u8_hwc_kernel",
       "splitk_finalize_kernel",      "conv3x3_mfma_kernel<1,2,1,KS=2>",
       "convt3x3s2_mfma_kernel<Z>",   "convout_tail_kernel",        "conv3x3_oneshot_kernel",
-      "conv3x3_wino_kernel",         "conv3x3_wino_chain_kernel",  "conv3x3_wino_resident_kernel"};
+      "conv3x3_wino_kernel",         "conv3x3_wino_chain_kernel",  "conv3x3_wino_resident_kernel",
+      "pack_input_f16_kernel",       "conv3x3_f16_kernel<false>",  "conv3x3_f16_kernel<true>"};
   return (kind >= 0 && kind < K_COUNT) ? names[kind] : "?";
 }
 

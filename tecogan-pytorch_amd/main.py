@@ -45,6 +45,9 @@ def parse_args(argv=None):
                    help='iteration to resume from: loads {G,D}_iter<k>.pth and state_iter<k>.pth from '
                         'train.ckpt_dir and continues at k + 1 (the reference leaves this as a TODO, '
                         'base_model.py:220-222)')
+    p.add_argument('--precision', type=str, default=None, choices=['fp32', 'fp16'],
+                   help="inference precision of the generator's SRNet body (overrides model.generator.precision of "
+                        "the yml; absent = 'fp32').  Training is always fp32")
     return p.parse_args(argv)
 
 
@@ -78,6 +81,8 @@ def setup(args):
     else:
         opt = default_opt()
     opt['is_train'] = args.mode == 'train'
+    if getattr(args, 'precision', None):
+        opt['model']['generator']['precision'] = args.precision
     local_rank = int(os.environ.get('LOCAL_RANK', args.local_rank))
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         dist_utils.init_dist(opt, max(local_rank, 0))

@@ -9,7 +9,7 @@ def define_generator(opt):
         return FRNet(in_nc=net_G_opt['in_nc'], out_nc=net_G_opt['out_nc'],
                      nf=net_G_opt['nf'], nb=net_G_opt['nb'],
                      degradation=opt['dataset']['degradation']['type'],
-                     scale=opt['scale'])
+                     scale=opt['scale'], precision=net_G_opt.get('precision', 'fp32'))
     raise ValueError(f'Unrecognized generator: {net_G_opt["name"]}')
 
 

@@ -235,7 +235,7 @@ class _StepPlan:
     """Caller-owned device state behind one tg_frnet_plan: packed weights,
     workspace, and the opaque plan handle."""
 
-    def __init__(self, net, n, h, w, device, fnet_only=False):
+    def __init__(self, net, n, h, w, device, fnet_only=False, precision='fp32'):
         lib = L.lib()
         self.cfg = L.FrnetCfg(net.in_nc, net.out_nc, net.nf, net.nb, net.scale,
                               net.srnet.up_mode(), n, h, w, 1 if fnet_only else 0)
@@ -268,6 +268,22 @@ class _StepPlan:
         L.check(lib.tg_frnet_plan_create(ctypes.byref(self.cfg), arr, len(layers),
                                          self.workspace.data_ptr(), ctypes.byref(self.handle)),
                 'tg_frnet_plan_create')
+        self.precision = 'fp32'
+        if precision == 'fp16' and not fnet_only:
+            # fp16 SRNet body: the plan packs fp16 weights from the plain tensors, once
+            nws = lib.tg_frnet_f16_workspace_bytes(ctypes.byref(self.cfg))
+            if nws == 0:
+                raise L.TecoganHipError(f"precision='fp16' needs nf = 64 (nf={net.nf}); there is no fp32 fallback")
+            self.workspace_f16 = torch.empty(nws, dtype=torch.uint8, device=device)
+            body = net.srnet.layers()[:2 + 2 * net.nb]         # conv_in, block convs, first up-sampling layer
+            plain = (L.LayerWeights * len(body))()
+            for i, m in enumerate(body):
+                wt, b = m.weight.detach().contiguous(), m.bias.detach().contiguous()
+                self.keep += [wt, b]
+                plain[i].w, plain[i].b, plain[i].u = wt.data_ptr(), b.data_ptr(), None
+            L.check(lib.tg_frnet_plan_set_precision(self.handle, L.PREC_F16, plain, len(body),
+                                                    self.workspace_f16.data_ptr()), 'tg_frnet_plan_set_precision')
+            self.precision = 'fp16'
 
     def check_chain(self):
         """Raise if a workgroup of the chained SRNet launch gave up waiting for a producer tile since
@@ -307,11 +323,13 @@ class _StepPlan:
 class FRNet(nn.Module):
     """Frame-recurrent generator, tecogan_nets.py:150-314."""
 
-    def __init__(self, in_nc, out_nc, nf, nb, degradation, scale):
+    def __init__(self, in_nc, out_nc, nf, nb, degradation, scale, precision='fp32'):
         super().__init__()
         self.in_nc, self.out_nc, self.nf, self.nb = in_nc, out_nc, nf, nb
         self.scale = scale
         self.degradation = degradation
+        self._precision = 'fp32'
+        self.precision = precision
         self.upsample_func = get_upsampling_func(self.scale, degradation)
         self.fnet = FNet(in_nc)
         self.srnet = SRNet(in_nc, out_nc, nf, nb, self.upsample_func, self.scale)
@@ -323,6 +341,25 @@ class FRNet(nn.Module):
         # the sweep runs beside it and the second flush only adds launches (measured: 24.5 vs 24.8 ms).
         # round 6: an int = that many hand-over points spread over the sweep (TG_WGRAD_SIDE, read at construction)
         self.wgrad_side_stream = int(os.environ.get('TG_WGRAD_SIDE', '0') or 0)
+
+    # -- precision of the inference frame -------------
+    @property
+    def precision(self):
+        """'fp32' (default) or 'fp16': SRNet's conv_in, residual blocks and first up-sampling layer on the f16 matrix
+        cores with fp32 accumulation, in step / infer_sequence only; forward_sequence (training) and step_ops are
+        always fp32.  Assigning drops the cached plans."""
+        return self._precision
+
+    @precision.setter
+    def precision(self, value):
+        if value not in ('fp32', 'fp16'):
+            raise ValueError(f"precision must be 'fp32' or 'fp16', got {value!r}")
+        if value != self._precision:
+            self._plan, self._plan_key = {}, None
+        self._precision = value
+
+    def _plan_cache_key(self, n, h, w, device, fnet_only):
+        return (n, h, w, str(device), fnet_only, self._precision)
 
     # -- plan cache ---------------------------------------------------------
     def _weights_key(self):
@@ -337,10 +374,10 @@ class FRNet(nn.Module):
             wk = self._weights_key()
         if self._plan_key != wk:
             self._plan, self._plan_key = {}, wk
-        key = (n, h, w, str(device), fnet_only)
+        key = self._plan_cache_key(n, h, w, device, fnet_only)
         plan = self._plan.get(key)
         if plan is None:
-            plan = self._plan[key] = _StepPlan(self, n, h, w, device, fnet_only)
+            plan = self._plan[key] = _StepPlan(self, n, h, w, device, fnet_only, self._precision)
         return plan
 
     # -- reference API ------------------------------------------------------

@@ -1421,3 +1421,87 @@ class WinoResident(WinoChain):
 
     def bailouts(self):
         return int(self.ws[-64].item())
+
+
+# ---- fp16 inference body of SRNet (tg_conv3x3_f16.hip) ---------------------------------
+# fp16 tensors are torch.float16, activations channels-last (n, h, w, 64).
+
+def f16_supported(n, cin, cout, h, w):
+    return bool(L.lib().tg_conv3x3_f16_supported(int(n), int(cin), int(cout), int(h), int(w)))
+
+
+def f16_pack_index(transposed=False, cin=64, cout=64):
+    """Host statement of the packed fp16 weight order: an int64 array `idx` of tg_conv3x3_f16_packed_halves
+    entries with packed[i] = weight.reshape(-1)[idx[i]] (or 0 where idx[i] < 0: channels padded to 64).
+    Element ((ks * 4 + ct) * 64 + lane) * 8 + j is W[cout = 16 ct + lane % 16][tap = ks // 2]
+    [cin = 32 (ks % 2) + 8 (lane // 16) + j] -- the A operand of v_mfma_f32_16x16x32_f16, K step ks."""
+    import numpy as np
+    i = np.arange(18 * 4 * 64 * 8, dtype=np.int64)
+    j, lane, ct, ks = i & 7, (i >> 3) & 63, (i >> 9) & 3, i >> 11
+    co, tap, ci = ct * 16 + (lane & 15), ks >> 1, (ks & 1) * 32 + (lane >> 4) * 8 + j
+    src = ((ci * cout + co) if transposed else (co * cin + ci)) * 9 + tap
+    return np.where((ci < cin) & (co < cout), src, -1)
+
+
+def f16_pack_weights(w, transposed=False):
+    """fp32 Conv2d (cout, cin, 3, 3) or ConvTranspose2d (cin, cout, 3, 3; transposed=True) weight -> packed fp16
+    (round to nearest even), cin / cout <= 64 zero padded."""
+    _chk(w, 'w')
+    cin, cout = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
+    lib = L.lib()
+    nh = lib.tg_conv3x3_f16_packed_halves(int(cin), int(cout))
+    if nh == 0 or tuple(w.shape[2:]) != (3, 3):
+        raise L.TecoganHipError(f'f16_pack_weights: weight {tuple(w.shape)} (3x3, at most 64 channels each way)')
+    out = torch.empty(nh, dtype=torch.float16, device=w.device)
+    L.check(lib.tg_conv3x3_f16_pack_weights(w.data_ptr(), int(cin), int(cout), 1 if transposed else 0, out.data_ptr(),
+                                            _stream()), 'tg_conv3x3_f16_pack_weights')
+    return out
+
+
+def f16_pack_input(x1, x2=None):
+    """fp32 NCHW x1 (and x2, concatenated behind it) -> fp16 channels-last (n, h, w, 64), zero padded."""
+    _chk(x1, 'x1')
+    n, c1, h, w = x1.shape
+    c2 = 0
+    if x2 is not None:
+        _chk(x2, 'x2')
+        c2 = x2.shape[1]
+        if (x2.shape[0], x2.shape[2], x2.shape[3]) != (n, h, w):
+            raise L.TecoganHipError('f16_pack_input: x1 / x2 shapes differ')
+    y = torch.empty(n, h, w, 64, dtype=torch.float16, device=x1.device)
+    L.check(L.lib().tg_conv3x3_f16_pack_input(x1.data_ptr(), c1 * h * w, c1, _ptr(x2), c2 * h * w, c2, y.data_ptr(),
+                                              n, h, w, _stream()), 'tg_conv3x3_f16_pack_input')
+    return y
+
+
+def conv3x3_f16(x, w_packed, bias, act=ACT_NONE, res=None, out=None):
+    """x (n, h, w, 64) fp16 -> fp16: round16(act(conv3x3(x) + bias) + res).  out may be res, never x."""
+    _chk(x, 'x', torch.float16); _chk(w_packed, 'w_packed', torch.float16); _chk(bias, 'bias')
+    n, h, w, c = x.shape
+    if res is not None:
+        _chk(res, 'res', torch.float16)
+        if res.shape != x.shape:
+            raise L.TecoganHipError('conv3x3_f16: res shape differs from x')
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _chk(out, 'out', torch.float16)
+        if out.shape != x.shape:
+            raise L.TecoganHipError('conv3x3_f16: out shape differs from x')
+    L.check(L.lib().tg_conv3x3_f16_fwd(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), _ptr(res), out.data_ptr(),
+                                       n, c, bias.numel(), h, w, act, _stream()), 'tg_conv3x3_f16_fwd')
+    return out
+
+
+def convt3x3s2_f16(x, w_packed, bias, act=ACT_NONE, out=None):
+    """x (n, h, w, 64) fp16 -> fp32 NCHW (n, 64, 2h, 2w), not rounded: act(ConvTranspose2d(3, 2, 1, 1)(x) + bias)."""
+    _chk(x, 'x', torch.float16); _chk(w_packed, 'w_packed', torch.float16); _chk(bias, 'bias')
+    n, h, w, c = x.shape
+    if out is None:
+        out = torch.empty(n, bias.numel(), 2 * h, 2 * w, dtype=torch.float32, device=x.device)
+    else:
+        _chk(out, 'out')
+    L.check(L.lib().tg_convt3x3s2_f16_fwd(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), out.data_ptr(),
+                                          bias.numel() * 4 * h * w, n, c, bias.numel(), h, w, act, _stream()),
+            'tg_convt3x3s2_f16_fwd')
+    return out

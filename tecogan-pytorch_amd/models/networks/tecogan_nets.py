@@ -320,6 +320,10 @@ class _StepPlan:
             pass
 
 
+# infer_sequence: most frame pairs (over all clips of the call) in a clip's FIRST batched flow pass
+FNET_FIRST_PASS_FRAMES = 8
+
+
 class FRNet(nn.Module):
     """Frame-recurrent generator, tecogan_nets.py:150-314."""
 
@@ -335,12 +339,6 @@ class FRNet(nn.Module):
         self.srnet = SRNet(in_nc, out_nc, nf, nb, self.upsample_func, self.scale)
         self._plan = {}
         self._plan_key = None
-        # training: True = the weight gradients of the swept half of the unroll go to a side stream
-        # under the rest of the sweep (train_graph.Tape.flush_deferred_async).  Off: the weight-gradient
-        # kernel holds a whole CU per workgroup (464 registers, 107 KB LDS), so on one GPU nothing of
-        # the sweep runs beside it and the second flush only adds launches (measured: 24.5 vs 24.8 ms).
-        # round 6: an int = that many hand-over points spread over the sweep (TG_WGRAD_SIDE, read at construction)
-        self.wgrad_side_stream = int(os.environ.get('TG_WGRAD_SIDE', '0') or 0)
 
     # -- precision of the inference frame -------------
     @property
@@ -498,7 +496,9 @@ class FRNet(nn.Module):
                 # split-K) while the main stream runs warp + SRNet frame by frame on the
                 # previous batch -- the serial part of the recurrence is SRNet alone.
                 nb_ = max(1, min(max(1, int(os.environ.get('TG_FNET_BATCH', '8')) // k), tot_frm))
-                nb0 = max(1, min(nb_, max(1, int(os.environ.get('TG_FNET_FIRST_BATCH', '8')) // k)))   # lab knob
+                # frame 1 waits for the first flow pass, so that pass stays short whatever TG_FNET_BATCH says
+                # (EXPERIMENTS.md, round 5)
+                nb0 = max(1, min(nb_, max(1, FNET_FIRST_PASS_FRAMES // k)))
                 batches, i0_ = [], 0           # (first frame, frames); frame 0 needs no flow: the first batch has one more
                 while i0_ < tot_frm:
                     cnt_ = min(nb0 + 1 if not batches else nb_, tot_frm - i0_)
@@ -613,7 +613,6 @@ class FRNet(nn.Module):
         n, t, c, h, w = lr_data.shape
         s = self.scale
         tape = TG.Tape()
-        tape.side = side_stream(lr_data.device, 'wgrad') if self.wgrad_side_stream else None
         lr_prev = ops.time_gather(lr_data, list(range(t - 1))).view(n * (t - 1), c, h, w)
         lr_curr = ops.time_gather(lr_data, list(range(1, t))).view(n * (t - 1), c, h, w)
         lr_flow = self.fnet(lr_curr, lr_prev, tape=tape)
@@ -643,13 +642,7 @@ class FRNet(nn.Module):
         bi_fm = ops.upsample(lr_fm.view(t * n, c, h, w), s, self.srnet.up_mode()).view(t, n, c, s * h, s * w)
         hr_prev = self.srnet(lr_fm[0], zeros, tape=tape, bi=bi_fm[0])
         frames.append(hr_prev)
-        k_side = int(self.wgrad_side_stream) if tape.side is not None else 0
-        flush_at = {max(1, round(t * j / (k_side + 1))) for j in range(1, k_side + 1)} if k_side else set()
         for i in range(1, t):
-            if i in flush_at:
-                # recorded BEFORE frame i's nodes => runs right after frames t-1 .. i have been swept:
-                # their weight gradients start on the side stream under the sweep of frames i-1 .. 0
-                tape.record(tape.flush_deferred_async)
             tran = TG.backward_warp(tape, hr_prev, flow_fm[i - 1],          # warp -> space_to_depth, one launch
                                     dflow_out=functools.partial(flow_grad_slice, i - 1), s2d=s)
             hr_prev = self.srnet(lr_fm[i], tran, tape=tape, bi=bi_fm[i])

@@ -45,8 +45,6 @@ class Tape:
         # the gradient of its output into the last slot of its dZ block) may reserve that buffer here; a
         # producer that can write into a given tensor then delivers the gradient in place
         self.reserved = {}
-        self.side = None        # side stream of the asynchronous weight-gradient flushes
-        self._inflight = []     # tensors the side stream still reads (kept alive until the join)
 
     # -- gradient bookkeeping -------------------------------------------------
     def add_grad(self, t, g, masked=False, act_applied=False):
@@ -84,39 +82,7 @@ class Tape:
         for fn in reversed(self.nodes):
             fn()
         self.nodes = []
-        if self.side is not None and (self.deferred or self.deferred_bias or self.deferred_body):
-            self.flush_deferred_async()      # the tail goes behind the earlier chunks on the side stream
-        else:
-            self.flush_deferred()
-        self.join()
-
-    # -- weight gradients beside the reverse sweep ------------------------------------------------
-    # The reverse sweep over the unrolled frames is a serial chain of small, latency-bound launches
-    # (one 64-channel layer of a 2 x 64 x 64 frame = 256 workgroups for ~11 us); the weight gradients
-    # are large, MFMA-bound launches that depend only on tensors the sweep has already produced.
-    # A checkpoint node (FRNet.forward_sequence places one in the middle of the unroll) hands the
-    # (dZ, X) pairs collected so far to ONE long-lived side stream; the rest follows at the end of
-    # backward(), behind the first chunk (both accumulate into the same gradient buffers: stream
-    # order makes that a fixed summation order, run to run).  join() orders the main stream after
-    # the side stream before anything reads the gradients.
-    def flush_deferred_async(self):
-        if self.side is None:
-            return self.flush_deferred()
-        main = torch.cuda.current_stream()
-        self.side.wait_stream(main)                      # everything deferred so far has been enqueued
-        for ent in self.deferred.values():
-            self._inflight += ent['p'] + ent['q']
-        for _, dzs in self.deferred_bias.values():
-            self._inflight += dzs
-        for ent in self.deferred_body.values():
-            self._inflight += ent['acts'] + ent['dz']
-        with torch.cuda.stream(self.side):
-            self.flush_deferred()
-
-    def join(self):
-        if self.side is not None and self._inflight:
-            torch.cuda.current_stream().wait_stream(self.side)
-        self._inflight = []
+        self.flush_deferred()
 
     # -- deferred parameter gradients -------------------------------------------
     # A layer is applied once per unrolled frame (19x for SRNet), each time on a small

@@ -767,12 +767,13 @@ def test_convt3x3s2_mfma(ops, n, cin, cout, h, w):
 
 @pytest.mark.parametrize('n,cin,cout,cz,h,w', [(1, 64, 64, 3, 12, 20), (2, 64, 64, 3, 7, 35), (1, 64, 64, 3, 33, 64),
                                                (1, 40, 48, 2, 9, 33), (2, 64, 64, 1, 21, 70), (1, 64, 64, 3, 70, 130)])
-def test_convt_z_forms_are_bit_identical_and_match_the_composition(ops, n, cin, cout, cz, h, w):
+def test_convt_z_forms_are_bit_identical_write_only_their_planes_and_match_the_composition(ops, n, cin, cout, cz, h, w):
     """tg_convt3x3s2_z_fwd_form: the last up-sampling layer + the output conv's channel contraction (Z mode,
-    tecogan_nets.py:119-131).  The streaming form (round 6: weights LDS-resident, autonomous waves, atomic work
-    counter) must equal the tiled form BIT FOR BIT on ragged shapes (w not a multiple of 32, odd h, n = 2, fewer
-    channels), three launches in a row (the work counter's slot is handed back clean by the last wave), and both must be the
-    reference composition: plane[tap * cz + o] = sum_c Wout[o, c, tap] * relu(convT(x))[c]."""
+    tecogan_nets.py:119-131).  The tiled form must be the reference composition, plane[tap * cz + o] =
+    sum_c Wout[o, c, tap] * relu(convT(x))[c], on ragged shapes (w not a multiple of 32, odd h, n = 2, fewer channels),
+    and every form a caller can ask for (0 one launch, 3 split tail -- one launch where the image has no whole round --,
+    -1 the rule), three launches in a row into a pre-filled buffer, must equal it BIT FOR BIT and leave the planes
+    behind 9 * cz untouched."""
     import torch.nn.functional as F
     x = rs(1, (n, cin, h, w), -1, 1)
     wt = rs(2, (cin, cout, 3, 3), -1, 1) / (1.5 * cin ** 0.5)
@@ -785,20 +786,20 @@ def test_convt_z_forms_are_bit_identical_and_match_the_composition(ops, n, cin, 
     xd, bd = dev(x), dev(b)
     tiled = ops.convt3x3s2_z(xd, pk, bd, wz, cz, cout, act=1, form=0)
     assert err(tiled[:, :9 * cz], ref) <= 1e-5, err(tiled[:, :9 * cz], ref)
-    for rep in range(4):
+    for form in (0, 3, -1):
         out = torch.full((n, 32, 2 * h, 2 * w), 7.0, device='cuda')
-        ops.convt3x3s2_z(xd, pk, bd, wz, cz, cout, act=1, form=2 if rep == 3 else 1, out=out)     # (2: static item list)
-        assert torch.equal(out[:, :9 * cz], tiled[:, :9 * cz]), (rep, (out[:, :9 * cz] - tiled[:, :9 * cz]).abs().max().item())
-        assert bool((out[:, 9 * cz:] == 7.0).all()), 'the streaming form wrote outside its planes'
+        ops.convt3x3s2_z(xd, pk, bd, wz, cz, cout, act=1, form=form, out=out)
+        assert torch.equal(out[:, :9 * cz], tiled[:, :9 * cz]), (form, (out[:, :9 * cz] - tiled[:, :9 * cz]).abs().max().item())
+        assert bool((out[:, 9 * cz:] == 7.0).all()), f'form {form} wrote outside its planes'
     auto = ops.convt3x3s2_z(xd, pk, bd, wz, cz, cout, act=1)
     assert torch.equal(auto[:, :9 * cz], tiled[:, :9 * cz])
 
 
 def test_convt_z_split_tail_is_bit_identical_at_the_frame_size(ops):
     """tg_convt3x3s2_z_fwd_form 3 (round 6, what the rule picks at this size): whole rounds of four-row workgroups and a
-    second launch of two-row workgroups for the remaining rows -- against the single-launch tiled form (0) and the
-    streaming form with the static list (2), bit for bit, at the 268x640 -> 536x1280 shape of the inference frame; rows
-    that the first launch does not cover must not be touched by it (the buffer is pre-filled)."""
+    second launch of two-row workgroups for the remaining rows -- against the single-launch tiled form (0), bit for bit,
+    at the 268x640 -> 536x1280 shape of the inference frame; rows that the first launch does not cover must not be
+    touched by it (the buffer is pre-filled)."""
     n, cin, cout, cz, h, w = 1, 64, 64, 3, 268, 640
     x = dev(rs(1, (n, cin, h, w), -1, 1))
     wt = rs(2, (cin, cout, 3, 3), -1, 1) / (1.5 * cin ** 0.5)
@@ -807,11 +808,25 @@ def test_convt_z_split_tail_is_bit_identical_at_the_frame_size(ops):
     pk, _, _, _ = ops.pack_conv3x3(dev(wt), transposed=True)
     wz = ops.convt_pack_wz(dev(wo))
     ref = ops.convt3x3s2_z(x, pk, b, wz, cz, cout, act=1, form=0)
-    for form in (3, -1, 2):
+    for form in (3, -1):
         out = torch.full((n, 32, 2 * h, 2 * w), 7.0, device='cuda')
         ops.convt3x3s2_z(x, pk, b, wz, cz, cout, act=1, form=form, out=out)
         assert torch.equal(out[:, :27], ref[:, :27]), (form, (out[:, :27] - ref[:, :27]).abs().max().item())
         assert bool((out[:, 27:] == 7.0).all()), form
+
+
+def test_convt_z_rejects_the_removed_forms(ops):
+    """Forms 1 and 2 (the streaming form, removed) are invalid arguments now, and the error names the valid ones."""
+    from tecogan_pytorch_amd._lib import TecoganHipError
+    n, cin, cout, cz, h, w = 1, 64, 64, 3, 12, 20
+    x, b = dev(rs(1, (n, cin, h, w), -1, 1)), dev(rs(3, (cout,), -0.5, 0.5))
+    pk, _, _, _ = ops.pack_conv3x3(dev(rs(2, (cin, cout, 3, 3), -1, 1)), transposed=True)
+    wz = ops.convt_pack_wz(dev(rs(4, (cz, cout, 3, 3), -1, 1)))
+    for form in (1, 2):
+        with pytest.raises(TecoganHipError) as e:
+            ops.convt3x3s2_z(x, pk, b, wz, cz, cout, act=1, form=form)
+        msg = str(e.value)
+        assert f'form={form}' in msg and all(v in msg for v in ('-1 the rule', '0 tiled', '3 tiled')), msg
 
 
 @pytest.mark.parametrize('n,cz,h,w,up', [(1, 3, 48, 80, ('BD', 4)), (2, 3, 44, 132, ('BI', 2)), (1, 3, 20, 36, ('BD', 2)),

@@ -891,6 +891,12 @@ int tg_frnet_plan_set_chain_poll_limit(tg_frnet_plan* plan, int poll_limit);
  * back-off in force (0 before the first fault). */
 int tg_frnet_plan_set_chain_rearm(tg_frnet_plan* plan, int first_after_frames);
 int tg_frnet_plan_chain_rearms(const tg_frnet_plan* plan, int* rearms, int* current_wait_frames);
+/* hold != 0: while it is set, frames enqueued on a fallen-back plan neither count towards the back-off nor arm the
+ * one-launch body again -- they are guaranteed to run one launch per layer, which has no waiting workgroups and
+ * cannot time out.  FRNet.infer_stream brackets the re-run of the batches a fault invalidated with it: a stream
+ * re-arms mid-clip by design, and a body armed again INSIDE the re-run could fault a second time in frames that
+ * are being repaired.  hold = 0 resumes the count where it stood.  No effect on a plan whose body is in use. */
+int tg_frnet_plan_hold_chain_rearm(tg_frnet_plan* plan, int hold);
 /* hr_out may alias nothing else; lr_curr/lr_prev (n,c,h,w), hr_prev/hr_out (n,c,s*h,s*w).
  * u8_out (optional): (n, s*h, s*w, c) uint8 quantised frames (n > 1 needs the fused HR stage:
  * out_nc <= 3, nf <= 64). */

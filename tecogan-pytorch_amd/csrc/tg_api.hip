@@ -63,6 +63,7 @@ struct tg_frnet_plan {
   // the wait (exponential back-off, capped), a permanent co-tenant therefore costs one faulted clip every 2^k * first
   // frames and never more.  rearm_first == 0: never re-arm (the round-5 behaviour).
   int rearm_first, rearm_wait, clean_frames, rearms;
+  bool rearm_hold;                  // tg_frnet_plan_hold_chain_rearm: frames enqueued meanwhile neither count as clean nor re-arm the body
   hipEvent_t rearm_fence;           // recorded behind the first per-layer frame after a report: the re-arm waits until the
   bool fence_set;                   // GPU has passed it, so a late fault of a PRE-report launch is never blamed on the re-armed body
   // fp16 body (tg_frnet_plan_set_precision): packed fp16 weights and two channels-last activation buffers in a
@@ -107,7 +108,7 @@ static int chain_poll(tg_frnet_plan* p) {
 // Called once per frame enqueued through phase 2 while the one-launch body is off: counts clean frames, and re-arms the
 // body once the back-off has passed, no new fault has arrived, and the GPU is past the first per-layer frame.
 static void chain_rearm_tick(tg_frnet_plan* p, tg_stream_t st) {
-  if (!p->chain_disabled || !p->chain_err || p->rearm_first <= 0) return;
+  if (!p->chain_disabled || !p->chain_err || p->rearm_first <= 0 || p->rearm_hold) return;
   if (!p->fence_set) {
     if (!p->rearm_fence && hipEventCreateWithFlags(&p->rearm_fence, hipEventDisableTiming) != hipSuccess) {
       (void)hipGetLastError(); p->rearm_fence = nullptr; p->rearm_first = 0; return;     // no fence -> never re-arm
@@ -223,6 +224,7 @@ extern "C" int tg_frnet_plan_create(const tg_frnet_cfg* cfg, const tg_layer_weig
   p->CHAINF = reinterpret_cast<int32_t*>(workspace + off[12]); p->chain_ready = false; p->epoch = 0; p->chain_layers = 0;
   p->chain_err = nullptr; p->chain_disabled = false; p->chain_faults = 0; p->chain_poll_limit = tg::TG_CHAIN_POLL_LIMIT_DEFAULT;
   p->rearm_first = 64; p->rearm_wait = 0; p->clean_frames = 0; p->rearms = 0; p->rearm_fence = nullptr; p->fence_set = false;
+  p->rearm_hold = false;
   if (!cfg->fnet_only) {
     void* hp = nullptr;
     if (hipHostMalloc(&hp, 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess && hp) {
@@ -713,6 +715,12 @@ extern "C" int tg_frnet_plan_set_chain_rearm(tg_frnet_plan* p, int first_after_f
   TG_REQUIRE(p && first_after_frames >= 0, TG_E_ARG, "frnet_plan_set_chain_rearm: bad argument");
   p->rearm_first = first_after_frames;
   if (p->chain_disabled && p->rearm_wait == 0) p->rearm_wait = first_after_frames;
+  return TG_OK;
+}
+
+extern "C" int tg_frnet_plan_hold_chain_rearm(tg_frnet_plan* p, int hold) {
+  TG_REQUIRE(p, TG_E_ARG, "frnet_plan_hold_chain_rearm: null plan");
+  p->rearm_hold = hold != 0;
   return TG_OK;
 }
 

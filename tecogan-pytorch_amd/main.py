@@ -1,5 +1,5 @@
 """Driver with the reference's three modes and CLI flags (codes/main.py,
-codes/utils/base_utils.py:14-30): train | test | profile.
+codes/utils/base_utils.py:14-30): train | test | profile -- and infer, which the reference has not.
 
 `train` reads the reference's LMDB training sets when `dataset.train.seq_dir` names one
 (tecogan_pytorch_amd/data: the decoded frames live in HBM, batches are cut out by a HIP
@@ -9,7 +9,13 @@ of the GT) and evaluates with the yml's `metric` section (PSNR, LPIPS).  Otherwi
 a synthetic source that honours the loader's output contract (unpaired_lmdb_dataset.py:89-93,
 paired_folder_dataset.py:57-63); any iterable of such dicts can be passed to `train()` / `test()`.
 
+`infer` upscales a folder of LR frames (`--input`: the frames themselves, or one sub-folder per sequence) into
+`--output` without ground truth: frames are decoded lazily, streamed through VSRModel.infer_stream in bounded memory
+(any length) and written as PNGs under the input's names.  PNG decoding and encoding bound its rate: what it prints
+is a codec number, not a GPU number.
+
   python -m tecogan_pytorch_amd.main --mode profile --lr_size 3x134x320 --test_speed
+  python -m tecogan_pytorch_amd.main --mode infer --opt my_test.yml --input lr_frames/ --output sr_frames/
   python -m tecogan_pytorch_amd.main --mode train --opt my_train.yml --gpu_ids 0
   torchrun --nproc-per-node 8 -m tecogan_pytorch_amd.main --mode train ...   (DDP over RCCL)
 """
@@ -31,7 +37,7 @@ from .utils import dist_utils
 def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument('--exp_dir', type=str, default='.')
-    p.add_argument('--mode', type=str, required=True, help='train|test|profile')
+    p.add_argument('--mode', type=str, required=True, help='train|test|profile|infer')
     p.add_argument('--opt', type=str, default=None, help='yaml config (reference schema)')
     p.add_argument('--gpu_ids', type=str, default='0')
     p.add_argument('--lr_size', type=str, default='3x256x256')
@@ -48,6 +54,12 @@ def parse_args(argv=None):
     p.add_argument('--precision', type=str, default=None, choices=['fp32', 'fp16'],
                    help="inference precision of the generator's SRNet body (overrides model.generator.precision of "
                         "the yml; absent = 'fp32').  Training is always fp32")
+    p.add_argument('--input', type=str, default=None,
+                   help='--mode infer: folder of LR frames (png | jpg), either the frames of one sequence or one '
+                        'sub-folder per sequence; no ground truth is needed')
+    p.add_argument('--output', type=str, default=None,
+                   help='--mode infer: folder the super-resolved PNGs are written to, under the names (and sub-folders) '
+                        'of the input')
     return p.parse_args(argv)
 
 
@@ -272,6 +284,95 @@ def folder_test_sets(opt):
     return out
 
 
+# --mode infer: threads that copy a frame out of the stream's ring slot, encode and write it (PNG encoding releases the
+# GIL).  A constant: the GPU boxes show hundreds of CPUs to a process that may use a few.
+INFER_WRITER_THREADS = 4
+
+
+def infer_sequences(input_dir):
+    """[(sequence name, [frame paths])] of an --input folder: frames directly inside it are ONE sequence named ''
+    (sub-folders are then ignored); otherwise every sub-folder that holds frames is a sequence (listed recursively and
+    sorted, as folder_dataset.retrieve_files does)."""
+    from .data.folder_dataset import retrieve_files
+    names = sorted(os.listdir(input_dir))
+    exts = ('.png', '.jpg')
+    flat = [os.path.join(input_dir, n) for n in names
+            if os.path.isfile(os.path.join(input_dir, n)) and os.path.splitext(n)[-1].lower() in exts]
+    if flat:
+        return [('', flat)]
+    out = []
+    for n in names:
+        d = os.path.join(input_dir, n)
+        if os.path.isdir(d):
+            files = retrieve_files(d)
+            if files:
+                out.append((n, files))
+    return out
+
+
+def infer_output_path(input_dir, output_dir, seq, path):
+    """Where the super-resolved frame of `path` goes: the input's name (and sub-folders) under output_dir, as .png."""
+    rel = os.path.relpath(path, os.path.join(input_dir, seq) if seq else input_dir)
+    return os.path.join(output_dir, seq, os.path.splitext(rel)[0] + '.png')
+
+
+def infer(opt, input_dir, output_dir):
+    """--mode infer: every sequence of input_dir through VSRModel.infer_stream.  Frames are decoded one by one as the
+    stream asks for them; the writers copy each frame out of the yielded ring slot before the generator is advanced.
+    Returns {sequence: frames written}."""
+    import threading
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image
+    from .data.folder_dataset import read_rgb
+    seqs = infer_sequences(input_dir)
+    if not seqs:
+        raise ValueError(f'--input {input_dir}: no png | jpg frames, directly or one level down')
+    model = define_model(opt)
+    done = {}
+    slots = threading.BoundedSemaphore(4 * INFER_WRITER_THREADS)       # frames copied out and not yet on disk
+
+    def write(view, path, copied):
+        try:
+            try:
+                frame = np.array(view)              # out of the ring slot
+            finally:
+                copied.release()
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            Image.fromarray(frame).save(path)
+        finally:
+            slots.release()
+
+    with ThreadPoolExecutor(max_workers=INFER_WRITER_THREADS) as pool:
+        for seq, files in seqs:
+            t0 = time.time()
+            targets = [infer_output_path(input_dir, output_dir, seq, p) for p in files]
+            jobs, k = [], 0
+            for chunk in model.infer_stream(read_rgb(p) for p in files):
+                copied = threading.Semaphore(0)
+                for i in range(len(chunk)):
+                    slots.acquire()
+                    jobs.append(pool.submit(write, chunk[i], targets[k], copied))
+                    k += 1
+                for _ in range(len(chunk)):         # the slot is the generator's again once it is advanced
+                    copied.acquire()
+                running = []
+                for j in jobs:                      # (the list does not grow with the clip; a writer's exception surfaces)
+                    if j.done():
+                        j.result()
+                    else:
+                        running.append(j)
+                jobs = running
+            for j in jobs:
+                j.result()                          # (a writer's exception surfaces here)
+            done[seq] = k
+            dt = time.time() - t0
+            print(f"{seq or os.path.basename(os.path.normpath(input_dir))}: {k} frames -> "
+                  f"{os.path.join(output_dir, seq)} ({k / max(dt, 1e-9):.1f} frames/s, bound by PNG decoding and encoding)",
+                  flush=True)
+    model.net_G.check_faults()
+    return done
+
+
 def profile(opt, lr_size, test_speed=False):
     """codes/main.py:210-264 protocol: FLOPs/params, then FPS of step() over 30 fresh random
     inputs with a device sync per frame."""
@@ -343,10 +444,14 @@ def main(argv=None):
             gt = (torch.rand(8, 32 * opt['scale'], 48 * opt['scale'], 3, generator=g) * 255).to(torch.uint8)
             seqs.append({'gt': gt, 'lr': lr, 'seq_idx': f'synthetic_{i:03d}'})
         test(opt, seqs)
+    elif args.mode == 'infer':
+        if not args.input or not args.output:
+            raise ValueError('--mode infer needs --input DIR and --output DIR')
+        infer(opt, args.input, args.output)
     elif args.mode == 'profile':
         profile(opt, tuple(int(v) for v in args.lr_size.split('x')), args.test_speed)
     else:
-        raise ValueError(f'Unrecognized mode: {args.mode} (train|test|profile)')
+        raise ValueError(f'Unrecognized mode: {args.mode} (train|test|profile|infer)')
 
 
 if __name__ == '__main__':

@@ -11,6 +11,33 @@ from ..utils import dist_utils
 from ..utils.data_utils import gaussian_kernel2d
 
 
+def front_pad_stream(frames, mode, n_pad, in_nc=3):
+    """pad_sequence for a stream whose length is not known: buffers the first n_pad + 1 frames of `frames` (items as
+    FRNet.infer_stream takes them), yields the reflected / replicated prefix, the buffered frames, then the rest of the
+    stream as it comes.  A stream shorter than n_pad + 1 frames is refused (pad_sequence's assert)."""
+    from .networks.tecogan_nets import stream_parts
+    if mode not in ('reflect', 'replicate'):
+        raise ValueError(f'Unrecognized padding mode: {mode}')
+    parts = stream_parts(frames, in_nc)
+    if n_pad > 0:
+        head, n = [], 0
+        for _, x in parts:
+            head.append(x.clone())              # (the caller may reuse its buffer for the next frame)
+            n += x.shape[0]
+            if n >= n_pad + 1:
+                break
+        if n < n_pad + 1:
+            raise ValueError(f'infer_stream: {n} frame(s), but num_pad_front = {n_pad} needs at least {n_pad + 1}')
+        head = torch.cat(head, 0)
+        if mode == 'reflect':
+            yield head[1:1 + n_pad].flip(0)
+        else:
+            yield head[:1].expand(n_pad, -1, -1, -1).contiguous()
+        yield head
+    for _, x in parts:
+        yield x
+
+
 class BaseModel:
     def __init__(self, opt):
         self.opt = opt

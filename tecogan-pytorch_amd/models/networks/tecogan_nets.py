@@ -312,6 +312,11 @@ class _StepPlan:
         L.check(L.lib().tg_frnet_plan_chain_rearms(self.handle, ctypes.byref(r), ctypes.byref(w)), 'tg_frnet_plan_chain_rearms')
         return r.value, w.value
 
+    def hold_chain_rearm(self, hold):
+        """While held, frames enqueued on a fallen-back plan neither count towards the back-off nor arm the one-launch
+        body again (tg_frnet_plan_hold_chain_rearm): infer_stream repairs a faulted batch under it."""
+        L.check(L.lib().tg_frnet_plan_hold_chain_rearm(self.handle, 1 if hold else 0), 'tg_frnet_plan_hold_chain_rearm')
+
     def __del__(self):
         try:
             if getattr(self, 'handle', None):
@@ -322,6 +327,372 @@ class _StepPlan:
 
 # infer_sequence: most frame pairs (over all clips of the call) in a clip's FIRST batched flow pass
 FNET_FIRST_PASS_FRAMES = 8
+
+# infer_stream: ring slots = batches enqueued and not yet handed to the caller.  While batch b is in the caller's hands
+# batches b+1 and b+2 are in flight (two flow slots' worth of work, ~11 ms of GPU time at 134x320), so the input is
+# never pulled more than three internal batches ahead of what has been yielded.
+STREAM_SLOTS = 3
+
+
+def stream_batch_sizes(fnet_batch=None):
+    """(frames of the first internal batch, frames of every later one) of a single-clip stream: the partition
+    infer_sequence(pipeline=True) uses, which does not depend on the clip length -- the first batch is the first flow
+    pass (at most FNET_FIRST_PASS_FRAMES pairs) plus frame 0, which needs no flow; later ones are TG_FNET_BATCH frames;
+    the last is whatever is left."""
+    if fnet_batch is None:
+        fnet_batch = int(os.environ.get('TG_FNET_BATCH', '8'))
+    later = max(1, int(fnet_batch))
+    return max(1, min(later, FNET_FIRST_PASS_FRAMES)) + 1, later
+
+
+def stream_frames(item, in_nc=3):
+    """One input item of infer_stream -> (kind, tensor with a leading frame axis).
+    kind 'u8': (h,w,c) / (n,h,w,c) uint8 on the host (numpy or torch) -> (n,h,w,c);
+    kind 'f32': (c,h,w) / (n,c,h,w) float32 in [0,1], host or device -> (n,c,h,w).
+    Anything else is a ValueError."""
+    x = item
+    if isinstance(x, np.ndarray):
+        if x.dtype not in (np.uint8, np.float32):
+            raise ValueError(f'infer_stream: frames are uint8 (h,w,c) or float32 (c,h,w); got numpy {x.dtype}')
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    if not torch.is_tensor(x):
+        raise ValueError(f'infer_stream: a frame is a numpy array or a torch tensor, got {type(item).__name__}')
+    if x.dim() not in (3, 4):
+        raise ValueError(f'infer_stream: a frame has 3 axes and a chunk of frames 4; got shape {tuple(x.shape)}')
+    if x.dim() == 3:
+        x = x.unsqueeze(0)
+    if x.dtype == torch.uint8:
+        if x.is_cuda:
+            raise ValueError('infer_stream: uint8 frames are taken from the host (they go up as bytes)')
+        if x.shape[3] != in_nc:
+            raise ValueError(f'infer_stream: uint8 frames are (h,w,{in_nc}); got shape {tuple(x.shape[1:])}')
+        return 'u8', x
+    if x.dtype == torch.float32:
+        if x.shape[1] != in_nc:
+            raise ValueError(f'infer_stream: float32 frames are ({in_nc},h,w); got shape {tuple(x.shape[1:])}')
+        return 'f32', x
+    raise ValueError(f'infer_stream: frames are uint8 (h,w,c) or float32 (c,h,w); got {x.dtype}')
+
+
+class StreamFormat:
+    """Form of a stream's frames, fixed by its first item: kind, size, and host or device.  check() refuses an item
+    of another form or size (ValueError) before any frame of it is taken."""
+
+    def __init__(self, kind, x):
+        self.kind, self.cuda = kind, bool(x.is_cuda)
+        self.h, self.w = (x.shape[1], x.shape[2]) if kind == 'u8' else (x.shape[2], x.shape[3])
+
+    def check(self, kind, x):
+        h, w = (x.shape[1], x.shape[2]) if kind == 'u8' else (x.shape[2], x.shape[3])
+        if (h, w) != (self.h, self.w):
+            raise ValueError(f'infer_stream: frame size changed mid-stream: {h}x{w} after {self.h}x{self.w}')
+        if kind != self.kind or bool(x.is_cuda) != self.cuda:
+            raise ValueError('infer_stream: every item of a stream has the form of the first '
+                             f"({self.kind}, {'device' if self.cuda else 'host'})")
+
+
+def stream_parts(frames, in_nc=3):
+    """Lazily: (kind, tensor (n, ...)) for every non-empty item of `frames`, each checked against the first."""
+    fmt = None
+    for item in frames:
+        kind, x = stream_frames(item, in_nc)
+        if fmt is None:
+            fmt = StreamFormat(kind, x)
+        else:
+            fmt.check(kind, x)
+        if x.shape[0]:
+            yield kind, x
+
+
+def stream_rebatch(parts, first, later):
+    """Cut a lazy sequence of (kind, tensor (n, ...)) parts into the engine's batches WITHOUT knowing the length: yields
+    (batch index, offset inside the batch, piece, batch full) piece by piece, and pulls the next part only when the
+    previous one has been handed out entirely.  The last batch is whatever has been handed out when the input ends."""
+    b, fill, size = 0, 0, first
+    for _, x in parts:
+        pos, n = 0, x.shape[0]
+        while pos < n:
+            m = min(size - fill, n - pos)
+            piece, off = x[pos:pos + m], fill
+            pos, fill = pos + m, fill + m
+            full = fill == size
+            if full:
+                nb, fill, size = b, 0, later
+                b += 1
+                yield nb, off, piece, True
+            else:
+                yield b, off, piece, False
+
+
+class StreamRing:
+    """Slot bookkeeping of infer_stream: batch b lives in slot b % slots from submit() to retire(); at most `slots`
+    batches are in flight, retired in order."""
+
+    def __init__(self, slots=STREAM_SLOTS):
+        self.slots, self.inflight = slots, []       # inflight: [batch index, first frame, frames], oldest first
+        self.next_batch, self.next_frame = 0, 0
+
+    def full(self):
+        return len(self.inflight) >= self.slots
+
+    def slot(self, b):
+        return b % self.slots
+
+    def submit(self, cnt):
+        if self.full():
+            raise RuntimeError('infer_stream: no free ring slot')
+        rec = (self.next_batch, self.next_frame, cnt)
+        self.inflight.append(rec)
+        self.next_batch, self.next_frame = self.next_batch + 1, self.next_frame + cnt
+        return rec
+
+    def oldest(self):
+        return self.inflight[0]
+
+    def retire(self):
+        return self.inflight.pop(0)
+
+
+class _StreamEngine:
+    """State of one FRNet.infer_stream (see there).  Everything the device touches is allocated once, at the first
+    frame: STREAM_SLOTS slots of {LR batch + the frame before it, uint8 frames on the device, pinned uint8 frames,
+    HR state snapshot, input staging, events}, and the HR ping-pong pair."""
+
+    def __init__(self, net, frames, device, on_fault):
+        if on_fault not in ('rerun', 'raise'):
+            raise ValueError(f"on_fault must be 'rerun' or 'raise', got {on_fault!r}")
+        self.net, self.frames, self.on_fault = net, frames, on_fault
+        self.dev = _norm_device(device if device is not None else next(net.parameters()).device)
+        self.closed, self.warned, self.reruns = False, False, 0
+        self.ring = StreamRing()
+        self.first, self.later = stream_batch_sizes()
+        self.plan, self.pending_dl, self.prev_rec = None, None, None
+
+    # -- allocation (once) ---------------------------------------------------------------------------------------
+    def _open(self, kind, x):
+        net, dev = self.net, self.dev
+        c, s, ns = net.in_nc, net.scale, self.ring.slots
+        self.kind, self.in_cuda = kind, bool(x.is_cuda)
+        self.h, self.w = (x.shape[1], x.shape[2]) if kind == 'u8' else (x.shape[2], x.shape[3])
+        h, w, m = self.h, self.w, max(self.first, self.later)
+        self.wk = net._weights_key()
+        self.plan = net._get_plan(1, h, w, dev, wk=self.wk)
+        self.fplans = {}
+        self.lib = L.lib()
+        self.main = torch.cuda.current_stream(dev)
+        self.side, self.copy = net._side_stream(dev), net._copy_stream(dev)
+        self.lr = torch.empty(ns, m + 1, c, h, w, dtype=torch.float32, device=dev)      # [slot][0] = the frame before the batch
+        self.hr = [torch.zeros(1, c, s * h, s * w, dtype=torch.float32, device=dev),
+                   torch.empty(1, c, s * h, s * w, dtype=torch.float32, device=dev)]
+        self.snap = torch.empty(ns, 1, c, s * h, s * w, dtype=torch.float32, device=dev)
+        self.u8 = torch.empty(ns, m, s * h, s * w, c, dtype=torch.uint8, device=dev)
+        self.host_out = torch.empty(ns, m, s * h, s * w, c, dtype=torch.uint8, pin_memory=True)
+        if kind == 'u8':
+            self.stage = torch.empty(ns, m, h, w, c, dtype=torch.uint8, pin_memory=True)
+            self.dev_in = torch.empty(ns, m, h, w, c, dtype=torch.uint8, device=dev)
+        elif not self.in_cuda:
+            self.stage = torch.empty(ns, m, c, h, w, dtype=torch.float32, pin_memory=True)
+        self.zflow = torch.zeros(2 * self.plan.fh * self.plan.fw, dtype=torch.float32, device=dev)
+        self.fsz = 2 * self.plan.fh * self.plan.fw * 4
+        ev = lambda: [torch.cuda.Event() for _ in range(ns)]
+        self.ev_in, self.ev_f, self.ev_s, self.ev_out = ev(), ev(), ev(), ev()
+        self.ev_arrive = torch.cuda.Event()
+        self.side.wait_stream(self.main)            # weights, the zeroed state and the rings are ready
+        self.copy.wait_stream(self.main)
+
+    def _fplan(self, npair):
+        fp = self.fplans.get(npair)
+        if fp is None:
+            if self.net._weights_key() != self.wk:
+                raise RuntimeError('infer_stream: the weights changed while the stream was live')
+            fp = self.fplans[npair] = self.net._get_plan(npair, self.h, self.w, self.dev, fnet_only=True, wk=self.wk)
+        return fp
+
+    # -- input ---------------------------------------------------------------------------------------------------
+    def _take(self, b, off, piece):
+        """A piece of the batch being filled: host frames into the slot's pinned staging (the caller's buffer is free
+        again when this returns), device frames straight into the LR slot on the copy stream."""
+        sl, n = self.ring.slot(b), piece.shape[0]
+        if not self.in_cuda:
+            self.stage[sl, off:off + n].copy_(piece)
+            return
+        piece = piece.contiguous()
+        self.ev_arrive.record(torch.cuda.current_stream(self.dev))
+        self.copy.wait_event(self.ev_arrive)
+        with torch.cuda.stream(self.copy):
+            self.lr[sl, 1 + off:1 + off + n].copy_(piece, non_blocking=True)
+        piece.record_stream(self.copy)
+
+    def _upload(self, rec):
+        b, i0, cnt = rec
+        sl = self.ring.slot(b)
+        with torch.cuda.stream(self.copy):
+            if b == 0:
+                self.lr[sl, 0].zero_()                                   # frame -1 = zeros (tecogan_nets.py:266)
+            else:
+                pb, _, pcnt = self.prev_rec
+                self.lr[sl, 0].copy_(self.lr[self.ring.slot(pb), pcnt], non_blocking=True)
+            if self.kind == 'u8':
+                self.dev_in[sl, :cnt].copy_(self.stage[sl, :cnt], non_blocking=True)
+                L.check(self.lib.tg_dequantize_u8_hwc(self.dev_in[sl].data_ptr(), self.lr[sl, 1].data_ptr(), cnt,
+                                                      self.net.in_nc, self.h, self.w, self.copy.cuda_stream),
+                        'tg_dequantize_u8_hwc')
+            elif not self.in_cuda:
+                self.lr[sl, 1:1 + cnt].copy_(self.stage[sl, :cnt], non_blocking=True)
+            self.ev_in[sl].record(self.copy)
+        self.prev_rec = rec
+
+    # -- launches of one batch: infer_sequence(pipeline=True)'s, on this slot's buffers ---------------------------------
+    def _frame(self, i, sl, j, flow_ptr):
+        hr = self.hr
+        L.check(self.lib.tg_frnet_step_srnet(self.plan.handle, flow_ptr, self.lr[sl, 1 + j].data_ptr(),
+                                             hr[i & 1].data_ptr(), hr[(i + 1) & 1].data_ptr(),
+                                             self.u8[sl, j].data_ptr(), self.main.cuda_stream), 'tg_frnet_step_srnet')
+
+    def _compute(self, rec):
+        b, i0, cnt = rec
+        sl, ns = self.ring.slot(b), self.ring.slots
+        main, side, lr = self.main, self.side, self.lr
+        self._flush_download()                      # (of the batch before: its successor's upload is queued by now)
+        side.wait_event(self.ev_in[sl])
+        main.wait_event(self.ev_in[sl])
+        with torch.cuda.stream(main):
+            self.snap[sl].copy_(self.hr[i0 & 1], non_blocking=True)     # what a rerun of this batch starts from
+        if i0 == 0:
+            self._frame(0, sl, 0, self.zflow.data_ptr())
+        f0 = 1 if i0 == 0 else 0
+        npair = cnt - f0
+        if npair > 0:
+            fplan = self._fplan(npair)
+            if b >= 2:
+                side.wait_event(self.ev_s[(b - 2) % ns])               # flow slot b & 1 consumed by batch b - 2
+            L.check(self.lib.tg_frnet_step_phase(fplan.handle, 1, b & 1, lr[sl, f0 + 1].data_ptr(),
+                                                 lr[sl, f0].data_ptr(), None, None, None, side.cuda_stream),
+                    'tg_frnet_step_phase(1)')
+            self.ev_f[sl].record(side)
+            main.wait_event(self.ev_f[sl])
+            flow0 = self.lib.tg_frnet_plan_flow(fplan.handle, b & 1)
+            for j in range(f0, cnt):
+                self._frame(i0 + j, sl, j, flow0 + (j - f0) * self.fsz)
+        self.ev_s[sl].record(main)
+        self.pending_dl = rec
+
+    def _flush_download(self):
+        """The download of the batch computed last goes onto the copy stream BEHIND the upload of the batch after it
+        (when there is one): a download waits for its batch's last frame, and an upload queued behind it would hold the
+        next flow pass back until then."""
+        rec, self.pending_dl = self.pending_dl, None
+        if rec is None:
+            return
+        b, _, cnt = rec
+        sl = self.ring.slot(b)
+        self.copy.wait_event(self.ev_s[sl])
+        with torch.cuda.stream(self.copy):
+            self.host_out[sl, :cnt].copy_(self.u8[sl, :cnt], non_blocking=True)
+            self.ev_out[sl].record(self.copy)
+
+    # -- faults --------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _timed_out(fn, *args):
+        """Run fn; a recorded time-out of the one-launch body comes back as a value, every other error is raised."""
+        try:
+            fn(*args)
+        except L.TecoganHipError as e:
+            if 'timed out' not in str(e):
+                raise
+            return e
+        return None
+
+    def _drain(self):
+        for st in (self.main, self.side, self.copy):
+            st.synchronize()
+
+    def _recover(self, err):
+        """The frames enqueued since the last clean check are invalid: those of the batches in flight, never one that
+        was yielded.  Drain, restore the HR state the oldest of them started from, and enqueue them all again with the
+        plan's re-arm held off -- one launch per layer, which cannot time out."""
+        if self.on_fault != 'rerun':
+            raise err
+        if not self.warned:
+            import warnings
+            warnings.warn('infer_stream: %s -- the batches in flight are computed again with one launch per layer' % err,
+                          RuntimeWarning)
+            self.warned = True
+        self.reruns += 1
+        self._drain()
+        self.plan.chain_state()                     # faults of launches that were still queued: counted, not reported
+        self.pending_dl = None                      # every batch in flight is downloaded again
+        self.plan.hold_chain_rearm(True)
+        try:
+            _, i0, _ = self.ring.oldest()
+            with torch.cuda.stream(self.main):
+                self.hr[i0 & 1].copy_(self.snap[self.ring.slot(self.ring.oldest()[0])], non_blocking=True)
+            for rec in list(self.ring.inflight):
+                self._compute(rec)
+        finally:
+            self.plan.hold_chain_rearm(False)
+
+    def _submit(self, cnt):
+        rec = self.ring.submit(cnt)
+        self._upload(rec)
+        err = self._timed_out(self._compute, rec)
+        if err is not None:
+            self._recover(err)                      # (enqueues rec again as well: it is in flight)
+
+    def _retire(self):
+        b, _, cnt = self.ring.oldest()
+        sl = self.ring.slot(b)
+        while True:
+            if self.pending_dl is not None and self.pending_dl[0] == b:
+                self._flush_download()              # nothing came after it
+            self.ev_out[sl].synchronize()
+            err = self._timed_out(self.plan.check_chain)
+            if err is None:
+                break
+            self._recover(err)
+        self.ring.retire()
+        return self.host_out[sl, :cnt].numpy()
+
+    # -- the generator -------------------------------------------------------------------------------------------
+    def run(self):
+        # (no torch.no_grad() around the yields: it would leak into the caller between them; nothing here records a graph)
+        try:
+            pending = 0                             # frames taken into the batch being filled
+            for b, off, piece, full in stream_rebatch(stream_parts(self.frames, self.net.in_nc),
+                                                      self.first, self.later):
+                if self.plan is None:
+                    self.net.check_faults()         # a fault of an EARLIER clip is never this stream's to repair
+                    self._open('u8' if piece.dtype == torch.uint8 else 'f32', piece)
+                self._take(b, off, piece)
+                pending = off + piece.shape[0]
+                if not full:
+                    continue
+                self._submit(pending)
+                pending = 0
+                if self.ring.full():
+                    yield self._retire()
+            if pending:
+                self._submit(pending)               # the last batch: whatever is left
+            while self.ring.inflight:
+                yield self._retire()
+        finally:
+            self._close()
+
+    def _close(self):
+        self.closed = True
+        if self.plan is None:
+            return
+        try:
+            # the side and copy streams use memory the caching allocator knows only by its allocation stream:
+            # nothing is released before all three are idle
+            self._drain()
+            self.main.wait_stream(self.side)
+            self.main.wait_stream(self.copy)
+            if self.ring.inflight:
+                self.plan.chain_state()             # a fault in frames nobody will see: counted, the plan has fallen back
+        finally:
+            for name in ('lr', 'hr', 'snap', 'u8', 'host_out', 'stage', 'dev_in', 'zflow'):
+                self.__dict__.pop(name, None)
 
 
 class FRNet(nn.Module):
@@ -339,6 +710,7 @@ class FRNet(nn.Module):
         self.srnet = SRNet(in_nc, out_nc, nf, nb, self.upsample_func, self.scale)
         self._plan = {}
         self._plan_key = None
+        self._stream_ref = None
 
     # -- precision of the inference frame -------------
     @property
@@ -579,6 +951,49 @@ class FRNet(nn.Module):
             out = u8.cpu().numpy()
         self._get_plan(k, h, w, dev).check_chain()   # (the clip has been synchronised: a 4-byte read)
         return out.transpose(1, 0, 2, 3, 4) if multi else out[:, 0]
+
+    def infer_stream(self, frames, device=None, on_fault='rerun'):
+        """Super-resolve a clip of ANY length in bounded memory: a generator over `frames` (any iterable, pulled lazily)
+        that yields (m, s*h, s*w, 3) uint8 numpy chunks in order, as many frames in total as it consumed.
+
+        frames: each item is one LR frame or a chunk of LR frames, either (h,w,3) / (n,h,w,3) uint8 on the host (numpy
+        or torch: what a decoder gives; the bytes go up as they are and tg_dequantize_u8_hwc divides by 255 on the
+        device) or (3,h,w) / (n,3,h,w) float32 in [0,1] on the host or the device (what prepare_inference_data makes).
+        The first item fixes form and size; an item of another size or form is a ValueError raised before any frame of
+        it is enqueued.  Host items are copied into pinned staging when they are pulled: the caller's buffer is its own
+        again at once.
+
+        The frames are those of infer_sequence(pipeline=True) on the concatenated clip, BIT FOR BIT, whatever the
+        length and however the input is chunked: the same launches in the same batch partition (stream_batch_sizes:
+        that partition never depended on the clip length), frame 0 on the zero flow ahead of the first flow pass, two
+        flow slots on the side stream, SRNet frame by frame on the caller's stream, uploads and downloads on the copy
+        stream.  Chunk sizes are the engine's batches, not the input's.
+
+        A YIELDED ARRAY IS A VIEW OF A PINNED RING SLOT: it is valid until the generator is advanced again (or closed);
+        copy what you keep.  The rings -- STREAM_SLOTS slots of an LR batch, its uint8 frames on the device and in
+        pinned memory, an HR state snapshot -- are allocated once, at the first frame; nothing is allocated per batch
+        and nothing grows with the length.  The input is never pulled more than STREAM_SLOTS internal batches ahead of
+        what has been yielded.
+
+        on_fault: a batch is yielded after its download has completed and the plan's fault counter has been read.  When
+        the one-launch SRNet body recorded a time-out (see infer_sequence), 'rerun' (default) drains the streams,
+        restores the HR state from the snapshot taken at the start of the oldest batch in flight and enqueues the
+        batches in flight again -- their inputs are still in the ring -- with the plan's re-arm held off, so the repair
+        runs one launch per layer, which cannot time out; one RuntimeWarning per stream.  Frames already yielded are
+        never touched.  A body that re-arms later in the stream (_StepPlan.set_chain_rearm) and faults again is repaired
+        the same way.  'raise': TecoganHipError at that batch.
+
+        One stream per network at a time: opening a second one while one is live raises RuntimeError.  The stream keeps
+        the plans of the weights it was opened with (do not update the weights under it).  Closing it early -- close(),
+        an exception from `frames`, a bad item -- drains all three streams before the rings are released and leaves the
+        network ready for the next call.  Single clips, host output only; precision='fp16' as for infer_sequence."""
+        import weakref
+        cur = self._stream_ref() if self._stream_ref is not None else None
+        if cur is not None and not cur.closed:
+            raise RuntimeError('infer_stream: this network already has a live stream (one at a time: close it first)')
+        eng = _StreamEngine(self, frames, device, on_fault)
+        self._stream_ref = weakref.ref(eng)
+        return eng.run()
 
     def check_faults(self):
         """Call after synchronising: raises TecoganHipError if any cached frame plan recorded a fault

@@ -6,7 +6,7 @@ import torch
 
 from .. import ops
 from . import train_graph as TG
-from .base_model import BaseModel
+from .base_model import BaseModel, front_pad_stream
 from .networks import define_generator
 from .optim import Adam, define_criterion, define_lr_schedule, pointwise_loss
 
@@ -91,6 +91,25 @@ class VSRModel(BaseModel):
         else:
             hr_seq = self.net_G(lr_data, self.device)
         return hr_seq[n_pad_front:]
+
+    def infer_stream(self, frames):
+        """infer() for a clip of any length (FRNet.infer_stream): `frames` is an iterable of LR frames or chunks, uint8
+        (h,w,3) or float32 (3,h,w); yields (m,H,W,3) uint8 chunks -- views of the generator's pinned ring, valid until
+        the next one is asked for.  The temporal padding of the front (test.padding_mode / num_pad_front) is applied
+        lazily: the first n_pad + 1 frames are buffered, the padded prefix runs first, its n_pad outputs are dropped."""
+        mode = self.opt['test'].get('padding_mode', 'reflect')
+        skip = self.opt['test'].get('num_pad_front', 0)
+        self.net_G.eval()
+        gen = self.net_G.infer_stream(front_pad_stream(frames, mode, skip, self.net_G.in_nc), self.device)
+        try:
+            for chunk in gen:
+                if skip >= len(chunk):
+                    skip -= len(chunk)
+                    continue
+                yield chunk[skip:]
+                skip = 0
+        finally:
+            gen.close()
 
     def save(self, current_iter):
         self.sync_log()          # (a pending fault check must run before weights are written)

@@ -716,6 +716,12 @@ int tg_bn_lrelu_train_bwd(const float* x, const float* y, const float* dy,
                           const float* save_invstd, float slope, float* dx,
                           float* dgamma, float* dbeta, int accumulate, float* scratch2c,
                           int n, int c, int hw, tg_stream_t stream);
+/* Host only, no device work: the launch form the per-channel reductions of the two entries above take for this
+ * shape (the launchers call the same rule).  *slices = equal slices of the batch reduced by separate workgroups
+ * (1: one workgroup per channel; 2..8: partial results parked in y / dx and merged by a second launch; the
+ * backward with dx == NULL always uses 1), *threads = workgroup size (256 | 1024) for the n / *slices images of
+ * one slice.  Tests ask it which path a shape selects. */
+int tg_bn_launch_geometry(int n, int c, int hw, int* threads, int* slices);
 /* SyncBatchNorm halves (base_model.py:133): per-channel reductions exposed so the host can
  * exchange the packed vectors over RCCL in between.
  *   forward : tg_bn_local_stats -> stats2c = [mean | centred sum of squares] of THIS rank's

@@ -146,6 +146,7 @@ SIGNATURES = {
     'tg_div_scalar': (I, [P, P, F, I64, P]),
     'tg_bn_lrelu_train_fwd': (I, [P, P, P, P, P, F, F, F, P, P, P, I, I, I, P]),
     'tg_bn_lrelu_train_bwd': (I, [P, P, P, P, P, P, F, P, P, P, I, P, I, I, I, P]),
+    'tg_bn_launch_geometry': (I, [I, I, I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'tg_bn_local_stats': (I, [P, P, I, I, I, P]),
     'tg_bn_merge_stats': (I, [P, I, F, F, F, P, P, P, P, I, P]),
     'tg_bn_lrelu_apply': (I, [P, P, P, P, P, F, P, I, I, I, P]),

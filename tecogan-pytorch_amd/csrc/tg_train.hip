@@ -977,6 +977,16 @@ extern "C" int tg_axpy(float* y, const float* x, float a, int64_t n, tg_stream_t
   return check_launch("axpy");
 }
 
+// host only: the launch form bn_threads / bn_slices pick for this shape (the two functions the launchers below call)
+extern "C" int tg_bn_launch_geometry(int n, int c, int hw, int* threads, int* slices) {
+  TG_REQUIRE(threads && slices, TG_E_ARG, "bn_launch_geometry: null pointer");
+  TG_REQUIRE(n > 0 && c > 0 && hw > 0, TG_E_SHAPE, "bn_launch_geometry: n=%d c=%d hw=%d", n, c, hw);
+  const int ns = bn_slices(n, c, hw);
+  *slices = ns;
+  *threads = bn_threads(n / ns, hw);
+  return TG_OK;
+}
+
 extern "C" int tg_bn_lrelu_train_fwd(const float* x, const float* gamma, const float* beta,
                                      float* running_mean, float* running_var, float momentum,
                                      float eps, float slope, float* y, float* save_mean,

@@ -506,6 +506,27 @@ int tg_quantize_u8_hwc(const float* x, uint8_t* y, int c, int h, int w,
 int tg_dequantize_u8_hwc(const uint8_t* x, float* y, int n, int c, int h, int w,
                          tg_stream_t stream);
 
+/* Planar YUV 4:2:0, 8 bit (I420), in and out of FRNet.infer_stream; the reference has no
+ * counterpart (it reads and writes PNG folders only).  A frame is the Y plane h*w, then U, then V, each ch*cw with
+ * ch = ceil(h/2), cw = ceil(w/2), tightly packed; frame k of a batch starts at k * (h*w + 2*ch*cw).
+ *   matrix: Kr, Kb = 0.299, 0.114 (BT601) or 0.2126, 0.0722 (BT709); Kg = 1 - Kr - Kb.
+ *   full_range 0: Y offset 16, scales 219 (luma) and 224 (chroma); 1: offset 0, scales 255.
+ *   siting: where a chroma sample sits in its 2x2 luma block: in the centre (y4m C420jpeg), or on the left luma
+ *   column and between the rows (y4m C420mpeg2).
+ * Any other enum value, a null pointer or n < 1 is TG_E_ARG. */
+enum { TG_YUV_BT601 = 0, TG_YUV_BT709 = 1 };
+enum { TG_YUV_CENTER = 0, TG_YUV_LEFT = 1 };
+/* yuv (n frames I420, h x w, any h, w >= 2) -> rgb_chw (n,3,h,w) fp32 in [0,1]: chroma up-sampled bilinearly in exact
+ * integers (weights (1,3)/(3,1) per axis around a centred sample, (4)/(2,2) along a co-sited axis, indices clamped),
+ * one fp32 matrix step, clamp.  Within 2e-6 of the fp64 formula. */
+int tg_yuv420_to_rgb_f32(const uint8_t* yuv, float* rgb_chw, int n, int h, int w, int matrix, int full_range,
+                         int siting, tg_stream_t stream);
+/* rgb_hwc (n,H,W,3) uint8 -> yuv (n frames I420, H x W; H and W even, else TG_E_ARG), exact integer arithmetic:
+ * Q = rint(M * 65536); Y = clip((Q_Y.RGB + (yo << 16) + 2^15) >> 16); chroma from the sum S of the 2x2 block
+ * (centre: shift 18) or of (1,2,1) x 2 rows around the left column, x-1 clamped (left: shift 19), plus 128. */
+int tg_rgb_u8_to_yuv420(const uint8_t* rgb_hwc, uint8_t* yuv, int n, int H, int W, int matrix, int full_range,
+                        int siting, tg_stream_t stream);
+
 /* MetricCalculator.compute_PSNR (codes/metrics/metric_calculator.py:228-244) on uint8 HWC
  * frames resident on the device: sse[f] = sum of squared differences of frame f, exact
  * (integers), on the Y channel of rgb_to_ycbcr (codes/utils/data_utils.py:56-77) when

@@ -15,6 +15,8 @@ ABI_MAJOR = 2            # include/tecogan_hip.h TG_ABI_MAJOR
 ACT_NONE, ACT_RELU, ACT_LRELU02, ACT_TANH24 = 0, 1, 2, 3
 UP_NONE, UP_BICUBIC, UP_BILINEAR = 0, 1, 2
 PREC_F32, PREC_F16 = 0, 1
+YUV_MATRIX = {'bt601': 0, 'bt709': 1}            # TG_YUV_BT601 / TG_YUV_BT709
+YUV_SITING = {'center': 0, 'left': 1}            # TG_YUV_CENTER / TG_YUV_LEFT
 
 P, I, I64, F, SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 
@@ -93,6 +95,8 @@ SIGNATURES = {
     'tg_maxpool2_fwd': (I, [P, P, I, I, I, P]),
     'tg_quantize_u8_hwc': (I, [P, P, I, I, I, P]),
     'tg_dequantize_u8_hwc': (I, [P, P, I, I, I, I, P]),
+    'tg_yuv420_to_rgb_f32': (I, [P, P, I, I, I, I, I, I, P]),
+    'tg_rgb_u8_to_yuv420': (I, [P, P, I, I, I, I, I, I, P]),
     'tg_psnr_sse_u8': (I, [P, P, P, I, I, I, I, P]),
     'tg_luma_u8': (I, [P, P, I64, P]),
     'tg_lpips_conv_fwd': (I, [P, P, I, P, P, P, P, I, I, I, I, I, I, I, I, P]),

@@ -1,0 +1,274 @@
+// Planar YUV 4:2:0 (I420, 8 bit) in and out of the stream: what a decoder hands over and an
+// encoder takes, converted on the device so that 1.5 bytes per pixel cross PCIe instead of 3.
+//
+//   tg_yuv420_to_rgb_f32: I420 -> fp32 CHW RGB in [0,1] (the LR slot of infer_stream).  Chroma is up-sampled
+//     bilinearly in exact integers (sixteenths), then ONE fp32 matrix step, then the clamp: no uint8 RGB in between.
+//   tg_rgb_u8_to_yuv420:  uint8 HWC RGB (what the HR tail writes) -> I420 in exact 16.16 integer arithmetic: the
+//     specification is the integer formula itself, tests/yuv_ref.py restates it in numpy and the bytes must be equal.
+//
+// Both are pure streaming kernels.  A thread owns whole chroma samples: a 2-row x 4-pixel strip on the way out (two U
+// and two V samples, 24 bytes read, 12 written), one row x 4 pixels on the way in (12 floats written).  The wide
+// accesses (dwords of RGB / Y, 16-bit chroma pairs, float4 rows) are taken only where every address is provably
+// aligned -- width a multiple of 4 and aligned base pointers, which makes the row stride 3W, the plane offsets and
+// the frame stride multiples of 4 as well; every other shape (W = 2 mod 4: rows 2-byte aligned; odd sizes: odd plane
+// offsets) takes the byte-wide form of the same kernel.
+#include "tg_common.h"
+
+namespace tg {
+
+struct yuv_q {          // rint(M * 65536) of the RGB -> YCbCr matrix, rows Y / Cb / Cr, and the luma offset
+  int y[3], cb[3], cr[3], yo;
+};
+
+struct yuv_f {          // the inverse step on integers: R = ky*(Y-yo) + rv*dv ... with du, dv = C16 - 2048 (sixteenths)
+  float ky, rv, gu, gv, bu;
+  int yo;
+};
+
+// {bt601, bt709} x {limited, full}; the four tables of DESIGN.md section 7e (tests/test_yuv_cpu.py recomputes them
+// from Kr and Kb in fp64)
+static const yuv_q Q_TABLE[2][2] = {
+    {{{16829, 33039, 6416}, {-9714, -19071, 28784}, {28784, -24103, -4681}, 16},
+     {{19595, 38470, 7471}, {-11058, -21710, 32768}, {32768, -27439, -5329}, 0}},
+    {{{11966, 40254, 4064}, {-6596, -22189, 28784}, {28784, -26145, -2639}, 16},
+     {{13933, 46871, 4732}, {-7509, -25259, 32768}, {32768, -29763, -3005}, 0}}};
+
+static yuv_f inverse_coefficients(int matrix, int full_range) {
+  const double kr = matrix == TG_YUV_BT601 ? 0.299 : 0.2126, kb = matrix == TG_YUV_BT601 ? 0.114 : 0.0722;
+  const double kg = 1.0 - kr - kb;
+  const double ys = full_range ? 255.0 : 219.0, cs16 = 16.0 * (full_range ? 255.0 : 224.0);
+  yuv_f f;
+  f.ky = (float)(1.0 / ys);
+  f.rv = (float)(2.0 * (1.0 - kr) / cs16);
+  f.bu = (float)(2.0 * (1.0 - kb) / cs16);
+  f.gu = (float)(-(2.0 * kb * (1.0 - kb) / kg) / cs16);
+  f.gv = (float)(-(2.0 * kr * (1.0 - kr) / kg) / cs16);
+  f.yo = full_range ? 0 : 16;
+  return f;
+}
+
+// clip(acc >> sh, 0, 255) of a floor shift, written as a clamp of the accumulator followed by a logical shift (the
+// same value: a negative acc gives 0, one of 256 << sh or more gives 255).  With the clamp AFTER the shift hipcc fuses
+// two neighbours into one v_ashr_pk_u8_i32, whose 16-bit result it then packed into the Y dword as if the upper half
+// of the register were zero: bytes 2 and 3 of the store came out wrong on the MI355X.
+__device__ __forceinline__ int shift_clip_u8(int acc, int sh) {
+  const int top = (256 << sh) - 1;
+  acc = acc < 0 ? 0 : (acc > top ? top : acc);
+  return (int)((unsigned)acc >> sh);
+}
+__device__ __forceinline__ int dot3(const int q[3], const int p[3]) { return q[0] * p[0] + q[1] * p[1] + q[2] * p[2]; }
+__device__ __forceinline__ float clamp01(float v) { return __builtin_fminf(__builtin_fmaxf(v, 0.f), 1.f); }
+
+// ---- RGB uint8 HWC -> I420 ---------------------------------------------------------------------------------------
+// thread = rows 2j, 2j+1 x pixels 4*tx .. 4*tx+3 of frame k.  H and W are even, so a strip holds 2 or 4 pixels.
+template <bool VEC, bool LEFT>
+__global__ __launch_bounds__(256) void rgb_u8_to_yuv420_kernel(const uint8_t* __restrict__ rgb,
+                                                               uint8_t* __restrict__ yuv, int H, int W, int strips,
+                                                               long long total, yuv_q q) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int tx = (int)(i % strips);
+  const long long r = i / strips;
+  const int j = (int)(r % (H >> 1));
+  const long long k = r / (H >> 1);
+  const int x0 = 4 * tx, cw = W >> 1, ch = H >> 1;
+  const int npx = W - x0 < 4 ? W - x0 : 4;                        // 2 or 4
+  const long long row3 = 3LL * W;
+  const uint8_t* src = rgb + (k * H + 2 * j) * row3 + 3 * x0;
+  int p[2][4][3];
+#pragma unroll
+  for (int rr = 0; rr < 2; ++rr) {
+    if (VEC) {                                                    // 12 bytes at a 4-byte aligned address
+      const uint32_t* s4 = reinterpret_cast<const uint32_t*>(src + rr * row3);
+      const uint32_t a = s4[0], b = s4[1], c = s4[2];
+      const uint32_t by[12] = {a & 255, (a >> 8) & 255, (a >> 16) & 255, a >> 24, b & 255, (b >> 8) & 255,
+                               (b >> 16) & 255, b >> 24, c & 255, (c >> 8) & 255, (c >> 16) & 255, c >> 24};
+#pragma unroll
+      for (int e = 0; e < 12; ++e) p[rr][e / 3][e % 3] = (int)by[e];
+    } else {
+#pragma unroll
+      for (int e = 0; e < 12; ++e) p[rr][e / 3][e % 3] = e < 3 * npx ? (int)src[rr * row3 + e] : 0;
+    }
+  }
+  uint8_t* yp = yuv + k * ((long long)H * W + 2LL * ch * cw);
+  uint8_t* up = yp + (long long)H * W;
+  uint8_t* vp = up + (long long)ch * cw;
+  const int yround = (q.yo << 16) + (1 << 15);
+#pragma unroll
+  for (int rr = 0; rr < 2; ++rr) {
+    int yv[4];
+#pragma unroll
+    for (int x = 0; x < 4; ++x) yv[x] = shift_clip_u8(dot3(q.y, p[rr][x]) + yround, 16);
+    uint8_t* dst = yp + (long long)(2 * j + rr) * W + x0;
+    if (VEC) {
+      *reinterpret_cast<uint32_t*>(dst) =
+          (uint32_t)yv[0] | ((uint32_t)yv[1] << 8) | ((uint32_t)yv[2] << 16) | ((uint32_t)yv[3] << 24);
+    } else {
+#pragma unroll
+      for (int x = 0; x < 4; ++x)
+        if (x < npx) dst[x] = (uint8_t)yv[x];
+    }
+  }
+  int uo[2], vo[2];
+#pragma unroll
+  for (int c2 = 0; c2 < 2; ++c2) {
+    int s[3];
+    if (LEFT) {                                                   // (1, 2, 1) over x-1, x, x+1 at x = 2i, x-1 clamped to 0
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        int acc = 0;
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+          int left;
+          if (c2 == 1) left = p[rr][1][c];
+          else left = x0 == 0 ? p[rr][0][c] : (int)src[rr * row3 - 3 + c];      // the left neighbour's last column
+          acc += left + 2 * p[rr][2 * c2][c] + p[rr][2 * c2 + 1][c];
+        }
+        s[c] = acc;
+      }
+      uo[c2] = shift_clip_u8(dot3(q.cb, s) + (128 << 19) + (1 << 18), 19);
+      vo[c2] = shift_clip_u8(dot3(q.cr, s) + (128 << 19) + (1 << 18), 19);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        s[c] = p[0][2 * c2][c] + p[0][2 * c2 + 1][c] + p[1][2 * c2][c] + p[1][2 * c2 + 1][c];
+      uo[c2] = shift_clip_u8(dot3(q.cb, s) + (128 << 18) + (1 << 17), 18);
+      vo[c2] = shift_clip_u8(dot3(q.cr, s) + (128 << 18) + (1 << 17), 18);
+    }
+  }
+  const long long co = (long long)j * cw + 2 * tx;
+  if (VEC) {                                                      // cw and both plane offsets are even here
+    *reinterpret_cast<uint16_t*>(up + co) = (uint16_t)(uo[0] | (uo[1] << 8));
+    *reinterpret_cast<uint16_t*>(vp + co) = (uint16_t)(vo[0] | (vo[1] << 8));
+  } else {
+    up[co] = (uint8_t)uo[0];
+    vp[co] = (uint8_t)vo[0];
+    if (npx == 4) {
+      up[co + 1] = (uint8_t)uo[1];
+      vp[co + 1] = (uint8_t)vo[1];
+    }
+  }
+}
+
+// ---- I420 -> fp32 CHW RGB ----------------------------------------------------------------------------------------
+// thread = row y x pixels 4*tx .. 4*tx+3 of frame k.  The strip needs chroma columns 2*tx-1 .. 2*tx+2 of two chroma
+// rows, every index clamped into the plane (so the loads are in bounds for the pixels past an odd width too).
+template <bool VEC, bool LEFT>
+__global__ __launch_bounds__(256) void yuv420_to_rgb_f32_kernel(const uint8_t* __restrict__ yuv,
+                                                                float* __restrict__ rgb, int h, int w, int strips,
+                                                                long long total, yuv_f f) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int tx = (int)(i % strips);
+  const long long r = i / strips;
+  const int y = (int)(r % h);
+  const long long k = r / h;
+  const int x0 = 4 * tx, ch = (h + 1) >> 1, cw = (w + 1) >> 1;
+  const uint8_t* yp = yuv + k * ((long long)h * w + 2LL * ch * cw);
+  const uint8_t* up = yp + (long long)h * w;
+  const uint8_t* vp = up + (long long)ch * cw;
+  // rows: even y -> (y/2 - 1, y/2) x (1, 3); odd y -> ((y-1)/2, (y+1)/2) x (3, 1)
+  int r0 = (y & 1) ? (y - 1) >> 1 : (y >> 1) - 1, r1 = r0 + 1;
+  const int w0 = (y & 1) ? 3 : 1, w1 = 4 - w0;
+  r0 = r0 < 0 ? 0 : r0;
+  r1 = r1 > ch - 1 ? ch - 1 : r1;
+  int u[4], v[4];                                                 // vertical sums of columns 2*tx-1 .. 2*tx+2, in quarters
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    int c = 2 * tx - 1 + m;
+    c = c < 0 ? 0 : (c > cw - 1 ? cw - 1 : c);
+    u[m] = w0 * (int)up[(long long)r0 * cw + c] + w1 * (int)up[(long long)r1 * cw + c];
+    v[m] = w0 * (int)vp[(long long)r0 * cw + c] + w1 * (int)vp[(long long)r1 * cw + c];
+  }
+  int u16[4], v16[4];                                             // sixteenths
+  if (LEFT) {                                                     // even x: its own column; odd x: the two around it
+    u16[0] = 4 * u[1]; u16[1] = 2 * (u[1] + u[2]); u16[2] = 4 * u[2]; u16[3] = 2 * (u[2] + u[3]);
+    v16[0] = 4 * v[1]; v16[1] = 2 * (v[1] + v[2]); v16[2] = 4 * v[2]; v16[3] = 2 * (v[2] + v[3]);
+  } else {                                                        // the row rule again
+    u16[0] = u[0] + 3 * u[1]; u16[1] = 3 * u[1] + u[2]; u16[2] = u[1] + 3 * u[2]; u16[3] = 3 * u[2] + u[3];
+    v16[0] = v[0] + 3 * v[1]; v16[1] = 3 * v[1] + v[2]; v16[2] = v[1] + 3 * v[2]; v16[3] = 3 * v[2] + v[3];
+  }
+  int yy[4];
+  const uint8_t* ysrc = yp + (long long)y * w + x0;
+  if (VEC) {
+    const uint32_t a = *reinterpret_cast<const uint32_t*>(ysrc);
+    yy[0] = (int)(a & 255); yy[1] = (int)((a >> 8) & 255); yy[2] = (int)((a >> 16) & 255); yy[3] = (int)(a >> 24);
+  } else {
+#pragma unroll
+    for (int x = 0; x < 4; ++x) yy[x] = x0 + x < w ? (int)ysrc[x] : 0;
+  }
+  float R[4], G[4], B[4];
+#pragma unroll
+  for (int x = 0; x < 4; ++x) {
+    const float yf = f.ky * (float)(yy[x] - f.yo);
+    const float du = (float)(u16[x] - 2048), dv = (float)(v16[x] - 2048);
+    R[x] = clamp01(__builtin_fmaf(f.rv, dv, yf));
+    G[x] = clamp01(__builtin_fmaf(f.gv, dv, __builtin_fmaf(f.gu, du, yf)));
+    B[x] = clamp01(__builtin_fmaf(f.bu, du, yf));
+  }
+  const long long plane = (long long)h * w;
+  float* dst = rgb + k * 3 * plane + (long long)y * w + x0;
+  if (VEC) {
+    *reinterpret_cast<f32x4*>(dst) = f32x4{R[0], R[1], R[2], R[3]};
+    *reinterpret_cast<f32x4*>(dst + plane) = f32x4{G[0], G[1], G[2], G[3]};
+    *reinterpret_cast<f32x4*>(dst + 2 * plane) = f32x4{B[0], B[1], B[2], B[3]};
+  } else {
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+      if (x0 + x < w) {
+        dst[x] = R[x];
+        dst[plane + x] = G[x];
+        dst[2 * plane + x] = B[x];
+      }
+  }
+}
+
+static bool yuv_enums_ok(int matrix, int full_range, int siting) {
+  return (matrix == TG_YUV_BT601 || matrix == TG_YUV_BT709) && (full_range == 0 || full_range == 1) &&
+         (siting == TG_YUV_CENTER || siting == TG_YUV_LEFT);
+}
+
+}  // namespace tg
+
+extern "C" int tg_yuv420_to_rgb_f32(const uint8_t* yuv, float* rgb_chw, int n, int h, int w, int matrix,
+                                    int full_range, int siting, tg_stream_t stream) {
+  TG_REQUIRE(yuv && rgb_chw, TG_E_ARG, "yuv420_to_rgb_f32: null pointer");
+  TG_REQUIRE(n >= 1 && h >= 2 && w >= 2, TG_E_ARG, "yuv420_to_rgb_f32: n=%d h=%d w=%d (n >= 1, h, w >= 2)", n, h, w);
+  TG_REQUIRE(tg::yuv_enums_ok(matrix, full_range, siting), TG_E_ARG,
+             "yuv420_to_rgb_f32: matrix=%d full_range=%d siting=%d", matrix, full_range, siting);
+  const int strips = (w + 3) / 4;
+  const long long total = (long long)n * h * strips;
+  TG_REQUIRE(total < (1LL << 38), TG_E_SHAPE, "yuv420_to_rgb_f32: %lld strips", total);
+  const bool vec = w % 4 == 0 && (uintptr_t)yuv % 4 == 0 && (uintptr_t)rgb_chw % 16 == 0;
+  const tg::yuv_f f = tg::inverse_coefficients(matrix, full_range);
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  const hipStream_t st = (hipStream_t)stream;
+#define TG_YUV_IN(V, L) \
+  hipLaunchKernelGGL((tg::yuv420_to_rgb_f32_kernel<V, L>), grid, block, 0, st, yuv, rgb_chw, h, w, strips, total, f)
+  if (vec) { if (siting == TG_YUV_LEFT) TG_YUV_IN(true, true); else TG_YUV_IN(true, false); }
+  else { if (siting == TG_YUV_LEFT) TG_YUV_IN(false, true); else TG_YUV_IN(false, false); }
+#undef TG_YUV_IN
+  return tg::check_launch("yuv420_to_rgb_f32");
+}
+
+extern "C" int tg_rgb_u8_to_yuv420(const uint8_t* rgb_hwc, uint8_t* yuv, int n, int H, int W, int matrix,
+                                   int full_range, int siting, tg_stream_t stream) {
+  TG_REQUIRE(rgb_hwc && yuv, TG_E_ARG, "rgb_u8_to_yuv420: null pointer");
+  TG_REQUIRE(n >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, TG_E_ARG,
+             "rgb_u8_to_yuv420: n=%d H=%d W=%d (n >= 1, H and W even)", n, H, W);
+  TG_REQUIRE(tg::yuv_enums_ok(matrix, full_range, siting), TG_E_ARG,
+             "rgb_u8_to_yuv420: matrix=%d full_range=%d siting=%d", matrix, full_range, siting);
+  const int strips = (W + 3) / 4;
+  const long long total = (long long)n * (H / 2) * strips;
+  TG_REQUIRE(total < (1LL << 38), TG_E_SHAPE, "rgb_u8_to_yuv420: %lld strips", total);
+  const bool vec = W % 4 == 0 && (uintptr_t)rgb_hwc % 4 == 0 && (uintptr_t)yuv % 4 == 0;
+  const tg::yuv_q q = tg::Q_TABLE[matrix][full_range];
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  const hipStream_t st = (hipStream_t)stream;
+#define TG_YUV_OUT(V, L) \
+  hipLaunchKernelGGL((tg::rgb_u8_to_yuv420_kernel<V, L>), grid, block, 0, st, rgb_hwc, yuv, H, W, strips, total, q)
+  if (vec) { if (siting == TG_YUV_LEFT) TG_YUV_OUT(true, true); else TG_YUV_OUT(true, false); }
+  else { if (siting == TG_YUV_LEFT) TG_YUV_OUT(false, true); else TG_YUV_OUT(false, false); }
+#undef TG_YUV_OUT
+  return tg::check_launch("rgb_u8_to_yuv420");
+}

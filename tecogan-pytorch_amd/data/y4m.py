@@ -1,0 +1,160 @@
+"""YUV4MPEG2 (y4m) streams of 8-bit 4:2:0 frames: the pipe format that joins a codec to the stream,
+`ffmpeg -i in.mp4 -f yuv4mpegpipe - | python -m tecogan_pytorch_amd.main --mode infer --input - --output - | ffmpeg -i - out.mp4`.
+
+A stream is one header line `YUV4MPEG2 W<w> H<h> F<n:d> I<p> A<n:d> C<colourspace> X<comment>...`, then per frame a line
+`FRAME[ parameters]` followed by exactly frame_bytes bytes of I420 (Y, U, V planes, tightly packed).  Only progressive
+8-bit 4:2:0 with a chroma siting the device kernels implement is taken: C420jpeg (centred), C420mpeg2
+(left), and bare C420 or no C tag, which both mean centred per the format.  Everything else is refused by name."""
+import numpy as np
+
+MAGIC = b'YUV4MPEG2'
+SITING_OF_TAG = {'420jpeg': 'center', '420mpeg2': 'left', '420': 'center'}
+MAX_LINE = 4096          # a header or FRAME line longer than this is not y4m
+
+
+class Y4MError(ValueError):
+    pass
+
+
+def _read_line(f, limit=MAX_LINE):
+    """Bytes up to (not including) the next newline; None at a clean end of the stream.  Byte by byte through a
+    pipe would be slow, so readline is used where the object has it."""
+    line = f.readline(limit + 1) if hasattr(f, 'readline') else None
+    if line is None:
+        buf = bytearray()
+        while len(buf) <= limit:
+            c = f.read(1)
+            if not c:
+                break
+            buf += c
+            if c == b'\n':
+                break
+        line = bytes(buf)
+    if not line:
+        return None
+    if not line.endswith(b'\n'):
+        raise Y4MError('y4m: a line of %d bytes without a newline (truncated stream, or not y4m)' % len(line))
+    return line[:-1]
+
+
+def parse_header(line):
+    """The header line (bytes, without the newline) -> dict(w, h, tags, siting, full_range).  `tags` keeps the F, A, C
+    and X tags as written, for the writer; full_range is True / False from XCOLORRANGE, None when the header has none."""
+    parts = line.decode('ascii', 'replace').split(' ')
+    if parts[0] != MAGIC.decode():
+        raise Y4MError('y4m: the stream does not start with YUV4MPEG2')
+    w = h = None
+    tags, ctag, full = [], None, None
+    for p in parts[1:]:
+        if not p:
+            continue
+        k, v = p[0], p[1:]
+        if k == 'W':
+            w = int(v)
+        elif k == 'H':
+            h = int(v)
+        elif k == 'I':
+            if v != 'p':
+                raise Y4MError(f'y4m: I{v}: interlaced material is not supported (progressive Ip only)')
+        elif k == 'C':
+            if v not in SITING_OF_TAG:
+                why = ('more than 8 bits per sample' if any(b in v for b in ('p10', 'p12', 'p14', 'p16')) else
+                       'PAL-DV chroma siting' if v == '420paldv' else 'not 4:2:0' if not v.startswith('420') else
+                       'unknown 4:2:0 variant')
+                raise Y4MError(f'y4m: C{v}: {why} (supported: C420jpeg, C420mpeg2, C420)')
+            ctag = v
+            tags.append(p)
+        elif k in 'FA':
+            tags.append(p)
+        elif k == 'X':
+            if v.startswith('COLORRANGE='):
+                r = v[len('COLORRANGE='):]
+                if r not in ('FULL', 'LIMITED'):
+                    raise Y4MError(f'y4m: X{v}: the range is FULL or LIMITED')
+                full = r == 'FULL'
+            tags.append(p)
+        else:
+            raise Y4MError(f'y4m: unknown header tag {p!r}')
+    if w is None or h is None or w < 2 or h < 2:
+        raise Y4MError(f'y4m: the header needs W and H of at least 2 (got W={w} H={h})')
+    return {'w': w, 'h': h, 'tags': tags, 'siting': SITING_OF_TAG[ctag or '420'], 'full_range': full}
+
+
+def frame_bytes(h, w):
+    return h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)
+
+
+class Y4MReader:
+    """Frames of a y4m stream, lazily: iterating yields ONE reused (frame_bytes,) uint8 numpy buffer per frame (copy
+    what you keep; FRNet.infer_stream copies an item when it pulls it).  fileobj: anything with read / readinto --
+    a file, sys.stdin.buffer, the read end of a pipe.  Short reads are looped over; the end of the stream inside a
+    frame is an error, at a frame boundary it ends the iteration."""
+
+    def __init__(self, fileobj):
+        self.f = fileobj
+        line = _read_line(fileobj)
+        if line is None:
+            raise Y4MError('y4m: empty stream')
+        self.header = parse_header(line)
+        self.w, self.h = self.header['w'], self.header['h']
+        self.siting, self.full_range = self.header['siting'], self.header['full_range']
+        self.frame_bytes = frame_bytes(self.h, self.w)
+        self.frames_read = 0
+        self._buf = np.empty(self.frame_bytes, np.uint8)
+
+    def _fill(self, view):
+        got, n = 0, len(view)
+        readinto = getattr(self.f, 'readinto', None)
+        while got < n:
+            if readinto is not None:
+                k = readinto(view[got:])
+            else:
+                piece = self.f.read(n - got)
+                k = len(piece)
+                view[got:got + k] = piece
+            if not k:
+                raise Y4MError(f'y4m: the stream ends inside frame {self.frames_read}: {got} of {n} bytes')
+            got += k
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        line = _read_line(self.f)
+        if line is None:
+            raise StopIteration
+        if line != b'FRAME' and not line.startswith(b'FRAME '):
+            raise Y4MError(f'y4m: frame {self.frames_read}: expected a FRAME line, got {line[:32]!r}')
+        self._fill(memoryview(self._buf))
+        self.frames_read += 1
+        return self._buf
+
+
+class Y4MWriter:
+    """Writes frames of W x H after a header that carries the F, A, C and X tags of `header_of_input` (a Y4MReader's
+    .header, or None: C420jpeg and nothing else), then Ip."""
+
+    def __init__(self, fileobj, W, H, header_of_input=None):
+        if W < 2 or H < 2:
+            raise Y4MError(f'y4m: W={W} H={H}')
+        self.f, self.w, self.h = fileobj, W, H
+        self.frame_bytes = frame_bytes(H, W)
+        tags = list(header_of_input['tags']) if header_of_input else ['C420jpeg']
+        self._write_all((' '.join(['YUV4MPEG2', f'W{W}', f'H{H}'] + tags + ['Ip']) + '\n').encode('ascii'))
+
+    def _write_all(self, data):
+        view = memoryview(data)
+        while len(view):                            # (an unbuffered pipe may take less than it is given)
+            k = self.f.write(view)
+            view = view[len(view) if k is None else k:]
+
+    def write(self, frame):
+        """One I420 frame: any uint8 buffer of frame_bytes bytes."""
+        view = memoryview(np.ascontiguousarray(frame)).cast('B')
+        if len(view) != self.frame_bytes:
+            raise Y4MError(f'y4m: a {self.w}x{self.h} frame has {self.frame_bytes} bytes, got {len(view)}')
+        self._write_all(b'FRAME\n')
+        self._write_all(view)
+
+    def flush(self):
+        self.f.flush()

@@ -12,7 +12,11 @@ paired_folder_dataset.py:57-63); any iterable of such dicts can be passed to `tr
 `infer` upscales a folder of LR frames (`--input`: the frames themselves, or one sub-folder per sequence) into
 `--output` without ground truth: frames are decoded lazily, streamed through VSRModel.infer_stream in bounded memory
 (any length) and written as PNGs under the input's names.  PNG decoding and encoding bound its rate: what it prints
-is a codec number, not a GPU number.
+is a codec number, not a GPU number.  With an `--input` that is a y4m file or `-` (stdin) the clip is raw 8-bit YUV 4:2:0
+video instead (data/y4m.py): I420 frames go up as they are, are converted on the device both ways (DESIGN.md section
+7e) and leave as a y4m stream to `--output` (a file, or `-` for stdout), so a codec can sit on either side of a pipe:
+
+  ffmpeg -i in.mp4 -f yuv4mpegpipe - | python -m tecogan_pytorch_amd.main --mode infer --input - --output - | ffmpeg -i - out.mp4
 
   python -m tecogan_pytorch_amd.main --mode profile --lr_size 3x134x320 --test_speed
   python -m tecogan_pytorch_amd.main --mode infer --opt my_test.yml --input lr_frames/ --output sr_frames/
@@ -56,10 +60,16 @@ def parse_args(argv=None):
                         "the yml; absent = 'fp32').  Training is always fp32")
     p.add_argument('--input', type=str, default=None,
                    help='--mode infer: folder of LR frames (png | jpg), either the frames of one sequence or one '
-                        'sub-folder per sequence; no ground truth is needed')
+                        'sub-folder per sequence; no ground truth is needed.  Or a y4m file (8-bit 4:2:0), or - for '
+                        'a y4m stream on stdin')
     p.add_argument('--output', type=str, default=None,
                    help='--mode infer: folder the super-resolved PNGs are written to, under the names (and sub-folders) '
-                        'of the input')
+                        'of the input.  With y4m input: the y4m file to write, or - for stdout (logging then goes to '
+                        'stderr)')
+    p.add_argument('--yuv-matrix', dest='yuv_matrix', type=str, default='bt709', choices=['bt601', 'bt709'],
+                   help='y4m input: the YCbCr matrix of the clip (y4m headers do not carry it)')
+    p.add_argument('--yuv-range', dest='yuv_range', type=str, default=None, choices=['limited', 'full'],
+                   help="y4m input: the range of the clip; default: the header's XCOLORRANGE, or limited without one")
     return p.parse_args(argv)
 
 
@@ -373,6 +383,60 @@ def infer(opt, input_dir, output_dir):
     return done
 
 
+def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None):
+    """--mode infer on raw video: the y4m stream `src` (a binary file object) through VSRModel.infer_stream(yuv=...)
+    into the y4m stream `dst`, in order.  The output header carries the scaled size and the input's F, A, C and X tags.
+    Each chunk is written out of the ring slot before the generator is advanced; nothing is held beyond it.  Returns
+    the number of frames written."""
+    from .data.y4m import Y4MReader, Y4MWriter
+    from .models.networks import Yuv420
+    reader = Y4MReader(src)
+    full = reader.full_range if yuv_range is None else yuv_range == 'full'
+    spec = Yuv420(reader.h, reader.w, matrix=matrix, full_range=bool(full), siting=reader.siting)
+    model = define_model(opt)
+    s = model.net_G.scale
+    writer = Y4MWriter(dst, s * reader.w, s * reader.h, reader.header)
+    t0, k = time.time(), 0
+    for chunk in model.infer_stream(reader, yuv=spec):
+        for frame in chunk:
+            writer.write(frame)
+            k += 1
+    writer.flush()
+    model.net_G.check_faults()
+    dt = time.time() - t0
+    print(f'y4m: {k} frames {reader.w}x{reader.h} -> {s * reader.w}x{s * reader.h} '
+          f'({k / max(dt, 1e-9):.1f} frames/s, {spec.matrix} {"full" if spec.full_range else "limited"} range, '
+          f'{spec.siting} siting)', flush=True)
+    return k
+
+
+def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range):
+    """Opens the two ends of infer_y4m.  With `--output -` the y4m bytes are the ONLY thing on stdout: the descriptor
+    is set aside for them and, for the length of the run, descriptor 1 and sys.stdout lead to stderr, so that neither
+    a print nor a library's message can land in the stream."""
+    import sys
+    src = sys.stdin.buffer if input_path == '-' else open(input_path, 'rb')
+    try:
+        if output_path != '-':
+            with open(output_path, 'wb') as dst:
+                return infer_y4m(opt, src, dst, matrix, yuv_range)
+        sys.stdout.flush()
+        keep = os.dup(1)
+        py_stdout = sys.stdout
+        os.dup2(2, 1)
+        sys.stdout = sys.stderr
+        try:
+            with os.fdopen(os.dup(keep), 'wb') as dst:
+                return infer_y4m(opt, src, dst, matrix, yuv_range)
+        finally:
+            sys.stdout = py_stdout
+            os.dup2(keep, 1)
+            os.close(keep)
+    finally:
+        if src is not sys.stdin.buffer:
+            src.close()
+
+
 def profile(opt, lr_size, test_speed=False):
     """codes/main.py:210-264 protocol: FLOPs/params, then FPS of step() over 30 fresh random
     inputs with a device sync per frame."""
@@ -446,8 +510,11 @@ def main(argv=None):
         test(opt, seqs)
     elif args.mode == 'infer':
         if not args.input or not args.output:
-            raise ValueError('--mode infer needs --input DIR and --output DIR')
-        infer(opt, args.input, args.output)
+            raise ValueError('--mode infer needs --input DIR and --output DIR (or a y4m file / - for both)')
+        if args.input == '-' or os.path.isfile(args.input):
+            infer_y4m_cli(opt, args.input, args.output, args.yuv_matrix, args.yuv_range)
+        else:
+            infer(opt, args.input, args.output)
     elif args.mode == 'profile':
         profile(opt, tuple(int(v) for v in args.lr_size.split('x')), args.test_speed)
     else:

@@ -11,14 +11,15 @@ from ..utils import dist_utils
 from ..utils.data_utils import gaussian_kernel2d
 
 
-def front_pad_stream(frames, mode, n_pad, in_nc=3):
+def front_pad_stream(frames, mode, n_pad, in_nc=3, yuv=None):
     """pad_sequence for a stream whose length is not known: buffers the first n_pad + 1 frames of `frames` (items as
     FRNet.infer_stream takes them), yields the reflected / replicated prefix, the buffered frames, then the rest of the
-    stream as it comes.  A stream shorter than n_pad + 1 frames is refused (pad_sequence's assert)."""
+    stream as it comes.  A stream shorter than n_pad + 1 frames is refused (pad_sequence's assert).  yuv (a Yuv420):
+    the items are I420 frames -- 1-D: one frame, 2-D: a chunk -- and so is what is yielded."""
     from .networks.tecogan_nets import stream_parts
     if mode not in ('reflect', 'replicate'):
         raise ValueError(f'Unrecognized padding mode: {mode}')
-    parts = stream_parts(frames, in_nc)
+    parts = stream_parts(frames, in_nc, yuv)
     if n_pad > 0:
         head, n = [], 0
         for _, x in parts:
@@ -32,7 +33,7 @@ def front_pad_stream(frames, mode, n_pad, in_nc=3):
         if mode == 'reflect':
             yield head[1:1 + n_pad].flip(0)
         else:
-            yield head[:1].expand(n_pad, -1, -1, -1).contiguous()
+            yield head[:1].expand(n_pad, *head.shape[1:]).contiguous()
         yield head
     for _, x in parts:
         yield x

@@ -391,8 +391,35 @@ class StreamFormat:
                              f"({self.kind}, {'device' if self.cuda else 'host'})")
 
 
-def stream_parts(frames, in_nc=3):
-    """Lazily: (kind, tensor (n, ...)) for every non-empty item of `frames`, each checked against the first."""
+def stream_frames_yuv(item, yuv):
+    """One input item of a yuv stream -> (n, frame_bytes) uint8 host tensor: a 1-D item is one I420 frame, a 2-D item
+    a chunk of frames.  Anything else is a ValueError."""
+    x = item
+    if isinstance(x, np.ndarray):
+        if x.dtype != np.uint8:
+            raise ValueError(f'infer_stream: I420 frames are uint8; got numpy {x.dtype}')
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    if not torch.is_tensor(x):
+        raise ValueError(f'infer_stream: a frame is a numpy array or a torch tensor, got {type(item).__name__}')
+    if x.dtype != torch.uint8:
+        raise ValueError(f'infer_stream: I420 frames are uint8; got {x.dtype}')
+    if x.is_cuda:
+        raise ValueError('infer_stream: I420 frames are taken from the host (they go up as bytes)')
+    if x.dim() not in (1, 2) or x.shape[-1] != yuv.frame_bytes:
+        raise ValueError(f'infer_stream: an I420 frame of {yuv.h}x{yuv.w} is ({yuv.frame_bytes},) and a chunk '
+                         f'(n, {yuv.frame_bytes}); got shape {tuple(x.shape)}')
+    return x.unsqueeze(0) if x.dim() == 1 else x
+
+
+def stream_parts(frames, in_nc=3, yuv=None):
+    """Lazily: (kind, tensor (n, ...)) for every non-empty item of `frames`, each checked against the first.
+    yuv (a Yuv420): the items are I420 frames / chunks, kind 'yuv', each checked against the spec."""
+    if yuv is not None:
+        for item in frames:
+            x = stream_frames_yuv(item, yuv)
+            if x.shape[0]:
+                yield 'yuv', x
+        return
     fmt = None
     for item in frames:
         kind, x = stream_frames(item, in_nc)
@@ -453,14 +480,85 @@ class StreamRing:
         return self.inflight.pop(0)
 
 
+class Yuv420:
+    """Raw-video form of a stream (FRNet.infer_stream(yuv=...)): planar 8-bit YUV 4:2:0 (I420)
+    frames of h x w on the way in and of s*h x s*w on the way out.  matrix 'bt601' | 'bt709', full_range (bool),
+    siting 'center' (y4m C420jpeg) | 'left' (y4m C420mpeg2).  Frozen."""
+    __slots__ = ('h', 'w', 'matrix', 'full_range', 'siting')
+
+    def __init__(self, h, w, matrix='bt709', full_range=False, siting='left'):
+        for name, v in (('h', h), ('w', w)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 2:
+                raise ValueError(f'Yuv420: {name} is an integer >= 2, got {v!r}')
+        if matrix not in L.YUV_MATRIX:
+            raise ValueError(f'Yuv420: matrix is one of {sorted(L.YUV_MATRIX)}, got {matrix!r}')
+        if siting not in L.YUV_SITING:
+            raise ValueError(f'Yuv420: siting is one of {sorted(L.YUV_SITING)}, got {siting!r}')
+        if not isinstance(full_range, (bool, np.bool_)):
+            raise ValueError(f'Yuv420: full_range is a bool, got {full_range!r}')
+        for name, v in (('h', int(h)), ('w', int(w)), ('matrix', matrix), ('full_range', bool(full_range)),
+                        ('siting', siting)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError('Yuv420 is frozen')
+
+    def __delattr__(self, name):
+        raise AttributeError('Yuv420 is frozen')
+
+    def _key(self):
+        return (self.h, self.w, self.matrix, self.full_range, self.siting)
+
+    def __eq__(self, other):
+        return isinstance(other, Yuv420) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return 'Yuv420(h=%d, w=%d, matrix=%r, full_range=%r, siting=%r)' % self._key()
+
+    @property
+    def frame_bytes(self):
+        return self.h * self.w + 2 * ((self.h + 1) // 2) * ((self.w + 1) // 2)
+
+    def out_frame_bytes(self, scale):
+        """Bytes of a super-resolved frame (s*h and s*w are even: the scale is 2 or 4)."""
+        if scale < 1 or (scale * self.h) % 2 or (scale * self.w) % 2:
+            raise ValueError(f'Yuv420: an output frame has even sides; scale {scale} gives {scale * self.h}x{scale * self.w}')
+        return scale * self.h * scale * self.w * 3 // 2
+
+    def codes(self):
+        """(matrix, full_range, siting) as the C ABI takes them."""
+        return L.YUV_MATRIX[self.matrix], int(self.full_range), L.YUV_SITING[self.siting]
+
+
+def yuv420_planes(chunk, H, W):
+    """(Y, U, V) views of I420 frames: chunk (m, frame_bytes) -> (m,H,W), (m,ch,cw), (m,ch,cw); a single frame
+    (frame_bytes,) -> (H,W), (ch,cw), (ch,cw).  numpy or torch; nothing is copied."""
+    ch, cw = (H + 1) // 2, (W + 1) // 2
+    if chunk.shape[-1] != H * W + 2 * ch * cw:
+        raise ValueError(f'yuv420_planes: {H}x{W} frames have {H * W + 2 * ch * cw} bytes; got shape {tuple(chunk.shape)}')
+    lead = tuple(chunk.shape[:-1])
+    return (chunk[..., :H * W].reshape(lead + (H, W)),
+            chunk[..., H * W:H * W + ch * cw].reshape(lead + (ch, cw)),
+            chunk[..., H * W + ch * cw:].reshape(lead + (ch, cw)))
+
+
 class _StreamEngine:
     """State of one FRNet.infer_stream (see there).  Everything the device touches is allocated once, at the first
     frame: STREAM_SLOTS slots of {LR batch + the frame before it, uint8 frames on the device, pinned uint8 frames,
-    HR state snapshot, input staging, events}, and the HR ping-pong pair."""
+    HR state snapshot, input staging, events}, and the HR ping-pong pair.  With a Yuv420 the staging and the pinned
+    output hold I420 frames, and a slot has its I420 output on the device as well."""
 
-    def __init__(self, net, frames, device, on_fault):
+    def __init__(self, net, frames, device, on_fault, yuv=None):
         if on_fault not in ('rerun', 'raise'):
             raise ValueError(f"on_fault must be 'rerun' or 'raise', got {on_fault!r}")
+        if yuv is not None:
+            if not isinstance(yuv, Yuv420):
+                raise ValueError(f'yuv must be a Yuv420 or None, got {type(yuv).__name__}')
+            yuv.out_frame_bytes(net.scale)
+        self.yuv = yuv
         self.net, self.frames, self.on_fault = net, frames, on_fault
         self.dev = _norm_device(device if device is not None else next(net.parameters()).device)
         self.closed, self.warned, self.reruns = False, False, 0
@@ -473,7 +571,10 @@ class _StreamEngine:
         net, dev = self.net, self.dev
         c, s, ns = net.in_nc, net.scale, self.ring.slots
         self.kind, self.in_cuda = kind, bool(x.is_cuda)
-        self.h, self.w = (x.shape[1], x.shape[2]) if kind == 'u8' else (x.shape[2], x.shape[3])
+        if kind == 'yuv':
+            self.h, self.w = self.yuv.h, self.yuv.w
+        else:
+            self.h, self.w = (x.shape[1], x.shape[2]) if kind == 'u8' else (x.shape[2], x.shape[3])
         h, w, m = self.h, self.w, max(self.first, self.later)
         self.wk = net._weights_key()
         self.plan = net._get_plan(1, h, w, dev, wk=self.wk)
@@ -486,8 +587,14 @@ class _StreamEngine:
                    torch.empty(1, c, s * h, s * w, dtype=torch.float32, device=dev)]
         self.snap = torch.empty(ns, 1, c, s * h, s * w, dtype=torch.float32, device=dev)
         self.u8 = torch.empty(ns, m, s * h, s * w, c, dtype=torch.uint8, device=dev)
-        self.host_out = torch.empty(ns, m, s * h, s * w, c, dtype=torch.uint8, pin_memory=True)
-        if kind == 'u8':
+        ofb = self.yuv.out_frame_bytes(s) if kind == 'yuv' else s * h * s * w * c
+        self.host_out = torch.empty((ns, m, ofb) if kind == 'yuv' else (ns, m, s * h, s * w, c), dtype=torch.uint8,
+                                    pin_memory=True)
+        if kind == 'yuv':                           # I420 both ways: 1.5 bytes per pixel through pinned memory
+            self.stage = torch.empty(ns, m, self.yuv.frame_bytes, dtype=torch.uint8, pin_memory=True)
+            self.dev_in = torch.empty(ns, m, self.yuv.frame_bytes, dtype=torch.uint8, device=dev)
+            self.yuv_out = torch.empty(ns, m, ofb, dtype=torch.uint8, device=dev)
+        elif kind == 'u8':
             self.stage = torch.empty(ns, m, h, w, c, dtype=torch.uint8, pin_memory=True)
             self.dev_in = torch.empty(ns, m, h, w, c, dtype=torch.uint8, device=dev)
         elif not self.in_cuda:
@@ -537,6 +644,11 @@ class _StreamEngine:
                 L.check(self.lib.tg_dequantize_u8_hwc(self.dev_in[sl].data_ptr(), self.lr[sl, 1].data_ptr(), cnt,
                                                       self.net.in_nc, self.h, self.w, self.copy.cuda_stream),
                         'tg_dequantize_u8_hwc')
+            elif self.kind == 'yuv':
+                self.dev_in[sl, :cnt].copy_(self.stage[sl, :cnt], non_blocking=True)
+                L.check(self.lib.tg_yuv420_to_rgb_f32(self.dev_in[sl].data_ptr(), self.lr[sl, 1].data_ptr(), cnt,
+                                                      self.h, self.w, *self.yuv.codes(), self.copy.cuda_stream),
+                        'tg_yuv420_to_rgb_f32')
             elif not self.in_cuda:
                 self.lr[sl, 1:1 + cnt].copy_(self.stage[sl, :cnt], non_blocking=True)
             self.ev_in[sl].record(self.copy)
@@ -574,6 +686,11 @@ class _StreamEngine:
             flow0 = self.lib.tg_frnet_plan_flow(fplan.handle, b & 1)
             for j in range(f0, cnt):
                 self._frame(i0 + j, sl, j, flow0 + (j - f0) * self.fsz)
+        if self.yuv is not None:                    # the batch's RGB frames -> I420, behind its last frame
+            s = self.net.scale
+            L.check(self.lib.tg_rgb_u8_to_yuv420(self.u8[sl].data_ptr(), self.yuv_out[sl].data_ptr(), cnt,
+                                                 s * self.h, s * self.w, *self.yuv.codes(), main.cuda_stream),
+                    'tg_rgb_u8_to_yuv420')
         self.ev_s[sl].record(main)
         self.pending_dl = rec
 
@@ -588,7 +705,8 @@ class _StreamEngine:
         sl = self.ring.slot(b)
         self.copy.wait_event(self.ev_s[sl])
         with torch.cuda.stream(self.copy):
-            self.host_out[sl, :cnt].copy_(self.u8[sl, :cnt], non_blocking=True)
+            done = self.yuv_out if self.yuv is not None else self.u8
+            self.host_out[sl, :cnt].copy_(done[sl, :cnt], non_blocking=True)
             self.ev_out[sl].record(self.copy)
 
     # -- faults --------------------------------------------------------------------------------------------------
@@ -658,11 +776,11 @@ class _StreamEngine:
         # (no torch.no_grad() around the yields: it would leak into the caller between them; nothing here records a graph)
         try:
             pending = 0                             # frames taken into the batch being filled
-            for b, off, piece, full in stream_rebatch(stream_parts(self.frames, self.net.in_nc),
+            for b, off, piece, full in stream_rebatch(stream_parts(self.frames, self.net.in_nc, self.yuv),
                                                       self.first, self.later):
                 if self.plan is None:
                     self.net.check_faults()         # a fault of an EARLIER clip is never this stream's to repair
-                    self._open('u8' if piece.dtype == torch.uint8 else 'f32', piece)
+                    self._open('yuv' if self.yuv is not None else 'u8' if piece.dtype == torch.uint8 else 'f32', piece)
                 self._take(b, off, piece)
                 pending = off + piece.shape[0]
                 if not full:
@@ -691,7 +809,7 @@ class _StreamEngine:
             if self.ring.inflight:
                 self.plan.chain_state()             # a fault in frames nobody will see: counted, the plan has fallen back
         finally:
-            for name in ('lr', 'hr', 'snap', 'u8', 'host_out', 'stage', 'dev_in', 'zflow'):
+            for name in ('lr', 'hr', 'snap', 'u8', 'host_out', 'stage', 'dev_in', 'yuv_out', 'zflow'):
                 self.__dict__.pop(name, None)
 
 
@@ -952,7 +1070,7 @@ class FRNet(nn.Module):
         self._get_plan(k, h, w, dev).check_chain()   # (the clip has been synchronised: a 4-byte read)
         return out.transpose(1, 0, 2, 3, 4) if multi else out[:, 0]
 
-    def infer_stream(self, frames, device=None, on_fault='rerun'):
+    def infer_stream(self, frames, device=None, on_fault='rerun', yuv=None):
         """Super-resolve a clip of ANY length in bounded memory: a generator over `frames` (any iterable, pulled lazily)
         that yields (m, s*h, s*w, 3) uint8 numpy chunks in order, as many frames in total as it consumed.
 
@@ -986,12 +1104,22 @@ class FRNet(nn.Module):
         One stream per network at a time: opening a second one while one is live raises RuntimeError.  The stream keeps
         the plans of the weights it was opened with (do not update the weights under it).  Closing it early -- close(),
         an exception from `frames`, a bad item -- drains all three streams before the rings are released and leaves the
-        network ready for the next call.  Single clips, host output only; precision='fp16' as for infer_sequence."""
+        network ready for the next call.  Single clips, host output only; precision='fp16' as for infer_sequence.
+
+        yuv: a Yuv420(h, w, matrix, full_range, siting) makes the stream raw video both ways.
+        Items are then host uint8 arrays of I420 frames, (frame_bytes,) or (n, frame_bytes); any other dtype, size or
+        device is a ValueError before a frame of the item is enqueued.  tg_yuv420_to_rgb_f32 writes the LR slot on the
+        copy stream (where tg_dequantize_u8_hwc writes it for uint8 RGB input); after a batch's last frame ONE
+        tg_rgb_u8_to_yuv420 launch on the caller's stream converts its uint8 RGB frames into the slot's I420 buffer,
+        and that is what is downloaded.  The generator yields (m, yuv.out_frame_bytes(scale)) uint8 views
+        (yuv420_planes splits them), valid until it is advanced: the bytes are ops.rgb_to_yuv420 of the frames the
+        stream yields without `yuv` for the same LR input, bit for bit.  Both launches sit inside the per-batch
+        enqueue functions, so a repaired batch has its I420 bytes derived again."""
         import weakref
         cur = self._stream_ref() if self._stream_ref is not None else None
         if cur is not None and not cur.closed:
             raise RuntimeError('infer_stream: this network already has a live stream (one at a time: close it first)')
-        eng = _StreamEngine(self, frames, device, on_fault)
+        eng = _StreamEngine(self, frames, device, on_fault, yuv)
         self._stream_ref = weakref.ref(eng)
         return eng.run()
 

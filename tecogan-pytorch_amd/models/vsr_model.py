@@ -92,15 +92,17 @@ class VSRModel(BaseModel):
             hr_seq = self.net_G(lr_data, self.device)
         return hr_seq[n_pad_front:]
 
-    def infer_stream(self, frames):
+    def infer_stream(self, frames, yuv=None):
         """infer() for a clip of any length (FRNet.infer_stream): `frames` is an iterable of LR frames or chunks, uint8
         (h,w,3) or float32 (3,h,w); yields (m,H,W,3) uint8 chunks -- views of the generator's pinned ring, valid until
         the next one is asked for.  The temporal padding of the front (test.padding_mode / num_pad_front) is applied
-        lazily: the first n_pad + 1 frames are buffered, the padded prefix runs first, its n_pad outputs are dropped."""
+        lazily: the first n_pad + 1 frames are buffered, the padded prefix runs first, its n_pad outputs are dropped.
+        yuv (a Yuv420): the items are I420 frames or chunks of them and (m, out_frame_bytes) I420 chunks are yielded."""
         mode = self.opt['test'].get('padding_mode', 'reflect')
         skip = self.opt['test'].get('num_pad_front', 0)
         self.net_G.eval()
-        gen = self.net_G.infer_stream(front_pad_stream(frames, mode, skip, self.net_G.in_nc), self.device)
+        gen = self.net_G.infer_stream(front_pad_stream(frames, mode, skip, self.net_G.in_nc, yuv), self.device,
+                                      yuv=yuv)
         try:
             for chunk in gen:
                 if skip >= len(chunk):

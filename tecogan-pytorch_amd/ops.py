@@ -447,6 +447,49 @@ def dequantize_u8_hwc(x):
     return out
 
 
+def _yuv_codes(matrix, full_range, siting, what):
+    """Names -> the C enums; integers pass through (the library refuses an unknown value with TG_E_ARG)."""
+    for name, val, table in (('matrix', matrix, L.YUV_MATRIX), ('siting', siting, L.YUV_SITING)):
+        if isinstance(val, str) and val not in table:
+            raise L.TecoganHipError(f'{what}: {name} is one of {sorted(table)}, got {val!r}')
+    return (L.YUV_MATRIX[matrix] if isinstance(matrix, str) else int(matrix), int(full_range),
+            L.YUV_SITING[siting] if isinstance(siting, str) else int(siting))
+
+
+def yuv420_frame_bytes(h, w):
+    """Bytes of one I420 frame: Y h*w, then U and V of ceil(h/2) x ceil(w/2)."""
+    return h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)
+
+
+def yuv420_to_rgb(yuv, h, w, matrix='bt709', full_range=False, siting='left'):
+    """(n, frame_bytes) / (frame_bytes,) uint8 I420 frames on device -> (n,3,h,w) fp32 RGB in [0,1]: integer bilinear
+    chroma up-sampling, one fp32 matrix step, clamp (tg_yuv420_to_rgb_f32)."""
+    _chk_u8(yuv, 'yuv')
+    if yuv.dim() == 1:
+        yuv = yuv.unsqueeze(0)
+    if yuv.dim() != 2 or yuv.shape[1] != yuv420_frame_bytes(h, w):
+        raise L.TecoganHipError(f'yuv420_to_rgb: {h}x{w} frames have {yuv420_frame_bytes(h, w)} bytes; '
+                                f'got shape {tuple(yuv.shape)}')
+    m, r, s = _yuv_codes(matrix, full_range, siting, 'yuv420_to_rgb')
+    n = yuv.shape[0]
+    out = torch.empty(n, 3, h, w, dtype=torch.float32, device=yuv.device)
+    L.check(L.lib().tg_yuv420_to_rgb_f32(_ptr(yuv), _ptr(out), n, h, w, m, r, s, _stream()), 'tg_yuv420_to_rgb_f32')
+    return out
+
+
+def rgb_to_yuv420(rgb_hwc, matrix='bt709', full_range=False, siting='left'):
+    """(n,H,W,3) uint8 RGB on device -> (n, frame_bytes) uint8 I420 frames, exact integer arithmetic; H and W even
+    (tg_rgb_u8_to_yuv420)."""
+    _chk_u8(rgb_hwc, 'rgb')
+    if rgb_hwc.dim() != 4 or rgb_hwc.shape[3] != 3:
+        raise L.TecoganHipError(f'rgb_to_yuv420: expected (n,H,W,3), got shape {tuple(rgb_hwc.shape)}')
+    m, r, s = _yuv_codes(matrix, full_range, siting, 'rgb_to_yuv420')
+    n, H, W, _ = rgb_hwc.shape
+    out = torch.empty(n, yuv420_frame_bytes(H, W), dtype=torch.uint8, device=rgb_hwc.device)
+    L.check(L.lib().tg_rgb_u8_to_yuv420(_ptr(rgb_hwc), _ptr(out), n, H, W, m, r, s, _stream()), 'tg_rgb_u8_to_yuv420')
+    return out
+
+
 def psnr_sse_u8(true_hwc, pred_hwc, y_only=True):
     """Per-frame sum of squared differences of (t,h,w,3) uint8 device tensors -> int64 (t,)."""
     _chk_u8(true_hwc, 'true'); _chk_u8(pred_hwc, 'pred')

@@ -584,6 +584,50 @@ int tg_psnr_yfloat_sse_u8(const uint8_t* true_hwc, const uint8_t* pred_hwc, int 
                           int pred_h, int pred_w, int y0, int x0, int h, int w, uint64_t* partials,
                           tg_stream_t stream);
 
+/* tOF: dense Farneback optical flow with the one parameter set of the reference's two call sites (pyr_scale 0.5,
+ * levels 3, winsize 15, iterations 3, poly_n 5, poly_sigma 1.2, flags 0) and the mean end-point error of two flow
+ * fields.  Specified by DESIGN.md section 7f / tests/farneback_ref.py: a restatement of the published algorithm that
+ * has NOT been compared with OpenCV.  There are no parameters.  fp32; results are bit-identical from run to run and
+ * for any batch split (every image of a call is worked on independently, tiles start at the image origin).
+ * h, w >= 16 everywhere; bad sizes, null pointers and a short workspace are TG_E_ARG.
+ * Layouts: gray (n, h, w) uint8; level images (n, lh, lw); expansions R and update matrices M as five planes per
+ * image, (n, 5, h, w): (r_y, r_x, r_yy, r_xx, r_xy) and (g11, g12, g22, h1, h2); flows (n, h, w, 2), channel 0 = x.
+ *
+ * The stages (tg_farneback_flow_u8 enqueues exactly these launches):
+ *   tg_fb_level_size       returns the coarsest level L (0..3) of an h x w frame (negative: error) and the size of
+ *                          `level` (rint(h / 2^level), half to even); host only
+ *   tg_fb_gray_u8          gray = (4899 R + 9617 G + 1868 B + 8192) >> 14 of the top-left h x w of `frames` frames
+ *                          stored frame_h x frame_w
+ *   tg_fb_level_image      Gaussian blur of the full-resolution gray frame (reflect-101; sizes 3, 3, 9, 19 for levels
+ *                          0..3) + bilinear resize to the level's size.  tmp: n * h * w floats
+ *   tg_fb_polyexp          polynomial expansion (11 x 11, sigma 1.2, replicate borders) of n images
+ *   tg_fb_update_matrices  r: pairs + 1 expansions, pair p = images p and p + 1; flow (pairs, h, w, 2) -> m_out
+ *   tg_fb_blur_solve       15 x 15 box mean of m (replicate borders) and the 2 x 2 solve -> flow_out; box_out (NULL, or
+ *                          (pairs, 5, h, w)) also receives the box means
+ *   tg_fb_resize_flow      bilinear resize of flows, values times 2 */
+int tg_fb_level_size(int h, int w, int level, int* level_h, int* level_w);
+int tg_fb_gray_u8(const uint8_t* rgb_hwc, int frames, int frame_h, int frame_w, int h, int w, uint8_t* gray,
+                  tg_stream_t stream);
+int tg_fb_level_image(const uint8_t* gray, int n, int h, int w, int level, float* tmp, float* out,
+                      tg_stream_t stream);
+int tg_fb_polyexp(const float* img, int n, int h, int w, float* r_out, tg_stream_t stream);
+int tg_fb_update_matrices(const float* r, const float* flow, float* m_out, int pairs, int h, int w,
+                          tg_stream_t stream);
+int tg_fb_blur_solve(const float* m, float* flow_out, float* box_out, int pairs, int h, int w, tg_stream_t stream);
+int tg_fb_resize_flow(const float* flow_in, int h_in, int w_in, float* flow_out, int h_out, int w_out, int pairs,
+                      tg_stream_t stream);
+/* tg_farneback_flow_u8: flow_out (frames - 1, h, w, 2) = flows of the consecutive pairs of `frames` uint8 HWC frames,
+ * computed on the top-left h x w of frames stored frame_h x frame_w (the protocol's size-matching crop needs no
+ * copy).  workspace: tg_farneback_workspace_bytes(frames - 1, h, w) bytes (-1: bad arguments). */
+int64_t tg_farneback_workspace_bytes(int pairs, int h, int w);
+int tg_farneback_flow_u8(const uint8_t* rgb_hwc, int frames, int frame_h, int frame_w, int h, int w, float* flow_out,
+                         void* workspace, size_t workspace_bytes, tg_stream_t stream);
+/* tg_flow_epe_mean: mean_f64[i] = mean over the window (y0, x0, ch, cw) of sqrt(dx^2 + dy^2) of flow_a[i] - flow_b[i],
+ * both (n, h, w, 2): the per-pixel value in fp32 (products, sum and square root each rounded once), the mean from
+ * fixed-order fp64 partials (pixel i of the window goes to partial i % 1024; the partials are added as a tree). */
+int tg_flow_epe_mean(const float* flow_a, const float* flow_b, int n, int h, int w, int y0, int x0, int ch, int cw,
+                     double* mean_f64, tg_stream_t stream);
+
 /* ========================================================================
  * Training side: backward kernels.
  * Conv data gradients reuse tg_conv3x3_fwd with weights packed by

@@ -107,6 +107,16 @@ SIGNATURES = {
     'tg_ssim_y_u8': (I, [P, P, I, I, I, I, I, I, I, I, I, P, P, SZ, P]),
     'tg_psnr_yfloat_partials': (I64, [I, I]),
     'tg_psnr_yfloat_sse_u8': (I, [P, P, I, I, I, I, I, I, I, I, I, P, P]),
+    'tg_fb_level_size': (I, [I, I, I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'tg_fb_gray_u8': (I, [P, I, I, I, I, I, P, P]),
+    'tg_fb_level_image': (I, [P, I, I, I, I, P, P, P]),
+    'tg_fb_polyexp': (I, [P, I, I, I, P, P]),
+    'tg_fb_update_matrices': (I, [P, P, P, I, I, I, P]),
+    'tg_fb_blur_solve': (I, [P, P, P, I, I, I, P]),
+    'tg_fb_resize_flow': (I, [P, I, I, P, I, I, I, P]),
+    'tg_farneback_workspace_bytes': (I64, [I, I, I]),
+    'tg_farneback_flow_u8': (I, [P, I, I, I, I, I, P, P, SZ, P]),
+    'tg_flow_epe_mean': (I, [P, P, I, I, I, I, I, I, I, P, P]),
     'tg_wgrad3x3_workspace_floats': (SZ, [I, I, I, I, I]),
     'tg_wgrad3x3': (I, [P, I64, P, I64, P, P, I, I, I, I, I, I, I, I, P]),
     'tg_wgrad3x3_multi': (I, [P, P, I, I64, I64, P, P, I, I, I, I, I, I, I, I, P]),

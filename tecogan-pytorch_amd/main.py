@@ -240,12 +240,14 @@ def evaluate(opt, sequences, model_idx, ds_name):
 
 def _official_metrics(opt):
     """test.official_metrics: the official protocol (metrics/official.py) next to the in-loop metrics.  Its LPIPS
-    is a second instance WITH ScalingLayer, built from the weight paths of the metric section."""
+    is a second instance WITH ScalingLayer, built from the weight paths of the metric section.  test.official_tof:
+    true adds its tOF column (metrics/official.py)."""
     from .metrics.lpips import LPIPS
     from .metrics.official import OfficialMetrics
     device = opt.get('device', 'cuda')
     cfg = dict((opt.get('metric') or {}).get('LPIPS') or {})
-    return OfficialMetrics(LPIPS.from_config(cfg, device=device, scaling=True), device=device)
+    return OfficialMetrics(LPIPS.from_config(cfg, device=device, scaling=True), device=device,
+                           tof=bool((opt.get('test') or {}).get('official_tof')))
 
 
 def _save_official(opt, official, per_seq, seq_ids, model_idx, ds_name):
@@ -267,6 +269,9 @@ def _save_official(opt, official, per_seq, seq_ids, model_idx, ds_name):
     doc = {'model': model_idx, 'keys': list(official.keys), 'skipped': official.skipped, 'cutfr': official.cutfr,
            'sequences': list(seq_ids), 'frames': info[:, 0].tolist(), 'evaluated': info[:, 1].tolist(),
            'windows': info[:, 2:].tolist()}
+    if official.tof:
+        from .metrics.official import TOF_FLOW_NOTE
+        doc['tOF_flow'] = TOF_FLOW_NOTE
     doc.update(agg)
     if world == 1:
         doc['per_frame'] = {sid: {k: per_seq[sid][k] for k in official.keys} for sid in seq_ids}

@@ -4,8 +4,10 @@ means, a cross-rank sum to rank 0, averages, display and the JSON file of `save`
 
 On the HIP path: PSNR (`y` / `rgb`) is compute_psnr_device (exact squared-error sums on the device),
 LPIPS is metrics/lpips.py (alex / net-lin / v0.1, spatial false).  Sequences may be device tensors or
-numpy arrays ((t,h,w,3) uint8); numpy inputs are uploaded.  tOF needs OpenCV's Farneback flow, which
-is not part of this port: it is announced once and left out of the results."""
+numpy arrays ((t,h,w,3) uint8); numpy inputs are uploaded.  tOF (:222-279) is computed only when its section
+says `backend: hip`: ops.tof, Farneback's flow as DESIGN.md section 7f restates it (not compared with OpenCV), on
+the whole size-matched frames, first frame skipped.  Any other tOF section is announced once and left out of the
+results, as OpenCV's flow is not part of this port."""
 import json
 import logging
 import os.path as osp
@@ -45,6 +47,9 @@ class MetricCalculator:
         use instead of loading the weights the `LPIPS` section names."""
         self.metric_opt = OrderedDict()
         for mtype, cfg in opt['metric'].items():
+            if mtype == 'tOF' and (cfg or {}).get('backend') == 'hip':
+                self.metric_opt[mtype] = cfg
+                continue
             if mtype == 'tOF':
                 log.warning('metric tOF (OpenCV Farneback optical flow) is not available here; it is left out')
                 continue
@@ -93,6 +98,9 @@ class MetricCalculator:
                 md['PSNR'] = [float(v) for v in compute_psnr_device(true_seq, pred_seq, self.psnr_colorspace)]
             elif mtype == 'LPIPS':
                 md['LPIPS'] = self.lpips(true_seq, pred_seq).tolist()
+            elif mtype == 'tOF' and true_seq.shape[0] > 1:
+                from .. import ops
+                md['tOF'] = ops.tof(true_seq, pred_seq).tolist()
 
     def gather(self, seq_idx_lst):
         """Sequence means, summed over ranks into avg_metric_dict on rank 0 (:68-117)."""

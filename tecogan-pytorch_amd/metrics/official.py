@@ -13,12 +13,16 @@ Per folder pair (results, targets), frames [cutfr, n - cutfr) only, temporal met
   * three averages with the script's float32 casts: Avg_<k> per folder, FolderAvg_<k>, FrameAvg_<k>.
 Both crops are window arguments of the kernels; only LPIPS reads a contiguous copy of the window.
 
-Not reproduced: tOF (OpenCV's Farneback flow; never reported, listed under "skipped") and metrics.csv (pandas'
-print format).  A folder with at most 2 * cutfr frames has empty lists; its averages are nan as numpy's 0 / 0 is in
-the script, and it is listed under "empty_folders".
+tOF is opt-in (tof=True, --tof, test.official_tof): Farneback flows of consecutive target and result frames
+(ops.tof; both on the size-matched, otherwise uncropped frames, crop_8x8 applied to the flows), computed by the HIP
+restatement of the algorithm that DESIGN.md section 7f specifies.  It has not been compared with OpenCV, which the
+JSON says under "tOF_flow".  Without the opt-in tOF is listed under "skipped", as before.
+Not reproduced: metrics.csv (pandas' print format).  A folder with at most 2 * cutfr frames has empty lists; its
+averages are nan as numpy's 0 / 0 is in the script, and it is listed under "empty_folders".
 
 CLI:  python -m tecogan_pytorch_amd.metrics.official --results a,b --targets c,d --output dir [--alexnet P --lin P]
-      python -m tecogan_pytorch_amd.metrics.official --model TecoGAN_BD [--data_root data --results_root results]"""
+      python -m tecogan_pytorch_amd.metrics.official --model TecoGAN_BD [--data_root data --results_root results]
+      --tof adds the tOF column."""
 import argparse
 import json
 import math
@@ -31,6 +35,8 @@ import torch
 
 KEYS = ('PSNR', 'SSIM', 'LPIPS', 'tLP100')
 SKIPPED = ('tOF',)
+KEYS_TOF = ('PSNR', 'SSIM', 'LPIPS', 'tOF', 'tLP100')     # the script's order, with tOF switched on
+TOF_FLOW_NOTE = 'farneback, restated, not compared with OpenCV'
 EVAL_SETS = (('Vid4', ('calendar', 'city', 'foliage', 'walk')), ('ToS3', ('bridge', 'face', 'room')))
 
 
@@ -91,9 +97,10 @@ class OfficialMetrics:
     """lpips: an LPIPS instance built with scaling=True (None: PSNR and SSIM only; LPIPS and tLP100 are then
     listed under "skipped").  chunk_frames bounds the frames whose AlexNet taps are alive at once (None: the
     LPIPS instance's own rule); no value depends on it.  reuse_features=False evaluates the three LPIPS terms
-    with three forward() calls (six backbone passes per frame): the same values, for timing and tests."""
+    with three forward() calls (six backbone passes per frame): the same values, for timing and tests.
+    tof=True adds tOF in the script's position (PSNR, SSIM, LPIPS, tOF, tLP100; PSNR, SSIM, tOF without lpips)."""
 
-    def __init__(self, lpips=None, device='cuda', cutfr=2, chunk_frames=None, reuse_features=True):
+    def __init__(self, lpips=None, device='cuda', cutfr=2, chunk_frames=None, reuse_features=True, tof=False):
         if lpips is not None and not lpips.scaling:
             raise ValueError('OfficialMetrics: the official protocol runs LPIPS with ScalingLayer (scaling=True)')
         self.lpips = lpips
@@ -101,8 +108,12 @@ class OfficialMetrics:
         self.cutfr = int(cutfr)
         self.chunk_frames = chunk_frames
         self.reuse_features = reuse_features
+        self.tof = bool(tof)
         self.keys = KEYS if lpips is not None else KEYS[:2]
         self.skipped = list(SKIPPED) + [k for k in KEYS if k not in self.keys]
+        if self.tof:
+            self.keys = tuple(k for k in KEYS_TOF if k == 'tOF' or k in self.keys)
+            self.skipped = [k for k in KEYS if k not in self.keys]
 
     @classmethod
     def from_paths(cls, alexnet=None, lin=None, device='cuda', **kw):
@@ -133,6 +144,8 @@ class OfficialMetrics:
         if ch < 7 or cw < 7 or (self.lpips is not None and (ch < 31 or cw < 31)):
             raise ValueError(f'frames of {h}x{w} crop to {ch}x{cw}: too small for '
                              f'{"LPIPS (31x31)" if ch >= 7 and cw >= 7 else "SSIM (7x7)"}')
+        if self.tof and (h < 16 or w < 16):
+            raise ValueError(f'frames of {h}x{w}: too small for tOF (16x16)')
         return y, x, ch, cw
 
     def _lpips_terms(self, tc, pc):
@@ -160,7 +173,8 @@ class OfficialMetrics:
 
     def compute_sequence(self, true_seq, pred_seq):
         """(t,h,w,3) uint8 frames (device tensors or numpy) of one folder pair -> per-frame lists PSNR, SSIM,
-        LPIPS (t - 2 cutfr values) and tLP100 (one fewer), plus 'frames' (t), 'evaluated' and 'window'
+        LPIPS (t - 2 cutfr values), tOF (with tof=True) and tLP100 (one fewer), plus 'frames' (t), 'evaluated' and
+        'window'
         (y, x, h, w; None when no frame is evaluated)."""
         lo, hi = self.frame_range(true_seq.shape[0], pred_seq.shape[0])
         out = self.compute_frames(true_seq[lo:hi], pred_seq[lo:hi])
@@ -190,6 +204,8 @@ class OfficialMetrics:
             tc, pc = t[:, y:y + h, x:x + w].contiguous(), p[:, y:y + h, x:x + w].contiguous()
             lp, tlp = self._lpips_terms(tc, pc)
             out['LPIPS'], out['tLP100'] = lp.tolist(), tlp.tolist()
+        if self.tof and t.shape[0] > 1:   # flows on the size-matched, uncropped frames; crop_8x8 on the flows
+            out['tOF'] = ops.tof(t, p, win).tolist()
         return out
 
     def evaluate_folders(self, result_dirs, target_dirs, output_dir, quiet=False):
@@ -213,6 +229,8 @@ class OfficialMetrics:
             sums.append(folder_sums(r, self.keys))
         doc = OrderedDict(keys=list(self.keys), skipped=self.skipped, cutfr=self.cutfr, folders=folders,
                           empty_folders=empty)
+        if self.tof:
+            doc['tOF_flow'] = TOF_FLOW_NOTE
         doc.update(aggregate(sums, self.keys))
         lines = summary_lines(doc, self.keys)
         with open(osp.join(output_dir, 'metricsfile.txt'), 'a') as f:
@@ -252,6 +270,8 @@ def main(argv=None):
     ap.add_argument('--alexnet', help='torchvision alexnet state dict')
     ap.add_argument('--lin', help="the v0.1 alex linear-layer weights (alex.pth)")
     ap.add_argument('--device', default='cuda')
+    ap.add_argument('--tof', action='store_true', help='add tOF (Farneback flow as DESIGN.md 7f restates it; '
+                                                       'not compared with OpenCV)')
     args = ap.parse_args(argv)
     jobs = []
     if args.model:
@@ -270,7 +290,7 @@ def main(argv=None):
     if not jobs:
         print(f'no result folder of {args.model} under {args.results_root}')
         return []
-    om = OfficialMetrics.from_paths(args.alexnet, args.lin, device=args.device)
+    om = OfficialMetrics.from_paths(args.alexnet, args.lin, device=args.device, tof=args.tof)
     docs = [om.evaluate_folders(*job) for job in jobs]
     print('Finished.')
     return docs

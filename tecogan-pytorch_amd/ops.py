@@ -622,6 +622,79 @@ def psnr_yfloat_sse_u8(true_hwc, pred_hwc, window=None):
     return [sum(v + (1 << 64) if v < 0 else v for v in row) for row in part.tolist()]
 
 
+def farneback_levels(h, w):
+    """[(lh, lw)] of pyramid levels 0..L of an h x w frame (tg_fb_level_size; no device work)."""
+    import ctypes
+    lh, lw = ctypes.c_int(), ctypes.c_int()
+    top = L.lib().tg_fb_level_size(h, w, 0, ctypes.byref(lh), ctypes.byref(lw))
+    if top < 0:
+        L.check(top, 'tg_fb_level_size')
+    out = []
+    for k in range(top + 1):
+        L.lib().tg_fb_level_size(h, w, k, ctypes.byref(lh), ctypes.byref(lw))
+        out.append((lh.value, lw.value))
+    return out
+
+
+def farneback_flow(frames_u8, size=None):
+    """tg_farneback_flow_u8: (t, fh, fw, 3) uint8 device frames -> (t-1, h, w, 2) fp32 flows of the consecutive pairs
+    (channel 0 = x), computed on the top-left size = (h, w) of the frames (None: the whole frames).  Farneback's
+    method with the reference's fixed parameters as DESIGN.md section 7f restates it; not compared with OpenCV."""
+    _chk_u8(frames_u8, 'frames')
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or frames_u8.shape[0] < 2:
+        raise L.TecoganHipError(f'farneback_flow: frames {tuple(frames_u8.shape)} (at least two (h,w,3) frames)')
+    t, fh, fw, _ = frames_u8.shape
+    h, w = (fh, fw) if size is None else (int(size[0]), int(size[1]))
+    nbytes = L.lib().tg_farneback_workspace_bytes(t - 1, h, w)
+    if nbytes < 0 or h > fh or w > fw:
+        raise L.TecoganHipError(f'farneback_flow: region {h}x{w} of {t} frames of {fh}x{fw} (at least 16x16, inside)')
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=frames_u8.device)
+    out = torch.empty(t - 1, h, w, 2, dtype=torch.float32, device=frames_u8.device)
+    L.check(L.lib().tg_farneback_flow_u8(frames_u8.data_ptr(), t, fh, fw, h, w, out.data_ptr(), ws.data_ptr(),
+                                         ws.numel() * 8, _stream()), 'tg_farneback_flow_u8')
+    return out
+
+
+def flow_epe_mean(flow_a, flow_b, window=None):
+    """tg_flow_epe_mean: (n, h, w, 2) fp32 flows -> float64 (n,) mean end-point errors over window = (y0, x0, h, w)
+    (None: the whole field)."""
+    _chk(flow_a, 'flow_a'); _chk(flow_b, 'flow_b')
+    if flow_a.dim() != 4 or flow_a.shape[3] != 2 or flow_a.shape != flow_b.shape or flow_a.shape[0] < 1:
+        raise L.TecoganHipError(f'flow_epe_mean: flows {tuple(flow_a.shape)} / {tuple(flow_b.shape)}')
+    n, h, w, _ = flow_a.shape
+    y0, x0, ch, cw = (0, 0, h, w) if window is None else (int(v) for v in window)
+    out = torch.empty(n, dtype=torch.float64, device=flow_a.device)
+    L.check(L.lib().tg_flow_epe_mean(flow_a.data_ptr(), flow_b.data_ptr(), n, h, w, y0, x0, ch, cw, out.data_ptr(),
+                                     _stream()), 'tg_flow_epe_mean')
+    return out
+
+
+TOF_CHUNK_BYTES = 256 << 20     # bound of one flow call's workspace + result in tof()
+
+
+def tof(true_hwc, pred_hwc, window=None):
+    """tOF of two (t, h, w, 3) uint8 device sequences: per consecutive pair, the mean end-point error between the
+    Farneback flow of the true frames and that of the predicted ones, both computed on the frames cropped at the
+    top left to the smaller of the two sizes; window = (y0, x0, h, w) of the flows enters the mean (None: all;
+    the official protocol passes crop_8x8's).  -> float64 (t-1,) on the device.  Flows are computed in chunks of
+    frames that overlap by one, so memory stays bounded; no value depends on the chunking."""
+    _chk_u8(true_hwc, 'true'); _chk_u8(pred_hwc, 'pred')
+    if true_hwc.dim() != 4 or pred_hwc.dim() != 4 or true_hwc.shape[0] != pred_hwc.shape[0] or true_hwc.shape[0] < 2:
+        raise L.TecoganHipError(f'tof: shapes {tuple(true_hwc.shape)} / {tuple(pred_hwc.shape)} (two frames at least)')
+    t = true_hwc.shape[0]
+    h, w = min(true_hwc.shape[1], pred_hwc.shape[1]), min(true_hwc.shape[2], pred_hwc.shape[2])
+    per_pair = L.lib().tg_farneback_workspace_bytes(2, h, w) - L.lib().tg_farneback_workspace_bytes(1, h, w)
+    if per_pair <= 0:
+        raise L.TecoganHipError(f'tof: frames of {h}x{w} (at least 16x16)')
+    step = max(1, min(t - 1, TOF_CHUNK_BYTES // (per_pair + h * w * 8)))
+    out = []
+    for f0 in range(0, t - 1, step):
+        f1 = min(t, f0 + step + 1)
+        out.append(flow_epe_mean(farneback_flow(true_hwc[f0:f1], (h, w)), farneback_flow(pred_hwc[f0:f1], (h, w)),
+                                 window))
+    return torch.cat(out)
+
+
 # ---------------------------------------------------------------------------
 # training-side wrappers (backward kernels, losses, optimiser)
 # ---------------------------------------------------------------------------

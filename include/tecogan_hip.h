@@ -178,7 +178,8 @@ int tg_conv3x3_fwd_masked(const float* x, int64_t x_nstride, int c1, const float
  * taps rotated by 180 degrees).  x2 / res / relu_mask as in tg_conv3x3_fwd / _masked (may be NULL). */
 int64_t tg_conv3x3_wino_packed_floats(int cin, int cout);
 /* 1 when the Winograd form is the faster one for this layer shape on an MI355X (at least 160 16-tile
- * workgroups, cout a multiple of 64, cin >= 16); the frame plan uses it to pick
+ * workgroups, cout a multiple of 64, cin >= 16; or cout = 32, cin >= 32 and at least 2048 32-tile
+ * workgroups: FNet's two full-resolution layers in a batched flow pass); the frame plan uses it to pick
  * the form of each layer whose tg_layer_weights.u is set. */
 int tg_conv3x3_prefers_wino(int n, int cin, int cout, int h, int w);
 int tg_pack_conv3x3_wino(const float* w, float* out, int cin, int cout, int transposed,
@@ -188,6 +189,18 @@ int tg_conv3x3_wino_fwd(const float* x, int64_t x_nstride, int c1, const float* 
                         const float* res, int64_t res_nstride, const float* relu_mask,
                         int64_t mask_nstride, float* y, int64_t y_nstride, int n, int cin,
                         int cout, int h, int w, int act, tg_stream_t stream);
+/* The same kernel with a neighbouring memory-bound layer folded in (single source, no residual, no mask); h, w are the
+ * conv's own map size and must be even, results are BIT-IDENTICAL to the two separate launches:
+ *   TG_WINO_POOL: y = MaxPool2d(2, 2)(act(conv(x))), y (n, cout, h/2, w/2) -- the max over the 2x2 output tile a lane
+ *                 holds anyway; the full-resolution tensor is never written.
+ *   TG_WINO_UP2:  y = act(conv(bilinear_x2(x))), x (n, cin, h/2, w/2) -- the input staging blends every element from its
+ *                 <= 4 source values (tg_upsample_fwd's taps, weights and expression); the up-sampled tensor never exists.
+ * The two flags are not combined.  Other shapes / combinations: TG_E_SHAPE / TG_E_ARG, nothing is launched. */
+#define TG_WINO_POOL 1
+#define TG_WINO_UP2 2
+int tg_conv3x3_wino_fused_fwd(const float* x, int64_t x_nstride, const float* u_packed, const float* bias,
+                              float* y, int64_t y_nstride, int n, int cin, int cout, int h, int w, int act,
+                              int fuse, tg_stream_t stream);
 
 /* Several DEPENDENT 3x3 layers (layer i+1 reads what layer i writes: SRNet's conv_in and residual
  * blocks, tecogan_nets.py:108-116,141-143) in ONE launch.  Every separate launch of the Winograd

@@ -191,6 +191,7 @@ SIGNATURES = {
     'tg_conv3x3_prefers_wino': (I, [I, I, I, I, I]),
     'tg_pack_conv3x3_wino': (I, [P, P, I, I, I, P]),
     'tg_conv3x3_wino_fwd': (I, [P, I64, I, P, I64, P, P, P, I64, P, I64, P, I64, I, I, I, I, I, I, P]),
+    'tg_conv3x3_wino_fused_fwd': (I, [P, I64, P, P, P, I64, I, I, I, I, I, I, I, P]),
     'tg_time_gather': (I, [P, P, P, I, I, I, I64, P]),
     'tg_transpose01': (I, [P, P, I, I, I64, P]),
     'tg_stack_time': (I, [P, I, P, I, I64, P]),

@@ -340,10 +340,14 @@ static int step_impl(tg_frnet_plan* p, const float* lr_curr, const float* lr_pre
     }
     if (active && (mask & (1u << kind))) rc = fn();
   };
-  // conv3x3 (+bias+act) [+ MaxPool2d(2,2) when pool]; y receives the final tensor.
+  // conv3x3 (+bias+act) [+ MaxPool2d(2,2) when pool]; y receives the final tensor.  up2: x is the (cin, hh/2, ww/2)
+  // source of a bilinear x2 up-sampling the Winograd form folds into its staging (the caller has checked that this
+  // layer runs that form, wino_up2_folds below).  Returns true when the pooled tensor was written to pool_tmp instead
+  // of y: the pool folded into the Winograd kernel's epilogue has no intermediate tensor, and y may be the layer's
+  // own input (the encoder blocks pool in place), which other workgroups are still reading.
   auto conv = [&](const float* x, int64_t xns, int c1, const float* x2, int64_t x2ns, int cin,
                   int cout, int hh, int ww, int act, const float* res, int64_t rns, float* y,
-                  int64_t yns, bool pool = false, float* pool_tmp = nullptr) {
+                  int64_t yns, bool pool = false, float* pool_tmp = nullptr, bool up2 = false) {
     const tg_layer_weights lw = p->L[li++];
     int ocb = tg_conv3x3_pick_ocb(cout);
     int kind = ocb == 32 ? K_CONV32
@@ -353,15 +357,25 @@ static int step_impl(tg_frnet_plan* p, const float* lr_curr, const float* lr_pre
     double fl = 2.0 * cin * 9 * cout * px;
     double by = 4.0 * px * (cin + cout + (res ? cout : 0)) + 4.0 * 9 * cin * cout;
     if (lw.u && tg_conv3x3_prefers_wino(n, cin, cout, hh, ww)) {
+      // the pool is the kernel's epilogue where the map has whole 2x2 tiles: no full-resolution tensor, no K_POOL launch
+      const bool fpool = pool && !res && tg::conv3x3_wino_fuse_ok(cin, hh, ww, TG_WINO_POOL);
+      const bool sep_pool = pool && !fpool;
       float* yw = pool ? pool_tmp : y;
+      const int fuse = (fpool ? TG_WINO_POOL : 0) | (up2 ? TG_WINO_UP2 : 0);
+      if (fpool) by -= 4.0 * px * cout * 0.75;      // writes the pooled tensor
+      if (up2) by -= 4.0 * px * cin * 0.75;         // reads the low-resolution source
       go(K_CONV_WINO, fl, by, [&] {
         return tg::conv3x3_wino_launch(x, xns, c1, x2, x2ns, lw.u, lw.b, res, rns, nullptr, 0, yw,
-                                       pool ? (int64_t)cout * hh * ww : yns, n, cin, cout, hh, ww, act, st);
+                                       sep_pool ? (int64_t)cout * hh * ww : yns, n, cin, cout, hh, ww, act, st, fuse);
       });
-      if (pool)
+      if (sep_pool)
         go(K_POOL, 0, 4.0 * n * cout * (hh * ww + (hh / 2) * (ww / 2)),
            [&] { return tg_maxpool2_fwd(yw, y, n * cout, hh, ww, st); });
-      return;
+      return fpool;
+    }
+    if (up2) {      // only the Winograd form reads through the up-sampling
+      if (rc == TG_OK) rc = TG_E_ARG;
+      return false;
     }
     int ks = res ? 1 : tg_conv3x3_pick_ksplit(n, cin, cout, hh, ww);
     if (ks == 1 && kind == K_CONV64_R2 && tg::conv3x3_uses_wg_ksplit(n, cin, cout, hh, ww))
@@ -375,7 +389,7 @@ static int step_impl(tg_frnet_plan* p, const float* lr_curr, const float* lr_pre
         return tg::conv3x3_splitk_finalize(part_buf, ks, lw.b, act, pool ? 1 : 0, y, n, cout, hh, ww,
                                            st);
       });
-      return;
+      return false;
     }
     float* yc = pool ? pool_tmp : y;
     go(kind, fl, by, [&] {
@@ -385,6 +399,7 @@ static int step_impl(tg_frnet_plan* p, const float* lr_curr, const float* lr_pre
     if (pool)
       go(K_POOL, 0, 4.0 * n * cout * (hh * ww + (hh / 2) * (ww / 2)),
          [&] { return tg_maxpool2_fwd(yc, y, n * cout, hh, ww, st); });
+    return false;
   };
   // ---- FNet (tecogan_nets.py:67-82) ------------------------------------------
   int hh = h, ww = w;
@@ -399,31 +414,40 @@ static int step_impl(tg_frnet_plan* p, const float* lr_curr, const float* lr_pre
     else
       conv(src, (int64_t)cin * hh * ww, cin, nullptr, 0, cin, co, hh, ww, TG_ACT_LRELU02, nullptr,
            0, A, (int64_t)co * hh * ww);
-    // second conv of the block + MaxPool2d: pooled result lands in A (B is scratch)
-    conv(A, (int64_t)co * hh * ww, co, nullptr, 0, co, co, hh, ww, TG_ACT_LRELU02, nullptr, 0, A,
-         (int64_t)co * (hh / 2) * (ww / 2), true, B);
+    // second conv of the block + MaxPool2d: pooled result lands in A (B is scratch), or straight in B (pool folded)
+    const bool in_b = conv(A, (int64_t)co * hh * ww, co, nullptr, 0, co, co, hh, ww, TG_ACT_LRELU02, nullptr, 0, A,
+                           (int64_t)co * (hh / 2) * (ww / 2), true, B);
     hh /= 2; ww /= 2; cin = co;
-    float* t = A; A = B; B = t;   // pooled result now in B
+    if (!in_b) { float* t = A; A = B; B = t; }   // pooled result now in B
     src = B;
   }
+  // A decoder block's x2 up-sampling can be folded into the staging of the conv that reads it (decoder2.0, decoder3.0,
+  // flow.0) when that conv runs the Winograd form: the block then leaves its low-resolution result in `src` and
+  // there is no K_UPSAMPLE launch.  tg::conv3x3_wino_folds_up2 says where (measured: nowhere unless the form is
+  // forced).  `li` is the consumer's layer here.
+  auto wino_up2_folds = [&](int ci, int co, int uh, int uw) {
+    return p->L[li].u && tg::conv3x3_wino_folds_up2(n, ci, co, uh, uw);
+  };
   const int dec[3] = {256, 128, 64};
+  bool up2 = false;      // src is the low-resolution source of the (hh, ww) map
   for (int d = 0; d < 3; ++d) {
     int co = dec[d];
-    conv(src, (int64_t)cin * hh * ww, cin, nullptr, 0, cin, co, hh, ww, TG_ACT_LRELU02, nullptr, 0,
-         A, (int64_t)co * hh * ww);
+    conv(src, (int64_t)cin * (up2 ? (hh / 2) * (ww / 2) : hh * ww), cin, nullptr, 0, cin, co, hh, ww, TG_ACT_LRELU02,
+         nullptr, 0, A, (int64_t)co * hh * ww, false, nullptr, up2);
     conv(A, (int64_t)co * hh * ww, co, nullptr, 0, co, co, hh, ww, TG_ACT_LRELU02, nullptr, 0, B,
          (int64_t)co * hh * ww);
-    {
+    up2 = wino_up2_folds(co, d < 2 ? dec[d + 1] : 32, 2 * hh, 2 * ww);
+    if (!up2) {
       float *pi = B, *po = A; int ph = hh, pw = ww;
       go(K_UPSAMPLE, 0, 4.0 * n * co * ph * pw * 5.0,
          [&] { return tg_upsample_fwd(pi, po, n * co, ph, pw, 2, TG_UP_BILINEAR, 1.0f, st); });
+      float* t = A; A = B; B = t;
     }
     hh *= 2; ww *= 2; cin = co;
-    float* t = A; A = B; B = t;
     src = B;
   }
-  conv(src, (int64_t)cin * hh * ww, cin, nullptr, 0, cin, 32, hh, ww, TG_ACT_LRELU02, nullptr, 0, A,
-       (int64_t)32 * hh * ww);
+  conv(src, (int64_t)cin * (up2 ? (hh / 2) * (ww / 2) : hh * ww), cin, nullptr, 0, cin, 32, hh, ww, TG_ACT_LRELU02,
+       nullptr, 0, A, (int64_t)32 * hh * ww, false, nullptr, up2);
   {
     const tg_layer_weights lw = p->L[li++];
     float* ai = A; int fh_ = hh, fw_ = ww;

@@ -73,11 +73,14 @@ __host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 // K-split variant of the conv kernel (1-row tiles, two wave groups over alternating chunks).
 bool conv3x3_uses_wg_ksplit(int n, int cin, int cout, int h, int w);
 bool conv3x3_uses_oneshot(int n, int cin, int cout, int h, int w);
-// Winograd F(2x2,3x3) form (tg_conv3x3_wino.hip); arguments as tg_conv3x3_wino_fwd, unchecked
+// Winograd F(2x2,3x3) form (tg_conv3x3_wino.hip); arguments as tg_conv3x3_wino_fwd, unchecked but for `fuse`
+// (TG_WINO_POOL / TG_WINO_UP2 as in tg_conv3x3_wino_fused_fwd; conv3x3_wino_fuse_ok says which shapes take them)
+bool conv3x3_wino_fuse_ok(int cin, int h, int w, int fuse);
+bool conv3x3_wino_folds_up2(int n, int cin, int cout, int h, int w);     // the plan's (measured) rule for TG_WINO_UP2
 int conv3x3_wino_launch(const float* x, int64_t x_ns, int c1, const float* x2, int64_t x2_ns, const float* u,
                         const float* bias, const float* res, int64_t res_ns, const float* mask,
                         int64_t mask_ns, float* y, int64_t y_ns, int n, int cin, int cout, int h, int w,
-                        int act, tg_stream_t stream);
+                        int act, tg_stream_t stream, int fuse = 0);
 
 // several dependent Winograd layers in one launch (tg_conv3x3_wino.hip); err: int32 fault counter in
 // device or pinned host memory, poll_limit < 0 injects a fault into every waiting workgroup
@@ -142,6 +145,18 @@ __device__ __forceinline__ void bilinear_src(int dst, int scale, int in_size,
   i1 = i0 + 1 < in_size ? i0 + 1 : in_size - 1;
   l1 = src - (float)i0;
   l0 = 1.0f - l1;
+}
+
+// The four taps of bilinear_src blended along x, then along y: `l0 * a + l1 * b` of the up-sampling kernels with the
+// multiply-add fusion written out (what -ffp-contract=on makes of that expression: the left product is fused, the
+// right one rounded) and further contraction off, so that every call site -- the up-sampling kernels of tg_warp.hip
+// and the x2 up-sampling folded into the Winograd conv's staging (tg_conv3x3_wino.hip) -- rounds alike, bit for bit.
+__device__ __forceinline__ float bilinear_blend(float lx0, float lx1, float ly0, float ly1, float v00, float v01,
+                                                float v10, float v11) {
+#pragma clang fp contract(off)
+  const float top = __builtin_fmaf(lx0, v00, lx1 * v01);
+  const float bot = __builtin_fmaf(lx0, v10, lx1 * v11);
+  return __builtin_fmaf(ly0, top, ly1 * bot);
 }
 
 // fp32 torch.linspace(-1, 1, n)[i] (ATen CPU: two fused multiply-adds)

@@ -135,16 +135,37 @@ template <int TR> struct WGeo3 {
   static_assert(PR * RS <= W_ICSTR, "patch of one channel fits the channel stride");
 };
 
-template <bool COH, int TR = 1>
+// POOL: MaxPool2d(2, 2) in the epilogue.  A lane holds one 2x2 output tile per channel and tiles start at even
+// coordinates, so the pool is a max over the lane's four values; y is the (cout, h/2, w/2) tensor (y_ns its batch stride),
+// h and w are even, no residual and no mask.  Same values in the same fmaxf order as maxpool2_kernel: bit-identical to
+// the two launches.
+// UP2: the layer's input is bilinear_x2(x), x of size (cin, h/2, w/2): every staged element is blended on the fly from
+// its <= 4 source values (bilinear_src's taps and weights, bilinear_blend's expression: bit-identical to
+// upsample_kernel + this kernel), the 4x larger tensor never exists.  One packed word per staged element (below)
+// replaces the byte offset; single source only.
+constexpr unsigned W_UP2_OOB = 0xFFFFFF80u;     // packed word of a padding element: offset 2^27 - 4 bytes (the launcher keeps the
+                                                 // source below that), both weights (1, 0) -> 0
+
+// OC32: the workgroup shape of the layers with at most 32 output channels: 2 output-channel waves (16 channels each) x
+// 2 tile groups (16 tiles each, side by side along x), stages of 8 input channels.  Wave wv owns channels
+// [16 (wv & 1), +16) of tile group wv >> 1, so all four waves issue useful MFMAs (the 64-channel shape on the zero-padded
+// pack wastes two of them).  LDS keeps its size and layout with the "channel" index of the raw patch and of V read as
+// 8 * group + channel: 2 x 8 patches per stage, one (channel, tile) window per thread, the two waves of a group read
+// the same V.  Same pack, same K steps of 4 channels in the same order, same epilogue: bit-identical to the
+// 64-channel shape called with cout <= 32.
+template <bool COH, int TR = 1, bool POOL = false, bool UP2 = false, bool OC32 = false>
 __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int ocg, int n) {
   using G = WGeo3<TR>;
+  constexpr int ICS = OC32 ? W_ICS / 2 : W_ICS;      // input channels per stage
+  constexpr int KPS = ICS / 4;                        // K steps per stage
   __shared__ __attribute__((aligned(16))) float s_raw[W_ICS * W_ICSTR];   // 10 KB
   __shared__ __attribute__((aligned(16))) float s_v[2 * W_ICS * 16 * W_VS];   // 2 x 20 KB: [buffer][ic][tile][16 positions + pad]
 
   const int t = threadIdx.x, l = t & 63;
   const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int x0 = tx * (2 * G::TC), y0 = ty * (2 * TR);
+  const int x0 = (OC32 ? 2 * tx : tx) * (2 * G::TC), y0 = ty * (2 * TR);      // (OC32: of tile group 0)
   const int hw = a.h * a.w;
+  const int shw = UP2 ? (a.h >> 1) * (a.w >> 1) : hw;      // elements of one source channel plane
 
   // ---- raw patch staging: element e = t + 256 k = (ic, row, col) of the 16 x 4 x 34 patch ------
   constexpr int RAW_ELEMS = W_ICS * G::PE;
@@ -158,18 +179,50 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
   for (int k = 0; k < RAW_PER_T; ++k) {
     const int e = t + 256 * k;
     const int ic = e / G::PE, rem = e - ic * G::PE, r = rem / G::PC, c = rem - r * G::PC;
-    const int gy = y0 - 1 + r, gx = x0 - 1 + c;
-    roff[k] = (e < RAW_ELEMS && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w)
-                  ? (unsigned)(ic * hw + gy * a.w + gx) * 4u : OOB;
+    const int gy = y0 - 1 + r, gx = x0 + (OC32 ? (ic >> 3) * (2 * G::TC) : 0) - 1 + c;
+    const int sc = OC32 ? (ic & 7) : ic;      // source channel inside the stage
+    if constexpr (UP2) {
+      // [31:7] element offset of tap (y0, x0) inside the stage's 16 source planes | [6] y1 - y0 | [5] x1 - x0 |
+      // [4:3] 4 * ly1 | [2:1] 4 * lx1 (0, 1 or 3: bilinear_src's weights at scale 2 are 0 / 0.25 / 0.75, and l0 = 1 - l1)
+      int sy0, sy1, sx0, sx1; float ly0, ly1, lx0, lx1;
+      bilinear_src(gy, 2, a.h >> 1, sy0, sy1, ly0, ly1);
+      bilinear_src(gx, 2, a.w >> 1, sx0, sx1, lx0, lx1);
+      roff[k] = (e < RAW_ELEMS && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w)
+                    ? ((unsigned)(sc * shw + sy0 * (a.w >> 1) + sx0) << 7) | ((unsigned)(sy1 - sy0) << 6) |
+                          ((unsigned)(sx1 - sx0) << 5) | ((unsigned)(int)(4.f * ly1) << 3) | ((unsigned)(int)(4.f * lx1) << 1)
+                    : W_UP2_OOB;
+    } else {
+      roff[k] = (e < RAW_ELEMS && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w)
+                    ? (unsigned)(sc * hw + gy * a.w + gx) * 4u : OOB;
+    }
   }
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x + (size_t)n * a.x_ns), 0, (unsigned)a.c1 * hw * 4u, 0x00020000);
+      const_cast<float*>(a.x + (size_t)n * a.x_ns), 0, (unsigned)a.c1 * shw * 4u, 0x00020000);
   const __amdgpu_buffer_rsrc_t rx2 = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(a.x2 ? a.x2 + (size_t)n * a.x2_ns : a.x), 0,
       a.x2 ? (unsigned)(a.cin - a.c1) * hw * 4u : 0u, 0x00020000);
-  const bool dual = a.x2 != nullptr;
+  const bool dual = !UP2 && a.x2 != nullptr;
   auto load_raw = [&](int s, float (&reg)[RAW_PER_T]) {
-    const unsigned so = (unsigned)(s * W_ICS) * hw * 4u;
+    const unsigned so = (unsigned)(s * ICS) * shw * 4u;
+    if constexpr (UP2) {
+      const unsigned ws4 = (unsigned)(a.w >> 1) * 4u;
+#pragma unroll
+      for (int k = 0; k < RAW_PER_T; ++k) {
+        // (the empty asm makes the word opaque: everything decoded from it is the same in every stage, and hoisted out
+        // of the K loop the 4 offsets and 4 weights of 9 elements are 70 registers the kernel does not have)
+        unsigned wd = roff[k];
+        asm volatile("" : "+v"(wd));
+        const unsigned o00 = ((wd >> 5) & ~3u) + so, dxb = (wd >> 3) & 4u;
+        const unsigned o10 = o00 + ((wd >> 6) & 1u) * ws4;
+        auto ld = [&](unsigned o) {
+          return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, (int)o, 0, COH ? AUX_SC1 : 0));
+        };
+        const float v00 = ld(o00), v01 = ld(o00 + dxb), v10 = ld(o10), v11 = ld(o10 + dxb);
+        const float ly1 = 0.25f * (float)((wd >> 3) & 3u), lx1 = 0.25f * (float)((wd >> 1) & 3u);
+        reg[k] = bilinear_blend(1.0f - lx1, lx1, 1.0f - ly1, ly1, v00, v01, v10, v11);
+      }
+      return;
+    }
 #pragma unroll
     for (int k = 0; k < RAW_PER_T; ++k) {
       float v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, (int)(roff[k] + so), 0, COH ? AUX_SC1 : 0));
@@ -189,9 +242,9 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
   };
 
   // ---- transformed weights: 4 x 16-byte loads per K step, perfectly coalesced ---------------
-  const f32x4* ug = reinterpret_cast<const f32x4*>(a.u) + ((size_t)(ocg * 4 + wv) * 4) * 64 + l;
+  const f32x4* ug = reinterpret_cast<const f32x4*>(a.u) + ((size_t)(OC32 ? (wv & 1) : ocg * 4 + wv) * 4) * 64 + l;
   const size_t ustep = (size_t)a.nocb * 4 * 64;
-  const int ktotal = 4 * a.nstage;
+  const int ktotal = KPS * a.nstage;
   // one half (positions 8*half .. 8*half+7) of the weights of K step `kstep`
   auto load_uh = [&](int kstep, int half, f32x4 (&u)[4]) {
     // BRANCH-FREE (round 5): behind `if (kstep < ktotal)` the compiler's s_waitcnt insertion merges both paths at the
@@ -212,7 +265,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
   constexpr int VBUF4 = W_ICS * 16 * W_VS / 4;          // one V buffer in 16-byte units
   const float* traw = s_raw + (t >> 4) * W_ICSTR + 2 * ((t & 15) / G::TC) * G::RS + 2 * ((t & 15) % G::TC);
   f32x4* tv = reinterpret_cast<f32x4*>(s_v + t * W_VS);                                        // 4 x 16 bytes per buffer
-  const f32x4* bv = reinterpret_cast<const f32x4*>(s_v + ((l >> 4) * 16 + (l & 15)) * W_VS);   // + ks * 4*16*W_VS floats
+  const f32x4* bv = reinterpret_cast<const f32x4*>(s_v + ((OC32 ? 8 * (wv >> 1) : 0) * 16 + (l >> 4) * 16 + (l & 15)) * W_VS);   // + ks * 4*16*W_VS floats
 
   // 8 MFMAs: positions 8*half .. 8*half+7 of K step ks (B operand from V[buf])
   auto mfma8 = [&](const f32x4 (&u)[4], int buf, int ks, int half) {
@@ -228,11 +281,11 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
   // block has been consumed, the same half of K step k+2 is requested into it -- 1.5 K steps
   // (24 MFMAs of this wave, ~3x that with three waves per SIMD) of distance on two blocks
   auto kstep = [&](int k, f32x4 (&u)[4], int buf, auto&& between) {
-    mfma8(u, buf, k & 3, 0);
+    mfma8(u, buf, k & (KPS - 1), 0);
     __builtin_amdgcn_sched_barrier(0);
     load_uh(k + 2, 0, u);
     between();
-    mfma8(u, buf, k & 3, 1);
+    mfma8(u, buf, k & (KPS - 1), 1);
     __builtin_amdgcn_sched_barrier(0);
     load_uh(k + 2, 1, u);
   };
@@ -257,11 +310,11 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
   };
 
   // epilogue geometry (needed early: the residual is fetched under the last stage's MFMAs)
-  const int ox = x0 + 2 * ((l & 15) % G::TC);
+  const int ox = x0 + (OC32 ? (wv >> 1) * (2 * G::TC) : 0) + 2 * ((l & 15) % G::TC);
   const int oy0 = y0 + 2 * ((l & 15) / G::TC);      // first output row of the lane's tile
-  const int oc_base = ocg * 64 + wv * 16 + 4 * (l >> 4);
+  const int oc_base = OC32 ? (wv & 1) * 16 + 4 * (l >> 4) : ocg * 64 + wv * 16 + 4 * (l >> 4);
   const float* rn = a.res ? a.res + (size_t)n * a.res_ns : nullptr;
-  const bool res_pre = rn && a.vec_ok;
+  const bool res_pre = !POOL && rn && a.vec_ok;
 
   // ---- prologue: stage 0 transformed, stage 1's patch in LDS (not yet published) -------------
   float rawreg[RAW_PER_T];
@@ -285,6 +338,17 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
   auto nothing = [] {};
   for (int s = 0; s < last; ++s) {
     const int cur = s & 1, nxt = cur ^ 1;
+    if constexpr (OC32) {      // two K steps per stage: the same hand-over points around 32 instead of 64 MFMAs
+      kstep(2 * s + 0, u0, cur, [&] {
+        __syncthreads();                       // patch of stage s+1 visible
+        if (s + 2 <= last) load_raw(s + 2, rawreg);
+        transform_half(nxt, 0);
+      });
+      kstep(2 * s + 1, u1, cur, [&] { transform_half(nxt, 1); });
+      __syncthreads();                         // V[nxt] visible, V[cur] and the patch free
+      if (s + 2 <= last) store_raw(rawreg);
+      continue;
+    }
     kstep(4 * s + 0, u0, cur, nothing);
     __syncthreads();                         // patch of stage s+1 visible
     if (s + 2 <= last) load_raw(s + 2, rawreg);    // (a branch-free form of THIS prefetch measured +-0: its loads are consumed
@@ -299,9 +363,11 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
   float2 rpre[4][2];
   {
     const int cur = last & 1;
-    kstep(4 * last + 0, u0, cur, nothing);
-    kstep(4 * last + 1, u1, cur, nothing);
-    kstep(4 * last + 2, u0, cur, nothing);
+    if constexpr (!OC32) {
+      kstep(4 * last + 0, u0, cur, nothing);
+      kstep(4 * last + 1, u1, cur, nothing);
+    }
+    kstep(KPS * last + KPS - 2, u0, cur, nothing);
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -310,7 +376,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
         if (res_pre && oc_base + r < a.cout && ox < a.w && oy0 + i < a.h)
           rpre[r][i] = ld2<COH>(rn + (size_t)(oc_base + r) * hw + (size_t)(oy0 + i) * a.w + ox);
       }
-    kstep(4 * last + 3, u1, cur, nothing);
+    kstep(KPS * last + KPS - 1, u1, cur, nothing);
   }
 
   // ---- inverse transform A^T m A, epilogue -------------------------------------------------
@@ -328,6 +394,23 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
     }
     if (oc >= a.cout || ox >= a.w) continue;
     const float bz = a.bias ? a.bias[oc] : 0.f;
+    if constexpr (POOL) {      // h, w even: the whole 2x2 tile is inside the map when its first pixel is
+      if (oy0 >= a.h) continue;
+      float m[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        float v0 = ((sr[i][0] + sr[i][1]) + sr[i][2]) + bz;
+        float v1 = ((sr[i][1] - sr[i][2]) - sr[i][3]) + bz;
+        if (a.act == TG_ACT_TANH24) { v0 = apply_act(v0, a.act); v1 = apply_act(v1, a.act); }
+        else {
+          v0 = __builtin_fmaxf(v0, slope * v0);
+          v1 = __builtin_fmaxf(v1, slope * v1);
+        }
+        m[i] = fmaxf(v0, v1);
+      }
+      st1<COH>(yn + (size_t)oc * (hw >> 2) + (size_t)(oy0 >> 1) * (a.w >> 1) + (ox >> 1), fmaxf(m[0], m[1]));
+      continue;
+    }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int oy = oy0 + i;
@@ -355,7 +438,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
   }
 }
 
-template <int TR>
+template <int TR, bool POOL = false, bool UP2 = false, bool OC32 = false>
 __global__ __launch_bounds__(256, 3) void conv3x3_wino_kernel(WinoArgs a) {
   int b = blockIdx.x;
   if (a.nblocks > 0) {      // XCD x gets the contiguous band of tiles [x*per, (x+1)*per)
@@ -367,7 +450,7 @@ __global__ __launch_bounds__(256, 3) void conv3x3_wino_kernel(WinoArgs a) {
   const int ty = __builtin_amdgcn_readfirstlane(b % a.tiles_y); b /= a.tiles_y;
   const int ocg = __builtin_amdgcn_readfirstlane(b % a.nocg);
   const int n = __builtin_amdgcn_readfirstlane(b / a.nocg);
-  wino_tile<false, TR>(a, tx, ty, ocg, n);
+  wino_tile<false, TR, POOL, UP2, OC32>(a, tx, ty, ocg, n);
 }
 
 // ---- several dependent layers in ONE launch ----------------------------------------------------
@@ -481,10 +564,34 @@ extern "C" int64_t tg_conv3x3_wino_packed_floats(int cin, int cout) {
 // training frames, FNet's low-resolution middle at batch 1: 33x80, 16x40) the one-shot / split-K
 // kernels win by 5-30 %.
 // TG_CONV_WINO=0/1 overrides (lab / A-B).
-extern "C" int tg_conv3x3_prefers_wino(int n, int cin, int cout, int h, int w) {
+// cout = 32 (tools/fnet_layers.sh, 8 frame pairs of 134x320, EXPERIMENTS.md): measured only in the batched flow pass,
+// where the form also takes the neighbouring pool / up-sampling launch with it; smaller passes keep the direct kernel.
+constexpr long long W32_MIN_WGS = 2048;
+static int wino_env() {
   static const int env = [] { const char* e = getenv("TG_CONV_WINO"); return e && *e ? atoi(e) : -1; }();
+  return env;
+}
+
+namespace tg {
+// Whether the frame plan folds the x2 up-sampling in front of this layer into it (UP2).  Measured at 8 frame pairs of
+// 134x320 (EXPERIMENTS.md): the four loads per staged element make the layer wait for the texture addresser -- -2 us
+// (128 -> 64 at 64x160) to +15 us (64 -> 32 at 128x320) against the separate launch -- so the plan keeps that launch.
+// With the form forced (TG_CONV_WINO=1: tests, lab) it folds wherever the shape allows.
+bool conv3x3_wino_folds_up2(int n, int cin, int cout, int h, int w) {
+  return wino_env() == 1 && tg_conv3x3_prefers_wino(n, cin, cout, h, w) && conv3x3_wino_fuse_ok(cin, h, w, TG_WINO_UP2);
+}
+}  // namespace tg
+
+extern "C" int tg_conv3x3_prefers_wino(int n, int cin, int cout, int h, int w) {
+  const int env = wino_env();
   if (env == 0) return 0;
-  if (n <= 0 || cin < 16 || cout <= 0 || cout % 64 != 0 || h < 2 || w < 2) return 0;
+  if (n <= 0 || cin < 16 || cout <= 0 || h < 2 || w < 2) return 0;
+  if (cout == 32) {      // the 32-channel workgroup shape (32 tiles): FNet's two full-resolution layers in a batched flow pass
+    if (cin < 32) return 0;
+    const long long wgs32 = (long long)cdiv(w, 64) * cdiv(h, 2) * n;
+    return env == 1 ? 1 : (wgs32 >= W32_MIN_WGS ? 1 : 0);
+  }
+  if (cout % 64 != 0) return 0;
   const long long wgs = (long long)cdiv(w, 32) * cdiv(h, 2) * (cout / 64) * n;
   // (narrow images waste the columns of a 2 x 32 pixel workgroup, but those of the direct kernel's
   // 32-pixel tiles just the same: at 16x16 x 36 frames the Winograd form still takes 0.6x the time)
@@ -504,28 +611,55 @@ extern "C" int tg_pack_conv3x3_wino(const float* w, float* out, int cin, int cou
 }
 
 namespace tg {
+// Shapes the fused forms take: POOL needs whole 2x2 tiles (h, w even); UP2 an even up-sampled map whose source
+// offsets fit the staging's packed word (25 bits of element offset inside a stage of 16 planes, the all-ones
+// offset kept for the padding and out of the source's bounds).
+bool conv3x3_wino_fuse_ok(int cin, int h, int w, int fuse) {
+  if (fuse & ~(TG_WINO_POOL | TG_WINO_UP2)) return false;
+  if ((fuse & TG_WINO_POOL) && (fuse & TG_WINO_UP2)) return false;
+  if (fuse && (h < 2 || w < 2 || h % 2 || w % 2)) return false;
+  if ((fuse & TG_WINO_UP2) && 16ll * cdiv(cin, 16) * (h / 2) * (w / 2) >= (1ll << 25) - 1) return false;
+  return true;
+}
+
+template <int TR, bool OC32>
+static void wino_launch_tr(int fuse, unsigned grid, hipStream_t st, const WinoArgs& a) {
+  if (fuse == TG_WINO_POOL) hipLaunchKernelGGL((conv3x3_wino_kernel<TR, true, false, OC32>), dim3(grid), dim3(256), 0, st, a);
+  else if (fuse == TG_WINO_UP2) hipLaunchKernelGGL((conv3x3_wino_kernel<TR, false, true, OC32>), dim3(grid), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((conv3x3_wino_kernel<TR, false, false, OC32>), dim3(grid), dim3(256), 0, st, a);
+}
+
 int conv3x3_wino_launch(const float* x, int64_t x_ns, int c1, const float* x2, int64_t x2_ns, const float* u,
                         const float* bias, const float* res, int64_t res_ns, const float* mask,
                         int64_t mask_ns, float* y, int64_t y_ns, int n, int cin, int cout, int h, int w,
-                        int act, tg_stream_t stream) {
+                        int act, tg_stream_t stream, int fuse) {
+  TG_REQUIRE(conv3x3_wino_fuse_ok(cin, h, w, fuse), TG_E_SHAPE,
+             "conv3x3_wino: fuse=%d needs even h=%d w=%d (pool and up2 not together, up2 source below 2^25 elements per stage)",
+             fuse, h, w);
+  TG_REQUIRE(!(fuse & TG_WINO_POOL) || (!res && !mask), TG_E_ARG, "conv3x3_wino: pool takes no residual and no mask");
+  TG_REQUIRE(!(fuse & TG_WINO_UP2) || !x2, TG_E_ARG, "conv3x3_wino: up2 takes a single source");
   WinoArgs a{};
   a.x = x; a.x2 = x2; a.u = u; a.bias = bias; a.res = res; a.mask = mask; a.y = y;
   a.x_ns = x_ns; a.x2_ns = x2_ns; a.res_ns = res_ns; a.mask_ns = mask_ns; a.y_ns = y_ns;
   a.c1 = x2 ? c1 : cin; a.cin = cin; a.cout = cout; a.h = h; a.w = w; a.act = act;
   // tile arrangement of a workgroup's 16 tiles: the one that covers the map with the fewest workgroups
   // (ties: the widest -- longest coalesced rows); lab builds: TG_WINO_TR forces one
+  // (cout <= 32: the workgroup of two 16-tile groups side by side, twice as wide)
+  const bool oc32 = cout <= 32;
+  const int wgw = oc32 ? 64 : 32;
   int tr = 1;
   {
-    long long best = (long long)cdiv(w, 32) * cdiv(h, 2);
+    long long best = (long long)cdiv(w, wgw) * cdiv(h, 2);
     for (int cand = 2; cand <= 4; cand *= 2) {
-      const long long c = (long long)cdiv(w, 32 / cand) * cdiv(h, 2 * cand);
+      const long long c = (long long)cdiv(w, wgw / cand) * cdiv(h, 2 * cand);
       if (c < best) { best = c; tr = cand; }
     }
     static const int tr_env = TG_LAB_ENV("TG_WINO_TR", 0);
     if (tr_env == 1 || tr_env == 2 || tr_env == 4) tr = tr_env;
   }
-  a.tiles_x = cdiv(w, 32 / tr); a.tiles_y = cdiv(h, 2 * tr);
-  a.nstage = cdiv(cin, 16); a.nocg = cdiv(cout, 64); a.nocb = 4 * a.nocg;
+  a.tiles_x = cdiv(w, wgw / tr); a.tiles_y = cdiv(h, 2 * tr);
+  a.nstage = (oc32 ? 2 : 1) * cdiv(cin, 16);      // (stages of 8 channels: the same K steps, the pack's zero padding included)
+  a.nocg = cdiv(cout, 64); a.nocb = 4 * a.nocg;
   auto al8 = [](const void* p, int64_t ns) { return ((uintptr_t)p % 8) == 0 && ns % 2 == 0; };
   a.vec_ok = (w % 2 == 0) && ((int64_t)h * w) % 2 == 0 && al8(y, y_ns) && (!res || al8(res, res_ns)) &&
              (!mask || al8(mask, mask_ns));
@@ -534,9 +668,13 @@ int conv3x3_wino_launch(const float* x, int64_t x_ns, int c1, const float* x2, i
   const bool xcd = xcd_env >= 0 ? xcd_env != 0 : blocks >= 512;
   a.nblocks = xcd ? (int)blocks : 0;
   const unsigned grid = xcd ? (unsigned)(8 * ((blocks + 7) / 8)) : (unsigned)blocks;
-  if (tr == 1) hipLaunchKernelGGL(conv3x3_wino_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-  else if (tr == 2) hipLaunchKernelGGL(conv3x3_wino_kernel<2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(conv3x3_wino_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+  if (oc32) {
+    if (tr == 1) wino_launch_tr<1, true>(fuse, grid, (hipStream_t)stream, a);
+    else if (tr == 2) wino_launch_tr<2, true>(fuse, grid, (hipStream_t)stream, a);
+    else wino_launch_tr<4, true>(fuse, grid, (hipStream_t)stream, a);
+  } else if (tr == 1) wino_launch_tr<1, false>(fuse, grid, (hipStream_t)stream, a);
+  else if (tr == 2) wino_launch_tr<2, false>(fuse, grid, (hipStream_t)stream, a);
+  else wino_launch_tr<4, false>(fuse, grid, (hipStream_t)stream, a);
   return check_launch("conv3x3_wino");
 }
 }  // namespace tg
@@ -554,6 +692,18 @@ extern "C" int tg_conv3x3_wino_fwd(const float* x, int64_t x_nstride, int c1, co
   TG_REQUIRE((long long)cin * h * w < (1ll << 29), TG_E_SHAPE, "conv3x3_wino: image too large");
   return conv3x3_wino_launch(x, x_nstride, c1, x2, x2_nstride, u_packed, bias, res, res_nstride, relu_mask,
                              mask_nstride, y, y_nstride, n, cin, cout, h, w, act, stream);
+}
+
+extern "C" int tg_conv3x3_wino_fused_fwd(const float* x, int64_t x_nstride, const float* u_packed, const float* bias,
+                                         float* y, int64_t y_nstride, int n, int cin, int cout, int h, int w, int act,
+                                         int fuse, tg_stream_t stream) {
+  TG_REQUIRE(x && u_packed && y, TG_E_ARG, "conv3x3_wino_fused: null pointer");
+  TG_REQUIRE(n > 0 && cin > 0 && cout > 0 && h > 0 && w > 0, TG_E_SHAPE, "conv3x3_wino_fused: n=%d cin=%d cout=%d h=%d w=%d",
+             n, cin, cout, h, w);
+  TG_REQUIRE(act >= TG_ACT_NONE && act <= TG_ACT_TANH24, TG_E_ARG, "conv3x3_wino_fused: act=%d", act);
+  TG_REQUIRE((long long)cin * h * w < (1ll << 29), TG_E_SHAPE, "conv3x3_wino_fused: image too large");
+  return conv3x3_wino_launch(x, x_nstride, cin, nullptr, 0, u_packed, bias, nullptr, 0, nullptr, 0, y, y_nstride, n, cin,
+                             cout, h, w, act, stream, fuse);
 }
 
 extern "C" int64_t tg_conv3x3_wino_chain_flag_ints(int n_layers, int n, int h, int w) {

@@ -464,9 +464,7 @@ __global__ void upsample_kernel(const float* __restrict__ x, float* __restrict__
       int y0, y1, x0, x1; float ly0, ly1, lx0, lx1;
       bilinear_src(oyy, s, h, y0, y1, ly0, ly1);
       bilinear_src(oxx, s, w, x0, x1, lx0, lx1);
-      float top = lx0 * src[y0 * w + x0] + lx1 * src[y0 * w + x1];
-      float bot = lx0 * src[y1 * w + x0] + lx1 * src[y1 * w + x1];
-      v = ly0 * top + ly1 * bot;
+      v = bilinear_blend(lx0, lx1, ly0, ly1, src[y0 * w + x0], src[y0 * w + x1], src[y1 * w + x0], src[y1 * w + x1]);
     }
     y[i] = mul * v;
   }
@@ -513,10 +511,7 @@ __global__ __launch_bounds__(256) void upsample_bilinear2x_kernel(const float* _
         const float ta = tv[ka], ba = bv[ka];
         const float tb = o == 0 ? (m ? tv[1] : tv[2]) : (o == 3 ? tv[3] : tv[2]);
         const float bb = o == 0 ? (m ? bv[1] : bv[2]) : (o == 3 ? bv[3] : bv[2]);
-        float top = lx0[o] * ta + lx1[o] * tb;
-        float bot = lx0[o] * ba + lx1[o] * bb;
-        float vv = ly0 * top + ly1 * bot;
-        o4[o] = mul * vv;
+        o4[o] = mul * bilinear_blend(lx0[o], lx1[o], ly0, ly1, ta, tb, ba, bb);
       }
       *reinterpret_cast<float4*>(dst + (size_t)e * ow) = make_float4(o4[0], o4[1], o4[2], o4[3]);
     }

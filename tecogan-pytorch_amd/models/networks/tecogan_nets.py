@@ -53,8 +53,8 @@ class _Conv(nn.Module):
 
     def packed_wino(self):
         """Winograd-form weights (tg_pack_conv3x3_wino) of a plain 3x3 layer, or None when the
-        layer has no such form (transposed, cout not a multiple of 64, cin < 16)."""
-        if self.transposed or self.cout % 64 != 0 or self.cin < 16:
+        layer has no such form (transposed, cout neither 32 nor a multiple of 64, cin < 16)."""
+        if self.transposed or (self.cout % 64 != 0 and self.cout != 32) or self.cin < 16:
             return None
         w = self.weight
         key = (ops.param_version(w), w.device)

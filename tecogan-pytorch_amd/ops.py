@@ -1403,8 +1403,28 @@ def pack_conv3x3_wino(w, transposed=0):
     return out
 
 
-def conv3x3_wino(x, u_packed, bias, cin, cout, act=ACT_NONE, x2=None, res=None, mask=None, out=None):
+WINO_POOL, WINO_UP2 = 1, 2       # TG_WINO_POOL / TG_WINO_UP2
+
+
+def conv3x3_wino(x, u_packed, bias, cin, cout, act=ACT_NONE, x2=None, res=None, mask=None, out=None, pool=False,
+                 up2=False):
+    """tg_conv3x3_wino_fwd.  pool: MaxPool2d(2, 2) folded into the epilogue, the result is (n, cout, h/2, w/2);
+    up2: x is the (n, cin, h/2, w/2) source of a bilinear x2 up-sampling folded into the input staging
+    (tg_conv3x3_wino_fused_fwd: single source, no residual, no mask; bit-identical to the separate launches)."""
     _chk(x, 'x'); _chk(u_packed, 'u_packed')
+    if pool or up2:
+        if x2 is not None or res is not None or mask is not None:
+            raise L.TecoganHipError('conv3x3_wino: pool / up2 take a single source, no residual and no mask')
+        n, c1, h, w = x.shape
+        assert c1 == cin
+        if up2:
+            h, w = 2 * h, 2 * w
+        y = out if out is not None else torch.empty(n, cout, h // 2 if pool else h, w // 2 if pool else w,
+                                                    dtype=torch.float32, device=x.device)
+        L.check(L.lib().tg_conv3x3_wino_fused_fwd(
+            x.data_ptr(), x.stride(0), u_packed.data_ptr(), _ptr(bias), y.data_ptr(), y.stride(0), n, cin, cout, h, w,
+            act, (WINO_POOL if pool else 0) | (WINO_UP2 if up2 else 0), _stream()), 'tg_conv3x3_wino_fused_fwd')
+        return y
     n, c1, h, w = x.shape
     if x2 is not None:
         _chk(x2, 'x2')

@@ -540,6 +540,27 @@ int tg_yuv420_to_rgb_f32(const uint8_t* yuv, float* rgb_chw, int n, int h, int w
 int tg_rgb_u8_to_yuv420(const uint8_t* rgb_hwc, uint8_t* yuv, int n, int H, int W, int matrix, int full_range,
                         int siting, tg_stream_t stream);
 
+/* The BI degradation: scripts/generate_lr_bi.m of the reference -- im2double, modcrop,
+ * imresize(img, 1/scale, 'bicubic'), imwrite -- on 8-bit frames, in exact integers, one launch per batch.  scale is 2
+ * or 4 (else TG_E_ARG).  The frame is cut to (h - h % scale, w - w % scale); LR pixel o of an axis reads the 4*scale
+ * pixels from scale*o - 3*scale/2 on, out-of-range indices mirrored with the edge pixel repeated, with the weights
+ * (-3, -9, 29, 111 | mirrored) / 256 for scale 2 and (-7, -45, -75, -49, 93, 399, 745, 987 | mirrored) / 4096 for
+ * scale 4.  With N the exact separable sum and D the squared denominator the byte is clamp((2N + D) // 2D, 0, 255).
+ *   pad 1: LR (h/scale, w/scale).  pad 0 (training crops that carry 2*scale GT pixels of border per side): the same
+ *   with 2 LR pixels cut from every side, (h/scale - 4, w/scale - 4); needs more than 4*scale pixels per axis.
+ * Outputs, either or both (the other NULL): y_u8_hwc (n, h', w', 3) uint8 and y_f32_chw (n, 3, h', w') = (float)byte /
+ * 255.0f, the value a loader makes of an LR PNG.
+ *   tg_downsample_bi_u8:  x_hwc (n, h, w, 3) uint8.
+ *   tg_downsample_bi_f32: x_chw (n, 3, h, w) fp32, each value first taken to its byte as tg_quantize_u8_hwc does
+ *   (exact for the k / 255 every loader delivers).
+ * A workgroup makes TG_BI_TILE_H x TG_BI_TILE_W LR pixels. */
+#define TG_BI_TILE_H 8
+#define TG_BI_TILE_W 32
+int tg_downsample_bi_u8(const uint8_t* x_hwc, uint8_t* y_u8_hwc, float* y_f32_chw, int n, int h, int w, int scale,
+                        int pad, tg_stream_t stream);
+int tg_downsample_bi_f32(const float* x_chw, uint8_t* y_u8_hwc, float* y_f32_chw, int n, int h, int w, int scale,
+                         int pad, tg_stream_t stream);
+
 /* MetricCalculator.compute_PSNR (codes/metrics/metric_calculator.py:228-244) on uint8 HWC
  * frames resident on the device: sse[f] = sum of squared differences of frame f, exact
  * (integers), on the Y channel of rgb_to_ycbcr (codes/utils/data_utils.py:56-77) when

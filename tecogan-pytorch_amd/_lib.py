@@ -97,6 +97,8 @@ SIGNATURES = {
     'tg_dequantize_u8_hwc': (I, [P, P, I, I, I, I, P]),
     'tg_yuv420_to_rgb_f32': (I, [P, P, I, I, I, I, I, I, P]),
     'tg_rgb_u8_to_yuv420': (I, [P, P, I, I, I, I, I, I, P]),
+    'tg_downsample_bi_u8': (I, [P, P, P, I, I, I, I, I, P]),
+    'tg_downsample_bi_f32': (I, [P, P, P, I, I, I, I, I, P]),
     'tg_psnr_sse_u8': (I, [P, P, P, I, I, I, I, P]),
     'tg_luma_u8': (I, [P, P, I64, P]),
     'tg_lpips_conv_fwd': (I, [P, P, I, P, P, P, P, I, I, I, I, I, I, I, I, P]),

@@ -11,7 +11,8 @@ from .unpaired_lmdb_dataset import ClipPlan, UnpairedLMDBDataset
 class TrainSource:
     """What codes/data/__init__.py:create_dataloader(opt, 'train', ...) provides: an iterable of
     {'gt': (n, t, 3, S + 2b, S + 2b) fp32} batches for BD training, {'gt': (n, t, 3, S, S), 'lr': (n, t, 3, S/s,
-    S/s)} for BI (paired sets), here already on the device.  Epoch order = DataLoader(shuffle=True, drop_last=True), or under
+    S/s)} for BI (paired sets; with degradation.on_device the bordered 'gt' alone, b = 2s), here already on the
+    device.  Epoch order = DataLoader(shuffle=True, drop_last=True), or under
     torch.distributed the DistributedSampler rule (permutation seeded with seed + epoch, padded
     to a multiple of the world size, every world-th index starting at rank)."""
 
@@ -26,8 +27,15 @@ class TrainSource:
         common = dict(tempo_extent=opt['train']['tempo_extent'],
                       moving_first_frame=opt['train'].get('moving_first_frame', False),
                       moving_factor=opt['train'].get('moving_factor', 1.0))
-        self.paired = deg == 'BI'
-        if deg == 'BI':          # paired GT / LR sets (paired_lmdb_dataset.py; data/__init__.py:22-29)
+        on_device = bool(opt['dataset']['degradation'].get('on_device', False))
+        self.paired = deg == 'BI' and not on_device
+        if deg == 'BI' and on_device:
+            # unpaired GT, the crop enlarged by 2 * scale per side: LR is made from it by ops.downsample_bi
+            # (prepare_training_data)
+            self.dataset = UnpairedLMDBDataset(data_opt, crop_size=data_opt['crop_size'] + 4 * opt['scale'], **common)
+            seqs = {parse_lmdb_key(k)[0] for k in self.dataset.keys}
+            self.store = self._load(data_opt['seq_dir'], seqs, dev)
+        elif deg == 'BI':        # paired GT / LR sets (paired_lmdb_dataset.py; data/__init__.py:22-29)
             self.dataset = PairedLMDBDataset(data_opt, scale=opt['scale'], **common)
             seqs = {parse_lmdb_key(g)[0] for g, _ in self.dataset.gt_lr_keys}
             self.store = self._load(data_opt['gt_seq_dir'], seqs, dev)

@@ -3,7 +3,8 @@ unpaired_folder_dataset.py:16-52, utils/base_utils.py:114-138), decoded with Pil
 
 `gt_seq_dir/<key>/...` holds one sequence per key (frames found recursively, sorted, png | jpg);
 with `lr_seq_dir` the sequences are paired (keys present in both), without it the LR frames are made
-from the GT by the BD degradation (prepare_inference_data).  `filter_file` (one key per line) or
+from the GT on the device (prepare_inference_data): by the BD degradation, or -- for an entry with `on_device: true` --
+by the BI degradation.  `filter_file` (one key per line) or
 `filter_list` selects keys."""
 import os
 import os.path as osp
@@ -44,8 +45,13 @@ class FolderDataset:
     def __init__(self, data_opt, degradation='BD'):
         self.gt_seq_dir = data_opt['gt_seq_dir']
         self.lr_seq_dir = data_opt.get('lr_seq_dir') or None
-        if self.lr_seq_dir is None and degradation != 'BD':
-            raise ValueError('"lr_seq_dir" is required for BI mode')
+        if degradation not in ('BD', 'BI'):
+            raise ValueError(f'Unrecognized degradation type: {degradation}')
+        # BI sets are paired unless the entry opts in to LR frames made from the GT on the device (`on_device: true`;
+        # main.folder_test_sets hands down dataset.degradation.on_device): DESIGN.md section 7g
+        if self.lr_seq_dir is None and degradation == 'BI' and not data_opt.get('on_device', False):
+            raise ValueError('"lr_seq_dir" is required for BI mode (or "on_device": true, to make the LR frames from '
+                             'the GT by the BI degradation on the device)')
         keys = set(os.listdir(self.gt_seq_dir))
         if self.lr_seq_dir is not None:
             keys &= set(os.listdir(self.lr_seq_dir))

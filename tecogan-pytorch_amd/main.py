@@ -4,8 +4,8 @@ codes/utils/base_utils.py:14-30): train | test | profile -- and infer, which the
 `train` reads the reference's LMDB training sets when `dataset.train.seq_dir` names one
 (tecogan_pytorch_amd/data: the decoded frames live in HBM, batches are cut out by a HIP
 kernel with the reference's augmentation).  `test` reads the reference's PNG folders when the
-yml's `dataset.test*` entries name an existing `gt_seq_dir` (and `lr_seq_dir`, or BD degradation
-of the GT) and evaluates with the yml's `metric` section (PSNR, LPIPS).  Otherwise clips come from
+yml's `dataset.test*` entries name an existing `gt_seq_dir` (and `lr_seq_dir`, or the BD degradation of the GT, or
+with `degradation.on_device` the BI one, on the device) and evaluates with the yml's `metric` section (PSNR, LPIPS).  Otherwise clips come from
 a synthetic source that honours the loader's output contract (unpaired_lmdb_dataset.py:89-93,
 paired_folder_dataset.py:57-63); any iterable of such dicts can be passed to `train()` / `test()`.
 
@@ -130,14 +130,19 @@ def seed_everything(seed):
 
 
 def synthetic_train_batches(opt, n_iter, seed):
-    """{'gt': n x t x 3 x (S+2b) x (S+2b) float32 in [0,1]} (BD; b = int(3 sigma))."""
+    """{'gt': n x t x 3 x (S+2b) x (S+2b) float32 in [0,1]} (BD: b = int(3 sigma); BI, degraded on the device: the
+    bytes k / 255 a loader delivers, b = 2 scale)."""
     g = torch.Generator().manual_seed(seed)
     n = opt['dataset']['train'].get('batch_size_per_gpu', 2)
     t = opt['train']['tempo_extent']
     s = opt['dataset']['train']['crop_size']
     b = int(opt['dataset']['degradation'].get('sigma', 1.5) * 3.0)
+    bi = opt['dataset']['degradation']['type'] == 'BI'
+    if bi:
+        b = 2 * opt['scale']
     for _ in range(n_iter):
-        yield {'gt': torch.rand(n, t, 3, s + 2 * b, s + 2 * b, generator=g)}
+        gt = torch.rand(n, t, 3, s + 2 * b, s + 2 * b, generator=g)
+        yield {'gt': (gt * 255).round() / 255 if bi else gt}
 
 
 def resume(model, opt, it):
@@ -295,6 +300,8 @@ def folder_test_sets(opt):
             continue
         if not os.path.isdir(d['gt_seq_dir']):
             continue
+        if 'on_device' not in d and opt['dataset'].get('degradation', {}).get('on_device'):
+            d = dict(d, on_device=True)         # BI without lr_seq_dir: LR from GT on the device
         out.append((d.get('name', key), FolderDataset(d, degradation=deg)))
     return out
 

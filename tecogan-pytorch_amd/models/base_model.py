@@ -95,6 +95,20 @@ class BaseModel:
         """base_model.py:42-85.  BD: LR = Gaussian blur + stride-s decimation of the
         bordered GT on the device (HIP kernel), GT border cropped."""
         deg = self.opt['dataset']['degradation']['type']
+        if deg == 'BI' and 'lr' not in data:
+            # degradation.on_device (DESIGN.md section 7g): unpaired GT crops that carry 2 * scale pixels of border
+            # per side; LR = the BI degradation of the crop in exact integers (HIP kernel), GT border cropped
+            scale = self.opt['scale']
+            border = 2 * scale
+            gt = data['gt'].to(self.device, dtype=torch.float32)
+            n, t, c, gh, gw = gt.shape
+            flat = gt.reshape(n * t, c, gh, gw).contiguous()
+            lr = ops.downsample_bi(flat, scale, pad=False)
+            lr_h, lr_w = lr.shape[2:]
+            self.lr_data = lr.view(n, t, c, lr_h, lr_w)
+            self.gt_data = flat[..., border:border + scale * lr_h, border:border + scale * lr_w] \
+                .contiguous().view(n, t, c, scale * lr_h, scale * lr_w)
+            return
         if deg == 'BI':
             self.gt_data = data['gt'].to(self.device)
             self.lr_data = data['lr'].to(self.device)
@@ -112,10 +126,17 @@ class BaseModel:
             .contiguous().view(n, t, c, scale * lr_h, scale * lr_w)
 
     def prepare_inference_data(self, data):
-        """base_model.py:87-122: thwc -> tchw; BD without 'lr': blur+decimate with reflect pad."""
+        """base_model.py:87-122: thwc -> tchw; BD without 'lr': blur+decimate with reflect pad; BI without 'lr': the
+        integer bicubic degradation of the uint8 GT (mirrored borders), one launch."""
         deg = self.opt['dataset']['degradation']['type']
-        if deg == 'BI' or 'lr' in data:
+        if 'lr' in data:
             lr = data['lr']
+        elif deg == 'BI':
+            gt = data['gt']
+            if gt.dtype != torch.uint8:
+                raise ValueError(f'BI without "lr": the GT frames must be uint8 thwc, got {gt.dtype}')
+            self.lr_data = ops.downsample_bi(gt.to(self.device).contiguous(), self.opt['scale'], pad=True)
+            return
         else:
             scale = self.opt['scale']
             sigma = self.opt['dataset']['degradation'].get('sigma', 1.5)

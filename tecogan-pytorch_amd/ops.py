@@ -1182,6 +1182,40 @@ def downsample_bd(x, kernel2d, scale, pad):
     return y
 
 
+BI_TILE = (8, 32)        # LR pixels one workgroup of tg_downsample_bi_* makes (TG_BI_TILE_H, TG_BI_TILE_W)
+BI_BORDER_LR = 2         # pad=False: LR pixels cut from every side (= 2 * scale GT pixels of border)
+
+
+def downsample_bi(x, scale, pad=True, out='f32'):
+    """The BI degradation (generate_lr_bi.m: modcrop + imresize(1 / scale, 'bicubic') + 8-bit write) in exact integers,
+    one launch (tg_downsample_bi_*).  x: uint8 (n,H,W,3) frames, or fp32 (n,3,H,W) in [0,1]
+    whose values are first taken to their bytes (exact for the k / 255 every loader delivers).  scale 2 or 4.
+    pad=True: LR (H // scale, W // scale), mirrored borders; pad=False: x carries 2 * scale pixels of border per side,
+    LR is 4 smaller per axis.  out: 'f32' -> (n,3,h,w) fp32 = byte / 255, 'u8' -> (n,h,w,3) uint8, 'both' -> (f32, u8)."""
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise L.TecoganHipError('downsample_bi: expected a CUDA/HIP tensor (no CPU path exists)')
+    if out not in ('f32', 'u8', 'both'):
+        raise L.TecoganHipError(f"downsample_bi: out is 'f32', 'u8' or 'both', got {out!r}")
+    if x.dtype == torch.uint8 and x.dim() == 4 and x.shape[3] == 3:
+        _chk_u8(x, 'x')
+        n, h, w, _ = x.shape
+        fn, name = L.lib().tg_downsample_bi_u8, 'tg_downsample_bi_u8'
+    elif x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3:
+        _chk(x, 'x')
+        n, _, h, w = x.shape
+        fn, name = L.lib().tg_downsample_bi_f32, 'tg_downsample_bi_f32'
+    else:
+        raise L.TecoganHipError(f'downsample_bi: expected uint8 (n,H,W,3) or fp32 (n,3,H,W), got {x.dtype} '
+                                f'{tuple(x.shape)}')
+    scale = int(scale)
+    cut = 0 if pad else 2 * BI_BORDER_LR
+    oh, ow = max(h // max(scale, 1) - cut, 0), max(w // max(scale, 1) - cut, 0)    # the library refuses what is empty
+    y32 = torch.empty(n, 3, oh, ow, dtype=torch.float32, device=x.device) if out != 'u8' else None
+    y8 = torch.empty(n, oh, ow, 3, dtype=torch.uint8, device=x.device) if out != 'f32' else None
+    L.check(fn(x.data_ptr(), _ptr(y8), _ptr(y32), n, h, w, scale, 1 if pad else 0, _stream()), name)
+    return y32 if out == 'f32' else (y8 if out == 'u8' else (y32, y8))
+
+
 # ---- SyncBatchNorm (+LeakyReLU): statistics exchanged over ranks between the halves ----
 def sync_bn_lrelu_train_fwd(x, gamma, beta, running_mean, running_var, momentum=0.1, eps=1e-5,
                             slope=0.2):

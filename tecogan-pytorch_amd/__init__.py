@@ -9,5 +9,5 @@ __version__ = '0.1.0'
 
 # (Rounds 1-2 set DEBUG_HIP_DYNAMIC_QUEUES=1 here.  The problem it papered over was a side stream
 # re-created on every clip; since round 3 there is ONE long-lived side stream per device
-# (models/networks/tecogan_nets.py side_stream) and importing this package
+# (models/networks/frnet_infer.py side_stream) and importing this package
 # no longer touches the environment.)

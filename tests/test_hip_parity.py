@@ -1078,6 +1078,29 @@ def test_pipelined_clip_inference_is_deterministic_and_matches_single_stream():
     assert np.array_equal(one.cpu().numpy(), first)
 
 
+def test_pipelined_clip_reusing_both_flow_slots_matches_every_other_path(monkeypatch):
+    """With the default batch size no short clip writes a flow slot a second time while the other stream is live.
+    TG_FNET_BATCH=2 cuts 9 frames into 3, 2, 2, 2: slots 0 and 1 are both written twice.  (That the wait for the batch
+    two back is enqueued is asserted by tests/test_infer_schedule_cpu.py; a race at this size would rarely show here.)
+    The pipelined clip is bit-identical run after run, to the same launches on ONE stream (no concurrency)
+    and to infer_stream fed frame by frame (the same enqueue_batch on ring slots); against the frame-by-frame path the
+    neighbouring tests' bound holds (summation order of the batched FNet layers)."""
+    monkeypatch.setenv('TG_FNET_BATCH', '2')
+    from tecogan_pytorch_amd.models.networks import frnet_infer
+    assert frnet_infer.clip_batches(9, *frnet_infer.stream_batch_sizes()) == [(0, 3), (3, 2), (5, 2), (7, 2)]
+    net, _ = make_net('BD', 4)
+    clip = smooth_clip(9, 3, 24, 40, seed=31)
+    first = net.infer_sequence(clip, 'cuda', pipeline=True)
+    for _ in range(2):
+        assert np.array_equal(net.infer_sequence(clip, 'cuda', pipeline=True), first)
+    assert np.array_equal(net.infer_sequence(clip, 'cuda', pipeline='one_stream'), first)
+    streamed = np.concatenate([chunk.copy() for chunk in net.infer_stream((f for f in clip), 'cuda')], 0)
+    assert np.array_equal(streamed, first)
+    d = np.abs(net.infer_sequence(clip, 'cuda', pipeline=False).astype(np.int16) - first.astype(np.int16))
+    print('pipeline=True (TG_FNET_BATCH=2) against pipeline=False: max %d, differing %.3g' % (d.max(), (d > 0).mean()))
+    assert d.max() <= 1 and (d > 0).mean() <= 2e-3, (d.max(), (d > 0).mean())
+
+
 # --------------------------------------------------- BASELINE full-size checks
 def test_fullsize_A_digest_vs_reference(golden):
     """config 1/2 shape: 4xBD, LR 1x3x134x320, seeded uniform inputs."""

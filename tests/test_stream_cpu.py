@@ -13,7 +13,8 @@ from tecogan_pytorch_amd.models.base_model import BaseModel, front_pad_stream
 
 
 def partition_of_infer_sequence(tot_frm, fnet_batch, k=1):
-    """Restatement of _infer_sequence's batch list (the lines that build `batches`), which is told the length."""
+    """Independent restatement of the batch list _infer_sequence built by hand before clip_batches(t,
+    *stream_batch_sizes(fb, k)) took its place: it is told the length and clamps to it."""
     nb_ = max(1, min(max(1, fnet_batch // k), tot_frm))
     nb0 = max(1, min(nb_, max(1, N.FNET_FIRST_PASS_FRAMES // k)))
     batches, i0 = [], 0
@@ -51,6 +52,13 @@ def test_partition_equals_infer_sequence_without_knowing_the_length(fnet_batch):
             cuts.append(frames[pos:pos + m])
             pos += m
         assert streamed_partition(cuts, fnet_batch) == partition_of_infer_sequence(t, fnet_batch)
+
+
+@pytest.mark.parametrize('k', [1, 2, 4, 8])
+def test_clip_batches_equal_the_restatement_for_lockstep_clips(k):
+    for fnet_batch in (1, 2, 3, 4, 5, 8, 12, 16, 32):
+        for t in range(1, 101):
+            assert N.clip_batches(t, *N.stream_batch_sizes(fnet_batch, k)) == partition_of_infer_sequence(t, fnet_batch, k)
 
 
 def test_batch_sizes_follow_the_environment(monkeypatch):

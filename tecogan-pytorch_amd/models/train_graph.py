@@ -67,7 +67,9 @@ class Tape:
             self.grads[k] = g
             self.keep.append(t)
         else:
-            ops.axpy_(cur, g, 1.0)
+            if not cur.is_contiguous():      # (a caller's strided first contribution: axpy_ walks flat memory)
+                cur = self.grads[k] = cur.contiguous()
+            ops.axpy_(cur, g if g.is_contiguous() else g.contiguous(), 1.0)
 
     def grad(self, t):
         return self.grads.get(id(t))

@@ -62,12 +62,12 @@ class BaseModel:
         the flat gradient buckets' sizes, the gradient transport."""
         import os
         from .. import _lib as L
-        from . import train_graph as TG
+        from .train_chain import _ChainState
         crop = int(self.opt.get('dataset', {}).get('train', {}).get('crop_size', 0) or 0)
         lr = crop // max(1, self.scale)
         chain = -1
         if self.device.type == 'cuda' and lr > 0:
-            chain = 0 if TG._ChainState.disabled else int(TG._ChainState.parts(2, lr, lr))
+            chain = 0 if _ChainState.disabled else int(_ChainState.parts(2, lr, lr))
         flat = [int(o.flat_grad.numel()) if getattr(o, 'flat_grad', None) is not None else -1
                 for o in (getattr(self, 'optim_G', None), getattr(self, 'optim_D', None)) if o is not None]
         return [int(L.lib().tg_version()), chain, int(bool(getattr(self, 'pair_pass', False))),

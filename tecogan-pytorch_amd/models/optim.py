@@ -36,7 +36,7 @@ class Adam:
         dev = self.params[0].device
         # one more aligned block behind the last tensor: its first float is the FAULT SLOT of the chained
         # launches' fail-safe -- it travels with the gradient all-reduce, and a non-zero value turns this
-        # network's step into a no-op on every rank (models/train_graph.py: stamp_fault)
+        # network's step into a no-op on every rank (models/train_chain.py: stamp_fault)
         self._ntot = tot
         self.flat_param = torch.zeros(tot + self.ALIGN, dtype=torch.float32, device=dev)
         self.flat_grad = torch.zeros(tot + self.ALIGN, dtype=torch.float32, device=dev)
@@ -74,7 +74,7 @@ class Adam:
                 p.grad.zero_()              # memset
 
     def undo_step_count(self):
-        """A step whose update the device-side guard DROPPED (chained-launch fault, models/train_graph.py) must not
+        """A step whose update the device-side guard DROPPED (chained-launch fault, models/train_chain.py) must not
         advance the bias-correction exponent: the caller takes the count back once it learns of the drop."""
         if self.steps > 0:
             self.steps -= 1

@@ -16,6 +16,9 @@ import os
 import torch
 
 from .. import ops
+# (the fail-safe of the chained launches lives in train_chain; its names stay reachable here)
+from .train_chain import (_ChainState, _distributed_world, chain_check, chain_epoch,  # noqa: F401
+                          guard_available, stamp_fault)
 
 NONE, RELU, LRELU, TANH24 = ops.ACT_NONE, ops.ACT_RELU, ops.ACT_LRELU02, ops.ACT_TANH24
 
@@ -92,75 +95,94 @@ class Tape:
     # are collected during the reverse sweep and reduced by ONE wgrad launch per layer
     # over the concatenated batch: 19x fewer launches / split-K reductions, and enough
     # pixel tiles per launch to fill the GPU.
-    def defer_wgrad(self, key, p, q, target, cb_off=0, post=None, phased=None, convt=False, bias=None):
-        """bias: the layer's bias-gradient buffer -- db = sum of p = dZ comes out of the same launch
-        (instead of defer_bias: a second pass over every dZ)."""
-        ent = self.deferred.setdefault(key, {'p': [], 'q': [], 'target': target, 'cb_off': cb_off,
-                                             'post': post, 'phased': phased, 'convt': convt, 'bias': bias})
-        ent['p'].append(p)
-        ent['q'].append(q)
+    # One queue entry per key: (flush function of its kind, what the key's first deferral fixed, a list, b list); each
+    # kind's function below names what its fields mean.  Weight gradients are flushed in order of first deferral.
+    def _defer(self, queue, key, flush, fixed, a, b=None):
+        ent = queue.get(key)
+        if ent is None:
+            ent = queue[key] = (flush, fixed, [], [])
+        ent[2].append(a)
+        ent[3].append(b)
+
+    def defer_wgrad(self, key, dz, x, gw, cb_off=0, bias=None):
+        """dW[:, cb_off:cb_off + channels of x] += dZ (*) x.  bias: the layer's bias-gradient buffer -- db = sum of dZ
+        comes out of the same launch (instead of defer_bias: a second pass over every dZ)."""
+        self._defer(self.deferred, key, _flush_plain, (gw, cb_off, bias), dz, x)
+
+    def defer_wgrad_embedded(self, key, p, q, scatter, phased=None):
+        """The (p channels, q channels, 3, 3) gradient of a space-to-depth embedding, made in a temporary that `scatter`
+        adds into the layer's own gradient.  phased: (channels per phase, tap rows, tap columns) of the masked kernel."""
+        self._defer(self.deferred, key, _flush_embedded, (scatter, phased), p, q)
+
+    def defer_wgrad_convt(self, key, x, dz, gw, gb):
+        """dW and db of a transposed conv straight from its input and dZ (at twice the resolution)."""
+        self._defer(self.deferred, key, _flush_convt, (gw, gb), x, dz)
 
     def defer_bias(self, buf, dz):
-        self.deferred_bias.setdefault(id(buf), (buf, []))[1].append(dz)
+        self._defer(self.deferred_bias, id(buf), _flush_bias, (buf,), dz)
 
     def defer_body(self, key, layers, acts, dz):
-        ent = self.deferred_body.setdefault(key, {'layers': layers, 'acts': [], 'dz': []})
-        ent['acts'].append(acts)
-        ent['dz'].append(dz)
+        self._defer(self.deferred_body, key, _flush_body, (layers,), dz, acts)
 
     def flush_deferred(self):
-        def same(ts):
-            return all(t.shape == ts[0].shape and t.is_contiguous() for t in ts)
-        for ent in self.deferred.values():
-            multi = len(ent['p']) > 1 and same(ent['p']) and same(ent['q'])
-            if ent.get('convt'):       # (x, dZ at twice the resolution) pairs of a transposed conv
-                # (`post` carries the layer's bias-gradient buffer: the same launch sums dZ)
-                if same(ent['p']) and same(ent['q']):
-                    ops.wgrad3x3_convt_multi(ent['p'], ent['q'], ent['target'], accumulate=True, bias_grad=ent['post'])
-                else:
-                    for x_, d_ in zip(ent['p'], ent['q']):
-                        ops.wgrad3x3_convt_multi([x_.contiguous()], [d_.contiguous()], ent['target'], accumulate=True,
-                                                 bias_grad=ent['post'])
-            elif ent['post'] is None:
-                if multi:      # one launch over the per-frame tensors where they lie
-                    ops.wgrad3x3_multi(ent['p'], ent['q'], ent['target'], cb_off=ent['cb_off'],
-                                       accumulate=True, bias_grad=ent.get('bias'))
-                else:
-                    P = ent['p'][0] if len(ent['p']) == 1 else torch.cat(ent['p'], 0)
-                    Q = ent['q'][0] if len(ent['q']) == 1 else torch.cat(ent['q'], 0)
-                    ops.wgrad3x3(P, Q, ent['target'], cb_off=ent['cb_off'], accumulate=True, bias_grad=ent.get('bias'))
-            else:
-                p0, q0 = ent['p'][0], ent['q'][0]
-                # accumulate=False below: every tap the post hook reads is overwritten
-                ge = torch.empty(p0.shape[1], q0.shape[1], 3, 3, dtype=torch.float32, device=p0.device)
-                phased = ent.get('phased')
-                if phased is not None and (phased[0] % 64 != 0 or not (same(ent['p']) and same(ent['q']))):
-                    phased = None                 # the kernel dispatches on 64-channel blocks
-                if phased is not None:            # skips the taps a sub-pixel phase does not own
-                    ops.wgrad3x3_multi(ent['p'], ent['q'], ge, accumulate=False, phased=phased)
-                elif multi:
-                    ops.wgrad3x3_multi(ent['p'], ent['q'], ge, accumulate=False)
-                else:
-                    P = p0 if len(ent['p']) == 1 else torch.cat(ent['p'], 0)
-                    Q = q0 if len(ent['q']) == 1 else torch.cat(ent['q'], 0)
-                    ops.wgrad3x3(P, Q, ge, accumulate=False)
-                ent['post'](ge)
-        for ent in self.deferred_body.values():
-            # the 2*nb residual-block convs of every swept frame: ONE weight-gradient launch (+ one
-            # reduce) and one bias-gradient launch instead of 2*nb of each per flush
-            layers = ent['layers']
-            if not layers[1].weight.requires_grad:
-                continue
-            ops.wgrad3x3_body(ent['dz'], ent['acts'], [_grad_buf(m.weight) for m in layers[1:]],
-                              dbs=[_grad_buf(m.bias) for m in layers[1:]])
-        self.deferred_body = {}
-        for buf, dzs in self.deferred_bias.values():
-            if len(dzs) > 1 and same(dzs):
-                ops.bias_grad_multi(dzs, buf, accumulate=True)
-            else:
-                D = dzs[0] if len(dzs) == 1 else torch.cat(dzs, 0)
-                ops.bias_grad(D, buf, accumulate=True)
-        self.deferred, self.deferred_bias = {}, {}
+        for queue in (self.deferred, self.deferred_body, self.deferred_bias):
+            for flush, fixed, a, b in queue.values():
+                flush(a, b, *fixed)
+            queue.clear()
+
+
+def _uniform(*lists):
+    """Every list's tensors share one shape and are contiguous: a multi-segment kernel reads them where they lie."""
+    return all(t.shape == ts[0].shape and t.is_contiguous() for ts in lists for t in ts)
+
+
+def _joined(ts):
+    return ts[0] if len(ts) == 1 else torch.cat(ts, 0)
+
+
+def _wgrad(ps, qs, grad, phased=None, **kw):
+    """One weight-gradient launch over the pairs: the per-frame tensors where they lie, else their concatenation."""
+    uniform = _uniform(ps, qs)
+    if phased is not None and phased[0] % 64 == 0 and uniform:     # (the kernel dispatches on 64-channel blocks)
+        ops.wgrad3x3_multi(ps, qs, grad, phased=phased, **kw)      # skips the taps a sub-pixel phase does not own
+    elif len(ps) > 1 and uniform:
+        ops.wgrad3x3_multi(ps, qs, grad, **kw)
+    else:
+        ops.wgrad3x3(_joined(ps), _joined(qs), grad, **kw)
+
+
+def _flush_plain(dzs, xs, gw, cb_off, bias):
+    _wgrad(dzs, xs, gw, cb_off=cb_off, accumulate=True, bias_grad=bias)
+
+
+def _flush_embedded(ps, qs, scatter, phased):
+    # accumulate=False: every tap the scatter hook reads is overwritten
+    ge = torch.empty(ps[0].shape[1], qs[0].shape[1], 3, 3, dtype=torch.float32, device=ps[0].device)
+    _wgrad(ps, qs, ge, phased=phased, accumulate=False)
+    scatter(ge)
+
+
+def _flush_convt(xs, dzs, gw, gb):
+    if _uniform(xs, dzs):
+        ops.wgrad3x3_convt_multi(xs, dzs, gw, accumulate=True, bias_grad=gb)
+    else:
+        for x, dz in zip(xs, dzs):
+            ops.wgrad3x3_convt_multi([x.contiguous()], [dz.contiguous()], gw, accumulate=True, bias_grad=gb)
+
+
+def _flush_body(dz_blocks, act_blocks, layers):
+    """The 2*nb residual-block convs of every swept frame of a chained body: ONE weight-gradient launch (+ one reduce)
+    and one bias-gradient launch instead of 2*nb of each per flush."""
+    if layers[1].weight.requires_grad:
+        ops.wgrad3x3_body(dz_blocks, act_blocks, [_grad_buf(m.weight) for m in layers[1:]],
+                          dbs=[_grad_buf(m.bias) for m in layers[1:]])
+
+
+def _flush_bias(dzs, _, buf):
+    if len(dzs) > 1 and _uniform(dzs):
+        ops.bias_grad_multi(dzs, buf, accumulate=True)
+    else:
+        ops.bias_grad(_joined(dzs), buf, accumulate=True)
 
 
 def _grad_buf(p):
@@ -297,189 +319,10 @@ def resblock(tape, conv1, conv2, x):
 # SRNet's conv_in + residual blocks of one unrolled frame as ONE chained launch
 # (tg_srnet_body_fwd / _bwd, csrc/tg_conv3x3_chain.hip), forward and reverse sweep.
 # ---------------------------------------------------------------------------
-class _ChainState:
-    """Process-wide state of the chained launches: flag buffers per shape, the epoch counter, the
-    pinned-host fault counter (the kernel adds to it with system scope when a workgroup gives up
-    waiting for a neighbour) and the permanent fallback switch."""
-    disabled = False
-    poll_limit = 1 << 21
-    epoch = 0
-    flags = {}
-    err = None
-    supported = {}
-    dirty = False           # chained launches were enqueued since the last SYNCHRONOUS look at the counter
-    reported_epoch = 0      # launches up to this epoch are covered by a fault that has already been raised
-    # Recovery from a transient fault (round 6, as in the frame plan: tg_frnet_plan_set_chain_rearm): after `rearm_wait`
-    # clean ITERATIONS on the per-layer path (counted by chain_check, which every rank calls once per iteration, and a
-    # fault reaches every rank through the all-reduced slot: the count is rank-symmetric) the chained body launches are
-    # tried again; a fault of the re-armed launches doubles the wait.  rearm_first = 0: off for good (rounds 3-5).
-    rearm_first = 64
-    rearm_wait = 0
-    clean_iters = 0
-    rearms = 0
-
-    @classmethod
-    def note_fault(cls):
-        cls.disabled = True
-        cls.clean_iters = 0
-        cls.rearm_wait = min(2 * cls.rearm_wait, 1 << 20) if cls.rearm_wait else cls.rearm_first
-
-    @classmethod
-    def note_clean_iteration(cls):
-        if cls.disabled and cls.rearm_first > 0 and cls.rearm_wait > 0:
-            cls.clean_iters += 1
-            if cls.clean_iters >= cls.rearm_wait:
-                cls.disabled = False
-                cls.clean_iters = 0
-                cls.rearms += 1
-
-    @classmethod
-    def buffers(cls, nlayer, n, h, w, device):
-        from .. import _lib as L
-        # one flag buffer per (shape, device, stream): two chained launches of one shape in flight at once
-        # (a second model, a side stream, another device) must not overwrite each other's epochs
-        key = (n, h, w, str(device), ops._stream())
-        fl = cls.flags.get(key)
-        need = L.lib().tg_conv3x3_chain_flag_ints(24, n, h, w)
-        if fl is None or fl.numel() < need:
-            fl = cls.flags[key] = torch.zeros(need, dtype=torch.int32, device=device)
-        if cls.err is None:
-            cls.err = torch.zeros(16, dtype=torch.int32).pin_memory()
-        cls.epoch = cls.epoch + 1 if cls.epoch < 0x7fffffff else 1
-        cls.dirty = True
-        return fl, cls.err, cls.epoch
-
-    @classmethod
-    def parts(cls, n, h, w):
-        """workgroups per tile the launcher uses for this shape (0: not supported): 4 needs the
-        16 x 16 x 4 weight layout (ops.pack_conv3x3_m16), 1 / 2 the 64-channel-block layout."""
-        key = (n, h, w, torch.cuda.current_device() if torch.cuda.is_available() else -1)
-        r = cls.supported.get(key)
-        if r is None:
-            from .. import _lib as L
-            r = cls.supported[key] = int(L.lib().tg_conv3x3_chain_supported(n, h, w, 64))
-        return r
-
-    MAX_LAYERS = 24      # RC_MAXL of tg_conv3x3_chain.hip: tg_srnet_body_fwd / _bwd walk 1 + 2 nb (+ 1) layers
-
-    @classmethod
-    def usable(cls, n, nf, cin0, h, w, nb):
-        """nb: residual blocks of the body (a free yml parameter in the reference, tecogan_nets.py:108-116):
-        beyond 11 the body does not fit one chained launch and runs one launch per layer."""
-        if cls.disabled or nf > 64 or cin0 > 64 or nb < 1 or 2 * nb + 2 > cls.MAX_LAYERS:
-            return False
-        return cls.parts(n, h, w) > 0
-
-
-def _distributed_world():
-    try:
-        import torch.distributed as dist
-        return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-    except ImportError:
-        return 1
-
-
-def guard_available(optim):
-    """The device-side guard of the chained launches' fail-safe exists for this optimiser: its flat gradient buffer
-    (with the fault slot behind the last tensor) is still what the parameters' .grad views point into."""
-    return optim is not None and getattr(optim, 'fault_slot', None) is not None and optim._is_flat()
-
-
-def stamp_fault(optim):
-    """Before a network's gradient exchange / optimiser step: add 1 to the FAULT SLOT of its flat gradient
-    buffer if a chained launch of this process has recorded a fault (a one-thread kernel reads the pinned
-    counter).  The slot is all-reduced with the gradients and guards the Adam step on the device
-    (tg_adam_step_guarded): gradients built on stale tiles are then applied on NO rank.
-
-    An optimiser WITHOUT that slot (`Adam(flatten=False)`, views replaced by `net.to()` / `p.grad = None`) has no
-    asynchronous guard: the step then falls back to the synchronous protocol ONCE -- wait for the device, look at the
-    counter (on every rank: one max-all-reduce of the flag), raise BEFORE the update is applied -- and every later
-    step runs one launch per layer, so the check is never needed again."""
-    err = _ChainState.err
-    if err is None or optim is None:
-        return
-    if guard_available(optim):
-        ops.fault_to_slot(err, optim.fault_slot)
-        return
-    # An optimiser that HAD its flat buffer at construction (every rank compared that: BaseModel.agreement_vector) and
-    # lost it on this rank only -- `p.grad = None`, a `net.to()` -- would enter the synchronous protocol below, whose
-    # max-all-reduce the other ranks never join: a hang.  A loud rank-local error instead (the peers then fail in RCCL's
-    # own time-out rather than waiting for ever; ADVICE r5).
-    if getattr(optim, 'fault_slot', None) is not None and _distributed_world() > 1:
-        from .. import _lib as L_
-        raise L_.TecoganHipError(
-            'an optimiser of a data-parallel run lost its flat gradient buffer on this rank (the .grad views were '
-            'replaced): the device-side fault guard and the one-collective gradient exchange are rank-symmetric by '
-            'construction -- rebuild the optimiser on every rank (Adam(..., flatten=True)) instead')
-    if not _ChainState.dirty:
-        return
-    if torch.cuda.is_available():
-        torch.cuda.synchronize()
-    _ChainState.dirty = False
-    _ChainState.disabled = True          # (for good: without the device-side guard every chained step would need this sync)
-    _ChainState.rearm_wait = 0
-    local = int(err[0]) != 0
-    anywhere = local
-    try:
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            from ..utils import dist_utils
-            anywhere = dist_utils.max_over_ranks(1.0 if local else 0.0, device=optim.params[0].device) != 0.0
-    except ImportError:
-        pass
-    if anywhere:
-        chain_check(0.0 if local else 1.0, counter=True)
-
-
-def chain_check(slot_value=0.0, counter=True, epoch=None):
-    """Raises if a chained launch recorded a fault: on any rank in the iteration whose scalars are being looked at
-    (`slot_value`: the fault slot of the generator's gradient buffer after its all-reduce, read with that iteration's
-    scalars), or -- `counter`, for callers that have just synchronised the device -- on this rank since the last check
-    (pinned counter).  The training step resolves its scalars asynchronously (base_model: a later iteration may
-    already be in flight and adding to the counter), so it passes counter=False and relies on the slot, which is
-    exact per iteration; the counter is cleared only after a device synchronisation.  The iteration's generator
-    update was dropped on every rank by the device-side guard; every later step runs one launch per layer.
-
-    `epoch`: the chained-launch epoch at which the iteration was stamped.  An iteration that was already in flight
-    when an earlier one raised carries the same fault in its slot (the pinned counter is cleared only by the raise):
-    it is reported ONCE -- the call then returns True (update dropped, nothing raised).  Returns False when the
-    iteration is clean."""
-    err = _ChainState.err
-    local = counter and err is not None and int(err[0]) != 0
-    if not (local or slot_value != 0.0):
-        if not counter:                  # (the per-iteration call of the training step)
-            _ChainState.note_clean_iteration()
-        return False
-    if not local and epoch is not None and epoch <= _ChainState.reported_epoch:
-        return True
-    from .. import _lib as L
-    if torch.cuda.is_available():
-        torch.cuda.synchronize()            # nothing in flight may add to the counter after it is cleared
-    lost = int(err[0]) if err is not None else 0
-    if err is not None:
-        err.zero_()
-    _ChainState.note_fault()
-    _ChainState.dirty = False
-    _ChainState.reported_epoch = _ChainState.epoch     # everything enqueued so far has completed (synchronised above)
-    raise L.TecoganHipError(
-        'chained SRNet launch (training): %s timed out waiting for a neighbour tile; the results of this '
-        'step are INVALID and its optimiser step was DROPPED on every rank (weights and Adam moments '
-        'untouched).  Later steps run one launch per layer%s.'
-        % (f'{lost} workgroup(s) of this rank' if lost else 'workgroups of another rank',
-           f'; the chained launches are tried again after {_ChainState.rearm_wait} clean iterations'
-           if _ChainState.rearm_first > 0 else ''))
-
-
-def chain_epoch():
-    """The epoch of the last chained launch enqueued by this process (see chain_check)."""
-    return _ChainState.epoch
-
-
 def srnet_body(tape, srnet, lr, tran):
     """conv_in + nb residual blocks (tecogan_nets.py:108-116, :141-143) of one frame: one launch
     forward, one launch for the whole reverse sweep of these 1 + 2*nb layers; the (dZ, X) pairs of
     the weight gradients are deferred exactly as the per-layer nodes defer them."""
-    import ctypes
     from .. import _lib as L
     conv_in = srnet.conv_in['0']
     blocks = [(rb.conv['0'], rb.conv['2']) for rb in srnet.resblocks]
@@ -602,18 +445,12 @@ def _embed_index(kind, a, b, device):
         table = _KT if kind == 'convt' else _K4
         k = len(table)
         src = torch.arange(a * b * k * k, dtype=torch.int64).view(a, b, k, k)
-        if kind == 'convt':          # (ci, co, 3, 3) -> (ci, 4co, 3, 3)
-            emb = torch.full((a, 4 * b, 3, 3), a * b * k * k, dtype=torch.int64)
-            for ky, (py, ty) in table.items():
-                for kx, (px, tx) in table.items():
-                    ph = py * 2 + px
-                    emb[:, ph * b:(ph + 1) * b, ty, tx] = src[:, :, ky, kx]
-        else:                        # (co, ci, 4, 4) -> (co, 4ci, 3, 3)
-            emb = torch.full((a, 4 * b, 3, 3), a * b * k * k, dtype=torch.int64)
-            for ky, (py, ty) in table.items():
-                for kx, (px, tx) in table.items():
-                    ph = py * 2 + px
-                    emb[:, ph * b:(ph + 1) * b, ty, tx] = src[:, :, ky, kx]
+        # convt: (ci, co, 3, 3) -> (ci, 4co, 3, 3); conv4: (co, ci, 4, 4) -> (co, 4ci, 3, 3)
+        emb = torch.full((a, 4 * b, 3, 3), a * b * k * k, dtype=torch.int64)
+        for ky, (py, ty) in table.items():
+            for kx, (px, tx) in table.items():
+                ph = py * 2 + px
+                emb[:, ph * b:(ph + 1) * b, ty, tx] = src[:, :, ky, kx]
         fwd = emb.reshape(-1)
         inv = torch.empty(a * b * k * k, dtype=torch.int64)
         valid = fwd < a * b * k * k
@@ -667,15 +504,15 @@ def convt3x3s2(tape, layer, x, act=RELU):
         if w.requires_grad:
             if direct:
                 # dW straight from dZ (tg_wgrad3x3_convt_multi): no s2d copy, no embedded gradient to gather back
-                tape.defer_wgrad(('ctw', id(layer)), x, dz, _grad_buf(w), convt=True, post=_grad_buf(b))
+                tape.defer_wgrad_convt(('ctw', id(layer)), x, dz, _grad_buf(w), _grad_buf(b))
             else:
                 if s is None:
                     s = ops.space_to_depth(dz, 2)
 
-                def post(ge):                                      # G[ci][(ph,co)][ty][tx]
+                def scatter(ge):                                   # G[ci][(ph,co)][ty][tx]
                     _, inv = _embed_index('convt', ci, co, ge.device)
                     ops.index_gather(ge, inv, out=_grad_buf(w), accumulate=True)
-                tape.defer_wgrad(('ct', id(layer)), x, s, None, 0, post, phased=(co, ops.TAPS_1, ops.TAPS_01))
+                tape.defer_wgrad_embedded(('ct', id(layer)), x, s, scatter, phased=(co, ops.TAPS_1, ops.TAPS_01))
                 tape.defer_bias(_grad_buf(b), dz)
     tape.record(bwd)
     return y
@@ -732,11 +569,11 @@ def conv4x4s2(tape, holder, x, need_dx=True):
         if g is None:
             return
         if w.requires_grad:
-            def post(ge):
+            def scatter(ge):
                 _, inv = _embed_index('conv4', co, ci, ge.device)
                 ops.index_gather(ge, inv, out=_grad_buf(w), accumulate=True)
             s = s_held[0] if s_held[0] is not None else ops.space_to_depth(x, 2)
-            tape.defer_wgrad(('c4', id(holder)), g, s, None, 0, post, phased=(ci, ops.TAPS_12, ops.TAPS_01))
+            tape.defer_wgrad_embedded(('c4', id(holder)), g, s, scatter, phased=(ci, ops.TAPS_12, ops.TAPS_01))
         if need_dx:
             a = tape.act_outputs.get(id(x))
             fuse = a is not None and tape.grad(x) is None
@@ -854,11 +691,6 @@ def space_to_depth(tape, x, scale):
     return y
 
 
-def _distributed():
-    import torch.distributed as dist
-    return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-
-
 def bn_lrelu(tape, bn, x, need_dx=True, sync=None, groups=1):
     """BatchNorm2d (train mode) + LeakyReLU(0.2); bn holds weight/bias/running stats.
     Under torch.distributed (or sync=True) the statistics are global (SyncBatchNorm).
@@ -866,63 +698,37 @@ def bn_lrelu(tape, bn, x, need_dx=True, sync=None, groups=1):
     batch statistics per group, the running statistics updated group after group -- exactly what the
     reference's separate passes do -- and, data parallel, ONE collective per layer for all groups."""
     if sync is None:
-        sync = _distributed()
+        sync = _distributed_world() > 1
     n = x.shape[0]
-    if groups > 1:
-        assert n % groups == 0
-        per = n // groups
-        if sync:
-            y, stats = ops.sync_bn_lrelu_train_fwd_groups(x, groups, bn.weight, bn.bias, bn.running_mean,
-                                                          bn.running_var)
-        else:
-            y, stats = torch.empty_like(x), []
-            for g in range(groups):
-                _, mean, invstd = ops.bn_lrelu_train_fwd(x[g * per:(g + 1) * per], bn.weight, bn.bias,
-                                                         bn.running_mean, bn.running_var,
-                                                         out=y[g * per:(g + 1) * per])
-                stats.append((mean, invstd, None))
-        for _ in range(groups):
-            bn.count_pass() if hasattr(bn, 'count_pass') else bn.num_batches_tracked.add_(1)
-        if tape is not None:
-            def bwd_groups():
-                g_ = tape.pop_grad(y)
-                if g_ is None:
-                    return
-                train = bn.weight.requires_grad
-                gw = _grad_buf(bn.weight) if train else None
-                gb = _grad_buf(bn.bias) if train else None
-                if sync:
-                    dx = ops.sync_bn_lrelu_train_bwd_groups(x, y, g_, groups, bn.weight, stats, gw, gb, need_dx)
-                else:
-                    dx = torch.empty_like(x) if need_dx else None
-                    for g in range(groups):
-                        sl = slice(g * per, (g + 1) * per)
-                        ops.bn_lrelu_train_bwd(x[sl], y[sl], g_[sl], bn.weight, stats[g][0], stats[g][1], gw, gb,
-                                               need_dx, dx_out=dx[sl] if need_dx else None)
-                if need_dx:
-                    tape.add_grad(x, dx)
-            tape.record(bwd_groups)
-        return y
+    assert n % groups == 0
+    per = n // groups
     if sync:
-        y, mean, invstd, count = ops.sync_bn_lrelu_train_fwd(x, bn.weight, bn.bias, bn.running_mean,
-                                                             bn.running_var)
+        y, stats = ops.sync_bn_lrelu_train_fwd_groups(x, groups, bn.weight, bn.bias, bn.running_mean, bn.running_var)
     else:
-        y, mean, invstd = ops.bn_lrelu_train_fwd(x, bn.weight, bn.bias, bn.running_mean,
-                                                 bn.running_var)
-    bn.count_pass() if hasattr(bn, 'count_pass') else bn.num_batches_tracked.add_(1)
+        y, stats = torch.empty_like(x), []
+        for g in range(groups):
+            _, mean, invstd = ops.bn_lrelu_train_fwd(x[g * per:(g + 1) * per], bn.weight, bn.bias,
+                                                     bn.running_mean, bn.running_var,
+                                                     out=y[g * per:(g + 1) * per])
+            stats.append((mean, invstd, None))
+    for _ in range(groups):
+        bn.count_pass() if hasattr(bn, 'count_pass') else bn.num_batches_tracked.add_(1)
     if tape is not None:
         def bwd():
-            g = tape.pop_grad(y)
-            if g is None:
+            g_ = tape.pop_grad(y)
+            if g_ is None:
                 return
             train = bn.weight.requires_grad
             gw = _grad_buf(bn.weight) if train else None
             gb = _grad_buf(bn.bias) if train else None
             if sync:
-                dx = ops.sync_bn_lrelu_train_bwd(x, y, g, bn.weight, mean, invstd, count, gw, gb,
-                                                 need_dx)
+                dx = ops.sync_bn_lrelu_train_bwd_groups(x, y, g_, groups, bn.weight, stats, gw, gb, need_dx)
             else:
-                dx = ops.bn_lrelu_train_bwd(x, y, g, bn.weight, mean, invstd, gw, gb, need_dx)
+                dx = torch.empty_like(x) if need_dx else None
+                for g in range(groups):
+                    sl = slice(g * per, (g + 1) * per)
+                    ops.bn_lrelu_train_bwd(x[sl], y[sl], g_[sl], bn.weight, stats[g][0], stats[g][1], gw, gb,
+                                           need_dx, dx_out=dx[sl] if need_dx else None)
             if need_dx:
                 tape.add_grad(x, dx)
         tape.record(bwd)

@@ -5,6 +5,7 @@ from collections import OrderedDict
 import torch
 
 from .. import ops
+from . import train_chain
 from . import train_graph as TG
 from .base_model import BaseModel, front_pad_stream
 from .networks import define_generator
@@ -58,17 +59,17 @@ class VSRModel(BaseModel):
             tape.add_grad(lr_warp, self._crit(self.warp_crit, lr_warp, out['lr_curr'], warp_w,
                                               losses[1:2]))
         tape.backward()
-        TG.stamp_fault(self.optim_G)                 # a chained-launch fault (any rank) turns the step into a no-op
+        train_chain.stamp_fault(self.optim_G)                 # a chained-launch fault (any rank) turns the step into a no-op
         self.allreduce_grads(self.net_G, 'G')
         self.optim_G.step()
         if getattr(self.optim_G, 'fault_slot', None) is not None:
             losses[2:3].copy_(self.optim_G.fault_slot)
         has_warp = self.warp_crit is not None
-        ep, optim_G = TG.chain_epoch(), self.optim_G
+        ep, optim_G = train_chain.chain_epoch(), self.optim_G
 
         def build(vals):                             # runs when the log is looked at (base_model: asynchronous scalars)
             try:                                     # fail-safe of the chained launches: raises on EVERY rank, the update was dropped
-                dropped = TG.chain_check(vals[2], counter=False, epoch=ep)
+                dropped = train_chain.chain_check(vals[2], counter=False, epoch=ep)
             except Exception:
                 optim_G.undo_step_count()
                 raise

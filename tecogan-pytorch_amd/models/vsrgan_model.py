@@ -8,6 +8,7 @@ from collections import OrderedDict
 import torch
 
 from .. import ops
+from . import train_chain
 from . import train_graph as TG
 from .networks import define_discriminator
 from .networks.vgg_nets import VGGFeatureExtractor
@@ -150,7 +151,7 @@ class VSRGANModel(VSRModel):
             tape_D.backward()
             # D's gradient all-reduce runs on RCCL's stream while the D-independent generator
             # losses below are evaluated on the compute stream
-            TG.stamp_fault(self.optim_D)
+            train_chain.stamp_fault(self.optim_D)
             bucket_D = self.start_grad_exchange(self.net_D)
         tape_D.nodes, tape_D.grads = [], {}
 
@@ -206,12 +207,12 @@ class VSRGANModel(VSRModel):
         tape_G.add_grad(fake_pred_G, ops.bce_logits(fake_pred_G, 1.0, st_g, 1.0 / n_clip,
                                                     grad_scale=gan_w * gsc, lsgan=lsgan))
         tape_G.backward()
-        TG.stamp_fault(self.optim_G)                 # a chained-launch fault (any rank) turns the step into a no-op
+        train_chain.stamp_fault(self.optim_G)                 # a chained-launch fault (any rank) turns the step into a no-op
         self.allreduce_grads(self.net_G, 'G')
         self.optim_G.step()
         if getattr(self.optim_G, 'fault_slot', None) is not None:
             scal[14:15].copy_(self.optim_G.fault_slot)
-        ep, optim_G, optim_D = TG.chain_epoch(), self.optim_G, self.optim_D
+        ep, optim_G, optim_D = train_chain.chain_epoch(), self.optim_G, self.optim_D
 
         # === logging: ONE asynchronous read of all scalars (base_model: resolved when the log is looked at) ===
         cnt_upd, adaptive = self.cnt_upd_D, update_policy == 'adaptive'
@@ -225,7 +226,7 @@ class VSRGANModel(VSRModel):
                 if upd_D and sc_[15] != 0.0:
                     optim_D.undo_step_count()
             try:                                    # fail-safe of the chained launches: raises on EVERY rank, G's update was dropped
-                dropped = TG.chain_check(sc_[14], counter=False, epoch=ep)
+                dropped = train_chain.chain_check(sc_[14], counter=False, epoch=ep)
             except Exception:
                 took_back()
                 raise

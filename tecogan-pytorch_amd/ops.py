@@ -1217,67 +1217,15 @@ def downsample_bi(x, scale, pad=True, out='f32'):
 
 
 # ---- SyncBatchNorm (+LeakyReLU): statistics exchanged over ranks between the halves ----
-def sync_bn_lrelu_train_fwd(x, gamma, beta, running_mean, running_var, momentum=0.1, eps=1e-5,
-                            slope=0.2):
-    """Same contract as bn_lrelu_train_fwd with statistics over the GLOBAL batch: every rank
-    computes (mean, centred M2) of its slice, ONE all-gather of 2c floats per layer, merged
-    with Chan's formula in rank order (equal per-rank batch sizes, as DistributedSampler
-    guarantees) -- the formulation torch's SyncBatchNorm uses, with no E[x^2] - mean^2
-    cancellation.  With one rank the result is bit-identical to bn_lrelu_train_fwd."""
-    from .utils import dist_utils
-    _chk(x, 'x')
-    n, c, h, w = x.shape
-    lib = L.lib()
-    local = torch.empty(2 * c, dtype=torch.float32, device=x.device)
-    L.check(lib.tg_bn_local_stats(x.data_ptr(), local.data_ptr(), n, c, h * w, _stream()),
-            'tg_bn_local_stats')
-    gathered = dist_utils.all_gather_flat(local).contiguous()
-    world = gathered.shape[0]
-    count = float(n * h * w * world)
-    mean = torch.empty(c, dtype=torch.float32, device=x.device)
-    invstd = torch.empty(c, dtype=torch.float32, device=x.device)
-    L.check(lib.tg_bn_merge_stats(gathered.data_ptr(), world, float(n * h * w), float(eps),
-                                  float(momentum), mean.data_ptr(), invstd.data_ptr(),
-                                  _ptr(running_mean), _ptr(running_var), c, _stream()),
-            'tg_bn_merge_stats')
-    y = torch.empty_like(x)
-    L.check(lib.tg_bn_lrelu_apply(x.data_ptr(), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(),
-                                  beta.data_ptr(), float(slope), y.data_ptr(), n, c, h * w,
-                                  _stream()), 'tg_bn_lrelu_apply')
-    return y, mean, invstd, count
-
-
-def sync_bn_lrelu_train_bwd(x, y, dy, gamma, mean, invstd, count, dgamma=None, dbeta=None,
-                            need_dx=True, slope=0.2):
-    """dgamma/dbeta receive the LOCAL sums (DDP averages parameter gradients afterwards, as
-    SyncBatchNorm does); dx uses the global sums."""
-    n, c, h, w = x.shape
-    lib = L.lib()
-    sums = torch.empty(2 * c, dtype=torch.float32, device=x.device)
-    L.check(lib.tg_bn_lrelu_bwd_reduce(x.data_ptr(), y.data_ptr(), dy.data_ptr(), mean.data_ptr(),
-                                       invstd.data_ptr(), float(slope), sums.data_ptr(), n, c, h * w,
-                                       _stream()), 'tg_bn_lrelu_bwd_reduce')
-    if dgamma is not None:
-        axpy_(dgamma, sums[c:], 1.0)           # contiguous slices of the packed vector
-        axpy_(dbeta, sums[:c], 1.0)
-    from .utils import dist_utils
-    dist_utils.all_reduce_sum_(sums)
-    dx = None
-    if need_dx:
-        dx = torch.empty_like(x)
-        L.check(lib.tg_bn_lrelu_bwd_apply(x.data_ptr(), y.data_ptr(), dy.data_ptr(), mean.data_ptr(),
-                                          invstd.data_ptr(), gamma.data_ptr(), sums.data_ptr(),
-                                          float(slope), 1.0 / count, dx.data_ptr(), n, c, h * w,
-                                          _stream()), 'tg_bn_lrelu_bwd_apply')
-    return dx
-
-
 def sync_bn_lrelu_train_fwd_groups(x, groups, gamma, beta, running_mean, running_var, momentum=0.1, eps=1e-5,
                                    slope=0.2):
-    """SyncBatchNorm + LeakyReLU of `groups` INDEPENDENT batches stacked along n (the critic's real and fake
-    pass run as one pair batch, vsrgan_model.py:137-153): statistics per group, ONE all-gather of
-    groups x 2c floats per layer instead of one per pass, running statistics updated group after group (the
-    order of the reference's separate passes).  Returns y and per-group (mean, invstd, count)."""
+    """bn_lrelu_train_fwd with statistics over the GLOBAL batch, for `groups` INDEPENDENT batches stacked along n (the
+    critic's real and fake pass run as one pair batch, vsrgan_model.py:137-153).  Every rank computes (mean, centred M2)
+    of its slice of each group, ONE all-gather of groups x 2c floats per layer, merged per group with Chan's formula in
+    rank order (equal per-rank batch sizes, as DistributedSampler guarantees) -- the formulation torch's SyncBatchNorm
+    uses, with no E[x^2] - mean^2 cancellation; running statistics updated group after group (the order of the
+    reference's separate passes).  Returns y and per-group (mean, invstd, count).  With one rank the result is
+    bit-identical to bn_lrelu_train_fwd."""
     from .utils import dist_utils
     _chk(x, 'x')
     n, c, h, w = x.shape
@@ -1307,7 +1255,9 @@ def sync_bn_lrelu_train_fwd_groups(x, groups, gamma, beta, running_mean, running
 
 
 def sync_bn_lrelu_train_bwd_groups(x, y, dy, groups, gamma, stats, dgamma=None, dbeta=None, need_dx=True, slope=0.2):
-    """Backward of sync_bn_lrelu_train_fwd_groups: ONE all-reduce of the groups x 2c sums per layer."""
+    """Backward of sync_bn_lrelu_train_fwd_groups: ONE all-reduce of the groups x 2c sums per layer.  dgamma/dbeta
+    receive the LOCAL sums (DDP averages parameter gradients afterwards, as SyncBatchNorm does); dx uses the global
+    sums."""
     from .utils import dist_utils
     n, c, h, w = x.shape
     per = n // groups
@@ -1332,6 +1282,16 @@ def sync_bn_lrelu_train_bwd_groups(x, y, dy, groups, gamma, stats, dgamma=None, 
                                               float(slope), 1.0 / stats[g][2], dx[sl].data_ptr(), per, c, h * w,
                                               _stream()), 'tg_bn_lrelu_bwd_apply')
     return dx
+
+
+def sync_bn_lrelu_train_fwd(x, gamma, beta, running_mean, running_var, momentum=0.1, eps=1e-5, slope=0.2):
+    """One batch: the one-group case.  Returns (y, mean, invstd, count)."""
+    y, stats = sync_bn_lrelu_train_fwd_groups(x, 1, gamma, beta, running_mean, running_var, momentum, eps, slope)
+    return (y,) + stats[0]
+
+
+def sync_bn_lrelu_train_bwd(x, y, dy, gamma, mean, invstd, count, dgamma=None, dbeta=None, need_dx=True, slope=0.2):
+    return sync_bn_lrelu_train_bwd_groups(x, y, dy, 1, gamma, [(mean, invstd, count)], dgamma, dbeta, need_dx, slope)
 
 
 # ---- data movement of the training step (tg_assemble.hip) ---------------------------------

@@ -47,6 +47,15 @@ inline int check_launch(const char* what) {
     }                               \
   } while (0)
 
+// The batch-stride contract of every entry that takes a `*_nstride` (KERNELS.md, "Buffer placement"): the images of one
+// operand do not overlap, i.e. with n > 1 the stride of a non-null operand is at least the floats of one image.  A
+// launcher indexes image b at b * nstride and nothing else, so a smaller stride silently computes on / over the
+// neighbouring image.  TG_E_SHAPE, nothing is launched.
+#define TG_REQUIRE_NSTRIDE(entry, name, ptr, ns, n, floats)                                                      \
+  TG_REQUIRE(!(ptr) || (n) <= 1 || (long long)(ns) >= (long long)(floats), TG_E_SHAPE,                           \
+             entry ": " name "_nstride=%lld is less than the %lld floats of one image", (long long)(ns), \
+             (long long)(floats))
+
 // whether tg_convt3x3s2_z_fwd_form(form) runs as two launches (whole rounds of 4-row workgroups + a 2-row tail)
 bool convt_z_split_rule(int n, int h, int w, int form);
 // whether tg_convt3x3s2_z_wino_fwd(split) runs as two launches (whole rounds of resident workgroups + a remainder)

@@ -269,6 +269,8 @@ extern "C" int tg_conv3x3_f16_pack_input(const float* x1, int64_t x1_nstride, in
   TG_REQUIRE(c1 >= 1 && c2 >= 0 && c1 + c2 <= HC && f16_shape_ok(n, HC, HC, h, w), TG_E_SHAPE,
              "conv3x3_f16_pack_input: n=%d c1=%d c2=%d h=%d w=%d (c1 + c2 <= 64)", n, c1, c2, h, w);
   const int64_t hw = (int64_t)h * w, tot = (int64_t)n * hw;
+  TG_REQUIRE_NSTRIDE("conv3x3_f16_pack_input", "x1", x1, x1_nstride, n, c1 * hw);
+  TG_REQUIRE_NSTRIDE("conv3x3_f16_pack_input", "x2", c2 ? x2 : nullptr, x2_nstride, n, c2 * hw);
   hipLaunchKernelGGL(pack_input_f16_kernel, dim3((unsigned)((tot + 255) / 256), 8), dim3(256), 0, (hipStream_t)stream, x1,
                      x1_nstride, c1, x2, x2_nstride, c2, reinterpret_cast<_Float16*>(y), n, hw);
   return check_launch("conv3x3_f16_pack_input");

@@ -923,6 +923,11 @@ static int conv3x3_impl(const float* x, int64_t x_nstride, int c1, const float* 
   TG_REQUIRE(ocb == 32 || ocb == 64, TG_E_ARG, "conv3x3_fwd: ocb=%d", ocb);
   TG_REQUIRE((long long)(cin + CK) * h * w * 4 < (1ll << 31), TG_E_SHAPE,
              "conv3x3_fwd: one batch item must be < 2 GiB (cin=%d h=%d w=%d)", cin, h, w);
+  TG_REQUIRE_NSTRIDE("conv3x3_fwd", "x", x, x_nstride, n, (long long)c1 * h * w);
+  TG_REQUIRE_NSTRIDE("conv3x3_fwd", "x2", c1 < cin ? x2 : nullptr, x2_nstride, n, (long long)(cin - c1) * h * w);
+  TG_REQUIRE_NSTRIDE("conv3x3_fwd", "res", res, res_nstride, n, (long long)cout * h * w);
+  TG_REQUIRE_NSTRIDE("conv3x3_fwd", "mask", mask, mask_nstride, n, (long long)cout * h * w);
+  TG_REQUIRE_NSTRIDE("conv3x3_fwd", "y", y, y_nstride, n, (long long)cout * h * w);
   Conv3x3Args a{};
   a.x = x; a.x2 = (c1 < cin) ? x2 : nullptr; a.wpk = w_packed; a.bias = bias; a.res = res;
   a.y = y; a.x_ns = x_nstride; a.x2_ns = x2_nstride; a.res_ns = res_nstride; a.y_ns = y_nstride;
@@ -1043,6 +1048,9 @@ extern "C" int tg_conv3x3s2_fwd(const float* x, int64_t x_nstride, const float* 
              "conv3x3s2_fwd: n=%d cin=%d cout=%d out %dx%d (cin, cout <= 64, <= 1024 row tiles)", n, cin, cout, h_out, w_out);
   TG_REQUIRE(act >= TG_ACT_NONE && act <= TG_ACT_LRELU02, TG_E_ARG, "conv3x3s2_fwd: act=%d", act);
   TG_REQUIRE((long long)(cin + CK) * 4 * h_out * w_out * 4 < (1ll << 31), TG_E_SHAPE, "conv3x3s2_fwd: item too large");
+  TG_REQUIRE_NSTRIDE("conv3x3s2_fwd", "x", x, x_nstride, n, (long long)cin * 4 * h_out * w_out);
+  TG_REQUIRE_NSTRIDE("conv3x3s2_fwd", "mask", relu_mask, mask_nstride, n, (long long)cout * h_out * w_out);
+  TG_REQUIRE_NSTRIDE("conv3x3s2_fwd", "y", y, y_nstride, n, (long long)cout * h_out * w_out);
   Conv3x3Args a{};
   a.x = x; a.wpk = w_packed; a.bias = bias; a.y = y; a.x_ns = x_nstride; a.y_ns = y_nstride;
   a.mask = relu_mask; a.mask_ns = mask_nstride;

@@ -611,6 +611,9 @@ static int small_launch(const float* x, int64_t x_nstride, const float* w_oihw,
                    h % up_scale == 0 && w % up_scale == 0,
                TG_E_SHAPE, "conv3x3_small_fwd: up_mode=%d up_scale=%d", up_mode, up_scale);
   }
+  TG_REQUIRE_NSTRIDE("conv3x3_small_fwd", "x", x, x_nstride, n, (long long)cin * h * w);
+  TG_REQUIRE_NSTRIDE("conv3x3_small_fwd", "res", res, res_nstride, n, (long long)cout * h * w);
+  TG_REQUIRE_NSTRIDE("conv3x3_small_fwd", "y", y, y_nstride, n, (long long)cout * h * w);
   SmallArgs a{};
   a.x = x; a.wt = w_oihw; a.bias = bias; a.up = up_src; a.y = y; a.x_ns = x_nstride;
   a.y_ns = y_nstride; a.cin = cin; a.cout = cout; a.h = h; a.w = w; a.act = act;
@@ -693,6 +696,9 @@ extern "C" int tg_conv3x3_fewin_fwd(const float* x, int64_t x_nstride, const flo
                  (y_nstride % 4 == 0) && (!relu_mask || (((uintptr_t)relu_mask % 16 == 0) && mask_nstride % 4 == 0)) &&
                  ((long long)cout * h * w * 4 < (1ll << 31)),
              TG_E_ARG, "conv3x3_fewin_fwd: needs w %% 4 == 0 and 16-byte aligned planes");
+  TG_REQUIRE_NSTRIDE("conv3x3_fewin_fwd", "x", x, x_nstride, n, (long long)cin * h * w);
+  TG_REQUIRE_NSTRIDE("conv3x3_fewin_fwd", "mask", relu_mask, mask_nstride, n, (long long)cout * h * w);
+  TG_REQUIRE_NSTRIDE("conv3x3_fewin_fwd", "y", y, y_nstride, n, (long long)cout * h * w);
   SmallArgs a{};
   a.x = x; a.wt = w_oihw; a.y = y; a.x_ns = x_nstride; a.y_ns = y_nstride; a.cin = cin; a.cout = cout; a.h = h; a.w = w;
   a.res = relu_mask; a.res_ns = mask_nstride;

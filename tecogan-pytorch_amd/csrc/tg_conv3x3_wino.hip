@@ -638,6 +638,14 @@ int conv3x3_wino_launch(const float* x, int64_t x_ns, int c1, const float* x2, i
              fuse, h, w);
   TG_REQUIRE(!(fuse & TG_WINO_POOL) || (!res && !mask), TG_E_ARG, "conv3x3_wino: pool takes no residual and no mask");
   TG_REQUIRE(!(fuse & TG_WINO_UP2) || !x2, TG_E_ARG, "conv3x3_wino: up2 takes a single source");
+  {
+    const long long hw = (long long)h * w, shw = (fuse & TG_WINO_UP2) ? hw / 4 : hw, yhw = (fuse & TG_WINO_POOL) ? hw / 4 : hw;
+    TG_REQUIRE_NSTRIDE("conv3x3_wino", "x", x, x_ns, n, (x2 ? c1 : cin) * shw);
+    TG_REQUIRE_NSTRIDE("conv3x3_wino", "x2", x2, x2_ns, n, (cin - c1) * hw);
+    TG_REQUIRE_NSTRIDE("conv3x3_wino", "res", res, res_ns, n, cout * hw);
+    TG_REQUIRE_NSTRIDE("conv3x3_wino", "mask", mask, mask_ns, n, cout * hw);
+    TG_REQUIRE_NSTRIDE("conv3x3_wino", "y", y, y_ns, n, cout * yhw);
+  }
   WinoArgs a{};
   a.x = x; a.x2 = x2; a.u = u; a.bias = bias; a.res = res; a.mask = mask; a.y = y;
   a.x_ns = x_ns; a.x2_ns = x2_ns; a.res_ns = res_ns; a.mask_ns = mask_ns; a.y_ns = y_ns;

@@ -725,6 +725,10 @@ extern "C" int tg_conv4x4s2_fwd(const float* x, const float* w_fwd, float* y, fl
   TG_REQUIRE(x && w_fwd && y, TG_E_ARG, "conv4x4s2_fwd: null pointer");
   TG_REQUIRE(tg_conv4x4s2_supported(n, ci, co, h, w), TG_E_SHAPE, "conv4x4s2_fwd: unsupported n=%d ci=%d co=%d h=%d w=%d", n, ci,
              co, h, w);
+  // the small-map forms that split the input channels add the partial sums in a second launch, 16 bytes per thread
+  if (w % 64 != 0 && c4_fwd_ksplit(n, ci, co, h, w) > 1)
+    TG_REQUIRE(workspace && (((uintptr_t)y | (uintptr_t)workspace) & 15) == 0, TG_E_ARG,
+               "conv4x4s2_fwd: the split form of this shape needs a workspace, and y and the workspace 16-byte aligned");
   c4_set_attrs();
   if (w % 64 != 0) {
     Conv4SmallArgs sa;
@@ -775,6 +779,12 @@ extern "C" int tg_conv4x4s2_dgrad(const float* g, const float* w_dgrad, const fl
   TG_REQUIRE(tg_conv4x4s2_supported(n, ci, co, h, w), TG_E_SHAPE, "conv4x4s2_dgrad: unsupported n=%d ci=%d co=%d h=%d w=%d", n,
              ci, co, h, w);
   TG_REQUIRE(!act_y || act == TG_ACT_RELU || act == TG_ACT_LRELU02, TG_E_ARG, "conv4x4s2_dgrad: act=%d (relu | lrelu)", act);
+  // the small-map forms sum the partial sums / apply act'(.) in a second launch, 16 bytes per thread
+  if (w % 64 != 0) {
+    const bool split = c4_dgrad_ksplit(n, ci, co, h, w) > 1;
+    TG_REQUIRE(!(split || act_y) || (((uintptr_t)dx | (uintptr_t)(split ? workspace : nullptr) | (uintptr_t)act_y) & 15) == 0,
+               TG_E_ARG, "conv4x4s2_dgrad: the two-pass form of this shape needs 16-byte aligned dx, workspace and act_y");
+  }
   c4_set_attrs();
   if (w % 64 != 0) {
     Conv4DgradSmallArgs sa;

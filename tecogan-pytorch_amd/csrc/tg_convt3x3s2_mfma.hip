@@ -703,6 +703,8 @@ extern "C" int tg_convt3x3s2_fwd(const float* x, int64_t x_nstride, const float*
              "convt3x3s2_fwd: output must be 8-byte aligned");
   TG_REQUIRE((long long)(cin + CK) * h * w * 4 < (1ll << 31), TG_E_SHAPE,
              "convt3x3s2_fwd: one batch item must be < 2 GiB");
+  TG_REQUIRE_NSTRIDE("convt3x3s2_fwd", "x", x, x_nstride, n, (long long)cin * h * w);
+  TG_REQUIRE_NSTRIDE("convt3x3s2_fwd", "y", y, y_nstride, n, (long long)cout * 4 * h * w);
   ConvTArgs a{};
   a.x = x; a.wpk = w_packed; a.bias = bias; a.y = y; a.x_ns = x_nstride; a.y_ns = y_nstride;
   a.cin = cin; a.cout = cout; a.h = h; a.w = w; a.act = act;
@@ -770,6 +772,8 @@ extern "C" int tg_convt3x3s2_z_fwd_form(const float* x, int64_t x_nstride, const
   TG_REQUIRE((z_nstride % 2) == 0 && ((uintptr_t)z % 8) == 0, TG_E_ARG, "convt3x3s2_z_fwd: z must be 8-byte aligned");
   TG_REQUIRE((long long)(cin + CK) * h * w * 4 < (1ll << 31) && 32ll * 4 * h * w * 4 < (1ll << 31), TG_E_SHAPE,
              "convt3x3s2_z_fwd: one batch item (input and the 32 planes) must be < 2 GiB");
+  TG_REQUIRE_NSTRIDE("convt3x3s2_z_fwd", "x", x, x_nstride, n, (long long)cin * h * w);
+  TG_REQUIRE_NSTRIDE("convt3x3s2_z_fwd", "z", z, z_nstride, n, 9ll * cz * 4 * h * w);      // the planes it writes
   ConvTArgs a{};
   a.x = x; a.wpk = w_packed; a.bias = bias; a.y = nullptr; a.x_ns = x_nstride; a.y_ns = 0;
   a.cin = cin; a.cout = cout; a.h = h; a.w = w; a.act = act;
@@ -826,6 +830,8 @@ extern "C" int tg_convout_tail_form(const float* z, int64_t z_nstride, int cz, c
   if (up_src)
     TG_REQUIRE((up_mode == TG_UP_BICUBIC || up_mode == TG_UP_BILINEAR) && up_scale >= 1 && h % up_scale == 0 &&
                    w % up_scale == 0, TG_E_SHAPE, "convout_tail: up_mode=%d up_scale=%d", up_mode, up_scale);
+  TG_REQUIRE_NSTRIDE("convout_tail", "z", z, z_nstride, n, 9ll * cz * h * w);              // the planes it reads
+  TG_REQUIRE_NSTRIDE("convout_tail", "y", y, y_nstride, n, (long long)cz * h * w);
   hipStream_t s = (hipStream_t)stream;
   // four pixels per thread wherever rows and planes are 16-byte aligned (and the uint8 rows 4-byte aligned for cz = 3)
   const bool vec_ok = (w % 4) == 0 && ((uintptr_t)z % 16) == 0 && ((uintptr_t)y % 16) == 0 && (z_nstride % 4) == 0 &&

@@ -372,6 +372,11 @@ extern "C" int tg_convt3x3s2_z_wino_fwd(const float* x, int64_t x_nstride, const
   TG_REQUIRE(split >= -1 && split <= 1, TG_E_ARG, "convt3x3s2_z_wino_fwd: split=%d (-1 the rule, 0 one launch, 1 split)", split);
   TG_REQUIRE(64ll * h * w * 4 < (1ll << 31) && 32ll * 4 * h * w * 4 < (1ll << 31), TG_E_SHAPE,
              "convt3x3s2_z_wino_fwd: one batch item (input and the 32 planes) must be < 2 GiB");
+  // the planes leave as 16-byte (8-byte in the last column of an odd-width map) buffer stores at even float offsets
+  // of an image: the same contract as the direct form, so that a caller can swap the two
+  TG_REQUIRE((z_nstride % 2) == 0 && ((uintptr_t)z % 8) == 0, TG_E_ARG, "convt3x3s2_z_wino_fwd: z must be 8-byte aligned");
+  TG_REQUIRE_NSTRIDE("convt3x3s2_z_wino_fwd", "x", x, x_nstride, n, (long long)cin * h * w);
+  TG_REQUIRE_NSTRIDE("convt3x3s2_z_wino_fwd", "z", z, z_nstride, n, 9ll * cz * 4 * h * w);      // the planes it writes
   static bool attr_set = false;
   if (!attr_set) {
     const void* fns[4] = {reinterpret_cast<const void*>(convt3x3s2_wino_z_kernel<false, false>),

@@ -628,6 +628,7 @@ extern "C" int tg_flowup_warp_s2d_fwd(const float* lr_flow, int fh, int fw, cons
   TG_REQUIRE(scale * h >= 2 && scale * w >= 2, TG_E_SHAPE, "flowup_warp_s2d: degenerate size");
   TG_REQUIRE((long long)scale * scale * c * h * w < (1ll << 31), TG_E_SHAPE,
              "flowup_warp_s2d: frame too large for 32-bit offsets");
+  TG_REQUIRE_NSTRIDE("flowup_warp_s2d", "out", out, out_nstride, n, (long long)scale * scale * c * h * w);
   const float nx = (float)(scale * w - 1), ny = (float)(scale * h - 1);
   FusedArgs a{lr_flow, hr_prev, out, hr_flow_out, out_nstride, n, c, h, w, fh, fw, up_mode,
               2.0f / nx, 2.0f / ny, nx / 2.0f, ny / 2.0f, 1.0f / (nx / 2.0f), 1.0f / (ny / 2.0f),
@@ -694,6 +695,7 @@ extern "C" int tg_space_to_depth(const float* x, float* y, int64_t y_nstride, in
   TG_REQUIRE(n > 0 && c > 0 && scale >= 1 && h >= scale && w >= scale, TG_E_SHAPE,
              "space_to_depth: n=%d c=%d h=%d w=%d s=%d", n, c, h, w, scale);
   long long total = (long long)n * scale * scale * c * (h / scale) * (w / scale);
+  TG_REQUIRE_NSTRIDE("space_to_depth", "y", y, y_nstride, n, total / n);
   const bool vec = (scale == 2 || scale == 4) && h % scale == 0 && w % (4 * scale) == 0 &&
                    (((uintptr_t)x | (uintptr_t)y) & 15) == 0 && y_nstride % 4 == 0;
   if (vec) {

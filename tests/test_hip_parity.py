@@ -167,7 +167,7 @@ WINO_CASES = [
     (1, 16, 64, 9, 33, 2, None, False),       # one K stage
     (1, 128, 128, 5, 9, 2, None, False),      # two output-channel groups, tiny map
     (1, 27, 64, 16, 16, 3, None, False),      # K padded 27 -> 32, tanh*24 epilogue
-    (2, 64, 64, 134, 64, 0, None, True),      # > 512 workgroups: XCD-banded order
+    (2, 64, 64, 134, 64, 0, None, True),      # 268 workgroups (the XCD-banded order starts at 512: the 134x320 tests)
     (1, 64, 48, 10, 34, 0, None, False),      # cout not a multiple of 16
     (1, 64, 64, 2, 2, 1, None, False),        # a single tile
 ]

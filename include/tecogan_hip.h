@@ -124,7 +124,10 @@ int tg_conv3x3_fwd_phased(const float* x, int64_t x_nstride, const float* w_pack
  * blocks, w = 32 (h % 8 == 0) / w = 16 (h % 16 == 0): 32 pixels of the matrix tile are then 2 / 4 rows, the input
  * channels are split over several workgroups and a second launch adds the partial sums in a fixed order; such calls
  * need tg_conv4x4s2_workspace_floats(.., dgrad) floats of workspace (0: none, workspace may be NULL).  Other shapes
- * keep the embedded form (tg_conv3x3_fwd_phased on tg_space_to_depth(x, 2)), and so does the weight gradient. */
+ * keep the embedded form (tg_conv3x3_fwd_phased on tg_space_to_depth(x, 2)), and so does the weight gradient.
+ * Alignment (TG_E_ARG otherwise): tg_conv4x4s2_dgrad stores dx and reads act_y as pairs of pixels, both 8-byte aligned;
+ * the calls that need a workspace, and the small-map dgrad with act_y, also run a 16-byte pass over y / dx, the
+ * workspace and act_y: 16-byte aligned. */
 int tg_conv4x4s2_supported(int n, int ci, int co, int h, int w);
 size_t tg_conv4x4s2_packed_floats(int ci, int co);
 int tg_conv4x4s2_pack(const float* w, float* w_fwd, float* w_dgrad, int ci, int co, tg_stream_t stream);
@@ -688,7 +691,8 @@ int tg_wgrad3x3_multi(const float* const* p_list, const float* const* q_list, in
                       int accumulate, tg_stream_t stream);
 /* tg_wgrad3x3_multi that also delivers the layer's bias gradient: bias_grad (ca floats) (+)= sum of p over
  * images and pixels, taken from the p values the kernel stages anyway (vector staging: w % 4 == 0, aligned
- * planes; other forms run tg_bias_grad_multi themselves) -- no second pass over dZ. */
+ * planes; other forms run tg_bias_grad_multi themselves) -- no second pass over dZ.  That reduction takes no stride:
+ * with more than one image per segment p_nstride must be the packed ca * h * w, TG_E_ARG otherwise. */
 int tg_wgrad3x3_multi_bias(const float* const* p_list, const float* const* q_list, int nseg,
                            int64_t p_nstride, int64_t q_nstride, float* grad, float* bias_grad,
                            float* workspace, int n_per_seg, int ca, int cb, int cb_total, int cb_off,
@@ -881,6 +885,8 @@ int tg_downsample_bd(const float* x, const float* kernel2d, float* y, int nc, in
  *                      of which the first t frames are used, warped is (n*t, c, h, w);
  *   tg_d_assemble_bwd  its adjoint: g -> g_data (n, t_data, c, h, w; zero beyond t), g_warped (n*t, c, h, w).
  * ---------------------------------------------------------------------- */
+/* tg_time_gather, tg_transpose01 and tg_stack_time move 16 bytes per thread: inner % 4 == 0 (tg_time_gather:
+ * TG_E_SHAPE otherwise; the other two: TG_E_ARG) and every source and y 16-byte aligned (TG_E_ARG otherwise). */
 int tg_time_gather(const float* x, float* y, const int* idx_host, int n, int t_in, int k,
                    int64_t inner, tg_stream_t stream);
 int tg_transpose01(const float* x, float* y, int a, int b, int64_t inner, tg_stream_t stream);

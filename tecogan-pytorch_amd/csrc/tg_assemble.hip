@@ -223,6 +223,7 @@ extern "C" int tg_stack_time(const float* const* src_host, int k, float* y, int 
                              tg_stream_t stream) {
   TG_REQUIRE(src_host && y && k > 0 && k <= 64 && n > 0 && inner > 0 && inner % 4 == 0, TG_E_ARG,
              "stack_time: k=%d (<=64) n=%d inner=%lld (%%4)", k, n, (long long)inner);
+  TG_REQUIRE(((uintptr_t)y % 16) == 0, TG_E_ARG, "stack_time: 16-byte alignment of y");
   StackSrc s{};
   for (int j = 0; j < k; ++j) {
     TG_REQUIRE(src_host[j] && ((uintptr_t)src_host[j] % 16) == 0, TG_E_ARG, "stack_time: source %d null / unaligned", j);

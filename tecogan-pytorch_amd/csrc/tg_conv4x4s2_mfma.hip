@@ -779,6 +779,8 @@ extern "C" int tg_conv4x4s2_dgrad(const float* g, const float* w_dgrad, const fl
   TG_REQUIRE(tg_conv4x4s2_supported(n, ci, co, h, w), TG_E_SHAPE, "conv4x4s2_dgrad: unsupported n=%d ci=%d co=%d h=%d w=%d", n,
              ci, co, h, w);
   TG_REQUIRE(!act_y || act == TG_ACT_RELU || act == TG_ACT_LRELU02, TG_E_ARG, "conv4x4s2_dgrad: act=%d (relu | lrelu)", act);
+  // every form stores dx (and reads act_y) as pairs of neighbouring pixels, 8 bytes at even offsets of an image
+  TG_REQUIRE((((uintptr_t)dx | (uintptr_t)act_y) & 7) == 0, TG_E_ARG, "conv4x4s2_dgrad: dx and act_y must be 8-byte aligned");
   // the small-map forms sum the partial sums / apply act'(.) in a second launch, 16 bytes per thread
   if (w % 64 != 0) {
     const bool split = c4_dgrad_ksplit(n, ci, co, h, w) > 1;

@@ -759,6 +759,9 @@ extern "C" int tg_bias_grad_body(const float* const* dz_bases, int nframes,
                                  int hw, tg_stream_t stream) {
   TG_REQUIRE(dz_bases && dbs && nframes >= 1 && nframes <= 64 && nlayers >= 1 && nlayers <= 25 &&
                  n_per_frame > 0 && c > 0 && hw > 0, TG_E_ARG, "bias_grad_body: bad argument");
+  TG_REQUIRE(nlayers == 1 || layer_stride >= (int64_t)n_per_frame * c * hw, TG_E_SHAPE,
+             "bias_grad_body: layer_stride=%lld is less than the %lld floats of one layer", (long long)layer_stride,
+             (long long)n_per_frame * c * hw);
   BiasBodyArgs a{};
   for (int i = 0; i < nframes; ++i) {
     TG_REQUIRE(dz_bases[i], TG_E_ARG, "bias_grad_body: null frame %d", i);

@@ -835,6 +835,13 @@ static int wgrad_launch(const float* const* p_list, const float* const* q_list, 
              cb_total, h, w);
   TG_REQUIRE((long long)(ca > (stride2 ? 4 * cb : cb) ? ca : (stride2 ? 4 * cb : cb)) * h * w * 4 < (1ll << 31), TG_E_SHAPE,
              "wgrad3x3: one batch item must be < 2 GiB");
+  // the images of a segment may not overlap (the strides are shared by the segments of a list)
+  TG_REQUIRE_NSTRIDE("wgrad3x3", "p", p_list, p_nstride, n_per_seg, (long long)ca * h * w);
+  TG_REQUIRE_NSTRIDE("wgrad3x3", "q", q_list, q_nstride, n_per_seg, (long long)cb * (stride2 ? 4 : 1) * h * w);
+  // the forms without the vector staging leave the bias gradient to tg_bias_grad_multi, which reads packed segments
+  TG_REQUIRE(!bias_grad || stride2 || n_per_seg <= 1 || p_nstride == (int64_t)ca * h * w, TG_E_ARG,
+             "wgrad3x3: the bias gradient needs packed p segments (p_nstride=%lld, one image is %lld floats)",
+             (long long)p_nstride, (long long)ca * h * w);
   const int geo = stride2 ? 3 : (cphase ? 0 : wgrad_geo(h, w));
   if (ca <= 4 && !cphase && !stride2) {
     WgradSmallArgs sa{};

@@ -25,6 +25,9 @@ tests safe on a shared machine.
     rc = lib.tg_...(x.data_ptr(), a.nstride(x), ..., y.data_ptr(), a.nstride(y), ...)
     a.check()            # guards, gaps and inputs bit for bit as they were; names the nearest operand otherwise
     a.finite(y)          # every element written, no guard NaN leaked in
+
+`inout` is the destination that already holds values (a gradient a launch adds to, or a gradient matrix of which a
+launch writes a column slice): the elements outside the writable mask are checked like an input.
 """
 import numpy as np
 import torch
@@ -124,6 +127,28 @@ class Arena:
         for b in range(op['n']):
             lo = op['base'] + b * op['ns_words']
             self.free[lo:lo + op['per_words']] = True
+        return view
+
+    def inout(self, t, writable=None, prefill=False, offset_floats=0, nstride=None, name='g'):
+        """A destination that already holds values (an accumulated gradient; a gradient matrix of which a launch
+        writes a column slice): a copy of fp32 `t`, placed as `place` does, of which the launch may write the elements
+        where the bool tensor `writable` (default: all) is set.  Every other element is checked bit for bit like an
+        input.  prefill: the writable elements start as the slot's guard pattern instead of t's values (a launch that
+        overwrites: finite() then tells an element that was never written)."""
+        assert t.dtype == torch.float32
+        view = self.place(t, offset_floats=offset_floats, nstride=nstride, name=name)
+        op = view._arena_op
+        op['is_out'] = True
+        mask = torch.ones(t.shape, dtype=torch.bool) if writable is None else writable.expand(t.shape).contiguous()
+        flat = mask.reshape(op['n'], -1).numpy()
+        for b in range(op['n']):
+            lo = op['base'] + b * op['ns_words']
+            self.free[lo:lo + op['per_words']] = flat[b]
+        if prefill:
+            view.view(torch.int32)[mask.to(view.device)] = pattern(op['slot'])
+            for b in range(op['n']):                 # (a refusal must leave the pre-fill as it is)
+                lo = op['base'] + b * op['ns_words']
+                self.expect[lo:lo + op['per_words']][flat[b]] = pattern(op['slot'])
         return view
 
     @staticmethod

@@ -196,7 +196,10 @@ def launch(lib, case, pl):
     for o in case.operands:
         off, ns = info[o.name]
         kw = dict(offset_floats=off, nstride=ns if len(o.shape) > 1 else None, name=o.name)
-        views[o.name] = arena.place(o.data, **kw) if o.data is not None else arena.out(o.shape, dtype=o.dtype, **kw)
+        if getattr(o, 'inout', False):      # (tests/test_hip_placement_bwd.py: a destination that already holds values)
+            views[o.name] = arena.inout(o.data, o.writable, o.prefill, **kw)
+        else:
+            views[o.name] = arena.place(o.data, **kw) if o.data is not None else arena.out(o.shape, dtype=o.dtype, **kw)
     ptr = {k: v.data_ptr() for k, v in views.items()}
     ns = {k: v[1] for k, v in info.items()}
     torch.cuda.synchronize()
@@ -232,14 +235,25 @@ def run_case(lib, case):
                 k = worst.setdefault(what, [0.0, bound])
                 k[0] = max(k[0], value)
                 assert value <= bound, f'{what}: {value:.3e} > {bound:.3e}'
+            same = base is None or case.same_bits(info)
             if base is None:
                 base = outs
-            elif case.same_bits(info):
+            elif same:
+                # same: True, or {output: bound} for the outputs that agree with the P0 result only to `bound` of its
+                # scale (the others bit for bit)
+                loose = same if isinstance(same, dict) else {}
                 for k, v in outs.items():
+                    if k in loose:
+                        d = (v.double() - base[k].double()).abs().max().item() / (base[k].double().abs().max().item() + 1e-30)
+                        assert d <= loose[k], f'{k} is {d:.3e} of its scale from the P0 result (bound {loose[k]:.1e})'
+                        continue
                     as_int = torch.int32 if v.element_size() == 4 else torch.int16
                     assert torch.equal(v.view(as_int), base[k].view(as_int)), f'{k} differs from the P0 result in {int((v != base[k]).sum())} elements, ' \
                                  f'max |d| {(v.double() - base[k].double()).abs().max().item():.3e}'
-                bits_checked += 1
+                if loose:
+                    bits_skipped.append(tag)
+                else:
+                    bits_checked += 1
             else:
                 bits_skipped.append(tag)
             launched.append(tag)

@@ -59,6 +59,7 @@ constexpr int WR_CS = 288;                        // channel stride: 10 rows x 2
 constexpr int WR_NC = 64;                         // channels (nf)
 constexpr int WR_THREADS = 768;                   // 12 waves: 3 per SIMD
 constexpr int WR_MAXL = 24;
+constexpr int WT_NP = 25;                         // the tail's products per tile and K step (WZ_NP of tg_convt3x3s2_wino.hip)
 constexpr int WR_SLOTS = 64;                      // published ring pixels of a block: top 24, bottom 24, left 8, right 8
 constexpr int WR_SC1 = 16;                        // agent-scope cache policy bit of the buffer instructions
 constexpr int WR_POLL_SLEEP = 2;                  // s_sleep units (64 cycles) between two polls of the ring
@@ -83,7 +84,7 @@ struct WResLayer {
   const float* bias;
   int act;
   int res;             // + the destination buffer's old content (residual input) after the activation
-  int nks;             // K steps of 4 input channels (4 * ceil(cin / 16))
+  int nks;             // K steps of 4 input channels, an even number (2 * ceil(cin / 8): the K loop walks in pairs)
   int pad;
 };
 struct WResArgs {
@@ -474,11 +475,21 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
   // ---- tail: ConvTranspose2d(64, 64, 3, stride 2, pad 1, output_padding 1) + act on the resident block ------------
   //   out[2y + py][2x + px] = bias + sum_ic sum_taps in[y + dy][x + dx] W[ic][oc][ky][kx],
   //   py = 0: (dy 0, ky 1);  py = 1: (dy 0, ky 2), (dy 1, ky 0)   (the same along x; 9 taps over the 4 phases).
-  // The wave keeps its (tile group, 16-channel block): MFMA column n = Winograd tile n of the group, four column
-  // blocks = the tile's 2 x 2 pixels (a, b), so a lane's 3 x 3 window at its tile origin holds every operand:
-  // 9 LDS reads and 36 MFMAs per K step, 16 accumulators (4 pixels x 4 phases).  Weights straight from L2 (two
-  // K steps in flight), output as 16-byte stores of 4 consecutive columns.  Direct fp32 products: as a launch of
-  // its own this layer ran at 0.51 of peak on 670 workgroups and cost a kernel boundary in the frame's serial chain.
+  // The wave keeps its (tile group, 16-channel block): MFMA column n = Winograd tile n of the group, and a lane's 3 x 3
+  // window at its tile origin holds every operand of the tile's 2 x 2 input pixels (ya, xb) -- the operand set of
+  // convt3x3s2_wino_z_kernel (tg_convt3x3s2_wino.hip), whose identity and conventions this tail follows: F(2,2) with
+  // coefficients +-1 along each axis,
+  //   data     c[i] = (d[i][0] - d[i][1], d[i][1], d[i][2] - d[i][1])   (the y-transform likewise over rows)
+  //   weights  (g0, g1, g2) = (W[.2], W[.2] + W[.0], W[.0])             y(b) = m[b] + m[b + 1]
+  // so the four phases need 4 + 6 + 6 + 9 = 25 products per tile and K step instead of the 36 of the direct form:
+  //   p  0.. 3  phase (0,0): raw d[ya][xb]                       against W11                    p = 2 ya + xb
+  //   p  4.. 9  phase (0,1): row ya, x-transform j               against (W12, W12 + W10, W10)  p = 4 + 3 ya + j
+  //   p 10..15  phase (1,0): y-transform i, column xb            against (W21, W21 + W01, W01)  p = 10 + 2 i + xb
+  //   p 16..24  phase (1,1): y-transform i, x-transform j        against G[i][j]                p = 16 + 3 i + j
+  // G: rows (W2., W2. + W0., W0.), columns likewise, the centre the row sum of the column sums (convt_pack_wino_kernel).
+  // 9 LDS reads, 16 subtractions, 7 weight sums (in registers, from the nine raw taps of the packed operand) and 25
+  // MFMAs per K step, 25 accumulators.  Weights straight from L2 (two K steps in flight), output transform in the
+  // epilogue (phase (1,1): rows first, as the Z kernel), output as 16-byte stores of 4 consecutive columns.
   __syncthreads();                            // the ring of the last layer is complete for EVERY wave
   {
     // (the tail's geometry is derived from an opaque copy of the lane id: computed ahead of the layer loop it cost the
@@ -492,9 +503,9 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
     const bool live = gy0 < a.h && gx0 < a.w;
     const float* src = s_act + (a.nlayer & 1) * (WR_NC * WR_CS);
     const int cb = kk * WR_CS + (2 * ty + 1) * WR_RS + (2 * tx + 1);
-    f32x4 ca[16];
+    f32x4 ca[WT_NP];
 #pragma unroll
-    for (int p = 0; p < 16; ++p) ca[p] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int p = 0; p < WT_NP; ++p) ca[p] = f32x4{0.f, 0.f, 0.f, 0.f};
     const f32x4* cu = reinterpret_cast<const f32x4*>(a.ct_u) + (size_t)(q * 3) * 64 + l2;
     constexpr size_t CSTEP = (size_t)4 * 3 * 64;
     constexpr int CT_NKS = WR_NC / 4;
@@ -524,6 +535,7 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
     auto wait_w = [&](f32x4 (&)[3]) {};
     auto drain_w = [&](f32x4 (&)[3], f32x4 (&)[3]) {};
 #endif
+    // one K step: window, weight sums, input transform -> 25 MFMAs in the order of the products (see above)
     auto cstep = [&](int ks, f32x4 (&w)[3]) {
       wait_w(w);
       const float* sp = src + cb + ks * (4 * WR_CS);
@@ -532,24 +544,49 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
       for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j) d[i][j] = sp[i * WR_RS + j];
+      auto W = [&](int ky, int kx) { return w[(ky * 3 + kx) >> 2][(ky * 3 + kx) & 3]; };
+      auto mm = [&](int p, float wv, float bv) { ca[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv, bv, ca[p], 0, 0, 0); };
+      // phase (0,0)
 #pragma unroll
-      for (int pa = 0; pa < 2; ++pa)
+      for (int ya = 0; ya < 2; ++ya)
 #pragma unroll
-        for (int pb2 = 0; pb2 < 2; ++pb2)
+        for (int xb = 0; xb < 2; ++xb) mm(2 * ya + xb, W(1, 1), d[ya][xb]);
+      // phase (0,1): x-transform of each window row (the third row is needed by phase (1,1) only)
+      float c3[3][3];
 #pragma unroll
-          for (int py = 0; py < 2; ++py)
+      for (int i = 0; i < 3; ++i) {
+        c3[i][0] = d[i][0] - d[i][1];
+        c3[i][1] = d[i][1];
+        c3[i][2] = d[i][2] - d[i][1];
+      }
+      {
+        const float gx[3] = {W(1, 2), W(1, 2) + W(1, 0), W(1, 0)};
 #pragma unroll
-            for (int px = 0; px < 2; ++px)
+        for (int ya = 0; ya < 2; ++ya)
 #pragma unroll
-              for (int ey = 0; ey <= py; ++ey)
+          for (int j = 0; j < 3; ++j) mm(4 + 3 * ya + j, gx[j], c3[ya][j]);
+      }
+      // phase (1,0): y-transform of the two columns
+      {
+        const float gy[3] = {W(2, 1), W(2, 1) + W(0, 1), W(0, 1)};
 #pragma unroll
-                for (int ex = 0; ex <= px; ++ex) {
-                  // phase coordinate 0: the single tap (d 0, k 1); coordinate 1: (d 0, k 2), (d 1, k 0)
-                  const int dy = py ? ey : 0, ky = py ? (ey ? 0 : 2) : 1;
-                  const int dx = px ? ex : 0, kx = px ? (ex ? 0 : 2) : 1;
-                  const int tap = ky * 3 + kx, ai = (pa * 2 + pb2) * 4 + py * 2 + px;
-                  ca[ai] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[tap >> 2][tap & 3], d[pa + dy][pb2 + dx], ca[ai], 0, 0, 0);
-                }
+        for (int xb = 0; xb < 2; ++xb) {
+          mm(10 + xb, gy[0], d[0][xb] - d[1][xb]);
+          mm(12 + xb, gy[1], d[1][xb]);
+          mm(14 + xb, gy[2], d[2][xb] - d[1][xb]);
+        }
+      }
+      // phase (1,1): both transforms; G's middle row is the row sum of the column sums
+      {
+        const float g0[3] = {W(2, 2), W(2, 2) + W(2, 0), W(2, 0)};
+        const float g2[3] = {W(0, 2), W(0, 2) + W(0, 0), W(0, 0)};
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          mm(16 + j, g0[j], c3[0][j] - c3[1][j]);
+          mm(19 + j, g0[j] + g2[j], c3[1][j]);
+          mm(22 + j, g2[j], c3[2][j] - c3[1][j]);
+        }
+      }
     };
     f32x4 w0[3], w1[3];
     load_w(0, w0);
@@ -574,17 +611,29 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
         const float bz = a.ct_bias[oc_base + r];
         float* yo = a.ct_y + (size_t)(oc_base + r) * ohw + (size_t)(2 * gy0) * ow + 2 * gx0;
 #pragma unroll
-        for (int pa = 0; pa < 2; ++pa)
+        for (int ya = 0; ya < 2; ++ya) {      // input row ya of the tile: HR rows 2 ya, 2 ya + 1
+          float o[2][4];                      // [py][column 2 xb + px]
+          float s3[3];
+#pragma unroll
+          for (int j = 0; j < 3; ++j) s3[j] = ca[16 + 3 * ya + j][r] + ca[16 + 3 * (ya + 1) + j][r];
+#pragma unroll
+          for (int xb = 0; xb < 2; ++xb) {
+            o[0][2 * xb] = ca[2 * ya + xb][r];
+            o[0][2 * xb + 1] = ca[4 + 3 * ya + xb][r] + ca[4 + 3 * ya + xb + 1][r];
+            o[1][2 * xb] = ca[10 + 2 * ya + xb][r] + ca[10 + 2 * (ya + 1) + xb][r];
+            o[1][2 * xb + 1] = s3[xb] + s3[xb + 1];
+          }
 #pragma unroll
           for (int py = 0; py < 2; ++py) {
             float o4[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {     // columns 4 tx' + e = (pixel b = e >> 1, phase px = e & 1)
-              float v = ca[(pa * 2 + (e >> 1)) * 4 + py * 2 + (e & 1)][r] + bz;
+            for (int e = 0; e < 4; ++e) {
+              const float v = o[py][e] + bz;
               o4[e] = __builtin_fmaxf(v, cslope * v);
             }
-            *reinterpret_cast<float4*>(yo + (size_t)(2 * pa + py) * ow) = make_float4(o4[0], o4[1], o4[2], o4[3]);
+            *reinterpret_cast<float4*>(yo + (size_t)(2 * ya + py) * ow) = make_float4(o4[0], o4[1], o4[2], o4[3]);
           }
+        }
       }
     }
   }
@@ -667,7 +716,9 @@ int conv3x3_wino_resident_launch(const tg_wino_layer* layers, int n_layers, int 
                  "conv3x3_wino_resident: layer %d: the residual input must be layer %d's input", i, i - 1);
     }
     WResLayer& d = a.L[i];
-    d.u = l.u_packed; d.bias = l.bias; d.act = l.act; d.res = l.res ? 1 : 0; d.nks = 4 * cdiv(l.cin, 16);
+    // (K steps: whole pairs up to cin, not whole 16-channel stages of U -- a step over channels that do not exist adds
+    // exact zeros (both LDS buffers are zero-filled); U is packed in whole stages, so the block index stays in range)
+    d.u = l.u_packed; d.bias = l.bias; d.act = l.act; d.res = l.res ? 1 : 0; d.nks = 2 * cdiv(l.cin, 8);
   }
   a.x = layers[0].x; a.x2 = layers[0].x2; a.c1 = layers[0].x2 ? layers[0].c1 : layers[0].cin; a.cin0 = layers[0].cin;
   a.y = layers[n_layers - 1].y;

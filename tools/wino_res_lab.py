@@ -1,7 +1,8 @@
 """Lab: SRNet's conv_in + 20 residual-block convs at 134x320 -- 21 per-layer Winograd launches against
 the ONE LDS-resident launch (tg_conv3x3_wino_resident).  HIP events around `reps` back-to-back bodies;
 prints us per body and per layer, and checks the two outputs bit for bit.
-  python tools/wino_res_lab.py [h w [nb]]"""
+  python tools/wino_res_lab.py [h w [nb [ct]]]
+ct: also time the launch with its transposed-conv tail (tg_conv3x3_wino_resident_ct), us per launch."""
 import os
 import sys
 
@@ -61,6 +62,14 @@ def main():
         t_res = timeit(res.run)
         print('per-layer launches: %.1f us (%.2f us/layer)   resident: %.1f us (%.2f us/layer)   ratio %.3f'
               % (t_seq, t_seq / nl, t_res, t_res / nl, t_res / t_seq))
+    if len(sys.argv) > 4 and sys.argv[4] == 'ct':
+        wt = torch.randn(64, 64, 3, 3, generator=g).to(dev) * 0.05
+        ct = dict(u=ops.pack_wres_convt(wt), bias=torch.randn(64, generator=g).to(dev) * 0.1,
+                  y=torch.empty(1, 64, 2 * h, 2 * w, device=dev), act=1)
+        for rep in range(3):
+            t_res = timeit(res.run)
+            t_ct = timeit(lambda: res.run(convt=ct))
+            print('resident + tail: %.1f us   resident: %.1f us   tail %+.1f us' % (t_ct, t_res, t_ct - t_res))
     print('bailouts', res.bailouts())
 
 

@@ -107,6 +107,56 @@ int conv3x3_wino_resident_launch(const tg_wino_layer* layers, int n_layers, int 
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+// ---- raw buffer access ----------------------------------------------------
+// How the kernels address an operand in global memory (KERNELS.md, "Buffer access"): a 128-bit descriptor {base, record
+// bytes} built once per operand from wave-uniform values, and a 32-bit per-lane BYTE offset checked against the record
+// bytes by the hardware -- a load past them returns 0 and a store past them is dropped, which is how every kernel gets
+// its zero padding, its channel padding and its masked lanes without a branch.  This section is the only place that
+// spells out the gfx950 builtins (tests/test_buffer_access_cpu.py).
+//
+// Word 3 of the descriptor: DATA_FORMAT (bits 18:15) = 4, a 32-bit format -- the field must not be 0 (an invalid
+// descriptor), the untyped buffer_load / buffer_store_dword* instructions do not otherwise read it.  All else is 0:
+// no swizzle, no add-tid, and with stride 0 (word 1) a raw buffer, whose range check is `offset + size > record bytes`.
+constexpr int BUF_RSRC_FLAGS = 0x00020000;
+// A macro and not a function: through an inline function the row chain's two output descriptors came out with a dozen
+// re-ordered scalar instructions and a few re-scheduled v_pk_add_f32 (EXPERIMENTS.md); the macro is the builtin call.
+// ptr: any (const) object pointer, wave-uniform; bytes: the record length, below 2^31 (BUF_OOB).
+#define TG_BUF_RSRC(ptr, bytes) \
+  __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(static_cast<const void*>(ptr)), 0, (bytes), ::tg::BUF_RSRC_FLAGS)
+
+// The offset of an element that does not exist.  Contract: every record length built here is below 2 GiB (one operand
+// of one batch item; the launchers' shape checks keep tensors under that), so this offset -- and any offset that
+// wrapped below zero, e.g. a channel that belongs to the other source tensor -- is out of range for EVERY descriptor:
+// the load returns 0, the store is dropped.
+constexpr unsigned BUF_OOB = 0x80000000u;
+
+// Cache-policy (aux) bit sc1 of the buffer instructions on gfx940+: agent scope.  The access goes to / comes from the
+// memory side of the cache hierarchy instead of this CU's L1 and this XCD's non-coherent L2 copy.  Mandatory on EVERY
+// store of, and EVERY load of, data that another workgroup of the SAME launch produces or consumes: the chained
+// Winograd launch (tg_conv3x3_wino.hip), the row chain (tg_conv3x3_chain.hip) and the resident launch's ring exchange
+// (tg_conv3x3_wino_res.hip).  Data written by an earlier launch needs no bit (0): a kernel boundary makes it visible.
+constexpr int BUF_SC1 = 16;
+
+// T: a 4-, 8- or 16-byte trivially copyable type (float, f32x2, f32x4, u32x4, ...); voff: per-lane byte offset (VGPR),
+// soff: wave-uniform byte offset (SGPR) added to it; AUX: 0 or BUF_SC1.
+template <typename T, int AUX = 0>
+__device__ __forceinline__ T buf_ld(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff = 0) {
+  static_assert(__is_trivially_copyable(T) && (sizeof(T) == 4 || sizeof(T) == 8 || sizeof(T) == 16), "b32 / b64 / b128");
+  if constexpr (sizeof(T) == 4) return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, AUX));
+  else if constexpr (sizeof(T) == 8) return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, (int)soff, AUX));
+  else return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, AUX));
+}
+template <int AUX = 0, typename T>
+__device__ __forceinline__ void buf_st(T v, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff = 0) {
+  static_assert(__is_trivially_copyable(T) && (sizeof(T) == 4 || sizeof(T) == 8 || sizeof(T) == 16), "b32 / b64 / b128");
+  if constexpr (sizeof(T) == 4) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)voff, (int)soff, AUX);
+  else if constexpr (sizeof(T) == 8) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, (int)voff, (int)soff, AUX);
+  else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)voff, (int)soff, AUX);
+}
 
 // input-channel chunk streamed through LDS per K-step group
 constexpr int CK = 8;

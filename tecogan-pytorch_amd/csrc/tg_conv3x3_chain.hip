@@ -40,8 +40,6 @@ constexpr int RC_MAXL = 24;
 constexpr int RC_TW = 32, RC_PW = 34, RC_RS = 34;
 constexpr int RC_IN_FLOATS = 3 * 2 * RC_RS * 4;     // one 8-channel chunk of the patch: 3 rows x 2 halves x 34 slots x 4
 constexpr int RC_ITEMS = 3 * 2 * RC_PW;             // 204 16-byte items per chunk
-constexpr unsigned RC_OOB = 0x80000000u;
-constexpr int RC_SC1 = 16;                          // cache-policy bit of the buffer instructions on gfx940+: agent scope
 
 struct RCLayer {
   const float *x, *x2, *wpk, *bias, *res, *mask;
@@ -64,10 +62,6 @@ struct RowChainArgs {
 #else
 #define RC_STAMP(k) do { } while (0)
 #endif
-
-template <bool COH> __device__ __forceinline__ float rc_ld(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, COH ? RC_SC1 : 0));
-}
 
 // KG = K groups per workgroup (8 waves): 4 -> 2 oc halves of 32 (one workgroup per tile),
 //                                        8 -> 1 oc half (two workgroups per tile).
@@ -147,12 +141,10 @@ __global__ __launch_bounds__(512, 4) void conv3x3_rowchain_kernel(RowChainArgs a
     // ---- the input patch of every chunk -> LDS (layer 0 reads tensors of earlier launches:
     // ordinary loads; later layers read what other workgroups of THIS launch wrote: sc1)
     {
-      const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<float*>(L.x + (long long)n * L.x_ns), 0, L.c1 * hw * 4, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rs1 = TG_BUF_RSRC(L.x + (long long)n * L.x_ns, L.c1 * hw * 4);
       const bool dual = L.x2 != nullptr;
-      const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<float*>(dual ? L.x2 + (long long)n * L.x2_ns : L.x), 0,
-          dual ? (L.cin - L.c1) * hw * 4 : 0, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rs2 = TG_BUF_RSRC(
+          dual ? L.x2 + (long long)n * L.x2_ns : L.x, dual ? (L.cin - L.c1) * hw * 4 : 0);
       const int total = nchunk * RC_ITEMS;
       // all the loads of a batch of items are issued before the first LDS store (a loop of
       // load -> store iterations pays the memory latency once per iteration: 2.2 us per layer)
@@ -170,12 +162,12 @@ __global__ __launch_bounds__(512, 4) void conv3x3_rowchain_kernel(RowChainArgs a
             const int hf = rem2 / RC_PW, col = rem2 - hf * RC_PW;
             const int gy = y0 - 1 + r, px = x0 - 1 + col;
             const bool ok = q < total && gy >= 0 && gy < a.h && px >= 0 && px < a.w;
-            const unsigned base = ok ? (unsigned)(((ch * CK + 4 * hf) * hw + gy * a.w + px) * 4) : RC_OOB;
+            const unsigned base = ok ? (unsigned)(((ch * CK + 4 * hf) * hw + gy * a.w + px) * 4) : BUF_OOB;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               const unsigned o1 = base + (unsigned)j * plane;
-              float t = rc_ld<COH>(rs1, o1);
-              if (dual) t += rc_ld<COH>(rs2, o1 - (unsigned)L.c1 * plane);
+              float t = buf_ld<float, COH ? BUF_SC1 : 0>(rs1, o1);
+              if (dual) t += buf_ld<float, COH ? BUF_SC1 : 0>(rs2, o1 - (unsigned)L.c1 * plane);
               v[k][j] = t;
             }
           }
@@ -268,24 +260,22 @@ __global__ __launch_bounds__(512, 4) void conv3x3_rowchain_kernel(RowChainArgs a
           v[e] = mm[e] > 0.f ? q : 0.f;
         }
         float* yp = L.y + (long long)n * L.y_ns;
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(yp, 0, L.cout * hw * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ry = TG_BUF_RSRC(yp, L.cout * hw * 4);
         const unsigned yo = (unsigned)eoff * 4u;
         if (vec && ((reinterpret_cast<uintptr_t>(yp) & 15) == 0) && (hw % 4 == 0) && (L.y_ns % 4 == 0)) {
           if constexpr (PER == 4) {
-            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
             u32x4 d = {__builtin_bit_cast(unsigned, v[0]), __builtin_bit_cast(unsigned, v[1]),
                        __builtin_bit_cast(unsigned, v[2]), __builtin_bit_cast(unsigned, v[3])};
-            __builtin_amdgcn_raw_buffer_store_b128(d, ry, (int)yo, 0, RC_SC1);
+            buf_st<BUF_SC1>(d, ry, yo);
           } else {
-            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
             u32x2 d = {__builtin_bit_cast(unsigned, v[0]), __builtin_bit_cast(unsigned, v[1])};
-            __builtin_amdgcn_raw_buffer_store_b64(d, ry, (int)yo, 0, RC_SC1);
+            buf_st<BUF_SC1>(d, ry, yo);
           }
         } else {
 #pragma unroll
           for (int e = 0; e < PER; ++e)
             if (gx + e < a.w)
-              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[e]), ry, (int)(yo + 4u * e), 0, RC_SC1);
+              buf_st<BUF_SC1>(__builtin_bit_cast(unsigned, v[e]), ry, yo + 4u * e);
         }
       }
     }
@@ -391,12 +381,10 @@ __global__ __launch_bounds__(512, 4) void conv3x3_rowchain16_kernel(RowChainArgs
     RC_STAMP(1);
     // ---- the patch: (channel c, row r, column) -> LDS [c >> 3][r][c & 3][col][(c >> 2) & 1]
     {
-      const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<float*>(L.x + (long long)n * L.x_ns), 0, L.c1 * hw * 4, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rs1 = TG_BUF_RSRC(L.x + (long long)n * L.x_ns, L.c1 * hw * 4);
       const bool dual = L.x2 != nullptr;
-      const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<float*>(dual ? L.x2 + (long long)n * L.x2_ns : L.x), 0,
-          dual ? (L.cin - L.c1) * hw * 4 : 0, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rs2 = TG_BUF_RSRC(
+          dual ? L.x2 + (long long)n * L.x2_ns : L.x, dual ? (L.cin - L.c1) * hw * 4 : 0);
       const int total = nchunk * 8 * 3 * R16_PW;
       auto stage = [&](auto coh) {
         constexpr bool COH = decltype(coh)::value;
@@ -409,9 +397,9 @@ __global__ __launch_bounds__(512, 4) void conv3x3_rowchain16_kernel(RowChainArgs
           const int r = t2 % 3, c = t2 / 3;
           const int gy = y0 - 1 + r, px = x0 - 1 + col;
           const bool ok = q < total && gy >= 0 && gy < a.h && px >= 0 && px < a.w;
-          const unsigned o1 = ok ? (unsigned)((c * hw + gy * a.w + px) * 4) : RC_OOB;
-          float t = rc_ld<COH>(rs1, o1);
-          if (dual) t += rc_ld<COH>(rs2, o1 - (unsigned)L.c1 * plane);
+          const unsigned o1 = ok ? (unsigned)((c * hw + gy * a.w + px) * 4) : BUF_OOB;
+          float t = buf_ld<float, COH ? BUF_SC1 : 0>(rs1, o1);
+          if (dual) t += buf_ld<float, COH ? BUF_SC1 : 0>(rs2, o1 - (unsigned)L.c1 * plane);
           v[k] = t;
         }
 #pragma unroll
@@ -463,8 +451,8 @@ __global__ __launch_bounds__(512, 4) void conv3x3_rowchain16_kernel(RowChainArgs
         q = (q >= 0.f ? q : q * slope + 0.f) + rr;
         q = mm > 0.f ? q : 0.f;
         float* yp = L.y + (long long)n * L.y_ns;
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(yp, 0, L.cout * hw * 4, 0x00020000);
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, q), ry, (int)((unsigned)eoff * 4u), 0, RC_SC1);
+        const __amdgpu_buffer_rsrc_t ry = TG_BUF_RSRC(yp, L.cout * hw * 4);
+        buf_st<BUF_SC1>(__builtin_bit_cast(unsigned, q), ry, (unsigned)eoff * 4u);
       }
     }
     RC_STAMP(4);

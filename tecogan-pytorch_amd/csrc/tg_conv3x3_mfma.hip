@@ -92,12 +92,6 @@ __global__ void pack3x3_kernel(const float* __restrict__ w, float* __restrict__ 
   }
 }
 
-__device__ __forceinline__ float buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, 0, 0));
-}
-
-constexpr unsigned OOB = 0x80000000u;   // >= any num_records we build (tensors < 2 GiB per item)
-
 // Tap subsets of the embedded strided convolutions.  A Conv2d(k4, s2, p1) on x equals a 3x3
 // conv on space_to_depth(x, 2) whose sub-pixel phase (py, px) only owns the kernel rows
 // {ky : 2*oy - 1 + ky = 2*(oy + ty - 1) + py}: py = 1 -> ty in {0, 1}, py = 0 -> ty in {1, 2}
@@ -208,7 +202,7 @@ __global__ __launch_bounds__(WM* WN* KS * 64) void conv3x3_mfma_kernel(Conv3x3Ar
   const int ch_end = (int)((long long)(ks + 1) * a.nchunk / a.ksplit);
 
   // ---- staging assignment: item q = (row r, half hf, col) -------------------
-  unsigned voff[I_PER_T];     // byte offset of channel (4*hf) at this pixel, or OOB
+  unsigned voff[I_PER_T];     // byte offset of channel (4*hf) at this pixel, or BUF_OOB
   int lds_item[I_PER_T];      // float index of the 16-byte LDS slot, -1 if none
 #pragma unroll
   for (int i = 0; i < I_PER_T; ++i) {
@@ -217,14 +211,12 @@ __global__ __launch_bounds__(WM* WN* KS * 64) void conv3x3_mfma_kernel(Conv3x3Ar
     int hf = rem / PW, col = rem - hf * PW;
     int gy = y0 - 1 + r, gx = x0 - 1 + col;
     bool ok = q < IN_ITEMS && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w;
-    voff[i] = ok ? (unsigned)((4 * hf * hw + gy * a.w + gx) * 4) : OOB;
+    voff[i] = ok ? (unsigned)((4 * hf * hw + gy * a.w + gx) * 4) : BUF_OOB;
     lds_item[i] = q < IN_ITEMS ? ((r * 2 + hf) * RS + col) * 4 : -1;
   }
-  const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x + (long long)n * a.x_ns), 0, a.c1 * hw * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(DUAL ? a.x2 + (long long)n * a.x2_ns : a.x), 0,
-      DUAL ? (a.cin - a.c1) * hw * 4 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs1 = TG_BUF_RSRC(a.x + (long long)n * a.x_ns, a.c1 * hw * 4);
+  const __amdgpu_buffer_rsrc_t rs2 = TG_BUF_RSRC(
+      DUAL ? a.x2 + (long long)n * a.x2_ns : a.x, DUAL ? (a.cin - a.c1) * hw * 4 : 0);
   const unsigned plane = (unsigned)hw * 4u;
 
   const f32x4* wsrc =
@@ -244,8 +236,8 @@ __global__ __launch_bounds__(WM* WN* KS * 64) void conv3x3_mfma_kernel(Conv3x3Ar
           // channel ch*8 + 4*hf + j.  Beyond c1 (or cin) the offset is past
           // num_records and the load returns 0; the second source then supplies it.
           unsigned o1 = voff[i] + cbase + (unsigned)j * plane;
-          float v = buf_load(rs1, o1);
-          if (DUAL) v += buf_load(rs2, o1 - (unsigned)a.c1 * plane);
+          float v = buf_ld<float>(rs1, o1);
+          if (DUAL) v += buf_ld<float>(rs2, o1 - (unsigned)a.c1 * plane);
           rin[k][i][j] = v;
         }
       }
@@ -506,11 +498,9 @@ __global__ __launch_bounds__(512) void conv3x3_oneshot_kernel(Conv3x3Args a) {
   const int hw = a.h * a.w;
   const unsigned plane = (unsigned)hw * 4u;
   const int nchunk = a.nchunk;
-  const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x + (long long)n * a.x_ns), 0, a.c1 * hw * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(DUAL ? a.x2 + (long long)n * a.x2_ns : a.x), 0,
-      DUAL ? (a.cin - a.c1) * hw * 4 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs1 = TG_BUF_RSRC(a.x + (long long)n * a.x_ns, a.c1 * hw * 4);
+  const __amdgpu_buffer_rsrc_t rs2 = TG_BUF_RSRC(
+      DUAL ? a.x2 + (long long)n * a.x2_ns : a.x, DUAL ? (a.cin - a.c1) * hw * 4 : 0);
 
   // ---- weights of this wave's chunks -> registers (issued first: longest latency)
   const int cpw = (nchunk + KG - 1) / KG;              // chunks per K group (<= 2)
@@ -544,12 +534,12 @@ __global__ __launch_bounds__(512) void conv3x3_oneshot_kernel(Conv3x3Args a) {
       const int hf = rem2 / PW, col = rem2 - hf * PW;
       const int gy = y0 - 1 + r, gx = x0 - 1 + col;
       const bool ok = q < total && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w;
-      const unsigned base = ok ? (unsigned)(((ch * CK + 4 * hf) * hw + gy * a.w + gx) * 4) : OOB;
+      const unsigned base = ok ? (unsigned)(((ch * CK + 4 * hf) * hw + gy * a.w + gx) * 4) : BUF_OOB;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const unsigned o1 = base + (unsigned)j * plane;
-        float t = buf_load(rs1, o1);
-        if (DUAL) t += buf_load(rs2, o1 - (unsigned)a.c1 * plane);
+        float t = buf_ld<float>(rs1, o1);
+        if (DUAL) t += buf_ld<float>(rs2, o1 - (unsigned)a.c1 * plane);
         v[k][j] = t;
       }
     }
@@ -664,8 +654,7 @@ __global__ __launch_bounds__(512) void conv3x3s2_oneshot_kernel(Conv3x3Args a) {
   const int ih = 2 * a.h, iw = 2 * a.w, ihw = ih * iw; // input plane
   const unsigned plane = (unsigned)ihw * 4u;
   const int nchunk = a.nchunk;
-  const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x + (long long)n * a.x_ns), 0, a.cin * ihw * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs1 = TG_BUF_RSRC(a.x + (long long)n * a.x_ns, a.cin * ihw * 4);
   const int cpw = (nchunk + KG - 1) / KG;
   const int c0 = wk * cpw;
   const f32x4* wlane = reinterpret_cast<const f32x4*>(a.wpk) + (lh * OCB + wn * 32 + ll);
@@ -694,9 +683,9 @@ __global__ __launch_bounds__(512) void conv3x3s2_oneshot_kernel(Conv3x3Args a) {
       const int hf = rem2 / RS2, col = rem2 - hf * RS2;
       const int gy = 2 * y0 - 1 + r, gx = 2 * x0 - 1 + col;
       const bool ok = (k0 + k) < MAXQ && q < total && gy >= 0 && gy < ih && gx >= 0 && gx < iw;
-      const unsigned base = ok ? (unsigned)(((ch * CK + 4 * hf) * ihw + gy * iw + gx) * 4) : OOB;
+      const unsigned base = ok ? (unsigned)(((ch * CK + 4 * hf) * ihw + gy * iw + gx) * 4) : BUF_OOB;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) v[k][j] = buf_load(rs1, base + (unsigned)j * plane);
+      for (int j = 0; j < 4; ++j) v[k][j] = buf_ld<float>(rs1, base + (unsigned)j * plane);
     }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {

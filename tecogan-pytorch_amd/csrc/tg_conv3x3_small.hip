@@ -204,7 +204,6 @@ constexpr int V_RS = 76;                // LDS row stride in floats (19 slots: o
 constexpr int V_CK = 4;
 constexpr int V_ITEMS = V_CK * S_PH * V_Q;          // 1296 float4 per chunk
 constexpr int V_PER_T = (V_ITEMS + 255) / 256;      // 6
-constexpr unsigned V_OOB = 0x80000000u;
 
 template <int COUT>
 __global__ __launch_bounds__(256) void conv3x3_small_v2_kernel(SmallArgs a) {
@@ -227,8 +226,7 @@ __global__ __launch_bounds__(256) void conv3x3_small_v2_kernel(SmallArgs a) {
   const int n = b / a.tiles_y;
   const int x0 = tx * S_TW, y0 = ty * S_TH;
   const int hw = a.h * a.w;
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x + (long long)n * a.x_ns), 0, a.cin * hw * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc = TG_BUF_RSRC(a.x + (long long)n * a.x_ns, a.cin * hw * 4);
 
   // per-thread staging slots (fixed for the whole kernel)
   unsigned voff[V_PER_T];
@@ -240,7 +238,7 @@ __global__ __launch_bounds__(256) void conv3x3_small_v2_kernel(SmallArgs a) {
     int r = rem / V_Q, q = rem - r * V_Q;
     int gy = y0 - 1 + r, gx = x0 - 4 + 4 * q;
     bool ok = idx < V_ITEMS && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w;
-    voff[i] = ok ? (unsigned)((c * hw + gy * a.w + gx) * 4) : V_OOB;
+    voff[i] = ok ? (unsigned)((c * hw + gy * a.w + gx) * 4) : BUF_OOB;
     lds_off[i] = idx < V_ITEMS ? (c * S_PH + r) * V_RS + 4 * q : -1;
   }
   const unsigned plane = (unsigned)hw * 4u;
@@ -252,8 +250,7 @@ __global__ __launch_bounds__(256) void conv3x3_small_v2_kernel(SmallArgs a) {
 #pragma unroll
     for (int i = 0; i < V_PER_T; ++i) {
       // channels past cin fall beyond num_records and read as 0
-      rin[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                             rsrc, (int)(voff[i] + (unsigned)c0 * plane), 0, 0));
+      rin[i] = buf_ld<f32x4>(rsrc, voff[i] + (unsigned)c0 * plane);
     }
   };
   auto store_chunk = [&](const f32x4 (&rin)[V_PER_T], int buf) {
@@ -384,8 +381,7 @@ __global__ __launch_bounds__(256) void conv3x3_small_ks_kernel(SmallArgs a) {
   const int n = b / a.tiles_y;
   const int x0 = tx * S_TW, y0 = ty * K_TH;
   const int hw = a.h * a.w;
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x + (long long)n * a.x_ns), 0, a.cin * hw * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc = TG_BUF_RSRC(a.x + (long long)n * a.x_ns, a.cin * hw * 4);
   unsigned voff[K_PER_T];
   int lds_off[K_PER_T];
 #pragma unroll
@@ -395,7 +391,7 @@ __global__ __launch_bounds__(256) void conv3x3_small_ks_kernel(SmallArgs a) {
     const int r = rem / V_Q, q = rem - r * V_Q;
     const int gy = y0 - 1 + r, gx = x0 - 4 + 4 * q;
     const bool ok = idx < K_ITEMS && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w;
-    voff[i] = ok ? (unsigned)((c * hw + gy * a.w + gx) * 4) : V_OOB;
+    voff[i] = ok ? (unsigned)((c * hw + gy * a.w + gx) * 4) : BUF_OOB;
     lds_off[i] = idx < K_ITEMS ? (c * K_PH + r) * V_RS + 4 * q : -1;
   }
   const unsigned plane = (unsigned)hw * 4u;
@@ -404,8 +400,7 @@ __global__ __launch_bounds__(256) void conv3x3_small_ks_kernel(SmallArgs a) {
   auto load_chunk = [&](f32x4 (&rin)[K_PER_T], int ch) {
 #pragma unroll
     for (int i = 0; i < K_PER_T; ++i)       // channels past cin fall beyond num_records and read as 0
-      rin[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                             rsrc, (int)(voff[i] + (unsigned)(ch * V_CK) * plane), 0, 0));
+      rin[i] = buf_ld<f32x4>(rsrc, voff[i] + (unsigned)(ch * V_CK) * plane);
   };
   auto store_chunk = [&](const f32x4 (&rin)[K_PER_T]) {
 #pragma unroll
@@ -519,8 +514,7 @@ __global__ __launch_bounds__(256) void conv3x3_fewin_kernel(SmallArgs a) {
   const int n = b / a.tiles_y;
   const int x0 = tx * S_TW, y0 = ty * K_TH;
   const int hw = a.h * a.w;
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x + (long long)n * a.x_ns), 0, CIN * hw * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc = TG_BUF_RSRC(a.x + (long long)n * a.x_ns, CIN * hw * 4);
   constexpr int ITEMS = CIN * K_PH * V_Q;                  // <= 432 float4
 #pragma unroll
   for (int i = 0; i < (ITEMS + 255) / 256; ++i) {
@@ -529,8 +523,7 @@ __global__ __launch_bounds__(256) void conv3x3_fewin_kernel(SmallArgs a) {
     const int r = rem / V_Q, q = rem - r * V_Q;
     const int gy = y0 - 1 + r, gx = x0 - 4 + 4 * q;
     const bool ok = idx < ITEMS && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w;
-    const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                  rsrc, ok ? (int)((c * hw + gy * a.w + gx) * 4) : (int)V_OOB, 0, 0));
+    const f32x4 v = buf_ld<f32x4>(rsrc, ok ? (int)((c * hw + gy * a.w + gx) * 4) : (int)BUF_OOB);
     if (idx < ITEMS) *reinterpret_cast<f32x4*>(&s_in[c][r][4 * q]) = v;
   }
   __syncthreads();

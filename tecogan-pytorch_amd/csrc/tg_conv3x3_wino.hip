@@ -120,7 +120,6 @@ template <bool COH> __device__ __forceinline__ void st1(float* p, float v) {
 // One workgroup's tile.  COH (chained launches, below): activations move with agent-scope (sc1)
 // loads / stores -- they bypass the XCD's non-coherent L2 copy -- because producer and consumer
 // workgroups of consecutive layers run in the same launch, possibly behind different L2s.
-constexpr int AUX_SC1 = 16;       // cache-policy bit of the buffer instructions on gfx940+
 
 // TR: tile rows of the workgroup's 16 Winograd tiles (TR x 16/TR tiles = 2 TR x 32/TR pixels).  1: one tile row of 32
 // pixels (the form everything was tuned on); 2 / 4: 4 x 16 / 8 x 8 pixels for maps narrower than a 32-pixel tile
@@ -170,10 +169,9 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
   // ---- raw patch staging: element e = t + 256 k = (ic, row, col) of the 16 x 4 x 34 patch ------
   constexpr int RAW_ELEMS = W_ICS * G::PE;
   constexpr int RAW_PER_T = (RAW_ELEMS + 255) / 256;   // 9
-  // byte offset of the element inside a channel plane, or OOB: the buffer bounds check then
+  // byte offset of the element inside a channel plane, or BUF_OOB: the buffer bounds check then
   // returns 0 for the zero padding, for channels past cin (K padded to a multiple of 16) and
   // for the channels that belong to the other source tensor
-  constexpr unsigned OOB = 0x80000000u;
   unsigned roff[RAW_PER_T];
 #pragma unroll
   for (int k = 0; k < RAW_PER_T; ++k) {
@@ -193,14 +191,12 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
                     : W_UP2_OOB;
     } else {
       roff[k] = (e < RAW_ELEMS && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w)
-                    ? (unsigned)(sc * hw + gy * a.w + gx) * 4u : OOB;
+                    ? (unsigned)(sc * hw + gy * a.w + gx) * 4u : BUF_OOB;
     }
   }
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x + (size_t)n * a.x_ns), 0, (unsigned)a.c1 * shw * 4u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rx2 = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x2 ? a.x2 + (size_t)n * a.x2_ns : a.x), 0,
-      a.x2 ? (unsigned)(a.cin - a.c1) * hw * 4u : 0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = TG_BUF_RSRC(a.x + (size_t)n * a.x_ns, (unsigned)a.c1 * shw * 4u);
+  const __amdgpu_buffer_rsrc_t rx2 = TG_BUF_RSRC(
+      a.x2 ? a.x2 + (size_t)n * a.x2_ns : a.x, a.x2 ? (unsigned)(a.cin - a.c1) * hw * 4u : 0u);
   const bool dual = !UP2 && a.x2 != nullptr;
   auto load_raw = [&](int s, float (&reg)[RAW_PER_T]) {
     const unsigned so = (unsigned)(s * ICS) * shw * 4u;
@@ -215,7 +211,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
         const unsigned o00 = ((wd >> 5) & ~3u) + so, dxb = (wd >> 3) & 4u;
         const unsigned o10 = o00 + ((wd >> 6) & 1u) * ws4;
         auto ld = [&](unsigned o) {
-          return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, (int)o, 0, COH ? AUX_SC1 : 0));
+          return buf_ld<float, COH ? BUF_SC1 : 0>(rx, o);
         };
         const float v00 = ld(o00), v01 = ld(o00 + dxb), v10 = ld(o10), v11 = ld(o10 + dxb);
         const float ly1 = 0.25f * (float)((wd >> 3) & 3u), lx1 = 0.25f * (float)((wd >> 1) & 3u);
@@ -225,10 +221,9 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& a, int tx, int ty, int
     }
 #pragma unroll
     for (int k = 0; k < RAW_PER_T; ++k) {
-      float v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, (int)(roff[k] + so), 0, COH ? AUX_SC1 : 0));
+      float v = buf_ld<float, COH ? BUF_SC1 : 0>(rx, roff[k] + so);
       if (dual)   // offsets below c1 wrap to > 2^31 and read 0
-        v += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                 rx2, (int)(roff[k] + so - (unsigned)a.c1 * hw * 4u), 0, COH ? AUX_SC1 : 0));
+        v += buf_ld<float, COH ? BUF_SC1 : 0>(rx2, roff[k] + so - (unsigned)a.c1 * hw * 4u);
       reg[k] = v;
     }
   };

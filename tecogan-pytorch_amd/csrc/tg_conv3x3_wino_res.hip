@@ -61,7 +61,6 @@ constexpr int WR_THREADS = 768;                   // 12 waves: 3 per SIMD
 constexpr int WR_MAXL = 24;
 constexpr int WT_NP = 25;                         // the tail's products per tile and K step (WZ_NP of tg_convt3x3s2_wino.hip)
 constexpr int WR_SLOTS = 64;                      // published ring pixels of a block: top 24, bottom 24, left 8, right 8
-constexpr int WR_SC1 = 16;                        // agent-scope cache policy bit of the buffer instructions
 constexpr int WR_POLL_SLEEP = 2;                  // s_sleep units (64 cycles) between two polls of the ring
 constexpr int WR_ACT_FLOATS = 2 * WR_NC * WR_CS;   // the two activation buffers: 147 456 bytes
 constexpr int WR_BIAS_OFF = WR_ACT_FLOATS;          // [layer][64] biases (read once per launch)
@@ -77,7 +76,6 @@ __constant__ unsigned char WR_TILE[48] = {
     2, 8, 16, 23, 35, 36, 37, 38, 40, 41, 42, 43, 44, 45, 46, 47,
     17, 18, 19, 20, 21, 22, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34};
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct WResLayer {
   const float* u;      // tg_pack_conv3x3_wino form
@@ -131,11 +129,9 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
   // every load of a batch is in flight before the first LDS store)
   {
     constexpr int WIN = (WR_BH + 2) * (WR_BW + 2);       // 260 pixels per channel
-    constexpr unsigned OOB = 0x80000000u;
     const int total = a.cin0 * WIN;
-    const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, (unsigned)a.c1 * hw * 4u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.x2 ? a.x2 : a.x), 0, a.x2 ? (unsigned)(a.cin0 - a.c1) * hw * 4u : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r1 = TG_BUF_RSRC(a.x, (unsigned)a.c1 * hw * 4u);
+    const __amdgpu_buffer_rsrc_t r2 = TG_BUF_RSRC(a.x2 ? a.x2 : a.x, a.x2 ? (unsigned)(a.cin0 - a.c1) * hw * 4u : 0u);
     constexpr int BATCH = 11;
     for (int e0 = 0; e0 < total; e0 += BATCH * WR_THREADS) {
       float v[BATCH];
@@ -147,10 +143,10 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
         const int gy = Y0 - 1 + r, gx = X0 - 1 + c;
         const bool in = e < total && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w;
         const unsigned px = (unsigned)(gy * a.w + gx) * 4u;
-        const unsigned o1 = (in && ic < a.c1) ? (unsigned)ic * hw * 4u + px : OOB;
-        const unsigned o2 = (in && ic >= a.c1) ? (unsigned)(ic - a.c1) * hw * 4u + px : OOB;
-        const float v1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r1, (int)o1, 0, 0));
-        const float v2 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r2, (int)o2, 0, 0));
+        const unsigned o1 = (in && ic < a.c1) ? (unsigned)ic * hw * 4u + px : BUF_OOB;
+        const unsigned o2 = (in && ic >= a.c1) ? (unsigned)(ic - a.c1) * hw * 4u + px : BUF_OOB;
+        const float v1 = buf_ld<float>(r1, o1);
+        const float v2 = buf_ld<float>(r2, o2);
         v[k] = ic < a.c1 ? v1 : v2;
         lo[k] = e < total ? ic * WR_CS + r * WR_RS + c : -1;
       }
@@ -172,8 +168,7 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
   const int gy0 = Y0 + 2 * ty, gx0 = X0 + 2 * tx;               // image position of the tile
   const bool live = gy0 < a.h && gx0 < a.w;                     // h, w even: a tile is inside or outside as a whole
   const bool e_top = ty == 0, e_bot = ty == WR_TH - 1, e_lft = tx == 0, e_rgt = tx == WR_TW - 1;
-  const __amdgpu_buffer_rsrc_t rxb = __builtin_amdgcn_make_buffer_rsrc(
-      a.xbuf, 0, (unsigned)(2u * nwg * WR_SLOTS * WR_NC * 8u), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rxb = TG_BUF_RSRC(a.xbuf, (unsigned)(2u * nwg * WR_SLOTS * WR_NC * 8u));
 
   const size_t ulane = (size_t)(q * 4) * 64 + l;               // this lane's 16 bytes inside a K step's block
   constexpr size_t USTEP = (size_t)4 * 4 * 64;                  // f32x4 per K step (64 output channels)
@@ -372,8 +367,8 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
           const u32x4 d0 = {__builtin_bit_cast(unsigned, v[0][i][j]), tag, __builtin_bit_cast(unsigned, v[1][i][j]), tag};
           const u32x4 d1 = {__builtin_bit_cast(unsigned, v[2][i][j]), tag, __builtin_bit_cast(unsigned, v[3][i][j]), tag};
           const unsigned o = pb + (unsigned)slot * (WR_NC / 2 * 16u);
-          __builtin_amdgcn_raw_buffer_store_b128(d0, rxb, (int)o, 0, WR_SC1);
-          __builtin_amdgcn_raw_buffer_store_b128(d1, rxb, (int)(o + 16u), 0, WR_SC1);
+          buf_st<BUF_SC1>(d0, rxb, o);
+          buf_st<BUF_SC1>(d1, rxb, o + 16u);
         };
         if (e_top) { pub(2 * tx, 0, 0); pub(2 * tx + 1, 0, 1); }
         if (e_bot) { pub(WR_BW + 2 * tx, 1, 0); pub(WR_BW + 2 * tx + 1, 1, 1); }
@@ -441,7 +436,7 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
 #pragma unroll
         for (int k = 0; k < PER_T; ++k)
           if (want_mask & (1u << k)) {
-            const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(rxb, (int)off[k], 0, WR_SC1);
+            const u32x4 q = buf_ld<u32x4, BUF_SC1>(rxb, off[k]);
             q0[k] = q[0]; q1[k] = q[1]; q2[k] = q[2]; q3[k] = q[3];
           }
         const unsigned before = pend;

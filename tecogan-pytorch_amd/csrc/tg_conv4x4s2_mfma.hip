@@ -22,7 +22,6 @@
 
 namespace tg {
 
-constexpr unsigned C4_OOB = 0x80000000u;
 constexpr int C4_CK = 4;      // input channels per chunk (forward): two K steps of v_mfma_f32_32x32x2_f32
 constexpr int C4_WCH = 16 * 2 * 64 * 2;   // packed weight floats per (64-oc group, chunk): [tap][ocb][lane][ks]
 
@@ -49,10 +48,6 @@ __global__ void conv4_pack_fwd_kernel(const float* __restrict__ w, float* __rest
     const int oc = 64 * ocg + 32 * ocb + (lane & 31), c = C4_CK * chunk + 2 * ks + (lane >> 5);
     out[i] = w[((size_t)oc * ci + c) * 16 + tap];
   }
-}
-
-__device__ __forceinline__ float c4_load(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, 0, 0));
 }
 
 template <int TXH>
@@ -91,11 +86,10 @@ __global__ __launch_bounds__(256) void conv4x4s2_mfma_kernel(Conv4Args a) {
     const int r = rem / PC, c = rem - r * PC;
     const int gy = 2 * oy0 - 1 + r, gx = 2 * ox0 - 1 + c;
     const bool ok = q < ITEMS && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w;
-    voff[i] = ok ? (unsigned)((k * hw + gy * a.w + gx) * 4) : C4_OOB;
+    voff[i] = ok ? (unsigned)((k * hw + gy * a.w + gx) * 4) : BUF_OOB;
     lds_item[i] = q < ITEMS ? ((r * 2 + k) * 2 + (c & 1)) * CPS + (c >> 1) * 2 : -1;
   }
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x + (long long)n * a.x_ns), 0, (unsigned)(a.ci * hw * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs = TG_BUF_RSRC(a.x + (long long)n * a.x_ns, (unsigned)(a.ci * hw * 4));
   const unsigned plane = (unsigned)hw * 4u;
   const f32x4* wsrc = reinterpret_cast<const f32x4*>(a.wpk + (size_t)ocg * a.nchunk * C4_WCH);
 
@@ -105,8 +99,8 @@ __global__ __launch_bounds__(256) void conv4x4s2_mfma_kernel(Conv4Args a) {
     const unsigned cbase = (unsigned)(ch * C4_CK) * plane;
 #pragma unroll
     for (int i = 0; i < I_PER_T; ++i) {
-      rin[i].x = c4_load(rs, voff[i] + cbase);                 // channel 4 ch + k      (K step 0)
-      rin[i].y = c4_load(rs, voff[i] + cbase + 2u * plane);    // channel 4 ch + 2 + k  (K step 1)
+      rin[i].x = buf_ld<float>(rs, voff[i] + cbase);                 // channel 4 ch + k      (K step 0)
+      rin[i].y = buf_ld<float>(rs, voff[i] + cbase + 2u * plane);    // channel 4 ch + 2 + k  (K step 1)
     }
     const f32x4* ws = wsrc + (size_t)ch * (C4_WCH / 4);
 #pragma unroll
@@ -242,11 +236,10 @@ __global__ __launch_bounds__(256) void conv4x4s2_dgrad_mfma_kernel(Conv4DgradArg
     const int r = rem / D4_PC, c = rem - r * D4_PC;
     const int gy = oyb + r, gx = oxb + c;
     const bool ok = q < ITEMS && gy >= 0 && gy < oh && gx >= 0 && gx < ow;
-    voff[i] = ok ? (unsigned)((k * ohw + gy * ow + gx) * 4) : C4_OOB;
+    voff[i] = ok ? (unsigned)((k * ohw + gy * ow + gx) * 4) : BUF_OOB;
     lds_item[i] = q < ITEMS ? (r * 2 + k) * D4_RS + c * 4 : -1;
   }
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.g + (long long)n * a.g_ns), 0, (unsigned)(a.co * ohw * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs = TG_BUF_RSRC(a.g + (long long)n * a.g_ns, (unsigned)(a.co * ohw * 4));
   const unsigned plane = (unsigned)ohw * 4u;
   const f32x4* wsrc = reinterpret_cast<const f32x4*>(a.wpk + (size_t)cig * a.nchunk * D4_WCH);
 
@@ -257,7 +250,7 @@ __global__ __launch_bounds__(256) void conv4x4s2_dgrad_mfma_kernel(Conv4DgradArg
 #pragma unroll
     for (int i = 0; i < I_PER_T; ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) rin[i][j] = c4_load(rs, voff[i] + cbase + (unsigned)(2 * j) * plane);
+      for (int j = 0; j < 4; ++j) rin[i][j] = buf_ld<float>(rs, voff[i] + cbase + (unsigned)(2 * j) * plane);
     const f32x4* ws = wsrc + (size_t)ch * (D4_WCH / 4);
 #pragma unroll
     for (int i = 0; i < W_PER_T; ++i) rw[i] = ws[tid + i * 256];
@@ -333,23 +326,19 @@ __global__ __launch_bounds__(256) void conv4x4s2_dgrad_mfma_kernel(Conv4DgradArg
   const int ix = 64 * tx + 2 * ln;
   const unsigned hw4 = (unsigned)(a.h * a.w) * 4u;
   const bool live = iy < a.h && ix < a.w;
-  const unsigned vo = live ? (unsigned)(iy * a.w + ix) * 4u + (unsigned)(4 * lk) * hw4 : C4_OOB;
+  const unsigned vo = live ? (unsigned)(iy * a.w + ix) * 4u + (unsigned)(4 * lk) * hw4 : BUF_OOB;
   const unsigned recs = 64u * hw4;
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-  typedef float c4f2 __attribute__((ext_vector_type(2)));
-  c4f2 yv[2][16];
+  f32x2 yv[2][16];
   if constexpr (ACT) {
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.act_y + (long long)n * a.act_ns + (size_t)(64 * cig) * a.h * a.w), 0, recs, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ra = TG_BUF_RSRC(
+        a.act_y + (long long)n * a.act_ns + (size_t)(64 * cig) * a.h * a.w, recs);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        yv[t][r] = __builtin_bit_cast(c4f2, __builtin_amdgcn_raw_buffer_load_b64(
-            ra, (int)vo, (int)((unsigned)(32 * t + 8 * (r >> 2) + (r & 3)) * hw4), 0));
+        yv[t][r] = buf_ld<f32x2>(ra, vo, (unsigned)(32 * t + 8 * (r >> 2) + (r & 3)) * hw4);
   }
-  const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
-      a.dx + (long long)n * a.dx_ns + (size_t)(64 * cig) * a.h * a.w, 0, recs, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rd = TG_BUF_RSRC(a.dx + (long long)n * a.dx_ns + (size_t)(64 * cig) * a.h * a.w, recs);
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -360,7 +349,7 @@ __global__ __launch_bounds__(256) void conv4x4s2_dgrad_mfma_kernel(Conv4DgradArg
         v1 = yv[t][r].y > 0.f ? v1 : v1 * a.slope;
       }
       const u32x2 d = {__builtin_bit_cast(unsigned, v0), __builtin_bit_cast(unsigned, v1)};
-      __builtin_amdgcn_raw_buffer_store_b64(d, rd, (int)vo, (int)((unsigned)(32 * t + 8 * (r >> 2) + (r & 3)) * hw4), 0);
+      buf_st(d, rd, vo, (unsigned)(32 * t + 8 * (r >> 2) + (r & 3)) * hw4);
     }
 }
 
@@ -419,11 +408,10 @@ __global__ __launch_bounds__(256) void conv4x4s2_small_kernel(Conv4SmallArgs a) 
     const int r = rem / PC, c = rem - r * PC;
     const int gy = 2 * oy0 - 1 + r, gx = c - 1;
     const bool ok = q < ITEMS && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w;
-    voff[i] = ok ? (unsigned)((k * hw + gy * a.w + gx) * 4) : C4_OOB;
+    voff[i] = ok ? (unsigned)((k * hw + gy * a.w + gx) * 4) : BUF_OOB;
     lds_item[i] = q < ITEMS ? ((r * 2 + k) * 2 + (c & 1)) * CPS + (c >> 1) * 2 : -1;
   }
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x + (long long)n * a.x_ns), 0, (unsigned)(a.ci * hw * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs = TG_BUF_RSRC(a.x + (long long)n * a.x_ns, (unsigned)(a.ci * hw * 4));
   const unsigned plane = (unsigned)hw * 4u;
   const f32x4* wsrc = reinterpret_cast<const f32x4*>(a.wpk + (size_t)ocg * a.nchunk * C4_WCH);
 
@@ -433,8 +421,8 @@ __global__ __launch_bounds__(256) void conv4x4s2_small_kernel(Conv4SmallArgs a) 
     const unsigned cbase = (unsigned)(ch * C4_CK) * plane;
 #pragma unroll
     for (int i = 0; i < I_PER_T; ++i) {
-      rin[i].x = c4_load(rs, voff[i] + cbase);
-      rin[i].y = c4_load(rs, voff[i] + cbase + 2u * plane);
+      rin[i].x = buf_ld<float>(rs, voff[i] + cbase);
+      rin[i].y = buf_ld<float>(rs, voff[i] + cbase + 2u * plane);
     }
     const f32x4* ws = wsrc + (size_t)ch * (C4_WCH / 4);
 #pragma unroll
@@ -554,11 +542,10 @@ __global__ __launch_bounds__(256) void conv4x4s2_dgrad_small_kernel(Conv4DgradSm
     const int r = rem / PCW, c = rem - r * PCW;
     const int gy = oyb + r, gx = c - 1;
     const bool ok = q < ITEMS && gy >= 0 && gy < oh && gx >= 0 && gx < ow;
-    voff = ok ? (unsigned)((k * ohw + gy * ow + gx) * 4) : C4_OOB;
+    voff = ok ? (unsigned)((k * ohw + gy * ow + gx) * 4) : BUF_OOB;
     lds_item = q < ITEMS ? (r * 2 + k) * RS + c * 4 : -1;
   }
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.g + (long long)n * a.g_ns), 0, (unsigned)(a.co * ohw * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs = TG_BUF_RSRC(a.g + (long long)n * a.g_ns, (unsigned)(a.co * ohw * 4));
   const unsigned plane = (unsigned)ohw * 4u;
   const f32x4* wsrc = reinterpret_cast<const f32x4*>(a.wpk + (size_t)cig * a.nchunk * D4_WCH);
 
@@ -567,7 +554,7 @@ __global__ __launch_bounds__(256) void conv4x4s2_dgrad_small_kernel(Conv4DgradSm
   auto load_chunk = [&](int ch) {
     const unsigned cbase = (unsigned)(ch * D4_CK) * plane;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) rin[j] = c4_load(rs, voff + cbase + (unsigned)(2 * j) * plane);
+    for (int j = 0; j < 4; ++j) rin[j] = buf_ld<float>(rs, voff + cbase + (unsigned)(2 * j) * plane);
     const f32x4* ws = wsrc + (size_t)ch * (D4_WCH / 4);
 #pragma unroll
     for (int i = 0; i < W_PER_T; ++i) rw[i] = ws[tid + i * 256];
@@ -632,17 +619,16 @@ __global__ __launch_bounds__(256) void conv4x4s2_dgrad_small_kernel(Conv4DgradSm
 
   const unsigned hw4 = (unsigned)(a.h * a.w) * 4u;
   const bool live = iy < a.h;
-  const unsigned vo = live ? (unsigned)(iy * a.w + 2 * jl) * 4u + (unsigned)(4 * lk) * hw4 : C4_OOB;
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-  const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
-      a.dx + (long long)ks * a.part_ss + (long long)n * a.dx_ns + (size_t)(64 * cig) * a.h * a.w, 0, 64u * hw4, 0x00020000);
+  const unsigned vo = live ? (unsigned)(iy * a.w + 2 * jl) * 4u + (unsigned)(4 * lk) * hw4 : BUF_OOB;
+  const __amdgpu_buffer_rsrc_t rd = TG_BUF_RSRC(
+      a.dx + (long long)ks * a.part_ss + (long long)n * a.dx_ns + (size_t)(64 * cig) * a.h * a.w, 64u * hw4);
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const float v0 = acc[0][t][r], v1 = acc[1][t][r];   // (scalars first: __builtin_bit_cast of a vector ELEMENT expression reads element 0)
       const u32x2 d = {__builtin_bit_cast(unsigned, v0), __builtin_bit_cast(unsigned, v1)};
-      __builtin_amdgcn_raw_buffer_store_b64(d, rd, (int)vo, (int)((unsigned)(32 * t + 8 * (r >> 2) + (r & 3)) * hw4), 0);
+      buf_st(d, rd, vo, (unsigned)(32 * t + 8 * (r >> 2) + (r & 3)) * hw4);
     }
 }
 

@@ -27,7 +27,6 @@ constexpr int TTW = 32;
 constexpr int TPW = TTW + 1;   // patch width: x .. x+32
 constexpr int TRS = 34;        // LDS row stride (16-byte slots)
 constexpr int TOCB = 64;
-constexpr unsigned TOOB = 0x80000000u;
 
 struct ConvTArgs {
   const float* x;
@@ -83,11 +82,10 @@ __global__ __launch_bounds__(WM* WN * 64, ZMODE ? 4 : 1) void convt3x3s2_mfma_ke
     int hf = rem / TPW, col = rem - hf * TPW;
     int gy = y0 + r, gx = x0 + col;
     bool ok = q < IN_ITEMS && gy < a.h && gx < a.w;
-    voff[i] = ok ? (unsigned)((4 * hf * hw + gy * a.w + gx) * 4) : TOOB;
+    voff[i] = ok ? (unsigned)((4 * hf * hw + gy * a.w + gx) * 4) : BUF_OOB;
     lds_item[i] = q < IN_ITEMS ? ((r * 2 + hf) * TRS + col) * 4 : -1;
   }
-  const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x + (long long)n * a.x_ns), 0, a.cin * hw * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs1 = TG_BUF_RSRC(a.x + (long long)n * a.x_ns, a.cin * hw * 4);
   const unsigned plane = (unsigned)hw * 4u;
   const f32x4* wsrc =
       reinterpret_cast<const f32x4*>(a.wpk + (size_t)ocg * a.nchunk * W_FLOATS);
@@ -100,9 +98,7 @@ __global__ __launch_bounds__(WM* WN * 64, ZMODE ? 4 : 1) void convt3x3s2_mfma_ke
     for (int i = 0; i < I_PER_T; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        rin[i][j] = __builtin_bit_cast(
-            float, __builtin_amdgcn_raw_buffer_load_b32(
-                       rs1, (int)(voff[i] + cbase + (unsigned)j * plane), 0, 0));
+        rin[i][j] = buf_ld<float>(rs1, voff[i] + cbase + (unsigned)j * plane);
     const f32x4* ws = wsrc + (size_t)ch * W_VEC4;
 #pragma unroll
     for (int i = 0; i < W_PER_T; ++i) {
@@ -177,11 +173,10 @@ __global__ __launch_bounds__(WM* WN * 64, ZMODE ? 4 : 1) void convt3x3s2_mfma_ke
   if constexpr (ZMODE) {
     // (a channel past cout reads 0 here where the other branch reads bias[cout - 1]: its accumulator is 0 and its row of
     // the contraction operand is 0, the contribution is 0 either way)
-    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.bias ? a.bias : a.wz), 0, a.bias ? a.cout * 4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rb = TG_BUF_RSRC(a.bias ? a.bias : a.wz, a.bias ? a.cout * 4 : 0);
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      bv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rb, (int)((unsigned)ocb0 * 4u + (unsigned)((r & 3) + 8 * (r >> 2)) * 4u), 0, 0));
+      bv[r] = buf_ld<float>(rb, (unsigned)ocb0 * 4u + (unsigned)((r & 3) + 8 * (r >> 2)) * 4u);
   } else {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -201,12 +196,12 @@ __global__ __launch_bounds__(WM* WN * 64, ZMODE ? 4 : 1) void convt3x3s2_mfma_ke
     // through buffer resources with immediate offsets (no 64-bit address arithmetic), the reduction buffer addressed
     // by one base + immediates, 8-byte buffer stores with the plane as the scalar offset and an out-of-range offset
     // instead of a branch for rows >= zrows.  Same arithmetic in the same order: bit-identical to the round-2 form.
-    const __amdgpu_buffer_rsrc_t rwz = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wz), 0, 2 * 16 * 64 * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rwz = TG_BUF_RSRC(a.wz, 2 * 16 * 64 * 4);
     const unsigned wzo = (unsigned)(wn * 16 * 64 + lane) * 4u;
     float az[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      az[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rwz, (int)(wzo + (unsigned)r * 256u), 0, 0));
+      az[r] = buf_ld<float>(rwz, wzo + (unsigned)r * 256u);
     const bool relu = slope == 0.f;              // launch-uniform
 #pragma unroll
     for (int p = 0; p < 4; ++p)
@@ -219,8 +214,7 @@ __global__ __launch_bounds__(WM* WN * 64, ZMODE ? 4 : 1) void convt3x3s2_mfma_ke
     const bool inimg = px < a.w && py < a.h;
     const int ow = 2 * a.w;
     const unsigned ohw = 4u * (unsigned)hw;
-    const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(
-        a.z + (long long)n * a.z_ns, 0, (int)(32u * ohw * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rz = TG_BUF_RSRC(a.z + (long long)n * a.z_ns, (int)(32u * ohw * 4u));
 #pragma unroll
     for (int pp = 0; pp < 2; ++pp) {            // phase pairs (py = pp; px = 0, 1)
       f32x16 z[2];
@@ -240,22 +234,21 @@ __global__ __launch_bounds__(WM* WN * 64, ZMODE ? 4 : 1) void convt3x3s2_mfma_ke
       }
       __syncthreads();
       if (wn == 0) {
-        const unsigned zo = inimg ? ((unsigned)(4 * lh) * ohw + (unsigned)((2 * py + pp) * ow + 2 * px)) * 4u : TOOB;
+        const unsigned zo = inimg ? ((unsigned)(4 * lh) * ohw + (unsigned)((2 * py + pp) * ow + 2 * px)) * 4u : BUF_OOB;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int mb = (r & 3) + 8 * (r >> 2);
           if (mb >= 27) continue;                // (step 15 holds rows 27 and 31: zrows <= 27, never stored)
-          typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
           // (locals first: __builtin_bit_cast of a vector ELEMENT expression reads element 0 whatever the index)
           float e0 = z[0][r] + red[(0 * WM * 16 + r) * 64];
           asm volatile("" : "+v"(e0));           // (keeps the SLP vectorizer from pairing the two adds: v_pk_add_f32 + 3 v_mov)
           const float e1 = z[1][r] + red[(1 * WM * 16 + r) * 64];
           const u32x2 v = {__builtin_bit_cast(unsigned, e0), __builtin_bit_cast(unsigned, e1)};
           if (mb + 4 < a.zrows) {                // uniform: both lane halves' rows exist (12 of the 15 steps at zrows = 27)
-            __builtin_amdgcn_raw_buffer_store_b64(v, rz, (int)zo, (int)((unsigned)mb * ohw * 4u), 0);
+            buf_st(v, rz, zo, (unsigned)mb * ohw * 4u);
           } else {
-            const unsigned off = (mb + 4 * lh < a.zrows) ? zo : TOOB;
-            __builtin_amdgcn_raw_buffer_store_b64(v, rz, (int)off, (int)((unsigned)mb * ohw * 4u), 0);
+            const unsigned off = (mb + 4 * lh < a.zrows) ? zo : BUF_OOB;
+            buf_st(v, rz, off, (unsigned)mb * ohw * 4u);
           }
         }
       }
@@ -311,8 +304,7 @@ __global__ __launch_bounds__(512) void convt3x3s2_oneshot_kernel(ConvTArgs a) {
   const int hw = a.h * a.w;
   const unsigned plane = (unsigned)hw * 4u;
   const int nchunk = a.nchunk;
-  const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x + (long long)n * a.x_ns), 0, a.cin * hw * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs1 = TG_BUF_RSRC(a.x + (long long)n * a.x_ns, a.cin * hw * 4);
   // ---- this wave's weights: chunks 2 wk, 2 wk + 1
   const f32x4* wl = reinterpret_cast<const f32x4*>(a.wpk) + (lh * TOCB + wn * 32 + ll);
   f32x4 aw[2][9];
@@ -339,10 +331,10 @@ __global__ __launch_bounds__(512) void convt3x3s2_oneshot_kernel(ConvTArgs a) {
     const int hf = rem2 / TPW, col = rem2 - hf * TPW;
     const int gy = y0 + r, gx = x0 + col;
     const bool ok = q < total && gy < a.h && gx < a.w;
-    const unsigned base = ok ? (unsigned)(((ch * CK + 4 * hf) * hw + gy * a.w + gx) * 4) : TOOB;
+    const unsigned base = ok ? (unsigned)(((ch * CK + 4 * hf) * hw + gy * a.w + gx) * 4) : BUF_OOB;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      v[k][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs1, (int)(base + (unsigned)j * plane), 0, 0));
+      v[k][j] = buf_ld<float>(rs1, base + (unsigned)j * plane);
   }
 #pragma unroll
   for (int k = 0; k < MAXQ; ++k) {
@@ -541,8 +533,7 @@ __global__ __launch_bounds__(256) void convout_tail4_kernel(const float* __restr
   if (X >= w || Y >= h) return;
   const unsigned hw = (unsigned)h * (unsigned)w;
   // one image's planes: 32-bit offsets against a buffer resource (out-of-range reads at the two ends of the buffer: 0)
-  const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(z + (long long)b * z_ns), 0, (int)(9u * CZ * hw * 4u), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rz = TG_BUF_RSRC(z + (long long)b * z_ns, (int)(9u * CZ * hw * 4u));
   float v[CZ][4];
 #pragma unroll
   for (int o = 0; o < CZ; ++o)
@@ -564,9 +555,9 @@ __global__ __launch_bounds__(256) void convout_tail4_kernel(const float* __restr
           t[0] = 0.f;
 #pragma unroll
           for (int e = 1; e < 4; ++e)
-            t[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rz, (int)(base + 4u * e + pl), 0, 0));
+            t[e] = buf_ld<float>(rz, base + 4u * e + pl);
         } else {
-          t = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rz, (int)(base + pl), 0, 0));
+          t = buf_ld<f32x4>(rz, base + pl);
           if (kx == 2 && right) t[3] = 0.f;                // X + 4 is the next row's first pixel: the conv's zero padding
         }
 #pragma unroll

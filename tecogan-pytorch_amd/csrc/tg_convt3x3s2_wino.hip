@@ -41,7 +41,6 @@ constexpr int WZ_NCH = 4;                                      // chunks (cin <=
 constexpr int WZ_B_FLOATS = WZ_NP * WZ_CH * WZ_TILES;          // [p 25][k 4][tile 16][s 4]
 constexpr int WZ_RED_FLOATS = 4 * 2 * 32 * WZ_TILES * 4;       // [wave 4][HR row 2][m 32][tile 16][HR col 4]
 constexpr size_t WZ_LDS_BYTES = (size_t)(WZ_RED_FLOATS > 2 * WZ_B_FLOATS ? WZ_RED_FLOATS : 2 * WZ_B_FLOATS) * sizeof(float);
-constexpr unsigned WZ_OOB = 0x80000000u;
 
 struct ConvTWinoArgs {
   const float* x;
@@ -87,8 +86,7 @@ __global__ __launch_bounds__(256, 2) void convt3x3s2_wino_z_kernel(ConvTWinoArgs
 
   // ---- staging role: channel 4 lk + wave of each chunk, tile lt: the 3x3 window rows y0 .. y0 + 2, columns
   // x0 + 2 lt .. + 2 (outside the image: 0 -- a column past the row's end would read the next row, hence the offsets)
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x + (long long)n * a.x_ns), 0, a.cin * hw * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = TG_BUF_RSRC(a.x + (long long)n * a.x_ns, a.cin * hw * 4);
   // (offsets of chunk 0; the chunk's channel offset is added to the VECTOR offset, so that a channel past cin is out of
   // the descriptor's range whatever the scalar offset: a zero)
   unsigned co[3][3];
@@ -97,7 +95,7 @@ __global__ __launch_bounds__(256, 2) void convt3x3s2_wino_z_kernel(ConvTWinoArgs
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       const int gy = y0 + i, gx = x0 + 2 * lt + j;
-      co[i][j] = (gy < a.h && gx < a.w) ? (unsigned)(4 * lk + wave) * plane + (unsigned)(gy * a.w + gx) * 4u : WZ_OOB;
+      co[i][j] = (gy < a.h && gx < a.w) ? (unsigned)(4 * lk + wave) * plane + (unsigned)(gy * a.w + gx) * 4u : BUF_OOB;
     }
   float raw[3][3];
   auto load_raw = [&](int c) {
@@ -106,7 +104,7 @@ __global__ __launch_bounds__(256, 2) void convt3x3s2_wino_z_kernel(ConvTWinoArgs
     for (int i = 0; i < 3; ++i)
 #pragma unroll
       for (int j = 0; j < 3; ++j)
-        raw[i][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, (int)(co[i][j] + cb), 0, 0));
+        raw[i][j] = buf_ld<float>(rx, co[i][j] + cb);
   };
   // the 16 subtractions of the input transform and the 25 B values into LDS buffer buf
   auto store_b = [&](int buf) {
@@ -145,10 +143,10 @@ __global__ __launch_bounds__(256, 2) void convt3x3s2_wino_z_kernel(ConvTWinoArgs
 
   // ---- this wave's weights: lane (lk, lt) holds matrix m's channels 4 lk + s (s = 0..3) of output channel 16 wave + lt
   // (a buffer resource: the lane's part once, the (chunk, matrix) block as the scalar offset -- no 64-bit addresses)
-  const __amdgpu_buffer_rsrc_t rwa = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wa), 0, TG_CONVT_WINO_FLOATS * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rwa = TG_BUF_RSRC(a.wa, TG_CONVT_WINO_FLOATS * 4);
   const unsigned wvo = (unsigned)(lk * 64 + 16 * wave + lt) * 16u;
   auto lda = [&](int c, int m) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rwa, (int)wvo, (c * WZ_NA + m) * 4096, 0));
+    return buf_ld<f32x4>(rwa, wvo, (c * WZ_NA + m) * 4096);
   };
   f32x4 A[WZ_NA];
   // The bias rides in the accumulators: every output of the output transform sums exactly one of the products
@@ -228,8 +226,7 @@ __global__ __launch_bounds__(256, 2) void convt3x3s2_wino_z_kernel(ConvTWinoArgs
   auto actv = [&](float t) { return RELU ? fmaxf(t, 0.f) : (t >= 0.f ? t : t * slope + 0.f); };
   const int ow = 2 * a.w;
   const unsigned ohw = 4u * (unsigned)hw;
-  const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(
-      a.z + (long long)n * a.z_ns, 0, (int)(32u * ohw * 4u), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rz = TG_BUF_RSRC(a.z + (long long)n * a.z_ns, (int)(32u * ohw * 4u));
   float* const red_w = smem + (wave * 2 * 32 + 4 * lk) * WZ_TILES * 4 + lt * 4;   // + ((R2 * 32 + 16 h + r) * 16) * 4
 #pragma unroll
   for (int ya = 0; ya < 2; ++ya) {                             // input row y0 + ya of the tile: HR rows 2 ya, 2 ya + 1
@@ -292,14 +289,12 @@ __global__ __launch_bounds__(256, 2) void convt3x3s2_wino_z_kernel(ConvTWinoArgs
       if (gyin < a.h && m < a.zrows && xin < a.w) {
         const unsigned zo = ((unsigned)m * ohw + (unsigned)((2 * gyin + R2) * ow + 2 * xin)) * 4u;
         if (xin + 1 < a.w) {
-          typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, s), rz, (int)zo, 0, 0);
+          buf_st(s, rz, zo);
         } else {                                               // last column of an odd-width row: two HR pixels
-          typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
           // (locals first: __builtin_bit_cast of a vector ELEMENT expression reads element 0 whatever the index)
           const float e0 = s[0], e1 = s[1];
           const u32x2 v2 = {__builtin_bit_cast(unsigned, e0), __builtin_bit_cast(unsigned, e1)};
-          __builtin_amdgcn_raw_buffer_store_b64(v2, rz, (int)zo, 0, 0);
+          buf_st(v2, rz, zo);
         }
       }
     }

@@ -64,15 +64,6 @@ __device__ __forceinline__ float div_const(float x, float d, float r) {
   return __builtin_fmaf(e, r, q);
 }
 
-template <int AUX = 0>
-__device__ __forceinline__ float bload(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, AUX));
-}
-template <int AUX = 0>
-__device__ __forceinline__ void bstore(float v, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), r, (int)voff, (int)soff, AUX);
-}
-
 // warp_coord (tg_common.h) with the loop-invariant pieces hoisted
 __device__ __forceinline__ float warp_coord_c(int i, int n, float flow, float step, float half,
                                               float rhalf) {
@@ -111,7 +102,6 @@ __device__ __forceinline__ float warp_coord_c(int i, int n, float flow, float st
 // zero flow and slower as soon as the flow varies inside a block; XCD-banded block order
 // +4 %; nontemporal stores +-0; nontemporal gathers +30 %.
 // All offsets are 32-bit against block-uniform buffer resources.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <int S, int C, int R, int RPT>
 __global__ __launch_bounds__(128 * (R / RPT)) void flowup_warp_s2d_kernel(FusedArgs a) {
   constexpr int SEG = 256;
@@ -143,14 +133,11 @@ __global__ __launch_bounds__(128 * (R / RPT)) void flowup_warp_s2d_kernel(FusedA
   const unsigned fhw = (unsigned)(a.fh * a.fw);
   const unsigned hrhw = (unsigned)(HH * WW);
   const unsigned lrhw = (unsigned)(a.h * a.w);
-  const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.lr_flow + (size_t)n * 2 * fhw), 0, 2 * fhw * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.hr_prev + (size_t)n * C * hrhw), 0, C * hrhw * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(
-      a.out + (size_t)n * a.out_ns, 0, S * S * C * lrhw * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-      a.hr_flow_out ? a.hr_flow_out + (size_t)n * 2 * hrhw : a.out, 0, 2 * hrhw * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rf = TG_BUF_RSRC(a.lr_flow + (size_t)n * 2 * fhw, 2 * fhw * 4);
+  const __amdgpu_buffer_rsrc_t ri = TG_BUF_RSRC(a.hr_prev + (size_t)n * C * hrhw, C * hrhw * 4);
+  const __amdgpu_buffer_rsrc_t rout = TG_BUF_RSRC(a.out + (size_t)n * a.out_ns, S * S * C * lrhw * 4);
+  const __amdgpu_buffer_rsrc_t ro = TG_BUF_RSRC(
+      a.hr_flow_out ? a.hr_flow_out + (size_t)n * 2 * hrhw : a.out, 2 * hrhw * 4);
   const int jbase = x0 / S - 1;
   const bool bicubic = a.up_mode == TG_UP_BICUBIC;
   const bool vec_out = (a.w & 3) == 0 && a.out_aligned;   // dwordx4 stores need 16-byte rows
@@ -167,7 +154,7 @@ __global__ __launch_bounds__(128 * (R / RPT)) void flowup_warp_s2d_kernel(FusedA
         const int k = it % NV, p = (it / NV) & 3, ch = it / (4 * NV);
         const unsigned cc = (unsigned)reflect_src(clampi(jbase + k, 0, a.w - 1), a.fw);
         const unsigned o = ((unsigned)reflect_src(clampi(oy - 1 + p, 0, a.h - 1), a.fh) * a.fw + cc) * 4u;
-        fv[i] = it < 2 * 4 * NV ? bload(rf, o, (ch & 1) * fhw * 4u) : 0.01f;
+        fv[i] = it < 2 * 4 * NV ? buf_ld<float>(rf, o, (ch & 1) * fhw * 4u) : 0.01f;
       }
 #pragma unroll
       for (int i = 0; i < FPT; ++i) {
@@ -205,8 +192,8 @@ __global__ __launch_bounds__(128 * (R / RPT)) void flowup_warp_s2d_kernel(FusedA
       unsigned o0 = ((unsigned)reflect_src(y0, a.fh) * a.fw + cc) * 4u;
       unsigned o1 = ((unsigned)reflect_src(y1, a.fh) * a.fw + cc) * 4u;
       if (it < R * NV) {
-        b0[i] = make_float2(bload(rf, o0, 0), bload(rf, o0, fhw * 4u));
-        b1[i] = make_float2(bload(rf, o1, 0), bload(rf, o1, fhw * 4u));
+        b0[i] = make_float2(buf_ld<float>(rf, o0), buf_ld<float>(rf, o0, fhw * 4u));
+        b1[i] = make_float2(buf_ld<float>(rf, o1), buf_ld<float>(rf, o1, fhw * 4u));
       }
     }
 #pragma unroll
@@ -263,8 +250,8 @@ __global__ __launch_bounds__(128 * (R / RPT)) void flowup_warp_s2d_kernel(FusedA
 #pragma unroll
       for (int j = 0; j < RPT; ++j) {
         const unsigned o = ((unsigned)(hy0 + r0 + j) * WW + hxa) * 4u;
-        bstore(fx[0][j], ro, o, 0); bstore(fy[0][j], ro, o, hrhw * 4u);
-        if (live_b) { bstore(fx[1][j], ro, o + 4u, 0); bstore(fy[1][j], ro, o + 4u, hrhw * 4u); }
+        buf_st(fx[0][j], ro, o); buf_st(fy[0][j], ro, o, hrhw * 4u);
+        if (live_b) { buf_st(fx[1][j], ro, o + 4u); buf_st(fy[1][j], ro, o + 4u, hrhw * 4u); }
       }
     }
 #pragma unroll
@@ -306,8 +293,8 @@ __global__ __launch_bounds__(128 * (R / RPT)) void flowup_warp_s2d_kernel(FusedA
 #pragma unroll
       for (int ch = 0; ch < C; ++ch) {
         const unsigned pl = ch * hrhw * 4u;
-        const f32x4 t4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ri, (int)o0[0], (int)pl, 0));
-        const f32x4 b4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ri, (int)o1[0], (int)pl, 0));
+        const f32x4 t4 = buf_ld<f32x4>(ri, o0[0], pl);
+        const f32x4 b4 = buf_ld<f32x4>(ri, o1[0], pl);
         va[ch] = ((t4[0] * w00[0] + t4[1] * w01[0]) + b4[0] * w10[0]) + b4[1] * w11[0];
         const float t0 = pick(t4[0], t4[1], t4[2]);
         const float t1 = pick(t4[1], t4[2], t4[3]);
@@ -319,8 +306,8 @@ __global__ __launch_bounds__(128 * (R / RPT)) void flowup_warp_s2d_kernel(FusedA
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) {
           const unsigned pl = ch * hrhw * 4u;
-          const f32x2 t2 = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(ri, (int)o0[1], (int)pl, 0));
-          const f32x2 b2 = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(ri, (int)o1[1], (int)pl, 0));
+          const f32x2 t2 = buf_ld<f32x2>(ri, o0[1], pl);
+          const f32x2 b2 = buf_ld<f32x2>(ri, o1[1], pl);
           vb[ch] = ((t2[0] * w00[1] + t2[1] * w01[1]) + b2[0] * w10[1]) + b2[1] * w11[1];
         }
       }
@@ -347,8 +334,7 @@ __global__ __launch_bounds__(128 * (R / RPT)) void flowup_warp_s2d_kernel(FusedA
         const int r = pl / (S * C), rem = pl - r * (S * C);   // rem = sx * C + ch
         const f32x4 v = *reinterpret_cast<const f32x4*>(&s_out[pl * PS + 4 * q]);
         const unsigned o = ((unsigned)((sy0 + r) * S * C + rem) * lrhw + (unsigned)oy * a.w + ox) * 4u;
-        __builtin_amdgcn_raw_buffer_store_b128(
-            __builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(int)))) int, v), rout, (int)o, 0, 0);
+        buf_st(v, rout, o);
       }
     }
   } else {
@@ -361,7 +347,7 @@ __global__ __launch_bounds__(128 * (R / RPT)) void flowup_warp_s2d_kernel(FusedA
         const unsigned o = ((unsigned)(((sy0 + r) * S + sx) * C) * lrhw + (unsigned)oy * a.w + ox) * 4u;
 #pragma unroll
         for (int ch = 0; ch < C; ++ch)
-          bstore(s_out[((r * S + sx) * C + ch) * PS + oxl], rout, o, ch * lrhw * 4u);
+          buf_st(s_out[((r * S + sx) * C + ch) * PS + oxl], rout, o, ch * lrhw * 4u);
       }
     }
   }

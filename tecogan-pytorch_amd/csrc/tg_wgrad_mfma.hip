@@ -22,7 +22,6 @@
 
 namespace tg {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int WG_R = 2;                 // rows per pixel tile
 constexpr int WG_TW = 32;               // cols per pixel tile
 constexpr int WG_CSA = WG_R * WG_TW + 4;         // 68: A channel stride (floats), 17 slots (odd)
@@ -30,7 +29,6 @@ constexpr int WG_RSB = WG_TW + 3;                // 35: B row stride
 constexpr int WG_CSB = (WG_R + 2) * WG_RSB + 1;  // 141: B channel stride (odd -> conflict free)
 constexpr int WG_A_FLOATS = 64 * WG_CSA;
 constexpr int WG_B_FLOATS = 64 * WG_CSB;
-constexpr unsigned WG_OOB = 0x80000000u;
 
 constexpr int WG_MAXSEG = 64;
 struct WgradArgs {
@@ -178,19 +176,16 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a) {
       pbase += (long long)(li + 1) * a.lstride;
       qbase += (long long)li * a.lstride;
     }
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(pbase + (long long)ln * a.p_ns), 0, a.ca * hw * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(qbase + (long long)ln * a.q_ns), 0, a.cb * hq * wq * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rp = TG_BUF_RSRC(pbase + (long long)ln * a.p_ns, a.ca * hw * 4);
+    const __amdgpu_buffer_rsrc_t rq = TG_BUF_RSRC(qbase + (long long)ln * a.q_ns, a.cb * hq * wq * 4);
     if constexpr (VEC) {
       {
         const int gy = y0 + va_r, gx = x0 + 4 * va_k;
         const bool ok = gy < a.h && gx < a.w;                  // w % 4 == 0: a group is inside or outside
-        const unsigned off0 = ok ? ((unsigned)(a0 + va_c) * plane + (unsigned)(gy * a.w + gx) * 4u) : WG_OOB;
+        const unsigned off0 = ok ? ((unsigned)(a0 + va_c) * plane + (unsigned)(gy * a.w + gx) * 4u) : BUF_OOB;
 #pragma unroll
         for (int i = 0; i < AV_PER_T; ++i) {                   // (channel tail: past num_records -> 0)
-          const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-              rp, (int)(off0 + (unsigned)(i * A_CSTEP) * plane), 0, 0));
+          const f32x4 v = buf_ld<f32x4>(rp, off0 + (unsigned)(i * A_CSTEP) * plane);
 #pragma unroll
           for (int e = 0; e < 4; ++e) ra[4 * i + e] = v[e];
         }
@@ -199,15 +194,15 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a) {
         const int gy = (G::S2 ? 2 * y0 : y0) - 1 + vb_r;
         const int gx = G::S2 ? 2 * x0 - 2 + 2 * vb_k : x0 - 4 + 4 * vb_k;
         const bool ok = vb_on && gy >= 0 && gy < hq && gx >= 0 && gx < wq;
-        const unsigned off0 = ok ? ((unsigned)(b0 + vb_c) * planeq + (unsigned)(gy * wq + gx) * 4u) : WG_OOB;
+        const unsigned off0 = ok ? ((unsigned)(b0 + vb_c) * planeq + (unsigned)(gy * wq + gx) * 4u) : BUF_OOB;
 #pragma unroll
         for (int i = 0; i < BV_PER_T; ++i) {
           const unsigned off = off0 + (unsigned)i * planeq;
           if constexpr (G::S2) {
-            const f32x2 v = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rq, (int)off, 0, 0));
+            const f32x2 v = buf_ld<f32x2>(rq, off);
             rb[2 * i] = v[0]; rb[2 * i + 1] = v[1];
           } else {
-            const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rq, (int)off, 0, 0));
+            const f32x4 v = buf_ld<f32x4>(rq, off);
 #pragma unroll
             for (int e = 0; e < 4; ++e) rb[4 * i + e] = v[e];
           }
@@ -220,8 +215,8 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a) {
       int c = idx / G::PIX, rc = idx % G::PIX, r = rc / G::TW, col = rc % G::TW;
       int gy = y0 + r, gx = x0 + col;
       bool ok = gy < a.h && gx < a.w;      // channel tail handled by num_records
-      unsigned off = ok ? ((unsigned)(a0 + c) * plane + (unsigned)(gy * a.w + gx) * 4u) : WG_OOB;
-      ra[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, (int)off, 0, 0));
+      unsigned off = ok ? ((unsigned)(a0 + c) * plane + (unsigned)(gy * a.w + gx) * 4u) : BUF_OOB;
+      ra[i] = buf_ld<float>(rp, off);
     }
 #pragma unroll
     for (int i = 0; i < B_PER_T; ++i) {
@@ -231,8 +226,8 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a) {
       int r = rem2 / G::BC, col = rem2 - r * G::BC;
       int gy = (G::S2 ? 2 * y0 : y0) - 1 + r, gx = (G::S2 ? 2 * x0 : x0) - 1 + col;
       bool ok = (B_EXACT || idx < B_ELEMS) && gy >= 0 && gy < hq && gx >= 0 && gx < wq;
-      unsigned off = ok ? ((unsigned)(b0 + c) * planeq + (unsigned)(gy * wq + gx) * 4u) : WG_OOB;
-      rb[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rq, (int)off, 0, 0));
+      unsigned off = ok ? ((unsigned)(b0 + c) * planeq + (unsigned)(gy * wq + gx) * 4u) : BUF_OOB;
+      rb[i] = buf_ld<float>(rq, off);
     }
     }
   };
@@ -558,25 +553,22 @@ __global__ __launch_bounds__(256) void wgrad3x3_smallca_kernel(WgradSmallArgs a)
     const int ty = rem / a.tiles_x, tx = rem - ty * a.tiles_x;
     const int x0 = tx * SC_TW, y0 = ty * SC_TR;
     const int seg = n / a.n_per_seg, ln = n - seg * a.n_per_seg;
-    const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.qseg[seg] + (long long)ln * a.q_ns), 0, a.cb * hw * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.pseg[seg] + (long long)ln * a.p_ns), 0, a.ca * hw * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rq = TG_BUF_RSRC(a.qseg[seg] + (long long)ln * a.q_ns, a.cb * hw * 4);
+    const __amdgpu_buffer_rsrc_t rp = TG_BUF_RSRC(a.pseg[seg] + (long long)ln * a.p_ns, a.ca * hw * 4);
     if constexpr (VEC) {
       const int gy = y0 - 1 + vq_r, gx = x0 - 4 + 4 * vq_k;
       const bool ok = vq_on && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w;
-      const unsigned off0 = ok ? (unsigned)(((b0 + vq_c) * hw + gy * a.w + gx) * 4) : WG_OOB;
+      const unsigned off0 = ok ? (unsigned)(((b0 + vq_c) * hw + gy * a.w + gx) * 4) : BUF_OOB;
 #pragma unroll
       for (int i = 0; i < QV; ++i) {
-        const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-            rq, (int)(off0 + (unsigned)(4 * i) * (unsigned)hw * 4u), 0, 0));
+        const f32x4 v = buf_ld<f32x4>(rq, off0 + (unsigned)(4 * i) * (unsigned)hw * 4u);
 #pragma unroll
         for (int e = 0; e < 4; ++e) rqv[4 * i + e] = v[e];
       }
       const int py = y0 + vp_r, px = x0 + 4 * vp_k;
       const bool pok = tid < 128 && py < a.h && px < a.w;
-      const unsigned poff = pok ? (unsigned)((vp_c * hw + py * a.w + px) * 4) : WG_OOB;
-      const f32x4 pv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rp, (int)poff, 0, 0));
+      const unsigned poff = pok ? (unsigned)((vp_c * hw + py * a.w + px) * 4) : BUF_OOB;
+      const f32x4 pv = buf_ld<f32x4>(rp, poff);
 #pragma unroll
       for (int e = 0; e < 4; ++e) rpv[e] = pv[e];
       return;
@@ -587,8 +579,8 @@ __global__ __launch_bounds__(256) void wgrad3x3_smallca_kernel(WgradSmallArgs a)
       const int c = i % SC_QRS, r = (i / SC_QRS) % (SC_TR + 2), ch = i / (SC_QRS * (SC_TR + 2));
       const int gy = y0 - 1 + r, gx = x0 - 1 + c;
       const bool ok = i < QN && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w;
-      const unsigned off = ok ? (unsigned)(((b0 + ch) * hw + gy * a.w + gx) * 4) : WG_OOB;
-      rqv[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rq, (int)off, 0, 0));
+      const unsigned off = ok ? (unsigned)(((b0 + ch) * hw + gy * a.w + gx) * 4) : BUF_OOB;
+      rqv[k] = buf_ld<float>(rq, off);
     }
 #pragma unroll
     for (int k = 0; k < (VEC ? 0 : PPT); ++k) {
@@ -596,8 +588,8 @@ __global__ __launch_bounds__(256) void wgrad3x3_smallca_kernel(WgradSmallArgs a)
       const int c = i % SC_TW, r = (i / SC_TW) % SC_TR, ch = i / (SC_TW * SC_TR);
       const int gy = y0 + r, gx = x0 + c;
       const bool ok = gy < a.h && gx < a.w;          // channels >= ca are past num_records: 0
-      const unsigned off = ok ? (unsigned)((ch * hw + gy * a.w + gx) * 4) : WG_OOB;
-      rpv[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, (int)off, 0, 0));
+      const unsigned off = ok ? (unsigned)((ch * hw + gy * a.w + gx) * 4) : BUF_OOB;
+      rpv[k] = buf_ld<float>(rp, off);
     }
   };
   auto commit = [&]() {

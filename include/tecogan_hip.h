@@ -543,6 +543,28 @@ int tg_yuv420_to_rgb_f32(const uint8_t* yuv, float* rgb_chw, int n, int h, int w
 int tg_rgb_u8_to_yuv420(const uint8_t* rgb_hwc, uint8_t* yuv, int n, int H, int W, int matrix, int full_range,
                         int siting, tg_stream_t stream);
 
+/* Scene cuts of FRNet.infer_stream, decided on the device; the reference has no counterpart (its
+ * test sets are single-shot clips).  The formula is the specification, tests/scene_cut_ref.py restates it in numpy and
+ * the three outputs must be equal bit for bit.
+ *   frames (n + 1, 3, h, w) fp32, 4-byte aligned: the frame before the batch, then the batch.  Per value
+ *   q = clamp(floor(fma(x, 255, 0.5)), 0, 255), NaN -> 0; luma Y = (77 R + 150 G + 29 B + 128) >> 8.  For pair j (frame
+ *   j + 1 of `frames` against frame j), N = h * w:
+ *     sad[j]   = sum |Y - Y'| over the pixels;
+ *     hdist[j] = sum over the 32 bins b of |H[b] - H'[b]|, H[b] = pixels with Y >> 3 == b (at most 2N);
+ *     flags[j] = forced[j] != 0 || (detect && sad[j] >= s_min && hdist[j] >= d_min).
+ *   forced: n bytes or NULL (none forced).  Integer sums through integer atomics: the result does not depend on the
+ *   order.  workspace: 8-byte aligned, at least the bytes the size query returns for n (0 for n < 1); zeroed on `stream`
+ *   by the call.  Null pointers, n < 1, h or w < 1, a misaligned or short workspace: TG_E_ARG; h * w > 2^28: TG_E_SHAPE.
+ *   Nothing is launched then. */
+int64_t tg_scene_cut_workspace_bytes(int n);
+int tg_scene_cut_flags(const float* frames, int n, int h, int w, uint64_t s_min, uint64_t d_min, const uint8_t* forced,
+                       int detect, int32_t* flags, uint64_t* sad, uint32_t* hdist, void* workspace,
+                       int64_t workspace_bytes, tg_stream_t stream);
+/* Zero-fill `bytes` bytes at dst (any alignment) if the int32 at `flag` (device memory, 4-byte aligned) is non-zero when
+ * the launch runs; a zero flag leaves every byte as it is.  The host never reads the flag.  bytes == 0: no launch.
+ * Null pointers, bytes < 0, a misaligned flag: TG_E_ARG. */
+int tg_zero_if_flag(void* dst, int64_t bytes, const int32_t* flag, tg_stream_t stream);
+
 /* The BI degradation: scripts/generate_lr_bi.m of the reference -- im2double, modcrop,
  * imresize(img, 1/scale, 'bicubic'), imwrite -- on 8-bit frames, in exact integers, one launch per batch.  scale is 2
  * or 4 (else TG_E_ARG).  The frame is cut to (h - h % scale, w - w % scale); LR pixel o of an axis reads the 4*scale

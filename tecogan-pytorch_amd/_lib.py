@@ -97,6 +97,9 @@ SIGNATURES = {
     'tg_dequantize_u8_hwc': (I, [P, P, I, I, I, I, P]),
     'tg_yuv420_to_rgb_f32': (I, [P, P, I, I, I, I, I, I, P]),
     'tg_rgb_u8_to_yuv420': (I, [P, P, I, I, I, I, I, I, P]),
+    'tg_scene_cut_workspace_bytes': (I64, [I]),
+    'tg_scene_cut_flags': (I, [P, I, I, I, C.c_uint64, C.c_uint64, P, I, P, P, P, P, I64, P]),
+    'tg_zero_if_flag': (I, [P, I64, P, P]),
     'tg_downsample_bi_u8': (I, [P, P, P, I, I, I, I, I, P]),
     'tg_downsample_bi_f32': (I, [P, P, P, I, I, I, I, I, P]),
     'tg_psnr_sse_u8': (I, [P, P, P, I, I, I, I, P]),

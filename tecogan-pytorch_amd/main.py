@@ -18,6 +18,9 @@ video instead (data/y4m.py): I420 frames go up as they are, are converted on the
 
   ffmpeg -i in.mp4 -f yuv4mpegpipe - | python -m tecogan_pytorch_amd.main --mode infer --input - --output - | ffmpeg -i - out.mp4
 
+`--scene-cut` (both forms of `infer`) restarts the recurrence at scene cuts, detected on the
+device; the cut frames are listed on stderr at the end, never on stdout.
+
   python -m tecogan_pytorch_amd.main --mode profile --lr_size 3x134x320 --test_speed
   python -m tecogan_pytorch_amd.main --mode infer --opt my_test.yml --input lr_frames/ --output sr_frames/
   python -m tecogan_pytorch_amd.main --mode train --opt my_train.yml --gpu_ids 0
@@ -70,6 +73,14 @@ def parse_args(argv=None):
                    help='y4m input: the YCbCr matrix of the clip (y4m headers do not carry it)')
     p.add_argument('--yuv-range', dest='yuv_range', type=str, default=None, choices=['limited', 'full'],
                    help="y4m input: the range of the clip; default: the header's XCOLORRANGE, or limited without one")
+    p.add_argument('--scene-cut', dest='scene_cut', action='store_true',
+                   help='--mode infer: restart the recurrence at scene cuts, detected on the GPU (DESIGN.md section 7h); '
+                        'the cut frames are listed on stderr at the end.  The default thresholds have not been '
+                        'validated on real footage')
+    p.add_argument('--scene-cut-mad', dest='scene_cut_mad', type=float, default=24.0,
+                   help='--scene-cut: least mean absolute luma difference of a cut, in 8-bit levels')
+    p.add_argument('--scene-cut-hist', dest='scene_cut_hist', type=float, default=0.25,
+                   help='--scene-cut: least distance of the two 32-bin luma histograms, as a share of its maximum')
     return p.parse_args(argv)
 
 
@@ -338,10 +349,25 @@ def infer_output_path(input_dir, output_dir, seq, path):
     return os.path.join(output_dir, seq, os.path.splitext(rel)[0] + '.png')
 
 
-def infer(opt, input_dir, output_dir):
+def scene_cut_option(args):
+    """The SceneCut of --scene-cut [--scene-cut-mad X --scene-cut-hist Y], or None."""
+    if not getattr(args, 'scene_cut', False):
+        return None
+    from .models.networks import SceneCut
+    return SceneCut(mad=args.scene_cut_mad, hist=args.scene_cut_hist)
+
+
+def log_scene_cuts(name, scene_cut):
+    """The cut frames of one sequence, on stderr: stdout may be carrying the video."""
+    import sys
+    print(f'{name}: scene cuts at frames {scene_cut.cuts} (mad >= {scene_cut.mad:g}, hist >= {scene_cut.hist:g})',
+          file=sys.stderr, flush=True)
+
+
+def infer(opt, input_dir, output_dir, scene_cut=None):
     """--mode infer: every sequence of input_dir through VSRModel.infer_stream.  Frames are decoded one by one as the
     stream asks for them; the writers copy each frame out of the yielded ring slot before the generator is advanced.
-    Returns {sequence: frames written}."""
+    scene_cut (a SceneCut): passed on for every sequence, its cuts logged to stderr.  Returns {sequence: frames written}."""
     import threading
     from concurrent.futures import ThreadPoolExecutor
     from PIL import Image
@@ -369,7 +395,8 @@ def infer(opt, input_dir, output_dir):
             t0 = time.time()
             targets = [infer_output_path(input_dir, output_dir, seq, p) for p in files]
             jobs, k = [], 0
-            for chunk in model.infer_stream(read_rgb(p) for p in files):
+            for chunk in model.infer_stream((read_rgb(p) for p in files),
+                                            **({} if scene_cut is None else {'scene_cut': scene_cut})):
                 copied = threading.Semaphore(0)
                 for i in range(len(chunk)):
                     slots.acquire()
@@ -387,6 +414,8 @@ def infer(opt, input_dir, output_dir):
             for j in jobs:
                 j.result()                          # (a writer's exception surfaces here)
             done[seq] = k
+            if scene_cut is not None:
+                log_scene_cuts(seq or os.path.basename(os.path.normpath(input_dir)), scene_cut)
             dt = time.time() - t0
             print(f"{seq or os.path.basename(os.path.normpath(input_dir))}: {k} frames -> "
                   f"{os.path.join(output_dir, seq)} ({k / max(dt, 1e-9):.1f} frames/s, bound by PNG decoding and encoding)",
@@ -395,7 +424,7 @@ def infer(opt, input_dir, output_dir):
     return done
 
 
-def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None):
+def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None):
     """--mode infer on raw video: the y4m stream `src` (a binary file object) through VSRModel.infer_stream(yuv=...)
     into the y4m stream `dst`, in order.  The output header carries the scaled size and the input's F, A, C and X tags.
     Each chunk is written out of the ring slot before the generator is advanced; nothing is held beyond it.  Returns
@@ -409,12 +438,14 @@ def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None):
     s = model.net_G.scale
     writer = Y4MWriter(dst, s * reader.w, s * reader.h, reader.header)
     t0, k = time.time(), 0
-    for chunk in model.infer_stream(reader, yuv=spec):
+    for chunk in model.infer_stream(reader, yuv=spec, **({} if scene_cut is None else {'scene_cut': scene_cut})):
         for frame in chunk:
             writer.write(frame)
             k += 1
     writer.flush()
     model.net_G.check_faults()
+    if scene_cut is not None:
+        log_scene_cuts('y4m', scene_cut)
     dt = time.time() - t0
     print(f'y4m: {k} frames {reader.w}x{reader.h} -> {s * reader.w}x{s * reader.h} '
           f'({k / max(dt, 1e-9):.1f} frames/s, {spec.matrix} {"full" if spec.full_range else "limited"} range, '
@@ -422,7 +453,7 @@ def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None):
     return k
 
 
-def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range):
+def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range, scene_cut=None):
     """Opens the two ends of infer_y4m.  With `--output -` the y4m bytes are the ONLY thing on stdout: the descriptor
     is set aside for them and, for the length of the run, descriptor 1 and sys.stdout lead to stderr, so that neither
     a print nor a library's message can land in the stream."""
@@ -431,7 +462,7 @@ def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range):
     try:
         if output_path != '-':
             with open(output_path, 'wb') as dst:
-                return infer_y4m(opt, src, dst, matrix, yuv_range)
+                return infer_y4m(opt, src, dst, matrix, yuv_range, scene_cut)
         sys.stdout.flush()
         keep = os.dup(1)
         py_stdout = sys.stdout
@@ -439,7 +470,7 @@ def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range):
         sys.stdout = sys.stderr
         try:
             with os.fdopen(os.dup(keep), 'wb') as dst:
-                return infer_y4m(opt, src, dst, matrix, yuv_range)
+                return infer_y4m(opt, src, dst, matrix, yuv_range, scene_cut)
         finally:
             sys.stdout = py_stdout
             os.dup2(keep, 1)
@@ -524,9 +555,9 @@ def main(argv=None):
         if not args.input or not args.output:
             raise ValueError('--mode infer needs --input DIR and --output DIR (or a y4m file / - for both)')
         if args.input == '-' or os.path.isfile(args.input):
-            infer_y4m_cli(opt, args.input, args.output, args.yuv_matrix, args.yuv_range)
+            infer_y4m_cli(opt, args.input, args.output, args.yuv_matrix, args.yuv_range, scene_cut_option(args))
         else:
-            infer(opt, args.input, args.output)
+            infer(opt, args.input, args.output, scene_cut_option(args))
     elif args.mode == 'profile':
         profile(opt, tuple(int(v) for v in args.lr_size.split('x')), args.test_speed)
     else:

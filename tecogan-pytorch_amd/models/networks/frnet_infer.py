@@ -159,7 +159,7 @@ def clip_batches(tot_frm, first, later):
 
 
 def enqueue_batch(lib, plan, flow_plan, b, i0, cnt, lr_prev, lr_stride, hr, u8, u8_stride, zflow, flow_bytes,
-                  main, side, ev_flow, ev_free):
+                  main, side, ev_flow, ev_free, *, reset=None):
     """Enqueue the launches of batch b = frames i0 .. i0 + cnt - 1 of a clip, and nothing else: the order both
     infer_sequence(pipeline=True) and infer_stream produce their frames in, which is why they agree bit for bit.
 
@@ -175,7 +175,12 @@ def enqueue_batch(lib, plan, flow_plan, b, i0, cnt, lr_prev, lr_stride, hr, u8, 
     lr_stride bytes apart; hr the two HR states; u8 the batch's first uint8 frame, u8_stride bytes a frame;
     flow_bytes one frame's flows.  The caller's own business stays around the call: the waits for the batch's input,
     recording its end on `main` (a later batch's ev_free), and what happens to the uint8 frames.  Every status goes
-    through _lib.check (the one thing not taken as an argument): a non-zero one raises before anything later is enqueued."""
+    through _lib.check (the one thing not taken as an argument): a non-zero one raises before anything later is enqueued.
+
+    reset = (flags_addr, hr_bytes) (infer_stream with a SceneCut): one int32 flag per frame of
+    the batch in device memory.  Directly in front of the tg_frnet_step_srnet of every frame j of the batch but the
+    stream's frame 0, tg_zero_if_flag(hr[i & 1], hr_bytes, flags_addr + 4 j) goes onto `main`: with the flag set the
+    frame warps the zero state, as a clip's frame 0 does, whatever its flow.  None: exactly the calls above."""
     check, step, handle, ms = L.check, lib.tg_frnet_step_srnet, plan.handle, main.cuda_stream
     lr = lr_prev + lr_stride
     if i0 == 0:
@@ -194,5 +199,7 @@ def enqueue_batch(lib, plan, flow_plan, b, i0, cnt, lr_prev, lr_stride, hr, u8, 
     flow0 = lib.tg_frnet_plan_flow(fplan.handle, b & 1)
     for j in range(f0, cnt):
         i = i0 + j
+        if reset is not None:                   # (i > 0: the stream's frame 0 ran above, and never starts a scene)
+            check(lib.tg_zero_if_flag(hr[i & 1], reset[1], reset[0] + 4 * j, ms), 'tg_zero_if_flag')
         check(step(handle, flow0 + (j - f0) * flow_bytes, lr + j * lr_stride, hr[i & 1], hr[(i + 1) & 1],
                    u8 + j * u8_stride, ms), 'tg_frnet_step_srnet')

@@ -1,6 +1,8 @@
-"""FRNet.infer_stream (DESIGN.md sections 7d, 7e): input parsing, the batch ring, the raw-video form Yuv420 and the
-engine that runs a clip of any length through rings of STREAM_SLOTS batches.  A batch's launches are frnet_infer's
+"""FRNet.infer_stream (DESIGN.md sections 7d, 7e, 7h): input parsing, the batch ring, the raw-video form Yuv420, the
+scene-cut option SceneCut and the engine that runs a clip of any length through rings of STREAM_SLOTS batches.  A batch's launches are frnet_infer's
 enqueue_batch, the ones infer_sequence(pipeline=True) enqueues.  Uses the network only through its attributes."""
+import math
+
 import numpy as np
 import torch
 
@@ -202,6 +204,72 @@ class Yuv420:
         return L.YUV_MATRIX[self.matrix], int(self.full_range), L.YUV_SITING[self.siting]
 
 
+class SceneCut:
+    """Scene-cut option of a stream (FRNet.infer_stream(scene_cut=...)) and the caller's handle on
+    what it found.  At a cut the recurrence restarts from the zero HR state, which makes the frame the frame 0 of a clip
+    of its own, bit for bit.  A frame is a cut when the mean absolute luma difference to the frame before it is at
+    least `mad` (in 8-bit levels) AND the L1 distance of the two 32-bin luma histograms is at least `hist` (as a share
+    of its maximum 2 h w), both in exact integers on the device; detect=False switches the detector off.  `at` forces
+    cuts at these frame indices whatever the detector says.  Frame 0 of the stream is never a cut.  The defaults have
+    NOT been validated on real footage; fades and dissolves are not detected, a flash resets.
+
+    .cuts: the cut frames' indices, in the numbering of the frames the caller fed, appended when a batch is retired,
+    before its chunk is yielded: once a chunk covering frames [a, b) has been received every cut < b is in the list.
+    .scores (keep_scores=True): (mean absolute luma difference, histogram distance / 2 h w) per frame, for tuning the
+    thresholds.  One SceneCut serves one stream at a time; a new stream clears both lists."""
+
+    def __init__(self, mad=24.0, hist=0.25, detect=True, at=(), keep_scores=False):
+        for name, v in (('mad', mad), ('hist', hist)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or \
+                    not math.isfinite(v) or v < 0:
+                raise ValueError(f'SceneCut: {name} is a finite number >= 0, got {v!r}')
+        for name, v in (('detect', detect), ('keep_scores', keep_scores)):
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError(f'SceneCut: {name} is a bool, got {v!r}')
+        try:
+            at = tuple(at)
+        except TypeError:
+            raise ValueError(f'SceneCut: at is a sequence of frame indices, got {at!r}') from None
+        for v in at:
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f'SceneCut: at holds integer frame indices, got {v!r}')
+        self.mad, self.hist, self.detect, self.keep_scores = float(mad), float(hist), bool(detect), bool(keep_scores)
+        self.at = frozenset(int(v) for v in at)
+        self.cuts, self.scores = [], []
+
+    def __repr__(self):
+        return 'SceneCut(mad=%r, hist=%r, detect=%r, at=%r, keep_scores=%r)' % (
+            self.mad, self.hist, self.detect, sorted(self.at), self.keep_scores)
+
+    def thresholds(self, h, w):
+        """(S_min, D_min) as the C ABI takes them: ceil(mad h w) and ceil(hist 2 h w)."""
+        top = 2 ** 64 - 1
+        return min(top, math.ceil(self.mad * h * w)), min(top, math.ceil(self.hist * 2 * h * w))
+
+    def forced(self, i0, cnt):
+        """uint8 mask of frames i0 .. i0 + cnt - 1: 1 where `at` forces a cut.  Never frame 0."""
+        return np.array([1 if i > 0 and i in self.at else 0 for i in range(i0, i0 + cnt)], np.uint8)
+
+    def report(self, i0, flags, sad, hdist, n_pixels):
+        """A retired batch's results (host arrays, one entry per frame from frame i0 on) into .cuts / .scores."""
+        self.cuts.extend(i0 + j for j, f in enumerate(flags) if f)
+        if self.keep_scores:
+            self.scores.extend((int(s) / n_pixels, int(d) / (2 * n_pixels)) for s, d in zip(sad, hdist))
+
+    def shifted(self, n_pad):
+        """The SceneCut of a stream that runs n_pad frames of padding in front of the caller's (VSRModel.infer_stream):
+        the same thresholds, `at` moved by n_pad; an index below 1 (the caller's frame 0 and before) is dropped."""
+        return SceneCut(self.mad, self.hist, self.detect, [a + n_pad for a in self.at if a > 0], self.keep_scores)
+
+    def absorb(self, inner, n_pad, seen):
+        """Take over what `inner` (= self.shifted(n_pad)) has reported since the last call, in the caller's numbering;
+        cuts and scores of the padded prefix are dropped.  seen = (cuts, scores) taken over so far; returns the new one."""
+        nc, ns = seen
+        self.cuts.extend(c - n_pad for c in inner.cuts[nc:] if c >= n_pad)
+        self.scores.extend(inner.scores[max(ns, n_pad):])
+        return len(inner.cuts), len(inner.scores)
+
+
 def yuv420_planes(chunk, H, W):
     """(Y, U, V) views of I420 frames: chunk (m, frame_bytes) -> (m,H,W), (m,ch,cw), (m,ch,cw); a single frame
     (frame_bytes,) -> (H,W), (ch,cw), (ch,cw).  numpy or torch; nothing is copied."""
@@ -218,16 +286,31 @@ class _StreamEngine:
     """State of one FRNet.infer_stream (see there).  Everything the device touches is allocated once, at the first
     frame: STREAM_SLOTS slots of {LR batch + the frame before it, uint8 frames on the device, pinned uint8 frames,
     HR state snapshot, input staging, events}, and the HR ping-pong pair.  With a Yuv420 the staging and the pinned
-    output hold I420 frames, and a slot has its I420 output on the device as well."""
+    output hold I420 frames, and a slot has its I420 output on the device as well.
 
-    def __init__(self, net, frames, device, on_fault, yuv=None):
+    With a SceneCut a slot also has, on the device, one flag, one SAD and one histogram distance
+    per frame, the forced mask and the detector's workspace, and pinned mirrors of the mask and of the results.
+    _upload runs tg_scene_cut_flags on the slot's LR frames on the copy stream, behind whatever wrote them; _compute
+    hands the flags' address to enqueue_batch, which puts one tg_zero_if_flag in front of every frame's SRNet launch;
+    the results come down behind the frames and reach SceneCut.cuts when the batch is retired.  The host never waits
+    for a decision.  The repair path needs no scene-cut code: it runs _compute again, which reads the same per-slot
+    flags, and the snapshot it restores was taken before the batch's first conditional fill."""
+
+    def __init__(self, net, frames, device, on_fault, yuv=None, scene_cut=None):
         if on_fault not in ('rerun', 'raise'):
             raise ValueError(f"on_fault must be 'rerun' or 'raise', got {on_fault!r}")
         if yuv is not None:
             if not isinstance(yuv, Yuv420):
                 raise ValueError(f'yuv must be a Yuv420 or None, got {type(yuv).__name__}')
             yuv.out_frame_bytes(net.scale)
-        self.yuv = yuv
+        if scene_cut is not None:
+            if not isinstance(scene_cut, SceneCut):
+                raise ValueError(f'scene_cut must be a SceneCut or None, got {type(scene_cut).__name__}')
+            if net.in_nc != 3:
+                raise ValueError(f'scene_cut needs RGB frames (in_nc = 3), this network has in_nc = {net.in_nc}')
+            scene_cut.cuts.clear()
+            scene_cut.scores.clear()
+        self.yuv, self.scene_cut = yuv, scene_cut
         self.net, self.frames, self.on_fault = net, frames, on_fault
         self.dev = _norm_device(device if device is not None else next(net.parameters()).device)
         self.closed, self.warned, self.reruns = False, False, 0
@@ -275,6 +358,17 @@ class _StreamEngine:
         self.lr_ptr, self.u8_ptr = [t.data_ptr() for t in self.lr], [t.data_ptr() for t in self.u8]
         self.lr_stride, self.u8_stride = c * h * w * 4, s * h * s * w * c
         self.hr_ptr = (self.hr[0].data_ptr(), self.hr[1].data_ptr())
+        self.reset = None
+        if self.scene_cut is not None:
+            # per slot and frame: SAD (8 bytes), flag (4), histogram distance (4) -- one buffer, one download
+            self.sc_out = torch.zeros(ns, 16 * m, dtype=torch.uint8, device=dev)
+            self.sc_host = torch.zeros(ns, 16 * m, dtype=torch.uint8, pin_memory=True)
+            self.sc_forced = torch.zeros(ns, m, dtype=torch.uint8, device=dev)
+            self.sc_forced_host = torch.zeros(ns, m, dtype=torch.uint8, pin_memory=True)
+            self.sc_wsb = self.lib.tg_scene_cut_workspace_bytes(m)
+            self.sc_ws = torch.empty(ns, (self.sc_wsb + 7) // 8 * 8, dtype=torch.uint8, device=dev)
+            self.sc_min = self.scene_cut.thresholds(h, w)
+            self.reset = [(self.sc_out[sl].data_ptr() + 8 * m, self.hr[0].numel() * 4) for sl in range(ns)]
         ev = lambda: [torch.cuda.Event() for _ in range(ns)]
         self.ev_in, self.ev_f, self.ev_s, self.ev_out = ev(), ev(), ev(), ev()
         self.ev_arrive = torch.cuda.Event()
@@ -325,8 +419,25 @@ class _StreamEngine:
                         'tg_yuv420_to_rgb_f32')
             elif not self.in_cuda:
                 self.lr[sl, 1:1 + cnt].copy_(self.stage[sl, :cnt], non_blocking=True)
+            if self.scene_cut is not None:
+                self._detect(sl, b, i0, cnt)
             self.ev_in[sl].record(self.copy)
         self.prev_rec = rec
+
+    def _detect(self, sl, b, i0, cnt):
+        """On the copy stream, behind the slot's LR frames: the forced mask goes up and tg_scene_cut_flags decides the
+        batch's cnt pairs.  Frame 0 of the stream is never a cut: its pair (against the zero frame) is scored, its flag
+        is cleared."""
+        sc, m = self.scene_cut, self.sc_forced.shape[1]
+        self.sc_forced_host[sl, :cnt].copy_(torch.from_numpy(sc.forced(i0, cnt)))
+        self.sc_forced[sl, :cnt].copy_(self.sc_forced_host[sl, :cnt], non_blocking=True)
+        out = self.sc_out[sl].data_ptr()
+        L.check(self.lib.tg_scene_cut_flags(self.lr[sl].data_ptr(), cnt, self.h, self.w, self.sc_min[0], self.sc_min[1],
+                                            self.sc_forced[sl].data_ptr(), 1 if sc.detect else 0, out + 8 * m, out,
+                                            out + 12 * m, self.sc_ws[sl].data_ptr(), self.sc_wsb,
+                                            self.copy.cuda_stream), 'tg_scene_cut_flags')
+        if b == 0:
+            self.sc_out[sl, 8 * m:8 * m + 4].zero_()
 
     # -- launches of one batch: infer_sequence(pipeline=True)'s, on this slot's buffers ---------------------------------
     def _compute(self, rec):
@@ -340,7 +451,8 @@ class _StreamEngine:
             self.snap[sl].copy_(self.hr[i0 & 1], non_blocking=True)     # what a rerun of this batch starts from
         enqueue_batch(self.lib, self.plan, self._fplan, b, i0, cnt, self.lr_ptr[sl], self.lr_stride, self.hr_ptr,
                       self.u8_ptr[sl], self.u8_stride, self.zflow.data_ptr(), self.fsz, main, side, self.ev_f[sl],
-                      self.ev_s[(b - 2) % ns] if b >= 2 else None)     # (flow slot b & 1 was batch b - 2's)
+                      self.ev_s[(b - 2) % ns] if b >= 2 else None,     # (flow slot b & 1 was batch b - 2's)
+                      **({} if self.reset is None else {'reset': self.reset[sl]}))
         if self.yuv is not None:                    # the batch's RGB frames -> I420, behind its last frame
             s = self.net.scale
             L.check(self.lib.tg_rgb_u8_to_yuv420(self.u8[sl].data_ptr(), self.yuv_out[sl].data_ptr(), cnt,
@@ -362,6 +474,8 @@ class _StreamEngine:
         with torch.cuda.stream(self.copy):
             done = self.yuv_out if self.yuv is not None else self.u8
             self.host_out[sl, :cnt].copy_(done[sl, :cnt], non_blocking=True)
+            if self.scene_cut is not None:
+                self.sc_host[sl].copy_(self.sc_out[sl], non_blocking=True)
             self.ev_out[sl].record(self.copy)
 
     # -- faults --------------------------------------------------------------------------------------------------
@@ -423,7 +537,11 @@ class _StreamEngine:
             if err is None:
                 break
             self._recover(err)
-        self.ring.retire()
+        _, i0, _ = self.ring.retire()
+        if self.scene_cut is not None:
+            m, res = self.sc_forced.shape[1], self.sc_host[sl].numpy()
+            self.scene_cut.report(i0, res[8 * m:12 * m].view(np.int32)[:cnt], res[:8 * m].view(np.uint64)[:cnt],
+                                  res[12 * m:].view(np.uint32)[:cnt], self.h * self.w)
         return self.host_out[sl, :cnt].numpy()
 
     # -- the generator -------------------------------------------------------------------------------------------
@@ -464,5 +582,6 @@ class _StreamEngine:
             if self.ring.inflight:
                 self.plan.chain_state()             # a fault in frames nobody will see: counted, the plan has fallen back
         finally:
-            for name in ('lr', 'hr', 'snap', 'u8', 'host_out', 'stage', 'dev_in', 'yuv_out', 'zflow'):
+            for name in ('lr', 'hr', 'snap', 'u8', 'host_out', 'stage', 'dev_in', 'yuv_out', 'zflow', 'sc_out',
+                         'sc_host', 'sc_forced', 'sc_forced_host', 'sc_ws'):
                 self.__dict__.pop(name, None)

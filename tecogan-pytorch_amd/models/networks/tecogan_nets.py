@@ -20,7 +20,7 @@ from ...utils.net_utils import get_upsampling_func
 # (what is not a network: every name stays reachable as tecogan_nets.<name>)
 from .frnet_infer import (FNET_FIRST_PASS_FRAMES, _SIDE_STREAMS, _StepPlan, _norm_device, clip_batches,  # noqa: F401
                           enqueue_batch, side_stream, stream_batch_sizes)
-from .stream import (STREAM_SLOTS, StreamFormat, StreamRing, Yuv420, _StreamEngine, stream_frames,  # noqa: F401
+from .stream import (STREAM_SLOTS, SceneCut, StreamFormat, StreamRing, Yuv420, _StreamEngine, stream_frames,  # noqa: F401
                      stream_frames_yuv, stream_parts, stream_rebatch, yuv420_planes)
 
 
@@ -435,7 +435,7 @@ class FRNet(nn.Module):
         self._get_plan(k, h, w, dev).check_chain()   # (the clip has been synchronised: a 4-byte read)
         return out.transpose(1, 0, 2, 3, 4) if multi else out[:, 0]
 
-    def infer_stream(self, frames, device=None, on_fault='rerun', yuv=None):
+    def infer_stream(self, frames, device=None, on_fault='rerun', yuv=None, scene_cut=None):
         """Super-resolve a clip of ANY length in bounded memory: a generator over `frames` (any iterable, pulled lazily)
         that yields (m, s*h, s*w, 3) uint8 numpy chunks in order, as many frames in total as it consumed.
 
@@ -479,12 +479,20 @@ class FRNet(nn.Module):
         and that is what is downloaded.  The generator yields (m, yuv.out_frame_bytes(scale)) uint8 views
         (yuv420_planes splits them), valid until it is advanced: the bytes are ops.rgb_to_yuv420 of the frames the
         stream yields without `yuv` for the same LR input, bit for bit.  Both launches sit inside the per-batch
-        enqueue functions, so a repaired batch has its I420 bytes derived again."""
+        enqueue functions, so a repaired batch has its I420 bytes derived again.
+
+        scene_cut: a SceneCut(mad, hist, detect, at, keep_scores) restarts the recurrence at scene cuts, decided on the
+        device; without one the stream enqueues exactly what it always did.  For every batch
+        tg_scene_cut_flags compares each LR frame with the one before it on the copy stream, behind whatever wrote the
+        LR slot (every input kind), and one tg_zero_if_flag per frame on the caller's stream clears the HR state in
+        front of tg_frnet_step_srnet if the frame's flag is set: the frame then is frame 0 of a clip of its own, bit for
+        bit, and the host never waits for the decision.  The cuts (and, with keep_scores, the per-frame scores) are
+        appended to the SceneCut when a batch is retired, before its chunk is yielded.  in_nc != 3 is a ValueError."""
         import weakref
         cur = self._stream_ref() if self._stream_ref is not None else None
         if cur is not None and not cur.closed:
             raise RuntimeError('infer_stream: this network already has a live stream (one at a time: close it first)')
-        eng = _StreamEngine(self, frames, device, on_fault, yuv)
+        eng = _StreamEngine(self, frames, device, on_fault, yuv, scene_cut)
         self._stream_ref = weakref.ref(eng)
         return eng.run()
 

@@ -490,6 +490,36 @@ def rgb_to_yuv420(rgb_hwc, matrix='bt709', full_range=False, siting='left'):
     return out
 
 
+def scene_cut_flags(frames, mad, hist, forced=None, detect=True):
+    """(n+1,3,h,w) fp32 frames on device -> (flags int32 (n,), sad int64 (n,), hdist int32 (n,)): pair j is frame
+    j + 1 against frame j.  sad = sum |dY| of the 8-bit lumas, hdist = L1 distance of their 32-bin histograms, flag =
+    forced[j] or (detect and sad >= ceil(mad h w) and hdist >= ceil(hist 2 h w)), exact integers (tg_scene_cut_flags;
+    DESIGN.md section 7h).  forced: n values, non-zero = cut whatever the detector says.  For tests and for tuning the
+    thresholds: sad / (h w) and hdist / (2 h w) are the scores SceneCut(keep_scores=True) reports."""
+    import math
+    _chk(frames, 'frames')
+    if frames.dim() != 4 or frames.shape[0] < 2 or frames.shape[1] != 3:
+        raise L.TecoganHipError(f'scene_cut_flags: expected (n+1,3,h,w) with n >= 1, got shape {tuple(frames.shape)}')
+    if not (math.isfinite(mad) and math.isfinite(hist) and mad >= 0 and hist >= 0):
+        raise L.TecoganHipError(f'scene_cut_flags: mad and hist are finite and >= 0, got {mad!r}, {hist!r}')
+    n, (h, w), dev = frames.shape[0] - 1, frames.shape[2:], frames.device
+    top = 2 ** 64 - 1
+    s_min, d_min = min(top, math.ceil(mad * h * w)), min(top, math.ceil(hist * 2 * h * w))
+    if forced is not None:
+        forced = torch.as_tensor(forced).reshape(-1).ne(0).to(torch.uint8).to(dev).contiguous()
+        if forced.numel() != n:
+            raise L.TecoganHipError(f'scene_cut_flags: forced has {forced.numel()} entries for {n} pairs')
+    lib = L.lib()
+    flags = torch.empty(n, dtype=torch.int32, device=dev)
+    sad = torch.empty(n, dtype=torch.int64, device=dev)
+    hdist = torch.empty(n, dtype=torch.int32, device=dev)
+    wsb = lib.tg_scene_cut_workspace_bytes(n)
+    ws = torch.empty((wsb + 7) // 8, dtype=torch.int64, device=dev)
+    L.check(lib.tg_scene_cut_flags(_ptr(frames), n, h, w, s_min, d_min, _ptr(forced), 1 if detect else 0, _ptr(flags),
+                                   _ptr(sad), _ptr(hdist), _ptr(ws), ws.numel() * 8, _stream()), 'tg_scene_cut_flags')
+    return flags, sad, hdist
+
+
 def psnr_sse_u8(true_hwc, pred_hwc, y_only=True):
     """Per-frame sum of squared differences of (t,h,w,3) uint8 device tensors -> int64 (t,)."""
     _chk_u8(true_hwc, 'true'); _chk_u8(pred_hwc, 'pred')

@@ -215,6 +215,9 @@ int tg_conv3x3_wino_fused_fwd(const float* x, int64_t x_nstride, const float* u_
  * the kernel is fail-safe: a poll limit turns a lost flag into a fault count instead of a hang.
  *   layers[i]: as tg_conv3x3_wino_fwd (x2 / bias / res may be NULL; res is added after the
  *              activation; y may alias res: in-place residual sum); cout <= 64 for every layer.
+ *              Any 4-byte aligned base; with n > 1 every *_nstride is at least one image (TG_E_SHAPE).
+ *              The float2 epilogue runs only while y and res of EVERY layer are 8-byte aligned with even
+ *              strides (and w, h w even), else every layer stores element by element: same results.
  *   flags:     tg_conv3x3_wino_chain_flag_ints(n_layers, n, h, w) int32, caller owned, zeroed ONCE
  *              before the first call; its last 16 ints are a fault counter the caller MUST read
  *              after synchronising (non-zero: a workgroup gave up waiting -- never seen; the
@@ -245,6 +248,7 @@ int tg_conv3x3_wino_chain(const tg_wino_layer* layers, int n_layers, int n, int 
  *              REQUIREMENT: layers[i].x == layers[i-1].y, layers[i].res in {NULL, layers[i-1].x},
  *              cin == 64 for i > 0, bias non-NULL.  Only layers[0].x / x2 are read and only
  *              layers[n_layers-1].y is written: the intermediate tensors never reach memory.
+ *              x / x2: any 4-byte aligned base; layers[n_layers-1].y: 8-byte aligned (TG_E_ARG), strides unused.
  *   workspace: tg_conv3x3_wino_resident_ws_bytes(h, w) bytes, 256-byte aligned, caller owned, zeroed ONCE
  *              before the first call; its last 256 bytes hold a fault counter (int32) the caller MUST
  *              read after synchronising (non-zero: a workgroup gave up waiting for a neighbour; the
@@ -283,7 +287,8 @@ int tg_conv3x3_wino_resident_ct(const tg_wino_layer* layers, int n_layers, int c
  * smallest frames); a mismatch is TG_E_ARG.
  *   layers[i]: x (+ x2: channels [c1, cin)) -> y = relu_mask > 0 ? act(conv + bias) + res : 0;
  *              cin, cout <= 64; bias / res / relu_mask / x2 may be NULL; buffers may be reused along the
- *              chain in SRNet's patterns only (ping-pong, in-place residual sum).
+ *              chain in SRNet's patterns only (ping-pong, in-place residual sum).  Any 4-byte aligned base;
+ *              with n > 1 every *_nstride is at least one image (TG_E_SHAPE).
  *   flags:     tg_conv3x3_chain_flag_ints(n_layers, n, h, w) int32, caller owned, zeroed ONCE.
  *   err:       int32 fault counter, device OR pinned host memory (the kernel adds with system scope):
  *              a workgroup that exhausts poll_limit polls (~32 cycles each; < 0: at once = fault

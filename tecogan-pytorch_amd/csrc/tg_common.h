@@ -55,6 +55,11 @@ inline int check_launch(const char* what) {
   TG_REQUIRE(!(ptr) || (n) <= 1 || (long long)(ns) >= (long long)(floats), TG_E_SHAPE,                           \
              entry ": " name "_nstride=%lld is less than the %lld floats of one image", (long long)(ns), \
              (long long)(floats))
+// ... of layer `i` of a launch that takes its strides per layer (the one-launch bodies)
+#define TG_REQUIRE_LAYER_NSTRIDE(entry, i, name, ptr, ns, n, floats)                                             \
+  TG_REQUIRE(!(ptr) || (n) <= 1 || (long long)(ns) >= (long long)(floats), TG_E_SHAPE,                           \
+             entry ": layer %d: " name "_nstride=%lld is less than the %lld floats of one image", (int)(i),      \
+             (long long)(ns), (long long)(floats))
 
 // whether tg_convt3x3s2_z_fwd_form(form) runs as two launches (whole rounds of 4-row workgroups + a 2-row tail)
 bool convt_z_split_rule(int n, int h, int w, int form);

@@ -620,6 +620,14 @@ extern "C" int tg_conv3x3_chain(const tg_chain_layer* layers, int n_layers, int 
     TG_REQUIRE(!l.x2 || (l.c1 > 0 && l.c1 < l.cin), TG_E_ARG, "conv3x3_chain: layer %d: c1=%d of cin=%d", i, l.c1, l.cin);
     TG_REQUIRE(l.act >= TG_ACT_NONE && l.act <= TG_ACT_LRELU02, TG_E_ARG, "conv3x3_chain: layer %d: act=%d", i, l.act);
     TG_REQUIRE((long long)(l.cin + CK) * h * w * 4 < (1ll << 31), TG_E_SHAPE, "conv3x3_chain: layer %d too large", i);
+    {
+      const long long hw = (long long)h * w;
+      TG_REQUIRE_LAYER_NSTRIDE("conv3x3_chain", i, "x", l.x, l.x_nstride, n, (l.x2 ? l.c1 : l.cin) * hw);
+      TG_REQUIRE_LAYER_NSTRIDE("conv3x3_chain", i, "x2", l.x2, l.x2_nstride, n, (l.cin - l.c1) * hw);
+      TG_REQUIRE_LAYER_NSTRIDE("conv3x3_chain", i, "res", l.res, l.res_nstride, n, l.cout * hw);
+      TG_REQUIRE_LAYER_NSTRIDE("conv3x3_chain", i, "mask", l.relu_mask, l.mask_nstride, n, l.cout * hw);
+      TG_REQUIRE_LAYER_NSTRIDE("conv3x3_chain", i, "y", l.y, l.y_nstride, n, l.cout * hw);
+    }
     RCLayer& d = a.L[i];
     d.x = l.x; d.x2 = l.x2; d.wpk = l.w_packed; d.bias = l.bias; d.res = l.res; d.mask = l.relu_mask; d.y = l.y;
     d.x_ns = l.x_nstride; d.x2_ns = l.x2_nstride; d.res_ns = l.res_nstride; d.mask_ns = l.mask_nstride; d.y_ns = l.y_nstride;

@@ -738,6 +738,13 @@ int conv3x3_wino_chain_launch(const tg_wino_layer* layers, int n_layers, int n, 
     TG_REQUIRE(l.cin > 0 && (!l.x2 || (l.c1 > 0 && l.c1 < l.cin)), TG_E_ARG, "conv3x3_wino_chain: layer %d: cin=%d c1=%d", i, l.cin, l.c1);
     TG_REQUIRE((long long)l.cin * h * w < (1ll << 29), TG_E_SHAPE, "conv3x3_wino_chain: layer %d too large", i);
     TG_REQUIRE(l.act >= TG_ACT_NONE && l.act <= TG_ACT_TANH24, TG_E_ARG, "conv3x3_wino_chain: layer %d: act=%d", i, l.act);
+    {
+      const long long hw = (long long)h * w;
+      TG_REQUIRE_LAYER_NSTRIDE("conv3x3_wino_chain", i, "x", l.x, l.x_nstride, n, (l.x2 ? l.c1 : l.cin) * hw);
+      TG_REQUIRE_LAYER_NSTRIDE("conv3x3_wino_chain", i, "x2", l.x2, l.x2_nstride, n, (l.cin - l.c1) * hw);
+      TG_REQUIRE_LAYER_NSTRIDE("conv3x3_wino_chain", i, "res", l.res, l.res_nstride, n, cout * hw);
+      TG_REQUIRE_LAYER_NSTRIDE("conv3x3_wino_chain", i, "y", l.y, l.y_nstride, n, cout * hw);
+    }
     WinoLayer& d = c.L[i];
     d.x = l.x; d.x2 = l.x2; d.u = l.u_packed; d.bias = l.bias; d.res = l.res; d.y = l.y;
     d.x_ns = l.x_nstride; d.x2_ns = l.x2_nstride; d.res_ns = l.res_nstride; d.y_ns = l.y_nstride;

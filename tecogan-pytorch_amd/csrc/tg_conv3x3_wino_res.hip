@@ -717,6 +717,8 @@ int conv3x3_wino_resident_launch(const tg_wino_layer* layers, int n_layers, int 
   }
   a.x = layers[0].x; a.x2 = layers[0].x2; a.c1 = layers[0].x2 ? layers[0].c1 : layers[0].cin; a.cin0 = layers[0].cin;
   a.y = layers[n_layers - 1].y;
+  // (the last layer's 2 x 2 tiles leave as float2 rows at even offsets of an even map; one rule with and without the tail)
+  TG_REQUIRE(((uintptr_t)a.y % 8) == 0, TG_E_ARG, "conv3x3_wino_resident: the last layer's y must be 8-byte aligned");
   a.xbuf = static_cast<float*>(ws);
   a.err = err; a.base = base; a.poll_limit = poll_limit;
   if (ct) {

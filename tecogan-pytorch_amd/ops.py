@@ -31,6 +31,37 @@ def _chk(t, name, dtype=torch.float32):
     return t
 
 
+def _chk_batched(t, name, dtype=torch.float32, device=True):
+    """_chk for an operand whose entry point takes a batch stride (the one-launch bodies): dtype and device as _chk,
+    the dimensions behind the batch dimension contiguous, the batch stride free (at least one image)."""
+    if not torch.is_tensor(t):
+        raise L.TecoganHipError(f'{name}: expected a tensor')
+    if t.dtype != dtype:
+        raise L.TecoganHipError(f'{name}: expected {dtype}, got {t.dtype}')
+    if t.dim() < 2 or not t[0].is_contiguous() or (t.shape[0] > 1 and t.stride(0) < t[0].numel()):
+        raise L.TecoganHipError(f'{name}: the dimensions behind the batch dimension must be contiguous and the images '
+                                f'apart (shape {tuple(t.shape)}, strides {tuple(t.stride())})')
+    if device and not t.is_cuda:
+        raise L.TecoganHipError(f'{name}: expected a CUDA/HIP tensor (no CPU path exists)')
+    return t
+
+
+def _chk_layers(layers, who, packed):
+    """Every tensor of the layer dicts of RowChain / WinoChain / WinoResident: activations through _chk_batched (dtype
+    and layout of all of them first, then the device), packed weights (`packed`: their key, or None where the class
+    packs them itself) and biases through _chk."""
+    acts = [(f'{who}: layer {i}: {k}', d[k]) for i, d in enumerate(layers) for k in ('x', 'x2', 'res', 'mask', 'y')
+            if d.get(k) is not None]
+    for name, t in acts:
+        _chk_batched(t, name, device=False)
+    for name, t in acts:
+        _chk_batched(t, name)
+    for i, d in enumerate(layers):
+        for k in (packed, 'bias'):
+            if k and d.get(k) is not None:
+                _chk(d[k], f'{who}: layer {i}: {k}')
+
+
 def _ptr(t):
     return None if t is None else t.data_ptr()
 
@@ -1470,6 +1501,7 @@ class RowChain:
     the weights are packed here in the layout the launcher's choice for this shape needs."""
 
     def __init__(self, layers, n, h, w):
+        _chk_layers(layers, 'RowChain', None)
         lib = L.lib()
         self.n, self.h, self.w = n, h, w
         self.parts = lib.tg_conv3x3_chain_supported(n, h, w, 64)
@@ -1512,7 +1544,7 @@ class WinoChain:
     counter live here."""
 
     def __init__(self, layers, n, cout, h, w):
-        import ctypes
+        _chk_layers(layers, type(self).__name__, 'u')
         self.n, self.cout, self.h, self.w = n, cout, h, w
         self.keep = layers
         self.arr = (L.WinoLayer * len(layers))()
@@ -1575,6 +1607,8 @@ class WinoResident(WinoChain):
                     'tg_conv3x3_wino_resident')
             return
         import ctypes as C
+        _chk(convt['u'], 'WinoResident: convt u'); _chk(convt['bias'], 'WinoResident: convt bias')
+        _chk_batched(convt['y'], 'WinoResident: convt y')
         ct = L.WresConvT(convt['u'].data_ptr(), convt['bias'].data_ptr(), convt['y'].data_ptr(), convt.get('act', ACT_RELU))
         L.check(L.lib().tg_conv3x3_wino_resident_ct(self.arr, len(self.keep), self.cout, self.h, self.w,
                                                     self.ws.data_ptr(), self.epoch, C.byref(ct), _stream()),

@@ -58,13 +58,24 @@ def _n_per(shape):
 
 
 class Arena:
-    def __init__(self, device, margin_floats, slots=10):
+    def __init__(self, device, margin_floats, slots=10, align_floats=ALIGN_WORDS):
+        """align_floats: the largest alignment an operand of this arena asks of `out` (a multiple of ALIGN_WORDS; the
+        default is what every operand gets)."""
         self.device = torch.device(device)
         self.margin = int(margin_floats)
-        # each slot: margin | up to ALIGN_WORDS of alignment and 2 * ALIGN_WORDS of offset | operand (<= margin) | margin
-        self.total = slots * (3 * self.margin + 4 * ALIGN_WORDS) + ALIGN_WORDS
-        self.words = torch.empty(self.total, dtype=torch.int32, device=self.device)
-        assert self.words.data_ptr() % 64 == 0, 'the allocator returned a block that is not 64-byte aligned'
+        self.max_align = int(align_floats)
+        assert self.max_align >= ALIGN_WORDS and self.max_align % ALIGN_WORDS == 0
+        # each slot: margin | up to align_floats of alignment and 2 * ALIGN_WORDS of offset | operand (<= margin) | margin
+        self.total = slots * (3 * self.margin + 3 * ALIGN_WORDS + self.max_align) + self.max_align
+        if self.max_align == ALIGN_WORDS:
+            self.words = torch.empty(self.total, dtype=torch.int32, device=self.device)
+            assert self.words.data_ptr() % 64 == 0, 'the allocator returned a block that is not 64-byte aligned'
+        else:       # the allocator promises no more: take the first word on the larger boundary
+            raw = torch.empty(self.total + self.max_align, dtype=torch.int32, device=self.device)
+            assert raw.data_ptr() % 4 == 0
+            skip = (-(raw.data_ptr() // 4)) % self.max_align
+            self.words = raw[skip:skip + self.total]
+            assert self.words.data_ptr() % (4 * self.max_align) == 0
         self.words.fill_(pattern(0))               # words no slot has claimed yet (never next to an operand)
         self.expect = np.full(self.total, pattern(0), dtype=np.int32)      # what check() wants to find
         self.free = np.zeros(self.total, dtype=bool)                        # words a kernel may write
@@ -73,7 +84,7 @@ class Arena:
         self.max_slots = slots
 
     # ---- carving --------------------------------------------------------------------------------------------------
-    def _carve(self, shape, dtype, offset_floats, nstride, name, is_out):
+    def _carve(self, shape, dtype, offset_floats, nstride, name, is_out, align=ALIGN_WORDS):
         shape = tuple(int(s) for s in shape)
         itemsize = torch.empty(0, dtype=dtype).element_size()
         n, per = _n_per(shape)
@@ -88,7 +99,8 @@ class Arena:
         assert len(self.ops) < self.max_slots and len(self.ops) < 255, 'out of slots'
         slot = len(self.ops) + 1
         start = self.cursor
-        base = (start + self.margin + ALIGN_WORDS - 1) // ALIGN_WORDS * ALIGN_WORDS + int(offset_floats)
+        assert ALIGN_WORDS <= align <= self.max_align and align % ALIGN_WORDS == 0, f'{name}: alignment {align}'
+        base = (start + self.margin + align - 1) // align * align + int(offset_floats)
         end = base + words + self.margin
         assert end <= self.total
         self.cursor = end
@@ -106,7 +118,7 @@ class Arena:
             acc *= s
         strides = (ns,) + tuple(reversed(inner)) if len(shape) > 1 else (1,)
         assert len(shape) == 1 or tuple(reversed(inner))[-1] == 1
-        view = torch.as_strided(flat, shape, strides, base * scale)
+        view = torch.as_strided(flat, shape, strides, flat.storage_offset() + base * scale)
         view._arena_op = op
         return view, op
 
@@ -121,12 +133,18 @@ class Arena:
             self.expect[op['base'] + lo:op['base'] + lo + op['per_words']] = now[lo:lo + op['per_words']]
         return view
 
-    def out(self, shape, offset_floats=0, nstride=None, dtype=torch.float32, name='y'):
-        """A destination of `shape`, pre-filled with its slot's guard pattern, placed as `place` does."""
-        view, op = self._carve(shape, dtype, offset_floats, nstride, name, True)
+    def out(self, shape, offset_floats=0, nstride=None, dtype=torch.float32, name='y', align_floats=ALIGN_WORDS, zero=False):
+        """A destination of `shape`, pre-filled with its slot's guard pattern, placed as `place` does.  align_floats:
+        the boundary the base is `offset_floats` past (a workspace that must be 256-byte aligned: 64).  zero: the
+        images start as zeros instead (a flag buffer or workspace the entry point wants zeroed once); the gaps and
+        margins keep the guard pattern."""
+        view, op = self._carve(shape, dtype, offset_floats, nstride, name, True, align_floats)
         for b in range(op['n']):
             lo = op['base'] + b * op['ns_words']
             self.free[lo:lo + op['per_words']] = True
+            if zero:
+                self.words[lo:lo + op['per_words']] = 0
+                self.expect[lo:lo + op['per_words']] = 0
         return view
 
     def inout(self, t, writable=None, prefill=False, offset_floats=0, nstride=None, name='g'):

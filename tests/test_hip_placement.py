@@ -191,7 +191,8 @@ def launch(lib, case, pl):
     """Place every operand as `pl` says (default P0), call the entry point, return (rc, arena, views, info)."""
     info = {o.name: o.resolve(pl.get(o.name, 'P0')) for o in case.operands}
     ext = [extent_floats(o.shape, info[o.name][1] if len(o.shape) > 1 else None, o.itemsize) for o in case.operands]
-    arena = Arena('cuda', margin_floats=max(ext) + 64, slots=len(case.operands))
+    arena = Arena('cuda', margin_floats=max(ext) + 64, slots=len(case.operands),
+                  align_floats=max(getattr(o, 'align', 16) for o in case.operands))
     views = {}
     for o in case.operands:
         off, ns = info[o.name]
@@ -199,7 +200,9 @@ def launch(lib, case, pl):
         if getattr(o, 'inout', False):      # (tests/test_hip_placement_bwd.py: a destination that already holds values)
             views[o.name] = arena.inout(o.data, o.writable, o.prefill, **kw)
         else:
-            views[o.name] = arena.place(o.data, **kw) if o.data is not None else arena.out(o.shape, dtype=o.dtype, **kw)
+            # (tests/test_hip_placement_chain.py: a workspace that wants its own alignment / to start as zeros)
+            extra = {k: v for k, v in (('align_floats', getattr(o, 'align', None)), ('zero', getattr(o, 'zero', None))) if v}
+            views[o.name] = arena.place(o.data, **kw) if o.data is not None else arena.out(o.shape, dtype=o.dtype, **kw, **extra)
     ptr = {k: v.data_ptr() for k, v in views.items()}
     ns = {k: v[1] for k, v in info.items()}
     torch.cuda.synchronize()

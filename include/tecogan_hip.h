@@ -20,6 +20,24 @@
  *   - every entry returns 0 (TG_OK) or a negative TG_E_* code;
  *     tg_last_error_string() describes the last failure on this thread.
  *     No C++ exception crosses the boundary.
+ *
+ * What this header may contain
+ *   tecogan-pytorch_amd/_lib.py derives the Python binding from this text (no C compiler is involved): an
+ *   entry is callable from Python once it is declared here and the library is rebuilt.  The parser refuses,
+ *   at import and by name, whatever is not one of these; it never skips or guesses:
+ *   - comments of this form only, and the preprocessor lines below as they stand, plus
+ *     `#define TG_NAME <integer or parenthesised product of integers>` on one line;
+ *   - `enum { TG_NAME = integer, ... };` -- anonymous, every value written out;
+ *   - `typedef void* NAME;` (a handle passed by value) and `typedef struct NAME NAME;` (opaque);
+ *   - `typedef struct [tag] { fields } NAME;` whose fields are int, int32_t, int64_t, unsigned, uint32_t,
+ *     uint64_t, size_t, float, double (several names may share one such declaration) or pointers, one per
+ *     declaration: no arrays, bit-fields, nested structs or function pointers.  A struct the package
+ *     constructs also gets its Python name in _lib.py;
+ *   - prototypes `type tg_name(type name, ...);` or `(void)`: every parameter named; one-word scalar
+ *     types from the list above by value; pointers and `type name[N]` arrays to those, to void, char,
+ *     uint8_t, uint16_t and to the types declared here, `const` where it belongs.  A `T*` parameter whose T
+ *     is a struct with fields is type-checked as that struct; every other pointer is an untyped address.
+ *     A struct must be declared above its first use.
  */
 #ifndef TECOGAN_HIP_H
 #define TECOGAN_HIP_H

@@ -1,256 +1,169 @@
-"""ctypes binding of libtecogan_hip.so (the C ABI in include/tecogan_hip.h).
+"""ctypes binding of libtecogan_hip.so, derived from the C ABI's own header.
+
+include/tecogan_hip.h is read once, at import, as text: its prototypes become SIGNATURES, its structs the
+Structure classes, its enumerators and integer `#define TG_*` the module's TG_* constants.  An entry becomes
+callable by declaring it there and rebuilding the library; nothing is restated here.  The header's leading
+comment says what it may contain; anything else raises at import and names the declaration.
 
 The library is built in-tree by `csrc/build.sh` (or __graft_entry__.build()).
 Loading failures are loud: there is no fallback path.
 """
+import collections
 import ctypes as C
+import math
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # TECOGAN_HIP_LIB: measurement builds of the same sources (tools/build_var.sh, or csrc/build.sh with TG_LAB_BUILD=1); never a fallback
 LIB_PATH = os.environ.get('TECOGAN_HIP_LIB') or os.path.join(_HERE, 'libtecogan_hip.so')
-
-TG_OK = 0
-ABI_MAJOR = 2            # include/tecogan_hip.h TG_ABI_MAJOR
-ACT_NONE, ACT_RELU, ACT_LRELU02, ACT_TANH24 = 0, 1, 2, 3
-UP_NONE, UP_BICUBIC, UP_BILINEAR = 0, 1, 2
-PREC_F32, PREC_F16 = 0, 1
-YUV_MATRIX = {'bt601': 0, 'bt709': 1}            # TG_YUV_BT601 / TG_YUV_BT709
-YUV_SITING = {'center': 0, 'left': 1}            # TG_YUV_CENTER / TG_YUV_LEFT
-
-P, I, I64, F, SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
-
-
-class FrnetCfg(C.Structure):
-    _fields_ = [(k, C.c_int) for k in
-                ('in_nc', 'out_nc', 'nf', 'nb', 'scale', 'up_mode', 'n', 'h', 'w', 'fnet_only')]
-
-
-class WinoLayer(C.Structure):
-    _fields_ = [('x', C.c_void_p), ('x2', C.c_void_p), ('u_packed', C.c_void_p), ('bias', C.c_void_p),
-                ('res', C.c_void_p), ('y', C.c_void_p), ('x_nstride', C.c_int64), ('x2_nstride', C.c_int64),
-                ('res_nstride', C.c_int64), ('y_nstride', C.c_int64), ('c1', C.c_int), ('cin', C.c_int),
-                ('act', C.c_int)]
-
-
-class ChainLayer(C.Structure):
-    _fields_ = [('x', C.c_void_p), ('x2', C.c_void_p), ('w_packed', C.c_void_p), ('bias', C.c_void_p),
-                ('res', C.c_void_p), ('relu_mask', C.c_void_p), ('y', C.c_void_p),
-                ('x_nstride', C.c_int64), ('x2_nstride', C.c_int64), ('res_nstride', C.c_int64),
-                ('mask_nstride', C.c_int64), ('y_nstride', C.c_int64),
-                ('c1', C.c_int), ('cin', C.c_int), ('cout', C.c_int), ('act', C.c_int)]
-
-
-class PackedLayer(C.Structure):
-    _fields_ = [('w', C.c_void_p), ('b', C.c_void_p)]
-
-
-class PackItem(C.Structure):
-    _fields_ = [('w', C.c_void_p), ('out', C.c_void_p), ('cin', C.c_int), ('cout', C.c_int), ('transposed', C.c_int),
-                ('i_total', C.c_int), ('i_off', C.c_int)]
-
-
-class WresConvT(C.Structure):
-    _fields_ = [('u_packed', C.c_void_p), ('bias', C.c_void_p), ('y', C.c_void_p), ('act', C.c_int)]
-
-
-class LayerWeights(C.Structure):
-    _fields_ = [('w', C.c_void_p), ('b', C.c_void_p), ('u', C.c_void_p)]
-
-
-# name -> (restype, argtypes); must list every symbol include/tecogan_hip.h declares
-SIGNATURES = {
-    'tg_version': (I, []),
-    'tg_last_error_string': (C.c_char_p, []),
-    'tg_build_info': (C.c_char_p, []),
-    'tg_conv3x3_pick_ocb': (I, [I]),
-    'tg_conv3x3_packed_floats': (SZ, [I, I, I]),
-    'tg_conv3x3_pack': (I, [P, P, I, I, I, I, P]),
-    'tg_conv3x3_fwd': (I, [P, I64, I, P, I64, P, I, P, P, I64, P, I64, I, I, I, I, I, I, P]),
-    'tg_conv3x3_fwd_phased': (I, [P, I64, P, I, P, P, I64, I, I, I, I, I, I, I, I, I, I, P]),
-    'tg_conv3x3_fwd_phased_masked': (I, [P, I64, P, I, P, P, I64, P, I64, I, I, I, I, I, I, I, I, I, I, P]),
-    'tg_conv3x3s2_supported': (I, [I, I, I, I, I]),
-    'tg_conv3x3s2_fwd': (I, [P, I64, P, P, P, I64, P, I64, I, I, I, I, I, I, P]),
-    'tg_conv3x3_fwd_masked': (I, [P, I64, I, P, I64, P, I, P, P, I64, P, I64, P, I64, I, I, I, I, I, I, P]),
-    'tg_conv3x3_pick_ksplit': (I, [I, I, I, I, I]),
-    'tg_conv3x3_splitk_fwd': (I, [P, I64, I, P, I64, P, I, P, P, I, I, I, I, I, I, I, P, I, P]),
-    'tg_convt3x3s2_fwd': (I, [P, I64, P, P, P, I64, I, I, I, I, I, I, P]),
-    'tg_convt_pack_wz': (I, [P, P, I, I, P]),
-    'tg_convt3x3s2_z_fwd': (I, [P, I64, P, P, P, I, P, I64, I, I, I, I, I, I, P]),
-    'tg_convt3x3s2_z_fwd_form': (I, [P, I64, P, P, P, I, P, I64, I, I, I, I, I, I, I, P]),
-    'tg_convt_pack_wino': (I, [P, P, I, I, P]),
-    'tg_convt3x3s2_z_wino_fwd': (I, [P, I64, P, P, P, I, P, I64, I, I, I, I, I, I, I, P]),
-    'tg_convout_tail': (I, [P, I64, I, P, P, I, I, P, I64, P, I, I, I, P]),
-    'tg_convout_tail_form': (I, [P, I64, I, P, P, I, I, P, I64, P, I, I, I, I, P]),
-    'tg_conv3x3_small_fwd': (I, [P, I64, P, P, P, I, I, P, I64, I, I, I, I, I, I, P]),
-    'tg_conv3x3_fewin_fwd': (I, [P, I64, P, P, I64, P, I64, I, I, I, I, I, P]),
-    'tg_conv3x3_small_fwd_res': (I, [P, I64, P, P, P, I64, P, I64, I, I, I, I, I, I, P]),
-    'tg_conv3x3_small_fwd_u8': (I, [P, I64, P, P, P, I, I, P, I64, P, I, I, I, I, I, I, P]),
-    'tg_conv3x3_small_can_fuse_u8': (I, [P, I64, P, I64, I, I, I, I]),
-    'tg_flowup_warp_s2d_fwd': (I, [P, I, I, P, P, I64, P, I, I, I, I, I, I, P]),
-    'tg_copy_ceiling': (I, [P, P, I64, I, I, P]),
-    'tg_backward_warp_fwd': (I, [P, P, P, I, I, I, I, P]),
-    'tg_space_to_depth': (I, [P, P, I64, I, I, I, I, I, P]),
-    'tg_upsample_fwd': (I, [P, P, I, I, I, I, I, F, P]),
-    'tg_maxpool2_fwd': (I, [P, P, I, I, I, P]),
-    'tg_quantize_u8_hwc': (I, [P, P, I, I, I, P]),
-    'tg_dequantize_u8_hwc': (I, [P, P, I, I, I, I, P]),
-    'tg_yuv420_to_rgb_f32': (I, [P, P, I, I, I, I, I, I, P]),
-    'tg_rgb_u8_to_yuv420': (I, [P, P, I, I, I, I, I, I, P]),
-    'tg_scene_cut_workspace_bytes': (I64, [I]),
-    'tg_scene_cut_flags': (I, [P, I, I, I, C.c_uint64, C.c_uint64, P, I, P, P, P, P, I64, P]),
-    'tg_zero_if_flag': (I, [P, I64, P, P]),
-    'tg_downsample_bi_u8': (I, [P, P, P, I, I, I, I, I, P]),
-    'tg_downsample_bi_f32': (I, [P, P, P, I, I, I, I, I, P]),
-    'tg_psnr_sse_u8': (I, [P, P, P, I, I, I, I, P]),
-    'tg_luma_u8': (I, [P, P, I64, P]),
-    'tg_lpips_conv_fwd': (I, [P, P, I, P, P, P, P, I, I, I, I, I, I, I, I, P]),
-    'tg_maxpool3s2_fwd': (I, [P, P, I, I, I, P]),
-    'tg_lpips_head_workspace_bytes': (I64, [I, I, I]),
-    'tg_lpips_head': (I, [P, P, P, I, I, I, I, P, P, I, P, P]),
-    'tg_ssim_workspace_bytes': (I64, [I, I, I]),
-    'tg_ssim_y_u8': (I, [P, P, I, I, I, I, I, I, I, I, I, P, P, SZ, P]),
-    'tg_psnr_yfloat_partials': (I64, [I, I]),
-    'tg_psnr_yfloat_sse_u8': (I, [P, P, I, I, I, I, I, I, I, I, I, P, P]),
-    'tg_fb_level_size': (I, [I, I, I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    'tg_fb_gray_u8': (I, [P, I, I, I, I, I, P, P]),
-    'tg_fb_level_image': (I, [P, I, I, I, I, P, P, P]),
-    'tg_fb_polyexp': (I, [P, I, I, I, P, P]),
-    'tg_fb_update_matrices': (I, [P, P, P, I, I, I, P]),
-    'tg_fb_blur_solve': (I, [P, P, P, I, I, I, P]),
-    'tg_fb_resize_flow': (I, [P, I, I, P, I, I, I, P]),
-    'tg_farneback_workspace_bytes': (I64, [I, I, I]),
-    'tg_farneback_flow_u8': (I, [P, I, I, I, I, I, P, P, SZ, P]),
-    'tg_flow_epe_mean': (I, [P, P, I, I, I, I, I, I, I, P, P]),
-    'tg_wgrad3x3_workspace_floats': (SZ, [I, I, I, I, I]),
-    'tg_wgrad3x3': (I, [P, I64, P, I64, P, P, I, I, I, I, I, I, I, I, P]),
-    'tg_wgrad3x3_multi': (I, [P, P, I, I64, I64, P, P, I, I, I, I, I, I, I, I, P]),
-    'tg_wgrad3x3_multi_bias': (I, [P, P, I, I64, I64, P, P, P, I, I, I, I, I, I, I, I, P]),
-    'tg_wgrad3x3_multi_phased': (I, [P, P, I, I64, I64, P, P, I, I, I, I, I, I, I, I, I, P]),
-    'tg_conv3x3_phased_pick_ksplit': (I, [I, I, I, I, I, I]),
-    'tg_conv3x3_fwd_phased_splitk': (I, [P, I64, P, I, P, P, I, I, I, I, I, I, I, I, I, I, I, P, P]),
-    'tg_wgrad3x3_convt_workspace_floats': (SZ, [I, I, I, I, I]),
-    'tg_wgrad3x3_convt_multi': (I, [P, P, I, P, P, P, I, I, I, I, I, I, P]),
-    'tg_bias_grad_multi': (I, [P, I, P, I, I, I, I, P]),
-    'tg_act_bwd': (I, [P, P, P, I64, I, P]),
-    'tg_bias_grad': (I, [P, P, I, I, I, I, P]),
-    'tg_maxpool2_bwd': (I, [P, P, P, I, I, I, P]),
-    'tg_upsample_bwd': (I, [P, P, I, I, I, I, I, F, P]),
-    'tg_backward_warp_bwd': (I, [P, P, P, P, P, I, I, I, I, P]),
-    'tg_backward_warp_bwd_acc': (I, [P, P, P, P, P, I, I, I, I, P]),
-    'tg_conv3x3_wino_resident_ct_floats': (SZ, []),
-    'tg_conv3x3_wino_resident_ct_pack': (I, [P, P, P]),
-    'tg_conv3x3_wino_resident_ct': (I, [P, I, I, I, I, P, I, P, P]),
-    'tg_conv4x4s2_supported': (I, [I, I, I, I, I]),
-    'tg_conv4x4s2_packed_floats': (SZ, [I, I]),
-    'tg_conv4x4s2_pack': (I, [P, P, P, I, I, P]),
-    'tg_conv4x4s2_workspace_floats': (SZ, [I, I, I, I, I, I]),
-    'tg_conv4x4s2_fwd': (I, [P, P, P, P, I, I, I, I, I, P]),
-    'tg_conv4x4s2_dgrad': (I, [P, P, P, I, P, P, I, I, I, I, I, P]),
-    'tg_backward_warp_s2d_fwd': (I, [P, P, P, I, I, I, I, I, P]),
-    'tg_backward_warp_s2d_bwd': (I, [P, P, P, P, I, P, I, I, I, I, I, P]),
-    'tg_depth_to_space': (I, [P, P, I, I, I, I, I, P]),
-    'tg_depth_to_space_act_bwd_supported': (I, [P, P, P, I, I]),
-    'tg_depth_to_space_act_bwd': (I, [P, P, I, P, I, I, I, I, I, P]),
-    'tg_charbonnier': (I, [P, P, I64, F, F, P, F, P, P]),
-    'tg_channel_norm': (I, [P, P, P, P, I, I, I64, P]),
-    'tg_cosine_loss': (I, [P, P, I, I, I64, F, F, P, F, P, P]),
-    'tg_pixel_loss': (I, [P, P, I64, I, F, P, F, P, P]),
-    'tg_bce_logits': (I, [P, I64, F, F, P, F, P, P]),
-    'tg_lsgan_loss': (I, [P, I64, F, F, P, F, P, P]),
-    'tg_adam_step': (I, [P, P, P, P, I64, F, F, F, F, F, I, P]),
-    'tg_adam_step_guarded': (I, [P, P, P, P, I64, F, F, F, F, F, I, P, P]),
-    'tg_fault_to_slot': (I, [P, P, P]),
-    'tg_axpy': (I, [P, P, F, I64, P]),
-    'tg_div_scalar': (I, [P, P, F, I64, P]),
-    'tg_bn_lrelu_train_fwd': (I, [P, P, P, P, P, F, F, F, P, P, P, I, I, I, P]),
-    'tg_bn_lrelu_train_bwd': (I, [P, P, P, P, P, P, F, P, P, P, I, P, I, I, I, P]),
-    'tg_bn_launch_geometry': (I, [I, I, I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    'tg_bn_local_stats': (I, [P, P, I, I, I, P]),
-    'tg_bn_merge_stats': (I, [P, I, F, F, F, P, P, P, P, I, P]),
-    'tg_bn_lrelu_apply': (I, [P, P, P, P, P, F, P, I, I, I, P]),
-    'tg_bn_lrelu_bwd_reduce': (I, [P, P, P, P, P, F, P, I, I, I, P]),
-    'tg_bn_lrelu_bwd_apply': (I, [P, P, P, P, P, P, P, F, F, P, I, I, I, P]),
-    'tg_linear1_fwd': (I, [P, P, P, P, I, I, P]),
-    'tg_linear1_bwd': (I, [P, P, P, P, P, P, I, I, I, P]),
-    'tg_downsample_bd': (I, [P, P, P, I, I, I, I, I, I, P]),
-    'tg_conv3x3_wino_packed_floats': (I64, [I, I]),
-    'tg_conv3x3_wino_chain_flag_ints': (I64, [I, I, I, I]),
-    'tg_conv3x3_wino_chain': (I, [C.POINTER(WinoLayer), I, I, I, I, I, P, I, P]),
-    'tg_conv3x3_wino_resident_supported': (I, [I, I, I, I]),
-    'tg_conv3x3_wino_resident_ws_bytes': (I64, [I, I]),
-    'tg_conv3x3_wino_resident': (I, [C.POINTER(WinoLayer), I, I, I, I, P, I, P]),
-    'tg_conv3x3_chain_flag_ints': (I64, [I, I, I, I]),
-    'tg_conv3x3_chain_supported': (I, [I, I, I, I]),
-    'tg_conv3x3_pack16_floats': (SZ, []),
-    'tg_conv3x3_pack16': (I, [P, P, I, I, I, P]),
-    'tg_conv3x3_chain_packed_floats': (SZ, [I, I]),
-    'tg_conv3x3_chain_pack': (I, [P, I, I, P]),
-    'tg_conv3x3_chain': (I, [C.POINTER(ChainLayer), I, I, I, I, I, P, P, C.c_uint32, I, P]),
-    'tg_srnet_body_fwd': (I, [C.POINTER(PackedLayer), I, I, P, I, P, I, P, I, I, I, I, P, P, C.c_uint32, I, P]),
-    'tg_srnet_body_bwd': (I, [C.POINTER(PackedLayer), I, I, P, P, P, I, I, I, I, I, P, P, C.c_uint32, I, P]),
-    'tg_wgrad3x3_body_workspace_floats': (SZ, [I, I, I, I, I, I]),
-    'tg_wgrad3x3_body': (I, [P, P, I, I64, I, P, P, I, I, I, I, I, P]),
-    'tg_wgrad3x3_body_bias': (I, [P, P, I, I64, I, P, P, P, I, I, I, I, I, P]),
-    'tg_bias_grad_body': (I, [P, I, I64, I, P, I, I, I, P]),
-    'tg_conv3x3_prefers_wino': (I, [I, I, I, I, I]),
-    'tg_pack_conv3x3_wino': (I, [P, P, I, I, I, P]),
-    'tg_conv3x3_wino_fwd': (I, [P, I64, I, P, I64, P, P, P, I64, P, I64, P, I64, I, I, I, I, I, I, P]),
-    'tg_conv3x3_wino_fused_fwd': (I, [P, I64, P, P, P, I64, I, I, I, I, I, I, I, P]),
-    'tg_time_gather': (I, [P, P, P, I, I, I, I64, P]),
-    'tg_transpose01': (I, [P, P, I, I, I64, P]),
-    'tg_stack_time': (I, [P, I, P, I, I64, P]),
-    'tg_index_gather': (I, [P, P, P, I64, I64, I, P]),
-    'tg_pingpong_grad': (I, [P, P, I, I, I64, P]),
-    'tg_d_assemble_fwd': (I, [P, I, P, P, I, P, I, I, I, I, I, I, I, P]),
-    'tg_d_assemble_bwd': (I, [P, P, I, P, I, I, I, I, I, I, I, P]),
-    'tg_gather_clips_u8': (I, [P, P, P, P, I, I, I, I, P]),
-    'tg_comm_get_unique_id': (I, [P]),
-    'tg_comm_init_rank': (I, [P, I, I, C.POINTER(C.c_void_p)]),
-    'tg_comm_destroy': (I, [P]),
-    'tg_comm_world': (I, [P]),
-    'tg_comm_rank': (I, [P]),
-    'tg_comm_query': (I, [P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    'tg_comm_library_origin': (C.c_char_p, []),
-    'tg_allreduce_sum_f32': (I, [P, P, I64, P]),
-    'tg_allgather_f32': (I, [P, P, P, I64, P]),
-    'tg_frnet_workspace_floats': (SZ, [C.POINTER(FrnetCfg)]),
-    'tg_frnet_plan_create': (I, [C.POINTER(FrnetCfg), C.POINTER(LayerWeights), I, P,
-                                 C.POINTER(C.c_void_p)]),
-    'tg_frnet_plan_destroy': (None, [P]),
-    'tg_frnet_plan_chain_status': (I, [P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    'tg_frnet_plan_set_chain_poll_limit': (I, [P, I]),
-    'tg_frnet_plan_set_chain_rearm': (I, [P, I]),
-    'tg_frnet_plan_chain_rearms': (I, [P, P, P]),
-    'tg_frnet_plan_hold_chain_rearm': (I, [P, I]),
-    'tg_frnet_step': (I, [P, P, P, P, P, P, P]),
-    'tg_frnet_step_phase': (I, [P, I, I, P, P, P, P, P, P]),
-    'tg_frnet_plan_launches': (I, [P]),
-    'tg_frnet_plan_flow': (P, [P, I]),
-    'tg_frnet_step_srnet': (I, [P, P, P, P, P, P, P]),
-    'tg_frnet_plan_kinds': (I, []),
-    'tg_frnet_kind_name': (C.c_char_p, [I]),
-    'tg_frnet_plan_kind_stats': (I, [P, I, C.POINTER(C.c_int), C.POINTER(C.c_double),
-                                     C.POINTER(C.c_double)]),
-    'tg_frnet_replay': (I, [P, P, P, P, P, C.c_uint, I, P]),
-    'tg_frnet_step_masked': (I, [P, P, P, P, P, P, C.c_uint, P]),
-    'tg_conv3x3_f16_supported': (I, [I, I, I, I, I]),
-    'tg_conv3x3_f16_packed_halves': (SZ, [I, I]),
-    'tg_conv3x3_f16_act_halves': (I64, [I, I, I]),
-    'tg_conv3x3_f16_pack_weights': (I, [P, I, I, I, P, P]),
-    'tg_conv3x3_f16_pack_input': (I, [P, I64, I, P, I64, I, P, I, I, I, P]),
-    'tg_conv3x3_f16_fwd': (I, [P, P, P, P, P, I, I, I, I, I, I, P]),
-    'tg_convt3x3s2_f16_fwd': (I, [P, P, P, P, I64, I, I, I, I, I, I, P]),
-    'tg_frnet_f16_workspace_bytes': (SZ, [C.POINTER(FrnetCfg)]),
-    'tg_frnet_plan_set_precision': (I, [P, I, C.POINTER(LayerWeights), I, P]),
-    'tg_frnet_plan_precision': (I, [P]),
-}
-
-_lib = None
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'tecogan_hip.h')
 
 
 class TecoganHipError(RuntimeError):
     pass
+
+
+# The type rule, whole: these by value; `typedef void* NAME` handles by value, and every pointer or array
+# parameter, as c_void_p (the pointee cannot tell device memory from a host out-parameter) -- except a single
+# pointer to a struct whose fields the header declares: POINTER(that Structure).  Returns: the same, with
+# `const char*` -> c_char_p and `void` -> None.
+_SCALARS = {'int': C.c_int, 'int32_t': C.c_int32, 'int64_t': C.c_int64, 'unsigned': C.c_uint,
+            'uint32_t': C.c_uint32, 'uint64_t': C.c_uint64, 'size_t': C.c_size_t,
+            'float': C.c_float, 'double': C.c_double}
+_POINTEES = set(_SCALARS) | {'void', 'char', 'uint8_t', 'uint16_t'}       # may stand behind a `*`
+_DECLARATOR = re.compile(r'(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\s*)?)*)(\w+)?\s*(\[\s*\w*\s*\])?')
+
+Header = collections.namedtuple('Header', 'constants structs signatures')
+
+
+def parse_header(text):
+    """Header(constants {TG_NAME: int}, structs {C name: Structure class}, signatures {tg_name: (restype,
+    argtypes)}) of header text.  Raises TecoganHipError naming the declaration it does not fully understand."""
+    constants, structs, signatures, handles, opaque = {}, {}, {}, set(), set()
+
+    def refuse(decl, why):
+        raise TecoganHipError(f'tecogan_hip.h: `{" ".join(decl.split())}`: {why}')
+
+    def integer(expr, decl):
+        """-1, 0x10, (16 * 64 * 64)"""
+        expr = expr.strip()
+        factors = expr[1:-1] if expr.startswith('(') and expr.endswith(')') else expr
+        try:
+            return math.prod(int(f, 0) for f in factors.split('*'))
+        except ValueError:
+            refuse(decl, f'`{expr}` is not an integer or a product of integers')
+
+    def ctype(part, decl, where):
+        """(ctypes type, declared name) of one parameter / field / return type."""
+        m = _DECLARATOR.fullmatch(part.strip())
+        if not m:
+            refuse(decl, f'cannot parse `{part.strip()}`')
+        base, stars, name, array = m.group(1), m.group(2).count('*'), m.group(3), m.group(4)
+        if (where == 'return') != (name is None) or (array and where != 'param'):
+            refuse(decl, f'cannot parse `{part.strip()}`')
+        if not stars and not array:
+            if base in _SCALARS:
+                return _SCALARS[base], name
+            if base in handles:
+                return C.c_void_p, name
+            if base == 'void' and where == 'return':
+                return None, name
+            refuse(decl, f'`{base}` is not a type this binding passes by value')
+        if base not in _POINTEES and base not in handles and base not in structs and base not in opaque:
+            refuse(decl, f'unknown type `{base}`')
+        if stars == 1 and not array and base in structs and where != 'field':
+            return C.POINTER(structs[base]), name
+        return (C.c_char_p if base == 'char' and where == 'return' else C.c_void_p), name
+
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    code, in_cplusplus = [], False
+    for line in text.splitlines():
+        s = line.strip()
+        if s == '#ifdef __cplusplus':
+            in_cplusplus = True
+        elif in_cplusplus:
+            if s not in ('extern "C" {', '}', '#endif', ''):
+                refuse(s, 'unexpected inside #ifdef __cplusplus')
+            in_cplusplus = s != '#endif'
+        elif s.startswith('#'):
+            m = re.fullmatch(r'#\s*define\s+(TG_\w+)\s+(.+)', s)
+            if m:
+                constants[m.group(1)] = integer(m.group(2), s)
+            elif not re.fullmatch(r'#\s*(include\s*<\w+\.h>|ifndef\s+TECOGAN_HIP_H|define\s+TECOGAN_HIP_H|endif)', s):
+                refuse(s, 'preprocessor line outside the parsing contract')
+        else:
+            code.append(line)
+
+    # a declaration ends at a `;` outside braces
+    code, decls, depth, start = '\n'.join(code), [], 0, 0
+    for m in re.finditer(r'[;{}]', code):
+        depth += (m.group() == '{') - (m.group() == '}')
+        if m.group() == ';' and depth == 0:
+            decls.append(code[start:m.start()].strip())
+            start = m.end()
+    if code[start:].strip():
+        refuse(code[start:], 'declaration without its `;`')
+    for decl in decls:
+        m = re.fullmatch(r'typedef\s+void\s*\*\s*(\w+)', decl)
+        if m:
+            handles.add(m.group(1))
+            continue
+        m = re.fullmatch(r'typedef\s+struct\s+(\w+)\s+(\w+)', decl)
+        if m:
+            opaque.add(m.group(2))
+            continue
+        m = re.fullmatch(r'enum\s*\{([^{}]*)\}', decl)
+        if m:
+            for item in filter(None, (i.strip() for i in m.group(1).split(','))):
+                k = re.fullmatch(r'(TG_\w+)\s*=\s*(.+)', item, flags=re.S)
+                if not k:
+                    refuse(decl, f'enumerator `{item}` needs the form TG_NAME = integer')
+                constants[k.group(1)] = integer(k.group(2), decl)
+            continue
+        m = re.fullmatch(r'typedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)', decl)
+        if m:
+            fields = []
+            for stmt in filter(None, (s.strip() for s in m.group(1).split(';'))):
+                first, *more = stmt.split(',')
+                typ, name = ctype(first, decl, 'field')
+                if more and (typ is C.c_void_p or not all(re.fullmatch(r'\s*\w+\s*', n) for n in more)):
+                    refuse(decl, f'`{stmt}`: only plain scalars may share one declaration')
+                fields += [(n.strip(), typ) for n in [name] + more]
+            structs[m.group(2)] = type(m.group(2), (C.Structure,), {'_fields_': fields})
+            continue
+        m = re.fullmatch(r'([\w\s*]+?)\b(tg_\w+)\s*\((.*)\)', decl, flags=re.S)
+        if not m or '(' in m.group(3) or '{' in decl or m.group(2) in signatures:
+            refuse(decl, 'not a declaration this binding understands, or declared twice')
+        params = m.group(3).strip()
+        signatures[m.group(2)] = (ctype(m.group(1), decl, 'return')[0],
+                                  [] if params == 'void' else [ctype(p, decl, 'param')[0] for p in params.split(',')])
+    return Header(constants, structs, signatures)
+
+
+try:
+    with open(HEADER_PATH) as _f:
+        _HEADER = parse_header(_f.read())
+except OSError as e:
+    raise TecoganHipError(f'{HEADER_PATH}: cannot read the C ABI header this binding is derived from ({e})')
+
+globals().update(_HEADER.constants)                 # every enumerator and integer #define: _lib.TG_<NAME>
+_K = _HEADER.constants
+TG_OK, ABI_MAJOR = _K['TG_OK'], _K['TG_ABI_MAJOR']
+ACT_NONE, ACT_RELU, ACT_LRELU02, ACT_TANH24 = (_K['TG_ACT_' + k] for k in ('NONE', 'RELU', 'LRELU02', 'TANH24'))
+UP_NONE, UP_BICUBIC, UP_BILINEAR = (_K['TG_UP_' + k] for k in ('NONE', 'BICUBIC', 'BILINEAR'))
+PREC_F32, PREC_F16 = _K['TG_PREC_F32'], _K['TG_PREC_F16']
+YUV_MATRIX = {'bt601': _K['TG_YUV_BT601'], 'bt709': _K['TG_YUV_BT709']}
+YUV_SITING = {'center': _K['TG_YUV_CENTER'], 'left': _K['TG_YUV_LEFT']}
+
+STRUCTS = _HEADER.structs                           # C name -> Structure class
+FrnetCfg, WinoLayer, ChainLayer = STRUCTS['tg_frnet_cfg'], STRUCTS['tg_wino_layer'], STRUCTS['tg_chain_layer']
+PackedLayer, PackItem = STRUCTS['tg_packed_layer'], STRUCTS['tg_pack_item']
+WresConvT, LayerWeights = STRUCTS['tg_wres_convt'], STRUCTS['tg_layer_weights']
+
+SIGNATURES = _HEADER.signatures                     # name -> (restype, argtypes)
+
+_lib = None
 
 
 def lib():
@@ -267,10 +180,10 @@ def lib():
         # runtimes coexist and ours sees no device.
         import torch  # noqa: F401
         handle = C.CDLL(LIB_PATH)
-        handle.tg_version.restype = I
+        handle.tg_version.restype = C.c_int
         if handle.tg_version() // 100 != ABI_MAJOR:
-            raise TecoganHipError(f'{LIB_PATH}: ABI {handle.tg_version()} but this binding is written for '
-                                  f'major {ABI_MAJOR} (include/tecogan_hip.h TG_ABI_MAJOR): rebuild the library')
+            raise TecoganHipError(f'{LIB_PATH}: ABI {handle.tg_version()} but include/tecogan_hip.h declares '
+                                  f'TG_ABI_MAJOR {ABI_MAJOR}: rebuild the library')
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(handle, name)      # AttributeError if a symbol is missing
             fn.restype = res

@@ -292,7 +292,7 @@ def convt_pack_wino(wpk, cin, cout):
     """tg_convt_pack_wino: the 16 Winograd-domain weight matrices of tg_convt3x3s2_z_wino_fwd from the direct form's
     packed ConvTranspose2d weights (pack_conv3x3(weight, transposed=True)[0])."""
     _chk(wpk, 'wpk')
-    wa = torch.empty(16 * 64 * 64, dtype=torch.float32, device=wpk.device)
+    wa = torch.empty(L.TG_CONVT_WINO_FLOATS, dtype=torch.float32, device=wpk.device)
     L.check(L.lib().tg_convt_pack_wino(wpk.data_ptr(), wa.data_ptr(), cin, cout, _stream()), 'tg_convt_pack_wino')
     return wa
 
@@ -1098,7 +1098,7 @@ def charbonnier(x, y, loss_accum, loss_scale, grad_scale=None, eps=1e-6):
     return dx
 
 
-LOSS_L1, LOSS_MSE = 1, 2
+LOSS_L1, LOSS_MSE = L.TG_LOSS_L1, L.TG_LOSS_MSE
 
 
 def pixel_loss(x, y, mode, loss_accum, loss_scale, grad_scale=None):
@@ -1243,7 +1243,7 @@ def downsample_bd(x, kernel2d, scale, pad):
     return y
 
 
-BI_TILE = (8, 32)        # LR pixels one workgroup of tg_downsample_bi_* makes (TG_BI_TILE_H, TG_BI_TILE_W)
+BI_TILE = (L.TG_BI_TILE_H, L.TG_BI_TILE_W)      # LR pixels one workgroup of tg_downsample_bi_* makes
 BI_BORDER_LR = 2         # pad=False: LR pixels cut from every side (= 2 * scale GT pixels of border)
 
 
@@ -1458,7 +1458,7 @@ def pack_conv3x3_wino(w, transposed=0):
     return out
 
 
-WINO_POOL, WINO_UP2 = 1, 2       # TG_WINO_POOL / TG_WINO_UP2
+WINO_POOL, WINO_UP2 = L.TG_WINO_POOL, L.TG_WINO_UP2
 
 
 def conv3x3_wino(x, u_packed, bias, cin, cout, act=ACT_NONE, x2=None, res=None, mask=None, out=None, pool=False,

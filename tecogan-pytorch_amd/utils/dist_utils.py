@@ -99,7 +99,7 @@ def reduce_sum_to_master(values, device='cpu'):
 # (CPU tests, or two test ranks sharing one GPU -- RCCL refuses duplicate devices) stages
 # device tensors through the host.  TECOGAN_COMM=c_abi routes the same calls through the
 # C-ABI communicator (include/tecogan_hip.h tg_comm_*, tg_allreduce_sum_f32,
-# tg_allgather_f32); the 128-byte unique id is shipped over the existing process group.
+# tg_allgather_f32); the TG_COMM_ID_BYTES unique id is shipped over the existing process group.
 # ---------------------------------------------------------------------------
 class _Done:
     def wait(self):
@@ -119,12 +119,12 @@ def _c_comm():
         rank, world = get_dist_info()
         ident = [None]
         if rank == 0:
-            buf = (ctypes.c_uint8 * 128)()
+            buf = (ctypes.c_uint8 * L.TG_COMM_ID_BYTES)()
             L.check(lib.tg_comm_get_unique_id(buf), 'tg_comm_get_unique_id')
             ident[0] = bytes(buf)
         if world > 1:
             dist.broadcast_object_list(ident, src=0)
-        buf = (ctypes.c_uint8 * 128).from_buffer_copy(ident[0])
+        buf = (ctypes.c_uint8 * L.TG_COMM_ID_BYTES).from_buffer_copy(ident[0])
         handle = ctypes.c_void_p()
         L.check(lib.tg_comm_init_rank(buf, world, rank, ctypes.byref(handle)), 'tg_comm_init_rank')
         _C_COMM = handle

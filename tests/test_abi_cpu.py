@@ -6,6 +6,7 @@ launched here."""
 import ctypes
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -35,6 +36,114 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(handle, s), f'{s} declared in tecogan_hip.h but not exported'
     # and the Python binding table covers the header exactly
     assert sorted(L.SIGNATURES) == syms
+
+
+def test_derived_signatures_match_hand_written_expectations():
+    """_lib.SIGNATURES is parsed from the header.  These entries, written out by hand, cover between them every
+    construct the parser handles."""
+    P, I, I64, F, SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
+    U64, PTR = ctypes.c_uint64, ctypes.POINTER
+    expected = {
+        'tg_version': (I, []),                                                      # (void)
+        'tg_last_error_string': (ctypes.c_char_p, []),                              # const char* return
+        'tg_frnet_plan_destroy': (None, [P]),                                       # void return
+        'tg_frnet_plan_flow': (P, [P, I]),                                          # float* return
+        'tg_conv3x3_packed_floats': (SZ, [I, I, I]),                                # size_t return
+        'tg_conv3x3_wino_packed_floats': (I64, [I, I]),                             # int64_t return
+        'tg_conv3x3_fwd': (I, [P, I64, I, P, I64, P, I, P, P, I64, P, I64, I, I, I, I, I, I, P]),
+        'tg_charbonnier': (I, [P, P, I64, F, F, P, F, P, P]),                       # floats
+        'tg_scene_cut_flags': (I, [P, I, I, I, U64, U64, P, I, P, P, P, P, I64, P]),    # uint64_t by value
+        'tg_frnet_replay': (I, [P, P, P, P, P, ctypes.c_uint, I, P]),               # unsigned
+        'tg_ssim_y_u8': (I, [P, P, I, I, I, I, I, I, I, I, I, P, P, SZ, P]),         # size_t parameter, double* device
+        'tg_wgrad3x3_multi': (I, [P, P, I, I64, I64, P, P, I, I, I, I, I, I, I, I, P]),     # const float* const*
+        'tg_comm_init_rank': (I, [P, I, I, P]),                                     # array parameter, tg_comm**
+        'tg_conv3x3_chain': (I, [PTR(L.ChainLayer), I, I, I, I, I, P, P, ctypes.c_uint32, I, P]),
+        'tg_frnet_plan_create': (I, [PTR(L.FrnetCfg), PTR(L.LayerWeights), I, P, P]),       # two struct pointers
+        'tg_frnet_plan_kind_stats': (I, [P, I, P, P, P]),                           # host scalar out-parameters
+    }
+    for name, (res, args) in expected.items():
+        got_res, got_args = L.SIGNATURES[name]
+        assert got_res is res, name
+        assert len(got_args) == len(args), name
+        for i, (g, e) in enumerate(zip(got_args, args)):
+            assert g is e, f'{name}: argument {i} is {g}, expected {e}'
+
+
+STRUCT_NAMES = {'tg_frnet_cfg': 'FrnetCfg', 'tg_wino_layer': 'WinoLayer', 'tg_chain_layer': 'ChainLayer',
+                'tg_packed_layer': 'PackedLayer', 'tg_pack_item': 'PackItem', 'tg_wres_convt': 'WresConvT',
+                'tg_layer_weights': 'LayerWeights'}
+
+
+def test_struct_layouts_match_the_c_compiler(tmp_path):
+    """sizeof and every offsetof of the seven structs, as gcc lays the header out, against the derived Structures."""
+    assert sorted(L.STRUCTS) == sorted(STRUCT_NAMES)
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "tecogan_hip.h"', 'int main(void) {']
+    for c_name, py_name in STRUCT_NAMES.items():
+        cls = getattr(L, py_name)
+        assert cls is L.STRUCTS[c_name]
+        lines.append(f'  printf("{c_name} %zu\\n", sizeof({c_name}));')
+        for field, _ in cls._fields_:
+            lines.append(f'  printf("{c_name}.{field} %zu\\n", offsetof({c_name}, {field}));')
+    lines += ['  return 0;', '}']
+    (tmp_path / 'layout.c').write_text('\n'.join(lines) + '\n')
+    exe = str(tmp_path / 'layout')
+    subprocess.run(['gcc', '-I', os.path.join(ROOT, 'include'), '-o', exe, str(tmp_path / 'layout.c')], check=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=60).stdout
+    c_layout = {k: int(v) for k, v in (line.split() for line in out.splitlines())}
+    py_layout = {}
+    for c_name, py_name in STRUCT_NAMES.items():
+        cls = getattr(L, py_name)
+        py_layout[c_name] = ctypes.sizeof(cls)
+        for field, _ in cls._fields_:
+            py_layout[f'{c_name}.{field}'] = getattr(cls, field).offset
+    assert py_layout == c_layout
+    assert c_layout['tg_layer_weights'] == 24            # the header's ABI note: 24 bytes since major 2
+    assert sum(len(getattr(L, p)._fields_) for p in STRUCT_NAMES.values()) == 55
+
+
+@pytest.mark.parametrize('text,named', [
+    ('int tg_good(int a);\nint tg_bad(const float* x, wchar_t y);\n', 'tg_bad'),                   # unknown type
+    ('int tg_cb(const float* x, void (*done)(int), int n);\n', 'tg_cb'),                           # function pointer
+    ('typedef struct { int a; struct { int b; } c; } tg_nested;\n', 'tg_nested'),                  # nested struct
+    ('typedef struct { int a : 3; } tg_bits;\n', 'tg_bits'),                                       # bit-field
+    ('typedef struct { int a; float v[4]; } tg_arr;\n', 'tg_arr'),                                 # neither scalar nor pointer
+    ('typedef struct { tg_unknown_t a; } tg_field;\n', 'tg_field'),
+    ('int tg_long(unsigned long n);\n', 'tg_long'),                                                # two-word type
+    ('#define TG_NAME "text"\n', 'TG_NAME'),
+    ('enum { TG_A, TG_B };\n', 'TG_A'),
+    ('int tg_unterminated(int a)\n', 'tg_unterminated'),
+])
+def test_parser_refuses_what_it_does_not_understand(text, named):
+    with pytest.raises(L.TecoganHipError) as e:
+        L.parse_header(text)
+    assert named in str(e.value)
+
+
+def test_parser_on_a_small_header():
+    h = L.parse_header('/* c */\n#define TG_N (2 * 3)\nenum { TG_A = -1, TG_B = 0x10 };\ntypedef void* tg_h;\n'
+                       'typedef struct tg_o tg_o;\ntypedef struct { const float* p; int a, b; } tg_s;\n'
+                       'void tg_f(const tg_s* s, tg_o** o, tg_h h, const uint8_t id[TG_N], /* why */ double d);\n')
+    assert h.constants == {'TG_N': 6, 'TG_A': -1, 'TG_B': 16}
+    assert h.structs['tg_s']._fields_ == [('p', ctypes.c_void_p), ('a', ctypes.c_int), ('b', ctypes.c_int)]
+    assert h.signatures == {'tg_f': (None, [ctypes.POINTER(h.structs['tg_s']), ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_double])}
+
+
+def test_abi_constants_keep_their_values():
+    """The constants the package used before it read them from the header, against a literal table."""
+    assert (L.ACT_NONE, L.ACT_RELU, L.ACT_LRELU02, L.ACT_TANH24) == (0, 1, 2, 3)
+    assert (L.TG_ACT_NONE, L.TG_ACT_RELU, L.TG_ACT_LRELU02, L.TG_ACT_TANH24) == (0, 1, 2, 3)
+    assert (L.UP_NONE, L.UP_BICUBIC, L.UP_BILINEAR) == (0, 1, 2)
+    assert (L.TG_OK, L.TG_E_SHAPE, L.TG_E_ARG, L.TG_E_HIP) == (0, -1, -2, -3)
+    assert (L.PREC_F32, L.PREC_F16) == (0, 1)
+    assert L.YUV_MATRIX == {'bt601': 0, 'bt709': 1} and L.YUV_SITING == {'center': 0, 'left': 1}
+    assert (L.TG_WINO_POOL, L.TG_WINO_UP2) == (1, 2)
+    assert (L.TG_LOSS_L1, L.TG_LOSS_MSE) == (1, 2)
+    assert L.TG_CONVT_WINO_FLOATS == 65536 and L.TG_COMM_ID_BYTES == 128
+    assert (L.TG_BI_TILE_H, L.TG_BI_TILE_W) == (8, 32)
+    assert L.TG_ABI_MAJOR == 2 and L.ABI_MAJOR == 2
+    from tecogan_pytorch_amd import ops
+    assert (ops.WINO_POOL, ops.WINO_UP2, ops.LOSS_L1, ops.LOSS_MSE, ops.BI_TILE) == (1, 2, 1, 2, (8, 32))
 
 
 def test_error_codes_not_exceptions():

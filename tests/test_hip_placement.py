@@ -28,11 +28,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tecogan_pytorch_amd._lib import TG_E_SHAPE, TG_E_ARG
 from tests.placement import Arena, PLACEMENTS, extent_floats
 
 pytestmark = pytest.mark.gpu
 
-TG_E_SHAPE, TG_E_ARG = -1, -2
 N = 2                            # image 1 exists in every case
 
 

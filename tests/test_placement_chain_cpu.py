@@ -15,12 +15,12 @@ import ctypes
 import pytest
 import torch
 
+from tecogan_pytorch_amd._lib import TG_E_SHAPE
 from tests import test_hip_placement_chain as G
 from tests.placement import Arena, GUARD
 from tests.test_hip_placement import al
 
 N = G.N
-TG_E_SHAPE = -1
 
 
 @pytest.fixture(scope='module')

@@ -276,6 +276,15 @@ int tg_conv3x3_wino_resident_supported(int n, int cout, int h, int w);
 int64_t tg_conv3x3_wino_resident_ws_bytes(int h, int w);
 int tg_conv3x3_wino_resident(const tg_wino_layer* layers, int n_layers, int cout, int h, int w,
                              void* workspace, int epoch, tg_stream_t stream);
+/* The launch's hand-over geometry, on the host (no device work): where workgroup `block` (row-major over
+ * ceil(h/8) x ceil(w/24)) finds pixel `ring_pixel` of its one-pixel ring (0..25 the row above the block from its
+ * top-left corner, 26..51 the row below, 52..59 the column to the left, 60..67 the column to the right).  The kernel
+ * tabulates the same function once per launch.  Writes the block that owns the pixel, the slot (0..63: top row,
+ * bottom row 24.., left column 48.., right column 56..) under which that block publishes it, and the pixel's float
+ * offset inside a channel of the LDS block (row stride 28); returns 1, or 0 for a pixel outside the image (owner and
+ * slot are then -1), TG_E_SHAPE for odd or non-positive h / w, TG_E_ARG for a bad block, ring pixel or pointer. */
+int tg_conv3x3_wino_resident_ring_item(int h, int w, int block, int ring_pixel, int* owner_block, int* owner_slot,
+                                       int* lds_offset);
 /* The same launch with SRNet's FIRST up-sampling layer (nn.ConvTranspose2d(64, 64, 3, 2, 1, output_padding=1) + ReLU,
  * tecogan_nets.py:119-126) as its tail: after the last conv layer's ring exchange every workgroup applies the
  * transposed convolution to its resident 8x24 block (+1 ring pixel right / below) and writes convt->y

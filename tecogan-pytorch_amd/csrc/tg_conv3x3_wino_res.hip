@@ -65,7 +65,36 @@ constexpr int WR_POLL_SLEEP = 2;                  // s_sleep units (64 cycles) b
 constexpr int WR_ACT_FLOATS = 2 * WR_NC * WR_CS;   // the two activation buffers: 147 456 bytes
 constexpr int WR_BIAS_OFF = WR_ACT_FLOATS;          // [layer][64] biases (read once per launch)
 constexpr int WR_SYNC_OFF = WR_BIAS_OFF + WR_MAXL * WR_NC;   // 16 bytes: arrival counter of the boundary waves
-constexpr size_t WR_LDS_BYTES = (size_t)(WR_SYNC_OFF + 4) * sizeof(float);   // 153 616 of 163 840
+constexpr int WR_NRING = 2 * (WR_BW + 2) + 2 * WR_BH;   // 68 ring pixels: top 26, bottom 26, left 8, right 8
+constexpr int WR_RING_TAB = 80;                   // ring table entries: a boundary thread's five pixels are pi, pi + 16, ... <= 79
+constexpr int WR_RING_OFF = WR_SYNC_OFF + 4;      // [80] one word per ring pixel, filled once per launch (wres_ring_item)
+constexpr size_t WR_LDS_BYTES = (size_t)(WR_RING_OFF + WR_RING_TAB) * sizeof(float);   // 153 936 of 163 840
+static_assert(WR_RING_OFF % 4 == 0 && WR_NRING <= WR_RING_TAB && WR_LDS_BYTES <= 163840, "ring table placement");
+
+// Ring pixel pi = 0..67 of block (bx, by) -- top row, bottom row, left column, right column of the block's one-pixel
+// ring -- and where the hand-over finds it: the block that owns the pixel, the slot under which that block publishes
+// it (top row 0.., bottom row WR_BW.., left column 2 WR_BW.., right column 2 WR_BW + WR_BH..: see `pub` in the kernel)
+// and the pixel's place in the LDS block.  valid = 0: the pixel lies outside the image (it is never fetched and stays 0).
+// A function of (h, w, block, pixel) only: the kernel tabulates it once per launch, the host exports it for the tests.
+struct WResRingItem { int valid, owner, slot, lds; };
+__host__ __device__ inline WResRingItem wres_ring_item(int h, int w, int nbx, int bx, int by, int pi) {
+  int ry, rx;
+  if (pi < WR_BW + 2) { ry = 0; rx = pi; }
+  else if (pi < 2 * (WR_BW + 2)) { ry = WR_BH + 1; rx = pi - (WR_BW + 2); }
+  else if (pi < 2 * (WR_BW + 2) + WR_BH) { ry = pi - 2 * (WR_BW + 2) + 1; rx = 0; }
+  else { ry = pi - 2 * (WR_BW + 2) - WR_BH + 1; rx = WR_BW + 1; }
+  const int gy = by * WR_BH - 1 + ry, gx = bx * WR_BW - 1 + rx;
+  WResRingItem it{0, -1, -1, ry * WR_RS + rx};
+  if (gy >= 0 && gy < h && gx >= 0 && gx < w) {
+    const int sby = gy / WR_BH, sbx = gx / WR_BW;
+    const int ly = gy - sby * WR_BH, lx = gx - sbx * WR_BW;
+    // which of the owner's published rows / columns holds the pixel
+    it.slot = ry == 0 ? WR_BW + lx : (ry == WR_BH + 1 ? lx : (rx == 0 ? 2 * WR_BW + WR_BH + ly : 2 * WR_BW + ly));
+    it.owner = sby * nbx + sbx;
+    it.valid = 1;
+  }
+  return it;
+}
 
 // Tile (ty * 12 + tx) of lane n = 0..15 of group g.  Group 2 holds INTERIOR tiles only (rows 1-2, columns
 // 1..10: their 4x4 windows never touch the ring), so its four waves start the next layer right behind the
@@ -121,6 +150,14 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
     for (int i = t; i < WR_ACT_FLOATS / 4; i += WR_THREADS) z[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int i = t; i < a.nlayer * WR_NC; i += WR_THREADS) s_act[WR_BIAS_OFF + i] = a.L[i >> 6].bias[i & 63];
     if (t == 0) *reinterpret_cast<unsigned*>(s_act + WR_SYNC_OFF) = 0u;
+    // the ring table: (owner block * 64 + slot + 1) << 16 | LDS offset of the pixel; high half 0 = nothing to fetch
+    // (a pixel outside the image, an entry past the ring).  owner * 64 + slot + 1 <= 2^16: at most 1023 blocks, and
+    // the launcher admits one per CU.  The hand-over of every layer decodes it instead of deriving it again.
+    if (t < WR_RING_TAB) {
+      const WResRingItem it = wres_ring_item(a.h, a.w, a.nbx, bx, by, t);
+      reinterpret_cast<unsigned*>(s_act + WR_RING_OFF)[t] =
+          t < WR_NRING && it.valid ? (unsigned)(it.owner * WR_SLOTS + it.slot + 1) << 16 | (unsigned)it.lds : 0u;
+    }
   }
   unsigned* const s_cnt = reinterpret_cast<unsigned*>(s_act + WR_SYNC_OFF);
   __syncthreads();
@@ -388,36 +425,32 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
     __syncthreads();
     if (interior) continue;
     {
-      constexpr int NRING = 2 * (WR_BW + 2) + 2 * WR_BH;           // 68
-      constexpr int ITEMS = NRING * (WR_NC / 2);                   // 2176
+      constexpr int ITEMS = WR_NRING * (WR_NC / 2);                // 2176: 68 ring pixels x 32 channel pairs
       constexpr int NBT = 512;
       constexpr int PER_T = (ITEMS + NBT - 1) / NBT;               // 5 (4.25 on average)
+      static_assert((NBT / 32) * (PER_T - 1) + NBT / 32 <= WR_RING_TAB, "every item of a boundary thread has a table entry");
       const unsigned target = a.base + (unsigned)(L + 1);
       unsigned off[PER_T];
       int ho[PER_T];
       unsigned pend = 0;
       int tt = t;
-      asm volatile("" : "+v"(tt));            // keeps this geometry out of the K loop's register budget (it would be hoisted and spilled)
+      asm volatile("" : "+v"(tt));            // keeps the decoded geometry out of the K loop's register budget (it would be hoisted and spilled)
+      // Item tt + 512 k is (ring pixel (tt >> 5) + 16 k, channel pair tt & 31): the pixel's word of the ring table (the
+      // 32 lanes of a half-wave read the same one), the thread's own channel pair, and the layer's parity -- one
+      // wave-uniform term.  (Derived from (h, w, block, thread) in every hand-over it was ~230 VALU and
+      // ~205 SALU instructions in front of the first ring load, 21 times per launch: EXPERIMENTS.md, "ring table".)
+      const unsigned* tab = reinterpret_cast<const unsigned*>(s_act + WR_RING_OFF) + (tt >> 5);
+      const unsigned c2 = (unsigned)tt & 31u;
+      const unsigned obase = ((unsigned)((L & 1) * nwg) * WR_SLOTS - 1u) * (WR_NC / 2 * 16u) + c2 * 16u;   // (the entry's + 1)
+      const int hbase = (int)(2u * c2) * WR_CS;
+      unsigned po = 0u;                       // the probe: the thread's lowest pending item
+      int ph = 0;
 #pragma unroll
-      for (int k = 0; k < PER_T; ++k) {
-        const int item = tt + k * NBT;
-        const int pi = item >> 5, c2 = item & 31;
-        int ry, rx;
-        if (pi < WR_BW + 2) { ry = 0; rx = pi; }
-        else if (pi < 2 * (WR_BW + 2)) { ry = WR_BH + 1; rx = pi - (WR_BW + 2); }
-        else if (pi < 2 * (WR_BW + 2) + WR_BH) { ry = pi - 2 * (WR_BW + 2) + 1; rx = 0; }
-        else { ry = pi - 2 * (WR_BW + 2) - WR_BH + 1; rx = WR_BW + 1; }
-        const int gy = Y0 - 1 + ry, gx = X0 - 1 + rx;
-        off[k] = 0u; ho[k] = 0;
-        if (item < ITEMS && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w) {
-          const int sby = gy / WR_BH, sbx = gx / WR_BW;
-          const int ly = gy - sby * WR_BH, lx = gx - sbx * WR_BW;
-          // which of the owner's published rows / columns holds the pixel
-          const int slot = ry == 0 ? WR_BW + lx : (ry == WR_BH + 1 ? lx : (rx == 0 ? 2 * WR_BW + WR_BH + ly : 2 * WR_BW + ly));
-          off[k] = ((unsigned)(((L & 1) * nwg + sby * a.nbx + sbx) * WR_SLOTS + slot) * (WR_NC / 2) + (unsigned)c2) * 16u;
-          ho[k] = (2 * c2) * WR_CS + ry * WR_RS + rx;
-          pend |= 1u << k;
-        }
+      for (int k = PER_T - 1; k >= 0; --k) {
+        const unsigned e = tab[k * (NBT / 32)];
+        off[k] = (e >> 16) * (WR_NC / 2 * 16u) + obase;
+        ho[k] = hbase + (int)(e & 0xffffu);
+        if (e >> 16) { pend |= 1u << k; po = off[k]; ph = ho[k]; }
       }
       // (plain scalars, initialised: with a vector array left undefined for items that are not pending the
       // compiler stored element 0 of an item into BOTH channels of its pair -- found on the GPU, round 4)
@@ -427,19 +460,40 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
       // While the neighbours are still computing, a thread polls ONE of its items (512 16-byte loads per
       // round and workgroup instead of 2176: the poll traffic queued in front of the interior waves'
       // weight loads was several times the weight traffic itself); once that one carries the tag the
-      // rest is fetched in one go.
+      // rest is fetched in one go.  The probe is a loop of its own -- one load, two compares, two LDS stores -- so
+      // that the usual hand-over (the probe carries the tag, so does everything fetched behind it) walks each item
+      // once; the same polls, sleeps and limit as the one loop over a `want` mask this replaces.
       int polls = 0;
       bool fault = a.poll_limit < 0;
-      bool probe = true;
+      // (The probe's granule, too, lives in plain initialised scalars and is stored BEHIND the loop: stored inside it,
+      // from the loaded vector, the compiler wrote element 0 into both channels again -- the ISA showed
+      // `ds_write_b32 v60, v50` twice -- and tests/test_hip_wres_handover.py failed at 16x48.)
+      {
+        unsigned p0 = 0u, p1 = 0u, p2 = 0u, p3 = 0u;
+        bool got = false;
+        while (pend != 0u && !got && !fault) {
+          const u32x4 q = buf_ld<u32x4, BUF_SC1>(rxb, po);
+          p0 = q[0]; p1 = q[1]; p2 = q[2]; p3 = q[3];
+          got = p1 == target && p3 == target;
+          if (!got) {
+            __builtin_amdgcn_s_sleep(WR_POLL_SLEEP);
+            fault = ++polls > a.poll_limit;
+          }
+        }
+        if (got) {
+          dst[ph] = __builtin_bit_cast(float, p0);
+          dst[ph + WR_CS] = __builtin_bit_cast(float, p2);
+          pend &= pend - 1u;                  // (the lowest pending item has arrived)
+        }
+      }
       while (pend != 0u && !fault) {
-        const unsigned want_mask = probe ? (pend & (0u - pend)) : pend;      // lowest pending item | all of them
 #pragma unroll
         for (int k = 0; k < PER_T; ++k)
-          if (want_mask & (1u << k)) {
+          if (pend & (1u << k)) {
             const u32x4 q = buf_ld<u32x4, BUF_SC1>(rxb, off[k]);
             q0[k] = q[0]; q1[k] = q[1]; q2[k] = q[2]; q3[k] = q[3];
           }
-        const unsigned before = pend;
+        const unsigned want_mask = pend;
 #pragma unroll
         for (int k = 0; k < PER_T; ++k)
           if ((want_mask & (1u << k)) && q1[k] == target && q3[k] == target) {
@@ -447,8 +501,7 @@ __global__ __launch_bounds__(WR_THREADS, 3) void conv3x3_wino_resident_kernel(WR
             dst[ho[k] + WR_CS] = __builtin_bit_cast(float, q2[k]);
             pend &= ~(1u << k);
           }
-        if (probe && pend != before) probe = false;
-        else if (pend != 0u) {
+        if (pend != 0u) {
           __builtin_amdgcn_s_sleep(WR_POLL_SLEEP);
           fault = ++polls > a.poll_limit;
         }
@@ -675,7 +728,7 @@ static long long wres_blocks(int h, int w) { return (long long)cdiv(h, WR_BH) * 
 bool conv3x3_wino_resident_ok(int n, int cout, int h, int w) {
   if (n != 1 || cout != WR_NC || h < 2 || w < 2 || (h & 1) || (w & 1)) return false;
   const int cap = wres_capacity();
-  return cap > 0 && wres_blocks(h, w) <= cap - 8;
+  return cap > 0 && wres_blocks(h, w) <= cap - 8 && wres_blocks(h, w) <= 1023;   // (1023: the ring table's 16-bit owner field)
 }
 
 int64_t conv3x3_wino_resident_ws_bytes(int h, int w) {
@@ -744,6 +797,18 @@ extern "C" int tg_conv3x3_wino_resident_supported(int n, int cout, int h, int w)
 extern "C" int64_t tg_conv3x3_wino_resident_ws_bytes(int h, int w) {
   if (h <= 0 || w <= 0) return -1;
   return conv3x3_wino_resident_ws_bytes(h, w);
+}
+
+extern "C" int tg_conv3x3_wino_resident_ring_item(int h, int w, int block, int ring_pixel, int* owner_block,
+                                                  int* owner_slot, int* lds_offset) {
+  TG_REQUIRE(owner_block && owner_slot && lds_offset, TG_E_ARG, "conv3x3_wino_resident_ring_item: null pointer");
+  TG_REQUIRE(h >= 2 && w >= 2 && !(h & 1) && !(w & 1), TG_E_SHAPE, "conv3x3_wino_resident_ring_item: h=%d w=%d (even, >= 2)", h, w);
+  const int nbx = cdiv(w, WR_BW);
+  TG_REQUIRE(block >= 0 && block < wres_blocks(h, w) && ring_pixel >= 0 && ring_pixel < WR_NRING, TG_E_ARG,
+             "conv3x3_wino_resident_ring_item: block %d of %lld, ring pixel %d of %d", block, wres_blocks(h, w), ring_pixel, WR_NRING);
+  const WResRingItem it = wres_ring_item(h, w, nbx, block % nbx, block / nbx, ring_pixel);
+  *owner_block = it.owner; *owner_slot = it.slot; *lds_offset = it.lds;
+  return it.valid;
 }
 
 extern "C" int tg_conv3x3_wino_resident(const tg_wino_layer* layers, int n_layers, int cout, int h, int w,

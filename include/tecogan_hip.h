@@ -575,6 +575,25 @@ int tg_yuv420_to_rgb_f32(const uint8_t* yuv, float* rgb_chw, int n, int h, int w
 int tg_rgb_u8_to_yuv420(const uint8_t* rgb_hwc, uint8_t* yuv, int n, int H, int W, int matrix, int full_range,
                         int siting, tg_stream_t stream);
 
+/* PNG files written on the device: what the reference's save_sequence does with cv2.imwrite
+ * (codes/utils/data_utils.py), without the host's zlib.  The specification is tests/png_ref.py and the bytes are
+ * equal: 8-bit RGB, no interlace, one IDAT; per row the filter type (adaptive: the one of None, Sub, Up, Average,
+ * Paeth with the smallest sum of |int8(byte)|, the lowest on a tie; none: type 0); the filtered stream in segments of
+ * 32768 bytes, each deflated on its own with Huffman codes only (a dynamic block and an empty stored block, or one
+ * stored block when that is not larger).  No LZ77 matches, so files are larger than zlib's.
+ *   rgb_hwc (n,h,w,3) uint8.  Frame k's complete file starts at out + k * out_stride (any alignment), its length goes
+ *   to sizes[k] (8-byte aligned); bytes past it inside the stride are unspecified, bytes outside
+ *   [out, out + n * out_stride) are never written.  out_stride is at least tg_png_capacity(h, w), the bytes a frame
+ *   needs when every segment is stored.  workspace: at least tg_png_workspace_bytes(n, h, w) bytes, any alignment.
+ *   Four launches on `stream`, ordered by the stream alone.
+ * Null pointers, h or w < 1, n outside 1..65535, a bad filter: TG_E_ARG; h * (3 w + 1) >= 2^31 or a stride below the
+ * capacity: TG_E_SHAPE (the two size queries return -1 then).  Nothing is launched then. */
+enum { TG_PNG_FILTER_NONE = 0, TG_PNG_FILTER_ADAPTIVE = 1 };
+int64_t tg_png_capacity(int h, int w);
+int64_t tg_png_workspace_bytes(int n, int h, int w);
+int tg_png_encode_u8(const uint8_t* rgb_hwc, int n, int h, int w, int filter, uint8_t* out, int64_t out_stride,
+                     int64_t* sizes, void* workspace, tg_stream_t stream);
+
 /* Scene cuts of FRNet.infer_stream, decided on the device; the reference has no counterpart (its
  * test sets are single-shot clips).  The formula is the specification, tests/scene_cut_ref.py restates it in numpy and
  * the three outputs must be equal bit for bit.

@@ -155,6 +155,7 @@ UP_NONE, UP_BICUBIC, UP_BILINEAR = (_K['TG_UP_' + k] for k in ('NONE', 'BICUBIC'
 PREC_F32, PREC_F16 = _K['TG_PREC_F32'], _K['TG_PREC_F16']
 YUV_MATRIX = {'bt601': _K['TG_YUV_BT601'], 'bt709': _K['TG_YUV_BT709']}
 YUV_SITING = {'center': _K['TG_YUV_CENTER'], 'left': _K['TG_YUV_LEFT']}
+PNG_FILTER = {'none': _K['TG_PNG_FILTER_NONE'], 'adaptive': _K['TG_PNG_FILTER_ADAPTIVE']}
 
 STRUCTS = _HEADER.structs                           # C name -> Structure class
 FrnetCfg, WinoLayer, ChainLayer = STRUCTS['tg_frnet_cfg'], STRUCTS['tg_wino_layer'], STRUCTS['tg_chain_layer']

@@ -12,7 +12,8 @@ paired_folder_dataset.py:57-63); any iterable of such dicts can be passed to `tr
 `infer` upscales a folder of LR frames (`--input`: the frames themselves, or one sub-folder per sequence) into
 `--output` without ground truth: frames are decoded lazily, streamed through VSRModel.infer_stream in bounded memory
 (any length) and written as PNGs under the input's names.  PNG decoding and encoding bound its rate: what it prints
-is a codec number, not a GPU number.  With an `--input` that is a y4m file or `-` (stdin) the clip is raw 8-bit YUV 4:2:0
+is a codec number, not a GPU number.  `--png-encoder device` has the GPU write the PNG files
+(Huffman-only deflate: larger files) and leaves the host the decoding of the input and the writes.  With an `--input` that is a y4m file or `-` (stdin) the clip is raw 8-bit YUV 4:2:0
 video instead (data/y4m.py): I420 frames go up as they are, are converted on the device both ways (DESIGN.md section
 7e) and leave as a y4m stream to `--output` (a file, or `-` for stdout), so a codec can sit on either side of a pipe:
 
@@ -81,7 +82,14 @@ def parse_args(argv=None):
                    help='--scene-cut: least mean absolute luma difference of a cut, in 8-bit levels')
     p.add_argument('--scene-cut-hist', dest='scene_cut_hist', type=float, default=0.25,
                    help='--scene-cut: least distance of the two 32-bin luma histograms, as a share of its maximum')
-    return p.parse_args(argv)
+    p.add_argument('--png-encoder', dest='png_encoder', type=str, default='pillow', choices=['pillow', 'device'],
+                   help='--mode infer into a PNG folder: pillow (default) encodes on writer threads with zlib; device '
+                        'encodes on the GPU (DESIGN.md section 7i: Huffman-only deflate, larger files, no host codec on '
+                        'the output side).  Not for y4m output')
+    args = p.parse_args(argv)
+    if args.png_encoder == 'device' and args.input and (args.input == '-' or os.path.isfile(args.input)):
+        p.error('--png-encoder device writes PNG folders; y4m input is written as y4m')
+    return args
 
 
 def default_opt():
@@ -364,18 +372,26 @@ def log_scene_cuts(name, scene_cut):
           file=sys.stderr, flush=True)
 
 
-def infer(opt, input_dir, output_dir, scene_cut=None):
+def infer(opt, input_dir, output_dir, scene_cut=None, png_encoder='pillow'):
     """--mode infer: every sequence of input_dir through VSRModel.infer_stream.  Frames are decoded one by one as the
     stream asks for them; the writers copy each frame out of the yielded ring slot before the generator is advanced.
-    scene_cut (a SceneCut): passed on for every sequence, its cuts logged to stderr.  Returns {sequence: frames written}."""
+    scene_cut (a SceneCut): passed on for every sequence, its cuts logged to stderr.  png_encoder 'device': the stream
+    yields finished PNG files (infer_stream(png=Png())) and a writer copies one out of the slot and writes it as it
+    is; 'pillow': the writers encode the RGB frames.  Returns {sequence: frames written}."""
     import threading
     from concurrent.futures import ThreadPoolExecutor
     from PIL import Image
     from .data.folder_dataset import read_rgb
+    if png_encoder not in ('pillow', 'device'):
+        raise ValueError(f"png_encoder is 'pillow' or 'device', got {png_encoder!r}")
     seqs = infer_sequences(input_dir)
     if not seqs:
         raise ValueError(f'--input {input_dir}: no png | jpg frames, directly or one level down')
     model = define_model(opt)
+    kw = {} if scene_cut is None else {'scene_cut': scene_cut}
+    if png_encoder == 'device':
+        from .models.networks import Png
+        kw['png'] = Png()
     done = {}
     slots = threading.BoundedSemaphore(4 * INFER_WRITER_THREADS)       # frames copied out and not yet on disk
 
@@ -386,7 +402,11 @@ def infer(opt, input_dir, output_dir, scene_cut=None):
             finally:
                 copied.release()
             os.makedirs(os.path.dirname(path), exist_ok=True)
-            Image.fromarray(frame).save(path)
+            if png_encoder == 'device':             # the file as the GPU wrote it
+                with open(path, 'wb') as f:
+                    f.write(frame.data)
+            else:
+                Image.fromarray(frame).save(path)
         finally:
             slots.release()
 
@@ -395,8 +415,7 @@ def infer(opt, input_dir, output_dir, scene_cut=None):
             t0 = time.time()
             targets = [infer_output_path(input_dir, output_dir, seq, p) for p in files]
             jobs, k = [], 0
-            for chunk in model.infer_stream((read_rgb(p) for p in files),
-                                            **({} if scene_cut is None else {'scene_cut': scene_cut})):
+            for chunk in model.infer_stream((read_rgb(p) for p in files), **kw):
                 copied = threading.Semaphore(0)
                 for i in range(len(chunk)):
                     slots.acquire()
@@ -418,7 +437,8 @@ def infer(opt, input_dir, output_dir, scene_cut=None):
                 log_scene_cuts(seq or os.path.basename(os.path.normpath(input_dir)), scene_cut)
             dt = time.time() - t0
             print(f"{seq or os.path.basename(os.path.normpath(input_dir))}: {k} frames -> "
-                  f"{os.path.join(output_dir, seq)} ({k / max(dt, 1e-9):.1f} frames/s, bound by PNG decoding and encoding)",
+                  f"{os.path.join(output_dir, seq)} ({k / max(dt, 1e-9):.1f} frames/s, bound by PNG decoding"
+                  f"{' and writing' if png_encoder == 'device' else ' and encoding'})",
                   flush=True)
     model.net_G.check_faults()
     return done
@@ -557,7 +577,7 @@ def main(argv=None):
         if args.input == '-' or os.path.isfile(args.input):
             infer_y4m_cli(opt, args.input, args.output, args.yuv_matrix, args.yuv_range, scene_cut_option(args))
         else:
-            infer(opt, args.input, args.output, scene_cut_option(args))
+            infer(opt, args.input, args.output, scene_cut_option(args), args.png_encoder)
     elif args.mode == 'profile':
         profile(opt, tuple(int(v) for v in args.lr_size.split('x')), args.test_speed)
     else:

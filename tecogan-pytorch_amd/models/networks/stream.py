@@ -1,5 +1,5 @@
-"""FRNet.infer_stream (DESIGN.md sections 7d, 7e, 7h): input parsing, the batch ring, the raw-video form Yuv420, the
-scene-cut option SceneCut and the engine that runs a clip of any length through rings of STREAM_SLOTS batches.  A batch's launches are frnet_infer's
+"""FRNet.infer_stream (DESIGN.md sections 7d, 7e, 7h, 7i): input parsing, the batch ring, the raw-video form Yuv420, the
+PNG output form Png, the scene-cut option SceneCut and the engine that runs a clip of any length through rings of STREAM_SLOTS batches.  A batch's launches are frnet_infer's
 enqueue_batch, the ones infer_sequence(pipeline=True) enqueues.  Uses the network only through its attributes."""
 import math
 
@@ -204,6 +204,38 @@ class Yuv420:
         return L.YUV_MATRIX[self.matrix], int(self.full_range), L.YUV_SITING[self.siting]
 
 
+class Png:
+    """PNG output form of a stream (FRNet.infer_stream(png=...)): every super-resolved frame
+    leaves the device as one complete 8-bit RGB PNG file, encoded there by tg_png_encode_u8.  filter 'adaptive' (per
+    row the type with the smallest sum of |int8(byte)|) | 'none' (type 0 on every row).  Huffman-only deflate: the
+    files are larger than zlib's.  Frozen."""
+    __slots__ = ('filter',)
+
+    def __init__(self, filter='adaptive'):
+        if not isinstance(filter, str) or filter not in L.PNG_FILTER:
+            raise ValueError(f'Png: filter is one of {sorted(L.PNG_FILTER)}, got {filter!r}')
+        object.__setattr__(self, 'filter', filter)
+
+    def __setattr__(self, name, value):
+        raise AttributeError('Png is frozen')
+
+    def __delattr__(self, name):
+        raise AttributeError('Png is frozen')
+
+    def __eq__(self, other):
+        return isinstance(other, Png) and self.filter == other.filter
+
+    def __hash__(self):
+        return hash(('Png', self.filter))
+
+    def __repr__(self):
+        return 'Png(filter=%r)' % self.filter
+
+    def code(self):
+        """The filter as the C ABI takes it."""
+        return L.PNG_FILTER[self.filter]
+
+
 class SceneCut:
     """Scene-cut option of a stream (FRNet.infer_stream(scene_cut=...)) and the caller's handle on
     what it found.  At a cut the recurrence restarts from the zero HR state, which makes the frame the frame 0 of a clip
@@ -286,7 +318,11 @@ class _StreamEngine:
     """State of one FRNet.infer_stream (see there).  Everything the device touches is allocated once, at the first
     frame: STREAM_SLOTS slots of {LR batch + the frame before it, uint8 frames on the device, pinned uint8 frames,
     HR state snapshot, input staging, events}, and the HR ping-pong pair.  With a Yuv420 the staging and the pinned
-    output hold I420 frames, and a slot has its I420 output on the device as well.
+    output hold I420 frames, and a slot has its I420 output on the device as well.  With a Png a slot has, on the device
+    and pinned, one buffer of the batch's file sizes followed by one tg_png_capacity region per frame; _compute puts ONE
+    tg_png_encode_u8 behind the batch's last frame, that buffer is what comes down, and the yielded views are cut from
+    the pinned slot by the sizes once the download event has passed.  The encoder's workspace is one for all slots:
+    every call is on the caller's stream.
 
     With a SceneCut a slot also has, on the device, one flag, one SAD and one histogram distance
     per frame, the forced mask and the detector's workspace, and pinned mirrors of the mask and of the results.
@@ -296,9 +332,16 @@ class _StreamEngine:
     for a decision.  The repair path needs no scene-cut code: it runs _compute again, which reads the same per-slot
     flags, and the snapshot it restores was taken before the batch's first conditional fill."""
 
-    def __init__(self, net, frames, device, on_fault, yuv=None, scene_cut=None):
+    def __init__(self, net, frames, device, on_fault, yuv=None, scene_cut=None, png=None):
         if on_fault not in ('rerun', 'raise'):
             raise ValueError(f"on_fault must be 'rerun' or 'raise', got {on_fault!r}")
+        if png is not None:
+            if not isinstance(png, Png):
+                raise ValueError(f'png must be a Png or None, got {type(png).__name__}')
+            if yuv is not None:
+                raise ValueError('infer_stream: png and yuv are two forms of the output; pass one of them')
+            if net.in_nc != 3:
+                raise ValueError(f'png needs RGB frames (in_nc = 3), this network has in_nc = {net.in_nc}')
         if yuv is not None:
             if not isinstance(yuv, Yuv420):
                 raise ValueError(f'yuv must be a Yuv420 or None, got {type(yuv).__name__}')
@@ -310,7 +353,7 @@ class _StreamEngine:
                 raise ValueError(f'scene_cut needs RGB frames (in_nc = 3), this network has in_nc = {net.in_nc}')
             scene_cut.cuts.clear()
             scene_cut.scores.clear()
-        self.yuv, self.scene_cut = yuv, scene_cut
+        self.yuv, self.scene_cut, self.png = yuv, scene_cut, png
         self.net, self.frames, self.on_fault = net, frames, on_fault
         self.dev = _norm_device(device if device is not None else next(net.parameters()).device)
         self.closed, self.warned, self.reruns = False, False, 0
@@ -341,7 +384,15 @@ class _StreamEngine:
         self.snap = torch.empty(ns, 1, c, s * h, s * w, dtype=torch.float32, device=dev)
         self.u8 = torch.empty(ns, m, s * h, s * w, c, dtype=torch.uint8, device=dev)
         ofb = self.yuv.out_frame_bytes(s) if kind == 'yuv' else s * h * s * w * c
-        self.host_out = torch.empty((ns, m, ofb) if kind == 'yuv' else (ns, m, s * h, s * w, c), dtype=torch.uint8,
+        if self.png is not None:                    # per slot: m int64 sizes, then m regions of one file each
+            cap, wsb = self.lib.tg_png_capacity(s * h, s * w), self.lib.tg_png_workspace_bytes(m, s * h, s * w)
+            if cap < 0 or wsb < 0:
+                L.check(L.TG_E_SHAPE, 'tg_png_capacity')
+            self.png_stride = (cap + 7) // 8 * 8
+            self.png_out = torch.empty(ns, 8 * m + m * self.png_stride, dtype=torch.uint8, device=dev)
+            self.png_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        self.host_out = torch.empty((ns, 8 * m + m * self.png_stride) if self.png is not None else
+                                    (ns, m, ofb) if kind == 'yuv' else (ns, m, s * h, s * w, c), dtype=torch.uint8,
                                     pin_memory=True)
         if kind == 'yuv':                           # I420 both ways: 1.5 bytes per pixel through pinned memory
             self.stage = torch.empty(ns, m, self.yuv.frame_bytes, dtype=torch.uint8, pin_memory=True)
@@ -458,6 +509,11 @@ class _StreamEngine:
             L.check(self.lib.tg_rgb_u8_to_yuv420(self.u8[sl].data_ptr(), self.yuv_out[sl].data_ptr(), cnt,
                                                  s * self.h, s * self.w, *self.yuv.codes(), main.cuda_stream),
                     'tg_rgb_u8_to_yuv420')
+        if self.png is not None:                    # the batch's RGB frames -> PNG files, behind its last frame
+            s, base = self.net.scale, self.png_out[sl].data_ptr()
+            L.check(self.lib.tg_png_encode_u8(self.u8[sl].data_ptr(), cnt, s * self.h, s * self.w, self.png.code(),
+                                              base + 8 * self.u8.shape[1], self.png_stride, base,
+                                              self.png_ws.data_ptr(), main.cuda_stream), 'tg_png_encode_u8')
         self.ev_s[sl].record(main)
         self.pending_dl = rec
 
@@ -472,8 +528,12 @@ class _StreamEngine:
         sl = self.ring.slot(b)
         self.copy.wait_event(self.ev_s[sl])
         with torch.cuda.stream(self.copy):
-            done = self.yuv_out if self.yuv is not None else self.u8
-            self.host_out[sl, :cnt].copy_(done[sl, :cnt], non_blocking=True)
+            if self.png is not None:                # the sizes and the first cnt regions
+                used = 8 * self.u8.shape[1] + cnt * self.png_stride
+                self.host_out[sl, :used].copy_(self.png_out[sl, :used], non_blocking=True)
+            else:
+                done = self.yuv_out if self.yuv is not None else self.u8
+                self.host_out[sl, :cnt].copy_(done[sl, :cnt], non_blocking=True)
             if self.scene_cut is not None:
                 self.sc_host[sl].copy_(self.sc_out[sl], non_blocking=True)
             self.ev_out[sl].record(self.copy)
@@ -542,6 +602,10 @@ class _StreamEngine:
             m, res = self.sc_forced.shape[1], self.sc_host[sl].numpy()
             self.scene_cut.report(i0, res[8 * m:12 * m].view(np.int32)[:cnt], res[:8 * m].view(np.uint64)[:cnt],
                                   res[12 * m:].view(np.uint32)[:cnt], self.h * self.w)
+        if self.png is not None:
+            m, buf = self.u8.shape[1], self.host_out[sl].numpy()
+            sizes = buf[:8 * m].view(np.int64)
+            return [buf[8 * m + k * self.png_stride:8 * m + k * self.png_stride + int(sizes[k])] for k in range(cnt)]
         return self.host_out[sl, :cnt].numpy()
 
     # -- the generator -------------------------------------------------------------------------------------------
@@ -582,6 +646,6 @@ class _StreamEngine:
             if self.ring.inflight:
                 self.plan.chain_state()             # a fault in frames nobody will see: counted, the plan has fallen back
         finally:
-            for name in ('lr', 'hr', 'snap', 'u8', 'host_out', 'stage', 'dev_in', 'yuv_out', 'zflow', 'sc_out',
-                         'sc_host', 'sc_forced', 'sc_forced_host', 'sc_ws'):
+            for name in ('lr', 'hr', 'snap', 'u8', 'host_out', 'stage', 'dev_in', 'yuv_out', 'png_out', 'png_ws', 'zflow',
+                         'sc_out', 'sc_host', 'sc_forced', 'sc_forced_host', 'sc_ws'):
                 self.__dict__.pop(name, None)

@@ -20,7 +20,7 @@ from ...utils.net_utils import get_upsampling_func
 # (what is not a network: every name stays reachable as tecogan_nets.<name>)
 from .frnet_infer import (FNET_FIRST_PASS_FRAMES, _SIDE_STREAMS, _StepPlan, _norm_device, clip_batches,  # noqa: F401
                           enqueue_batch, side_stream, stream_batch_sizes)
-from .stream import (STREAM_SLOTS, SceneCut, StreamFormat, StreamRing, Yuv420, _StreamEngine, stream_frames,  # noqa: F401
+from .stream import (STREAM_SLOTS, Png, SceneCut, StreamFormat, StreamRing, Yuv420, _StreamEngine, stream_frames,  # noqa: F401
                      stream_frames_yuv, stream_parts, stream_rebatch, yuv420_planes)
 
 
@@ -435,7 +435,7 @@ class FRNet(nn.Module):
         self._get_plan(k, h, w, dev).check_chain()   # (the clip has been synchronised: a 4-byte read)
         return out.transpose(1, 0, 2, 3, 4) if multi else out[:, 0]
 
-    def infer_stream(self, frames, device=None, on_fault='rerun', yuv=None, scene_cut=None):
+    def infer_stream(self, frames, device=None, on_fault='rerun', yuv=None, scene_cut=None, png=None):
         """Super-resolve a clip of ANY length in bounded memory: a generator over `frames` (any iterable, pulled lazily)
         that yields (m, s*h, s*w, 3) uint8 numpy chunks in order, as many frames in total as it consumed.
 
@@ -487,12 +487,20 @@ class FRNet(nn.Module):
         LR slot (every input kind), and one tg_zero_if_flag per frame on the caller's stream clears the HR state in
         front of tg_frnet_step_srnet if the frame's flag is set: the frame then is frame 0 of a clip of its own, bit for
         bit, and the host never waits for the decision.  The cuts (and, with keep_scores, the per-frame scores) are
-        appended to the SceneCut when a batch is retired, before its chunk is yielded.  in_nc != 3 is a ValueError."""
+        appended to the SceneCut when a batch is retired, before its chunk is yielded.  in_nc != 3 is a ValueError.
+
+        png: a Png(filter) makes every output frame one complete PNG file, encoded on the device (DESIGN.md section
+        7i); the input forms are unchanged, and without it the stream enqueues exactly what it always did.  `png`
+        together with `yuv` is a ValueError before anything is enqueued.  After a batch's last frame ONE
+        tg_png_encode_u8 call on the caller's stream writes the batch's files and their sizes into the slot's buffer,
+        which comes down in place of the RGB frames.  The generator yields, per batch, a LIST of 1-D uint8 views, one
+        file each, valid until it is advanced: the bytes are ops.png_encode of the frames the stream yields without
+        `png`.  A repaired batch is encoded again with it."""
         import weakref
         cur = self._stream_ref() if self._stream_ref is not None else None
         if cur is not None and not cur.closed:
             raise RuntimeError('infer_stream: this network already has a live stream (one at a time: close it first)')
-        eng = _StreamEngine(self, frames, device, on_fault, yuv, scene_cut)
+        eng = _StreamEngine(self, frames, device, on_fault, yuv, scene_cut, png)
         self._stream_ref = weakref.ref(eng)
         return eng.run()
 

@@ -93,12 +93,13 @@ class VSRModel(BaseModel):
             hr_seq = self.net_G(lr_data, self.device)
         return hr_seq[n_pad_front:]
 
-    def infer_stream(self, frames, yuv=None, scene_cut=None):
+    def infer_stream(self, frames, yuv=None, scene_cut=None, png=None):
         """infer() for a clip of any length (FRNet.infer_stream): `frames` is an iterable of LR frames or chunks, uint8
         (h,w,3) or float32 (3,h,w); yields (m,H,W,3) uint8 chunks -- views of the generator's pinned ring, valid until
         the next one is asked for.  The temporal padding of the front (test.padding_mode / num_pad_front) is applied
         lazily: the first n_pad + 1 frames are buffered, the padded prefix runs first, its n_pad outputs are dropped.
         yuv (a Yuv420): the items are I420 frames or chunks of them and (m, out_frame_bytes) I420 chunks are yielded.
+        png (a Png): lists of 1-D uint8 views are yielded, each view one complete PNG file (not together with yuv).
         scene_cut (a SceneCut): the recurrence restarts at scene cuts (FRNet.infer_stream).  Its `at`, `cuts` and
         `scores` are in the numbering of `frames`: the padded stream runs a shifted copy, and what that finds inside
         the padded prefix is dropped.  Known limit: the front padding is NOT repeated after a cut -- a new shot starts
@@ -112,7 +113,8 @@ class VSRModel(BaseModel):
             scene_cut.cuts.clear()
             scene_cut.scores.clear()
         gen = self.net_G.infer_stream(front_pad_stream(frames, mode, skip, self.net_G.in_nc, yuv), self.device,
-                                      yuv=yuv, **({} if inner is None else {'scene_cut': inner}))
+                                      yuv=yuv, **({} if inner is None else {'scene_cut': inner}),
+                                      **({} if png is None else {'png': png}))
         try:
             for chunk in gen:
                 if inner is not None:

@@ -521,6 +521,33 @@ def rgb_to_yuv420(rgb_hwc, matrix='bt709', full_range=False, siting='left'):
     return out
 
 
+def png_encode(rgb_hwc, filter='adaptive'):
+    """(n,H,W,3) / (H,W,3) uint8 RGB on device -> a list of n host `bytes`, each one complete PNG file, encoded on
+    the device (tg_png_encode_u8): filter 'adaptive' | 'none', Huffman-only deflate in segments
+    of 32768 bytes, the bytes of tests/png_ref.py.  Synchronises: for tools and tests; a stream writes files through
+    FRNet.infer_stream(png=...)."""
+    _chk_u8(rgb_hwc, 'rgb')
+    if rgb_hwc.dim() == 3:
+        rgb_hwc = rgb_hwc.unsqueeze(0)
+    if rgb_hwc.dim() != 4 or rgb_hwc.shape[3] != 3 or rgb_hwc.shape[0] < 1:
+        raise L.TecoganHipError(f'png_encode: expected (n,H,W,3) or (H,W,3), got shape {tuple(rgb_hwc.shape)}')
+    if isinstance(filter, str) and filter not in L.PNG_FILTER:
+        raise L.TecoganHipError(f'png_encode: filter is one of {sorted(L.PNG_FILTER)}, got {filter!r}')
+    code = L.PNG_FILTER[filter] if isinstance(filter, str) else int(filter)
+    n, H, W, _ = rgb_hwc.shape
+    lib, dev = L.lib(), rgb_hwc.device
+    cap, wsb = lib.tg_png_capacity(H, W), lib.tg_png_workspace_bytes(n, H, W)
+    if cap < 0 or wsb < 0:
+        L.check(L.TG_E_SHAPE, 'tg_png_capacity')
+    out = torch.empty(n, cap, dtype=torch.uint8, device=dev)
+    sizes = torch.empty(n, dtype=torch.int64, device=dev)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    L.check(lib.tg_png_encode_u8(_ptr(rgb_hwc), n, H, W, code, _ptr(out), cap, _ptr(sizes), _ptr(ws), _stream()),
+            'tg_png_encode_u8')
+    sizes, out = sizes.cpu().tolist(), out.cpu().numpy()
+    return [out[k, :sizes[k]].tobytes() for k in range(n)]
+
+
 def scene_cut_flags(frames, mad, hist, forced=None, detect=True):
     """(n+1,3,h,w) fp32 frames on device -> (flags int32 (n,), sad int64 (n,), hdist int32 (n,)): pair j is frame
     j + 1 against frame j.  sad = sum |dY| of the 8-bit lumas, hdist = L1 distance of their 32-bin histograms, flag =

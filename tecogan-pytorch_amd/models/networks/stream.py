@@ -1,7 +1,9 @@
 """FRNet.infer_stream (DESIGN.md sections 7d, 7e, 7h, 7i): input parsing, the batch ring, the raw-video form Yuv420, the
-PNG output form Png, the scene-cut option SceneCut and the engine that runs a clip of any length through rings of STREAM_SLOTS batches.  A batch's launches are frnet_infer's
-enqueue_batch, the ones infer_sequence(pipeline=True) enqueues.  Uses the network only through its attributes."""
+PNG output form Png, the scene-cut option SceneCut, one small object per input form, output form and option, and the engine
+that runs a clip of any length through rings of STREAM_SLOTS batches.  A batch's launches are frnet_infer's enqueue_batch,
+the ones infer_sequence(pipeline=True) enqueues.  Uses the network only through its attributes."""
 import math
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -151,43 +153,30 @@ class StreamRing:
         return self.inflight.pop(0)
 
 
+@dataclass(frozen=True)
 class Yuv420:
     """Raw-video form of a stream (FRNet.infer_stream(yuv=...)): planar 8-bit YUV 4:2:0 (I420)
     frames of h x w on the way in and of s*h x s*w on the way out.  matrix 'bt601' | 'bt709', full_range (bool),
     siting 'center' (y4m C420jpeg) | 'left' (y4m C420mpeg2).  Frozen."""
-    __slots__ = ('h', 'w', 'matrix', 'full_range', 'siting')
+    h: int
+    w: int
+    matrix: str = 'bt709'
+    full_range: bool = False
+    siting: str = 'left'
 
-    def __init__(self, h, w, matrix='bt709', full_range=False, siting='left'):
-        for name, v in (('h', h), ('w', w)):
+    def __post_init__(self):
+        for name in ('h', 'w'):
+            v = getattr(self, name)
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 2:
                 raise ValueError(f'Yuv420: {name} is an integer >= 2, got {v!r}')
-        if matrix not in L.YUV_MATRIX:
-            raise ValueError(f'Yuv420: matrix is one of {sorted(L.YUV_MATRIX)}, got {matrix!r}')
-        if siting not in L.YUV_SITING:
-            raise ValueError(f'Yuv420: siting is one of {sorted(L.YUV_SITING)}, got {siting!r}')
-        if not isinstance(full_range, (bool, np.bool_)):
-            raise ValueError(f'Yuv420: full_range is a bool, got {full_range!r}')
-        for name, v in (('h', int(h)), ('w', int(w)), ('matrix', matrix), ('full_range', bool(full_range)),
-                        ('siting', siting)):
-            object.__setattr__(self, name, v)
-
-    def __setattr__(self, name, value):
-        raise AttributeError('Yuv420 is frozen')
-
-    def __delattr__(self, name):
-        raise AttributeError('Yuv420 is frozen')
-
-    def _key(self):
-        return (self.h, self.w, self.matrix, self.full_range, self.siting)
-
-    def __eq__(self, other):
-        return isinstance(other, Yuv420) and self._key() == other._key()
-
-    def __hash__(self):
-        return hash(self._key())
-
-    def __repr__(self):
-        return 'Yuv420(h=%d, w=%d, matrix=%r, full_range=%r, siting=%r)' % self._key()
+            object.__setattr__(self, name, int(v))
+        if self.matrix not in L.YUV_MATRIX:
+            raise ValueError(f'Yuv420: matrix is one of {sorted(L.YUV_MATRIX)}, got {self.matrix!r}')
+        if self.siting not in L.YUV_SITING:
+            raise ValueError(f'Yuv420: siting is one of {sorted(L.YUV_SITING)}, got {self.siting!r}')
+        if not isinstance(self.full_range, (bool, np.bool_)):
+            raise ValueError(f'Yuv420: full_range is a bool, got {self.full_range!r}')
+        object.__setattr__(self, 'full_range', bool(self.full_range))
 
     @property
     def frame_bytes(self):
@@ -204,32 +193,17 @@ class Yuv420:
         return L.YUV_MATRIX[self.matrix], int(self.full_range), L.YUV_SITING[self.siting]
 
 
+@dataclass(frozen=True)
 class Png:
     """PNG output form of a stream (FRNet.infer_stream(png=...)): every super-resolved frame
     leaves the device as one complete 8-bit RGB PNG file, encoded there by tg_png_encode_u8.  filter 'adaptive' (per
     row the type with the smallest sum of |int8(byte)|) | 'none' (type 0 on every row).  Huffman-only deflate: the
     files are larger than zlib's.  Frozen."""
-    __slots__ = ('filter',)
+    filter: str = 'adaptive'
 
-    def __init__(self, filter='adaptive'):
-        if not isinstance(filter, str) or filter not in L.PNG_FILTER:
-            raise ValueError(f'Png: filter is one of {sorted(L.PNG_FILTER)}, got {filter!r}')
-        object.__setattr__(self, 'filter', filter)
-
-    def __setattr__(self, name, value):
-        raise AttributeError('Png is frozen')
-
-    def __delattr__(self, name):
-        raise AttributeError('Png is frozen')
-
-    def __eq__(self, other):
-        return isinstance(other, Png) and self.filter == other.filter
-
-    def __hash__(self):
-        return hash(('Png', self.filter))
-
-    def __repr__(self):
-        return 'Png(filter=%r)' % self.filter
+    def __post_init__(self):
+        if not isinstance(self.filter, str) or self.filter not in L.PNG_FILTER:
+            raise ValueError(f'Png: filter is one of {sorted(L.PNG_FILTER)}, got {self.filter!r}')
 
     def code(self):
         """The filter as the C ABI takes it."""
@@ -314,23 +288,227 @@ def yuv420_planes(chunk, H, W):
             chunk[..., H * W + ch * cw:].reshape(lead + (ch, cw)))
 
 
-class _StreamEngine:
-    """State of one FRNet.infer_stream (see there).  Everything the device touches is allocated once, at the first
-    frame: STREAM_SLOTS slots of {LR batch + the frame before it, uint8 frames on the device, pinned uint8 frames,
-    HR state snapshot, input staging, events}, and the HR ping-pong pair.  With a Yuv420 the staging and the pinned
-    output hold I420 frames, and a slot has its I420 output on the device as well.  With a Png a slot has, on the device
-    and pinned, one buffer of the batch's file sizes followed by one tg_png_capacity region per frame; _compute puts ONE
-    tg_png_encode_u8 behind the batch's last frame, that buffer is what comes down, and the yielded views are cut from
-    the pinned slot by the sizes once the download event has passed.  The encoder's workspace is one for all slots:
-    every call is on the caller's stream.
+# -- the forms of a stream: each object owns its buffers and is the only place that knows their layout.  alloc(eng) runs
+# once, inside the engine's _open; the engine decides when every other method runs, and on which stream (see there).
+class _DeviceF32:
+    """Input form: float32 frames on the device go straight into the LR slot on the copy stream; nothing is staged."""
 
-    With a SceneCut a slot also has, on the device, one flag, one SAD and one histogram distance
-    per frame, the forced mask and the detector's workspace, and pinned mirrors of the mask and of the results.
-    _upload runs tg_scene_cut_flags on the slot's LR frames on the copy stream, behind whatever wrote them; _compute
-    hands the flags' address to enqueue_batch, which puts one tg_zero_if_flag in front of every frame's SRNet launch;
-    the results come down behind the frames and reach SceneCut.cuts when the batch is retired.  The host never waits
-    for a decision.  The repair path needs no scene-cut code: it runs _compute again, which reads the same per-slot
-    flags, and the snapshot it restores was taken before the batch's first conditional fill."""
+    def __init__(self, h, w):
+        self.h, self.w = h, w
+
+    def alloc(self, eng):
+        self.dev, self.copy, self.lr, self.ev_arrive = eng.dev, eng.copy, eng.lr, torch.cuda.Event()
+
+    def take(self, sl, off, piece):
+        piece = piece.contiguous()
+        self.ev_arrive.record(torch.cuda.current_stream(self.dev))
+        self.copy.wait_event(self.ev_arrive)
+        with torch.cuda.stream(self.copy):
+            self.lr[sl, 1 + off:1 + off + piece.shape[0]].copy_(piece, non_blocking=True)
+        piece.record_stream(self.copy)
+
+    def upload(self, sl, cnt):
+        pass
+
+
+class _HostF32:
+    """Input form: float32 frames on the host, through pinned staging (the caller's buffer is free again when take
+    returns) into the LR slot."""
+
+    def __init__(self, h, w):
+        self.h, self.w = h, w
+
+    def alloc(self, eng):
+        self.lr = eng.lr
+        self.stage = torch.empty(eng.ring.slots, eng.m, eng.net.in_nc, self.h, self.w, dtype=torch.float32, pin_memory=True)
+
+    def take(self, sl, off, piece):
+        self.stage[sl, off:off + piece.shape[0]].copy_(piece)
+
+    def upload(self, sl, cnt):
+        self.lr[sl, 1:1 + cnt].copy_(self.stage[sl, :cnt], non_blocking=True)
+
+
+class _HostBytes:
+    """Input form: uint8 frames on the host go up as bytes, through pinned staging, and ONE launch converts a batch
+    into the LR slot: `launch`(bytes, LR frames, cnt, *args, stream).  uint8 RGB frames and I420 frames differ only in
+    that launch and in the shape of a frame."""
+
+    def __init__(self, h, w, frame_shape, launch, args):
+        self.h, self.w, self.frame_shape, self.launch, self.args = h, w, frame_shape, launch, args
+
+    def alloc(self, eng):
+        self.lr, self.fn, self.stream = eng.lr, getattr(eng.lib, self.launch), eng.copy.cuda_stream
+        self.stage = torch.empty(eng.ring.slots, eng.m, *self.frame_shape, dtype=torch.uint8, pin_memory=True)
+        self.dev_in = torch.empty(eng.ring.slots, eng.m, *self.frame_shape, dtype=torch.uint8, device=eng.dev)
+
+    def take(self, sl, off, piece):
+        self.stage[sl, off:off + piece.shape[0]].copy_(piece)
+
+    def upload(self, sl, cnt):
+        self.dev_in[sl, :cnt].copy_(self.stage[sl, :cnt], non_blocking=True)
+        L.check(self.fn(self.dev_in[sl].data_ptr(), self.lr[sl, 1].data_ptr(), cnt, *self.args, self.stream), self.launch)
+
+
+def _input_form(piece, c, yuv):
+    """The input form of a stream, from its options and its first item (as stream_parts hands it out)."""
+    if yuv is not None:
+        return _HostBytes(yuv.h, yuv.w, (yuv.frame_bytes,), 'tg_yuv420_to_rgb_f32', (yuv.h, yuv.w, *yuv.codes()))
+    if piece.dtype == torch.uint8:
+        h, w = piece.shape[1:3]
+        return _HostBytes(h, w, (h, w, c), 'tg_dequantize_u8_hwc', (c, h, w))
+    return (_DeviceF32 if piece.is_cuda else _HostF32)(piece.shape[2], piece.shape[3])
+
+
+class _RgbOut:
+    """Output form: the batch's uint8 RGB frames come down as they are; the chunk is a view of the pinned slot."""
+
+    def alloc(self, eng):
+        self.u8 = eng.u8
+        self.host_out = torch.empty(tuple(eng.u8.shape), dtype=torch.uint8, pin_memory=True)
+
+    def encode(self, sl, cnt):
+        pass
+
+    def download(self, sl, cnt):
+        self.host_out[sl, :cnt].copy_(self.u8[sl, :cnt], non_blocking=True)
+
+    def result(self, sl, cnt):
+        return self.host_out[sl, :cnt].numpy()
+
+
+class _I420Out:
+    """Output form I420: ONE tg_rgb_u8_to_yuv420 turns the batch's RGB frames into the slot's
+    I420 frames on the device, and those come down: out_frame_bytes per frame, on the device and pinned."""
+
+    def __init__(self, yuv):
+        self.yuv = yuv
+
+    def alloc(self, eng):
+        ns, m, H, W = eng.u8.shape[:4]
+        self.lib, self.u8, self.args = eng.lib, eng.u8, (H, W, *self.yuv.codes(), eng.main.cuda_stream)
+        self.host_out = torch.empty(ns, m, self.yuv.out_frame_bytes(eng.net.scale), dtype=torch.uint8, pin_memory=True)
+        self.yuv_out = torch.empty(tuple(self.host_out.shape), dtype=torch.uint8, device=eng.dev)
+
+    def encode(self, sl, cnt):
+        L.check(self.lib.tg_rgb_u8_to_yuv420(self.u8[sl].data_ptr(), self.yuv_out[sl].data_ptr(), cnt, *self.args),
+                'tg_rgb_u8_to_yuv420')
+
+    def download(self, sl, cnt):
+        self.host_out[sl, :cnt].copy_(self.yuv_out[sl, :cnt], non_blocking=True)
+
+    def result(self, sl, cnt):
+        return self.host_out[sl, :cnt].numpy()
+
+
+class _PngOut:
+    """Output form PNG.  A slot, on the device and pinned, is m int64 file sizes followed by m
+    regions of png_stride bytes (tg_png_capacity rounded up to 8), file k from the first byte of region k: the layout is
+    defined here and nowhere else.  ONE tg_png_encode_u8 writes a batch's files and sizes; the sizes and the first cnt
+    regions come down; the chunk is a list of views cut from the pinned slot by the sizes.  The encoder's workspace is
+    one for all slots: every call is on the caller's stream."""
+
+    def __init__(self, png):
+        self.png = png
+
+    def layout(self, m, cap):
+        self.m, self.png_stride = m, (cap + 7) // 8 * 8
+        self.files_at, self.slot_bytes = 8 * m, 8 * m + m * self.png_stride
+
+    def alloc(self, eng):
+        ns, m, H, W = eng.u8.shape[:4]
+        cap, wsb = eng.lib.tg_png_capacity(H, W), eng.lib.tg_png_workspace_bytes(m, H, W)
+        if cap < 0 or wsb < 0:
+            L.check(L.TG_E_SHAPE, 'tg_png_capacity')
+        self.layout(m, cap)
+        self.lib, self.u8, self.size, self.stream = eng.lib, eng.u8, (H, W), eng.main.cuda_stream
+        self.png_out = torch.empty(ns, self.slot_bytes, dtype=torch.uint8, device=eng.dev)
+        self.png_ws = torch.empty(wsb, dtype=torch.uint8, device=eng.dev)
+        self.host_out = torch.empty(ns, self.slot_bytes, dtype=torch.uint8, pin_memory=True)
+
+    def encode(self, sl, cnt):
+        base = self.png_out[sl].data_ptr()
+        L.check(self.lib.tg_png_encode_u8(self.u8[sl].data_ptr(), cnt, *self.size, self.png.code(), base + self.files_at,
+                                          self.png_stride, base, self.png_ws.data_ptr(), self.stream), 'tg_png_encode_u8')
+
+    def download(self, sl, cnt):
+        used = self.files_at + cnt * self.png_stride
+        self.host_out[sl, :used].copy_(self.png_out[sl, :used], non_blocking=True)
+
+    def result(self, sl, cnt):
+        buf = self.host_out[sl].numpy()
+        sizes = buf[:self.files_at].view(np.int64)
+        at = [self.files_at + k * self.png_stride for k in range(cnt)]
+        return [buf[a:a + int(sizes[k])] for k, a in enumerate(at)]
+
+
+class _CutSlots:
+    """The scene-cut slots of a stream with a SceneCut.  A slot's result record, on the device
+    and pinned, is m uint64 SADs at byte 0, m int32 flags at 8 m and m uint32 histogram distances at 12 m -- one buffer,
+    one download; the layout is defined here and nowhere else.  A slot also has the forced mask (device and pinned) and
+    the detector's workspace."""
+
+    def __init__(self, scene_cut):
+        self.sc = scene_cut
+
+    def layout(self, m):
+        self.m, self.flags_at, self.dist_at, self.slot_bytes = m, 8 * m, 12 * m, 16 * m
+
+    def alloc(self, eng):
+        ns, m, dev = eng.ring.slots, eng.m, eng.dev
+        self.layout(m)
+        self.lib, self.lr, self.stream, self.h, self.w = eng.lib, eng.lr, eng.copy.cuda_stream, eng.h, eng.w
+        self.n_pixels, self.hr_bytes = eng.h * eng.w, eng.hr[0].numel() * 4
+        self.sc_out = torch.zeros(ns, self.slot_bytes, dtype=torch.uint8, device=dev)
+        self.sc_host = torch.zeros(ns, self.slot_bytes, dtype=torch.uint8, pin_memory=True)
+        self.sc_forced = torch.zeros(ns, m, dtype=torch.uint8, device=dev)
+        self.sc_forced_host = torch.zeros(ns, m, dtype=torch.uint8, pin_memory=True)
+        self.sc_wsb = self.lib.tg_scene_cut_workspace_bytes(m)
+        self.sc_ws = torch.empty(ns, (self.sc_wsb + 7) // 8 * 8, dtype=torch.uint8, device=dev)
+        self.sc_min = self.sc.thresholds(eng.h, eng.w)
+
+    def detect(self, sl, b, i0, cnt):
+        """Behind the slot's LR frames: the forced mask goes up and tg_scene_cut_flags decides the batch's cnt pairs.
+        Frame 0 of the stream is never a cut: its pair (against the zero frame) is scored, its flag is cleared."""
+        self.sc_forced_host[sl, :cnt].copy_(torch.from_numpy(self.sc.forced(i0, cnt)))
+        self.sc_forced[sl, :cnt].copy_(self.sc_forced_host[sl, :cnt], non_blocking=True)
+        out = self.sc_out[sl].data_ptr()
+        L.check(self.lib.tg_scene_cut_flags(self.lr[sl].data_ptr(), cnt, self.h, self.w, self.sc_min[0], self.sc_min[1],
+                                            self.sc_forced[sl].data_ptr(), 1 if self.sc.detect else 0, out + self.flags_at,
+                                            out, out + self.dist_at, self.sc_ws[sl].data_ptr(), self.sc_wsb, self.stream),
+                'tg_scene_cut_flags')
+        if b == 0:
+            self.sc_out[sl, self.flags_at:self.flags_at + 4].zero_()
+
+    def reset(self, sl):
+        """(address of the slot's flags, bytes of the HR state): what enqueue_batch takes as `reset`."""
+        return self.sc_out[sl].data_ptr() + self.flags_at, self.hr_bytes
+
+    def download(self, sl):
+        self.sc_host[sl].copy_(self.sc_out[sl], non_blocking=True)
+
+    def report(self, sl, i0, cnt):
+        res = self.sc_host[sl].numpy()
+        self.sc.report(i0, res[self.flags_at:self.dist_at].view(np.int32)[:cnt], res[:self.flags_at].view(np.uint64)[:cnt],
+                       res[self.dist_at:].view(np.uint32)[:cnt], self.n_pixels)
+
+
+class _StreamEngine:
+    """State of one FRNet.infer_stream (see there): the part that is the same for every form.  Everything the device
+    touches is allocated once, at the first item: STREAM_SLOTS slots of {LR batch + the frame before it, uint8 frames on
+    the device, HR state snapshot, four events}, the HR ping-pong pair, the zero flow, and what the three form objects
+    above allocate for themselves -- `inp` (staging and raw input), `out` (the pinned output ring and what is encoded
+    into it), `cut` (None without a SceneCut).  Per batch:
+
+    _upload, copy stream: the frame before the batch, inp.upload, cut.detect, ev_in.
+    _compute, caller's stream: the HR snapshot, enqueue_batch (given cut.reset: one tg_zero_if_flag in front of every
+    frame's SRNet launch), out.encode behind the batch's last frame, ev_s.
+    _flush_download, copy stream, behind the NEXT batch's upload or at retire: out.download, cut.download, ev_out.
+    _retire: waits for ev_out, reads the fault counter, cut.report, returns out.result.
+
+    The host never waits for a scene-cut decision.  The repair path knows no form: it runs _compute again, which
+    encodes again and reads the same per-slot flags, and the snapshot it restores was taken before the batch's first
+    conditional fill."""
 
     def __init__(self, net, frames, device, on_fault, yuv=None, scene_cut=None, png=None):
         if on_fault not in ('rerun', 'raise'):
@@ -353,8 +531,11 @@ class _StreamEngine:
                 raise ValueError(f'scene_cut needs RGB frames (in_nc = 3), this network has in_nc = {net.in_nc}')
             scene_cut.cuts.clear()
             scene_cut.scores.clear()
-        self.yuv, self.scene_cut, self.png = yuv, scene_cut, png
-        self.net, self.frames, self.on_fault = net, frames, on_fault
+        # the forms: the output and the scene-cut slots follow from the options, the input from the first item as well
+        self.inp, self.input_form = None, lambda piece: _input_form(piece, net.in_nc, yuv)
+        self.out = _PngOut(png) if png is not None else _I420Out(yuv) if yuv is not None else _RgbOut()
+        self.cut = _CutSlots(scene_cut) if scene_cut is not None else None
+        self.net, self.on_fault, self.parts = net, on_fault, stream_parts(frames, net.in_nc, yuv)
         self.dev = _norm_device(device if device is not None else next(net.parameters()).device)
         self.closed, self.warned, self.reruns = False, False, 0
         self.ring = StreamRing()
@@ -362,16 +543,12 @@ class _StreamEngine:
         self.plan, self.pending_dl, self.prev_rec = None, None, None
 
     # -- allocation (once) ---------------------------------------------------------------------------------------
-    def _open(self, kind, x):
+    def _open(self, piece):
         net, dev = self.net, self.dev
+        self.inp = self.input_form(piece)
         c, s, ns = net.in_nc, net.scale, self.ring.slots
-        self.kind, self.in_cuda = kind, bool(x.is_cuda)
-        if kind == 'yuv':
-            self.h, self.w = self.yuv.h, self.yuv.w
-        else:
-            fmt = StreamFormat(kind, x)
-            self.h, self.w = fmt.h, fmt.w
-        h, w, m = self.h, self.w, max(self.first, self.later)
+        h, w, m = self.inp.h, self.inp.w, max(self.first, self.later)
+        self.h, self.w, self.m = h, w, m
         self.wk = net._weights_key()
         self.plan = net._get_plan(1, h, w, dev, wk=self.wk)
         self.fplans = {}
@@ -383,46 +560,18 @@ class _StreamEngine:
                    torch.empty(1, c, s * h, s * w, dtype=torch.float32, device=dev)]
         self.snap = torch.empty(ns, 1, c, s * h, s * w, dtype=torch.float32, device=dev)
         self.u8 = torch.empty(ns, m, s * h, s * w, c, dtype=torch.uint8, device=dev)
-        ofb = self.yuv.out_frame_bytes(s) if kind == 'yuv' else s * h * s * w * c
-        if self.png is not None:                    # per slot: m int64 sizes, then m regions of one file each
-            cap, wsb = self.lib.tg_png_capacity(s * h, s * w), self.lib.tg_png_workspace_bytes(m, s * h, s * w)
-            if cap < 0 or wsb < 0:
-                L.check(L.TG_E_SHAPE, 'tg_png_capacity')
-            self.png_stride = (cap + 7) // 8 * 8
-            self.png_out = torch.empty(ns, 8 * m + m * self.png_stride, dtype=torch.uint8, device=dev)
-            self.png_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        self.host_out = torch.empty((ns, 8 * m + m * self.png_stride) if self.png is not None else
-                                    (ns, m, ofb) if kind == 'yuv' else (ns, m, s * h, s * w, c), dtype=torch.uint8,
-                                    pin_memory=True)
-        if kind == 'yuv':                           # I420 both ways: 1.5 bytes per pixel through pinned memory
-            self.stage = torch.empty(ns, m, self.yuv.frame_bytes, dtype=torch.uint8, pin_memory=True)
-            self.dev_in = torch.empty(ns, m, self.yuv.frame_bytes, dtype=torch.uint8, device=dev)
-            self.yuv_out = torch.empty(ns, m, ofb, dtype=torch.uint8, device=dev)
-        elif kind == 'u8':
-            self.stage = torch.empty(ns, m, h, w, c, dtype=torch.uint8, pin_memory=True)
-            self.dev_in = torch.empty(ns, m, h, w, c, dtype=torch.uint8, device=dev)
-        elif not self.in_cuda:
-            self.stage = torch.empty(ns, m, c, h, w, dtype=torch.float32, pin_memory=True)
+        self.out.alloc(self)
+        self.inp.alloc(self)
         self.zflow = torch.zeros(2 * self.plan.fh * self.plan.fw, dtype=torch.float32, device=dev)
         self.fsz = 2 * self.plan.fh * self.plan.fw * 4
         # what enqueue_batch is given: addresses per slot, and the bytes from one frame to the next
         self.lr_ptr, self.u8_ptr = [t.data_ptr() for t in self.lr], [t.data_ptr() for t in self.u8]
         self.lr_stride, self.u8_stride = c * h * w * 4, s * h * s * w * c
         self.hr_ptr = (self.hr[0].data_ptr(), self.hr[1].data_ptr())
-        self.reset = None
-        if self.scene_cut is not None:
-            # per slot and frame: SAD (8 bytes), flag (4), histogram distance (4) -- one buffer, one download
-            self.sc_out = torch.zeros(ns, 16 * m, dtype=torch.uint8, device=dev)
-            self.sc_host = torch.zeros(ns, 16 * m, dtype=torch.uint8, pin_memory=True)
-            self.sc_forced = torch.zeros(ns, m, dtype=torch.uint8, device=dev)
-            self.sc_forced_host = torch.zeros(ns, m, dtype=torch.uint8, pin_memory=True)
-            self.sc_wsb = self.lib.tg_scene_cut_workspace_bytes(m)
-            self.sc_ws = torch.empty(ns, (self.sc_wsb + 7) // 8 * 8, dtype=torch.uint8, device=dev)
-            self.sc_min = self.scene_cut.thresholds(h, w)
-            self.reset = [(self.sc_out[sl].data_ptr() + 8 * m, self.hr[0].numel() * 4) for sl in range(ns)]
+        if self.cut is not None:
+            self.cut.alloc(self)
         ev = lambda: [torch.cuda.Event() for _ in range(ns)]
         self.ev_in, self.ev_f, self.ev_s, self.ev_out = ev(), ev(), ev(), ev()
-        self.ev_arrive = torch.cuda.Event()
         self.side.wait_stream(self.main)            # weights, the zeroed state and the rings are ready
         self.copy.wait_stream(self.main)
 
@@ -434,21 +583,7 @@ class _StreamEngine:
             fp = self.fplans[npair] = self.net._get_plan(npair, self.h, self.w, self.dev, fnet_only=True, wk=self.wk)
         return fp
 
-    # -- input ---------------------------------------------------------------------------------------------------
-    def _take(self, b, off, piece):
-        """A piece of the batch being filled: host frames into the slot's pinned staging (the caller's buffer is free
-        again when this returns), device frames straight into the LR slot on the copy stream."""
-        sl, n = self.ring.slot(b), piece.shape[0]
-        if not self.in_cuda:
-            self.stage[sl, off:off + n].copy_(piece)
-            return
-        piece = piece.contiguous()
-        self.ev_arrive.record(torch.cuda.current_stream(self.dev))
-        self.copy.wait_event(self.ev_arrive)
-        with torch.cuda.stream(self.copy):
-            self.lr[sl, 1 + off:1 + off + n].copy_(piece, non_blocking=True)
-        piece.record_stream(self.copy)
-
+    # -- launches of one batch: infer_sequence(pipeline=True)'s, on this slot's buffers ---------------------------------
     def _upload(self, rec):
         b, i0, cnt = rec
         sl = self.ring.slot(b)
@@ -458,39 +593,12 @@ class _StreamEngine:
             else:
                 pb, _, pcnt = self.prev_rec
                 self.lr[sl, 0].copy_(self.lr[self.ring.slot(pb), pcnt], non_blocking=True)
-            if self.kind == 'u8':
-                self.dev_in[sl, :cnt].copy_(self.stage[sl, :cnt], non_blocking=True)
-                L.check(self.lib.tg_dequantize_u8_hwc(self.dev_in[sl].data_ptr(), self.lr[sl, 1].data_ptr(), cnt,
-                                                      self.net.in_nc, self.h, self.w, self.copy.cuda_stream),
-                        'tg_dequantize_u8_hwc')
-            elif self.kind == 'yuv':
-                self.dev_in[sl, :cnt].copy_(self.stage[sl, :cnt], non_blocking=True)
-                L.check(self.lib.tg_yuv420_to_rgb_f32(self.dev_in[sl].data_ptr(), self.lr[sl, 1].data_ptr(), cnt,
-                                                      self.h, self.w, *self.yuv.codes(), self.copy.cuda_stream),
-                        'tg_yuv420_to_rgb_f32')
-            elif not self.in_cuda:
-                self.lr[sl, 1:1 + cnt].copy_(self.stage[sl, :cnt], non_blocking=True)
-            if self.scene_cut is not None:
-                self._detect(sl, b, i0, cnt)
+            self.inp.upload(sl, cnt)
+            if self.cut is not None:
+                self.cut.detect(sl, b, i0, cnt)     # behind whatever wrote the slot's LR frames
             self.ev_in[sl].record(self.copy)
         self.prev_rec = rec
 
-    def _detect(self, sl, b, i0, cnt):
-        """On the copy stream, behind the slot's LR frames: the forced mask goes up and tg_scene_cut_flags decides the
-        batch's cnt pairs.  Frame 0 of the stream is never a cut: its pair (against the zero frame) is scored, its flag
-        is cleared."""
-        sc, m = self.scene_cut, self.sc_forced.shape[1]
-        self.sc_forced_host[sl, :cnt].copy_(torch.from_numpy(sc.forced(i0, cnt)))
-        self.sc_forced[sl, :cnt].copy_(self.sc_forced_host[sl, :cnt], non_blocking=True)
-        out = self.sc_out[sl].data_ptr()
-        L.check(self.lib.tg_scene_cut_flags(self.lr[sl].data_ptr(), cnt, self.h, self.w, self.sc_min[0], self.sc_min[1],
-                                            self.sc_forced[sl].data_ptr(), 1 if sc.detect else 0, out + 8 * m, out,
-                                            out + 12 * m, self.sc_ws[sl].data_ptr(), self.sc_wsb,
-                                            self.copy.cuda_stream), 'tg_scene_cut_flags')
-        if b == 0:
-            self.sc_out[sl, 8 * m:8 * m + 4].zero_()
-
-    # -- launches of one batch: infer_sequence(pipeline=True)'s, on this slot's buffers ---------------------------------
     def _compute(self, rec):
         b, i0, cnt = rec
         sl, ns = self.ring.slot(b), self.ring.slots
@@ -503,17 +611,8 @@ class _StreamEngine:
         enqueue_batch(self.lib, self.plan, self._fplan, b, i0, cnt, self.lr_ptr[sl], self.lr_stride, self.hr_ptr,
                       self.u8_ptr[sl], self.u8_stride, self.zflow.data_ptr(), self.fsz, main, side, self.ev_f[sl],
                       self.ev_s[(b - 2) % ns] if b >= 2 else None,     # (flow slot b & 1 was batch b - 2's)
-                      **({} if self.reset is None else {'reset': self.reset[sl]}))
-        if self.yuv is not None:                    # the batch's RGB frames -> I420, behind its last frame
-            s = self.net.scale
-            L.check(self.lib.tg_rgb_u8_to_yuv420(self.u8[sl].data_ptr(), self.yuv_out[sl].data_ptr(), cnt,
-                                                 s * self.h, s * self.w, *self.yuv.codes(), main.cuda_stream),
-                    'tg_rgb_u8_to_yuv420')
-        if self.png is not None:                    # the batch's RGB frames -> PNG files, behind its last frame
-            s, base = self.net.scale, self.png_out[sl].data_ptr()
-            L.check(self.lib.tg_png_encode_u8(self.u8[sl].data_ptr(), cnt, s * self.h, s * self.w, self.png.code(),
-                                              base + 8 * self.u8.shape[1], self.png_stride, base,
-                                              self.png_ws.data_ptr(), main.cuda_stream), 'tg_png_encode_u8')
+                      reset=self.cut.reset(sl) if self.cut is not None else None)
+        self.out.encode(sl, cnt)                    # behind the batch's last frame
         self.ev_s[sl].record(main)
         self.pending_dl = rec
 
@@ -528,14 +627,9 @@ class _StreamEngine:
         sl = self.ring.slot(b)
         self.copy.wait_event(self.ev_s[sl])
         with torch.cuda.stream(self.copy):
-            if self.png is not None:                # the sizes and the first cnt regions
-                used = 8 * self.u8.shape[1] + cnt * self.png_stride
-                self.host_out[sl, :used].copy_(self.png_out[sl, :used], non_blocking=True)
-            else:
-                done = self.yuv_out if self.yuv is not None else self.u8
-                self.host_out[sl, :cnt].copy_(done[sl, :cnt], non_blocking=True)
-            if self.scene_cut is not None:
-                self.sc_host[sl].copy_(self.sc_out[sl], non_blocking=True)
+            self.out.download(sl, cnt)
+            if self.cut is not None:
+                self.cut.download(sl)
             self.ev_out[sl].record(self.copy)
 
     # -- faults --------------------------------------------------------------------------------------------------
@@ -598,27 +692,20 @@ class _StreamEngine:
                 break
             self._recover(err)
         _, i0, _ = self.ring.retire()
-        if self.scene_cut is not None:
-            m, res = self.sc_forced.shape[1], self.sc_host[sl].numpy()
-            self.scene_cut.report(i0, res[8 * m:12 * m].view(np.int32)[:cnt], res[:8 * m].view(np.uint64)[:cnt],
-                                  res[12 * m:].view(np.uint32)[:cnt], self.h * self.w)
-        if self.png is not None:
-            m, buf = self.u8.shape[1], self.host_out[sl].numpy()
-            sizes = buf[:8 * m].view(np.int64)
-            return [buf[8 * m + k * self.png_stride:8 * m + k * self.png_stride + int(sizes[k])] for k in range(cnt)]
-        return self.host_out[sl, :cnt].numpy()
+        if self.cut is not None:
+            self.cut.report(sl, i0, cnt)
+        return self.out.result(sl, cnt)
 
     # -- the generator -------------------------------------------------------------------------------------------
     def run(self):
         # (no torch.no_grad() around the yields: it would leak into the caller between them; nothing here records a graph)
         try:
             pending = 0                             # frames taken into the batch being filled
-            for b, off, piece, full in stream_rebatch(stream_parts(self.frames, self.net.in_nc, self.yuv),
-                                                      self.first, self.later):
+            for b, off, piece, full in stream_rebatch(self.parts, self.first, self.later):
                 if self.plan is None:
                     self.net.check_faults()         # a fault of an EARLIER clip is never this stream's to repair
-                    self._open('yuv' if self.yuv is not None else 'u8' if piece.dtype == torch.uint8 else 'f32', piece)
-                self._take(b, off, piece)
+                    self._open(piece)
+                self.inp.take(self.ring.slot(b), off, piece)
                 pending = off + piece.shape[0]
                 if not full:
                     continue
@@ -646,6 +733,6 @@ class _StreamEngine:
             if self.ring.inflight:
                 self.plan.chain_state()             # a fault in frames nobody will see: counted, the plan has fallen back
         finally:
-            for name in ('lr', 'hr', 'snap', 'u8', 'host_out', 'stage', 'dev_in', 'yuv_out', 'png_out', 'png_ws', 'zflow',
-                         'sc_out', 'sc_host', 'sc_forced', 'sc_forced_host', 'sc_ws'):
-                self.__dict__.pop(name, None)
+            self.inp = self.out = self.cut = None   # the forms' buffers go with them
+            self.lr = self.hr = self.snap = self.u8 = self.zflow = None
+

@@ -254,6 +254,13 @@ def test_uint8_and_i420_input(net4):
     sc = SceneCut()
     out = np.concatenate([x.copy() for x in net4.infer_stream(iter([f for f in i420]), DEV, yuv=spec, scene_cut=sc)], 0)
     assert sc.cuts == [8] and out.shape == (26, spec.out_frame_bytes(4))
+    # uint8 input with png and a forced cut: the files are those of the frames the same stream yields without png
+    from tecogan_pytorch_amd.models.networks import Png
+    d, e = SceneCut(detect=False, at=[8]), SceneCut(detect=False, at=[8])
+    frames = streamed(net4, [f.numpy() for f in u8], scene_cut=d)
+    files = [v.tobytes() for chunk in net4.infer_stream(iter([f.numpy() for f in u8]), DEV, png=Png(), scene_cut=e)
+             for v in chunk]
+    assert files == ops.png_encode(torch.from_numpy(frames).to(DEV)) and d.cuts == e.cuts == [8]
 
 
 # ------------------------------------------------------------------ 7. the other networks

@@ -206,6 +206,66 @@ def test_one_stream_per_network_without_a_gpu():
     net.infer_stream(iter([]), device='cpu')
 
 
+# ------------------------------------------------------------------ slot layouts of the form objects
+@pytest.mark.parametrize('m,cnt', [(1, 1), (3, 1), (3, 3)])
+def test_png_slot_layout(m, cnt):
+    """A PNG slot is m int64 sizes, then m regions of `stride` bytes (the capacity rounded up to 8), file k from the
+    first byte of region k: result() cuts exactly the first cnt files out of a hand-built pinned ring, as views."""
+    from tecogan_pytorch_amd.models.networks.stream import Png, _PngOut
+    ns, cap = 3, 21
+    stride = 24
+    out = _PngOut(Png())
+    out.layout(m, cap)
+    assert (out.png_stride, out.slot_bytes) == (stride, 8 * m + m * stride)
+    sizes = np.array([[(0, stride, 5)[(sl + k) % 3] for k in range(m)] for sl in range(ns)], np.int64)
+    ring = (np.arange(ns * (8 * m + m * stride)) % 251).astype(np.uint8).reshape(ns, 8 * m + m * stride)
+    for sl in range(ns):
+        ring[sl, :8 * m] = np.frombuffer(sizes[sl].tobytes(), np.uint8)
+    assert {0, stride} <= set(sizes.ravel().tolist())
+    want = ring.copy()
+    out.host_out = torch.from_numpy(ring)
+    for sl in range(ns):
+        files = out.result(sl, cnt)
+        assert isinstance(files, list) and len(files) == cnt
+        for k, f in enumerate(files):
+            lo = 8 * m + k * stride
+            assert f.dtype == np.uint8 and f.shape == (int(sizes[sl, k]),)
+            assert np.array_equal(f, want[sl, lo:lo + int(sizes[sl, k])])
+            if f.size:                              # a view of the ring at exactly that offset, not a copy
+                assert f.__array_interface__['data'][0] == ring[sl].__array_interface__['data'][0] + lo
+    assert np.array_equal(ring, want)
+
+
+@pytest.mark.parametrize('m,cnt', [(1, 1), (3, 1), (3, 3)])
+def test_scene_cut_record_layout(m, cnt):
+    """A slot's result record is m uint64 SADs at byte 0, m int32 flags at 8 m, m uint32 histogram distances at 12 m:
+    report() hands the first cnt of each to SceneCut.report, and reset() is the address of the slot's flags."""
+    from tecogan_pytorch_amd.models.networks.stream import SceneCut, _CutSlots
+    ns, n_pixels, i0 = 3, 10, 17
+    sc = SceneCut(keep_scores=True)
+    slots = _CutSlots(sc)
+    slots.layout(m)
+    assert slots.slot_bytes == 16 * m
+    sad = np.array([[1000 * sl + 10 * k + 2 ** 40 for k in range(m)] for sl in range(ns)], np.uint64)
+    flags = np.array([[(sl + k) % 2 for k in range(m)] for sl in range(ns)], np.int32)
+    dist = np.array([[7 * sl + k + 1 for k in range(m)] for sl in range(ns)], np.uint32)
+    rec = np.zeros((ns, 16 * m), np.uint8)
+    for sl in range(ns):
+        rec[sl, :8 * m] = np.frombuffer(sad[sl].tobytes(), np.uint8)
+        rec[sl, 8 * m:12 * m] = np.frombuffer(flags[sl].tobytes(), np.uint8)
+        rec[sl, 12 * m:] = np.frombuffer(dist[sl].tobytes(), np.uint8)
+    slots.sc_host, slots.n_pixels = torch.from_numpy(rec), n_pixels
+    for sl in range(ns):
+        sc.cuts.clear()
+        sc.scores.clear()
+        slots.report(sl, i0, cnt)
+        assert sc.cuts == [i0 + k for k in range(cnt) if flags[sl, k]]
+        assert sc.scores == [(int(sad[sl, k]) / n_pixels, int(dist[sl, k]) / (2 * n_pixels)) for k in range(cnt)]
+    slots.sc_out, slots.hr_bytes = torch.zeros(ns, 16 * m, dtype=torch.uint8), 4 * 3 * 96 * 160
+    for sl in range(ns):
+        assert slots.reset(sl) == (slots.sc_out.data_ptr() + sl * 16 * m + 8 * m, 4 * 3 * 96 * 160)
+
+
 # ------------------------------------------------------------------ CLI
 def test_parse_args_accepts_the_infer_mode():
     from tecogan_pytorch_amd.main import parse_args

@@ -7,7 +7,7 @@ import os
 import torch
 
 from ... import _lib as L
-from ... import ops
+from .. import packs
 
 
 def _norm_device(device):
@@ -66,7 +66,7 @@ class _StepPlan:
                     os.environ.get('TG_WINO_RES_CT', '1') != '0':
                 # SRNet's first up-sampling layer as the tail of the resident body launch (tg_conv3x3_wino_res.hip);
                 # the plan uses it when the frame runs that launch.  TG_WINO_RES_CT=0: always a launch of its own.
-                u = ops.pack_wres_convt(m.weight.detach().contiguous())
+                u = packs.get(m, 'wres_convt')
             self.keep += [wt, b, u]
             arr[i].w, arr[i].b = wt.data_ptr(), b.data_ptr()
             arr[i].u = u.data_ptr() if u is not None else None

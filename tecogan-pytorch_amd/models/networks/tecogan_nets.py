@@ -15,6 +15,7 @@ import torch.nn as nn
 
 from ... import _lib as L
 from ... import ops
+from .. import packs
 from .. import train_graph as TG
 from ...utils.net_utils import get_upsampling_func
 # (what is not a network: every name stays reachable as tecogan_nets.<name>)
@@ -39,41 +40,21 @@ class _Conv(nn.Module):
         fan_in = self.weight.shape[1] * 9
         bound = 1 / math.sqrt(fan_in)
         nn.init.uniform_(self.bias, -bound, bound)
-        self._cache = None
-        self._cache_u = None
 
     def packed(self):
         """(packed weights, ocb) on the parameter's device; re-packed only when
-        the parameter changed (optimizer step / load_state_dict)."""
-        w = self.weight
-        key = (ops.param_version(w), w.device)
-        if self._cache is None or self._cache[0] != key:
-            pk, _, _, ocb = ops.pack_conv3x3(w, transposed=self.transposed)
-            self._cache = (key, pk, ocb)
-        return self._cache[1], self._cache[2]
+        the parameter changed (models/packs.py)."""
+        return packs.get(self, 'direct')
 
     def packed_wino(self):
         """Winograd-form weights (tg_pack_conv3x3_wino) of a plain 3x3 layer, or None when the
         layer has no such form (transposed, cout neither 32 nor a multiple of 64, cin < 16)."""
         if self.transposed or (self.cout % 64 != 0 and self.cout != 32) or self.cin < 16:
             return None
-        w = self.weight
-        key = (ops.param_version(w), w.device)
-        if self._cache_u is None or self._cache_u[0] != key:
-            self._cache_u = (key, ops.pack_conv3x3_wino(w.detach().contiguous()))
-        return self._cache_u[1]
+        return packs.get(self, 'wino')
 
     def forward(self, x, act=ops.ACT_NONE, x2=None, res=None, out=None, pool=False):
-        if not self.transposed and not pool and \
-                TG._prefers_wino(x.shape[0], self.cin, self.cout, x.shape[2], x.shape[3]):
-            u = self.packed_wino()
-            if u is not None:
-                return ops.conv3x3_wino(x, u, self.bias, self.cin, self.cout, act, x2=x2, res=res, out=out)
-        pk, ocb = self.packed()
-        if self.transposed:
-            return ops.convt3x3s2(x, pk, self.bias, self.cout, act, out=out)
-        return ops.conv3x3(x, pk, self.bias, self.cin, self.cout, ocb, act, x2=x2, res=res,
-                           out=out, pool=pool)
+        return packs.conv3x3_forward(self, x, act, x2, res, out, pool)
 
 
 def _block(pairs):
@@ -118,7 +99,6 @@ class FNet(nn.Module):
         out = self.flow['0'](out, ops.ACT_LRELU02)
         head = self.flow['2']
         return ops.conv3x3_small(out, head.weight, head.bias, ops.ACT_TANH24)
-
 
     def _forward_train(self, x1, x2, tape):
         """Same network on the tape (activations kept, backward closures recorded)."""
@@ -166,12 +146,7 @@ class SRNet(nn.Module):
         self.upsample_func = upsample_func
 
     def layers(self):
-        out = [self.conv_in['0']]
-        for rb in self.resblocks:
-            out += [rb.conv['0'], rb.conv['2']]
-        out += [self.conv_up[k] for k in self.conv_up]
-        out.append(self.conv_out)
-        return out
+        return packs.body_layers(self) + [self.conv_up[k] for k in self.conv_up] + [self.conv_out]
 
     def up_mode(self):
         return ops.UP_BICUBIC if isinstance(self.upsample_func, nn.Module) else ops.UP_BILINEAR

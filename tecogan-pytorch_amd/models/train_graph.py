@@ -16,6 +16,9 @@ import os
 import torch
 
 from .. import ops
+from . import packs
+# (what moved next to the packed-weight store stays reachable here: tests and labs use these names)
+from .packs import _K4, _KT, _conv4_embed, _convt_embed, _embed_index, prefers_wino as _prefers_wino  # noqa: F401
 # (the fail-safe of the chained launches lives in train_chain; its names stay reachable here)
 from .train_chain import (_ChainState, _distributed_world, chain_check, chain_epoch,  # noqa: F401
                           guard_available, stamp_fault)
@@ -191,60 +194,16 @@ def _grad_buf(p):
     return p.grad
 
 
-class ConvCache:
-    """Per-layer packed weights for the training step (forward, data-gradient and the
-    space-to-depth embeddings), rebuilt when the parameter version changes.  The entries live
-    ON the layer object: a process-wide table keyed by id(layer) would hand a new model the
-    stale packs of a freed one whose id, storage address and version counters it re-uses."""
-
-    @staticmethod
-    def get(owner, key, version, build):
-        store = owner.__dict__.setdefault('_tg_pack_cache', {})
-        ent = store.get(key)
-        if ent is None or ent[0] != version:
-            ent = (version, build())
-            store[key] = ent
-        return ent[1]
-
-
-_CACHE = ConvCache()
-
-
-def _ver(w):
-    return ops.param_version(w)
-
-
 # ---------------------------------------------------------------------------
 # conv3x3 (+bias, +activation, two-source input, residual)
 # ---------------------------------------------------------------------------
-_WINO_RULE = {}
-
-
-def _prefers_wino(n, cin, cout, h, w):
-    """tg_conv3x3_prefers_wino, memoised per shape (the tape asks ~2000 times per training step)."""
-    if cout % 64 or cin < 16:
-        return False
-    key = (n, cin, cout, h, w)
-    r = _WINO_RULE.get(key)
-    if r is None:
-        from .. import _lib as L
-        r = _WINO_RULE[key] = bool(L.lib().tg_conv3x3_prefers_wino(n, cin, cout, h, w))
-    return r
-
-
 def conv3x3(tape, layer, x, act=NONE, x2=None, res=None, need_dx=True, need_dx2=True):
     w, b = layer.weight, layer.bias
     cout, cin = w.shape[0], w.shape[1]
-    n_, _, h_, w_ = x.shape
-    u = layer.packed_wino() if hasattr(layer, 'packed_wino') and _prefers_wino(n_, cin, cout, h_, w_) else None
-    if u is not None:     # large layers (D's conv_in, VGG19 on the HR frames): Winograd form
-        y = ops.conv3x3_wino(x, u, b, cin, cout, act, x2=x2, res=res)
-    else:
-        pk, ocb = layer.packed()
-        y = ops.conv3x3(x, pk, b, cin, cout, ocb, act, x2=x2, res=res, ksplit=None if res is None else 1)
+    n_, c1, h_, w_ = x.shape
+    y = packs.conv3x3_forward(layer, x, act, x2, res)    # (D's conv_in, VGG19 on the HR frames: Winograd form)
     if tape is None:
         return y
-    c1 = x.shape[1]
     if act in (RELU, LRELU) and res is None:
         tape.act_outputs[id(y)] = act
 
@@ -264,23 +223,17 @@ def conv3x3(tape, layer, x, act=NONE, x2=None, res=None, need_dx=True, need_dx2=
             tape.defer_wgrad(('w', id(layer), 0), dz, x, gw, 0, bias=None if x2 is not None else _grad_buf(b))
             if x2 is not None:
                 tape.defer_wgrad(('w', id(layer), 1), dz, x2, gw, c1, bias=_grad_buf(b))
-        wd = w.detach()
         if need_dx and c1 <= 4 and cout <= 64 and x2 is None:
             # data gradient onto an image (VGG's first conv): cout -> <=4 channels is the small
             # kernel's shape; its weights are the 180-degree rotated, transposed taps
-            wdg = _CACHE.get(layer, ('dgs',), _ver(w),
-                             lambda: wd.flip(2, 3).permute(1, 0, 2, 3).contiguous())
-            tape.add_grad(x, ops.conv3x3_small(dz, wdg, None))
+            tape.add_grad(x, ops.conv3x3_small(dz, packs.get(layer, 'dgrad_small'), None))
         elif need_dx and x2 is None and _prefers_wino(n_, cout, cin, h_, w_):
-            ud = _CACHE.get(layer, ('dgu',), _ver(w), lambda: ops.pack_conv3x3_wino(wd.contiguous(), transposed=2))
-            tape.add_grad(x, ops.conv3x3_wino(dz, ud, None, cout, cin, NONE))
+            tape.add_grad(x, ops.conv3x3_wino(dz, packs.get(layer, 'dgrad_wino'), None, cout, cin, NONE))
         elif need_dx:
-            pkd = _CACHE.get(layer, ('dg', 0), _ver(w), lambda: ops.pack_conv3x3_dgrad(
-                wd[:, :c1].contiguous()))
+            pkd = packs.get(layer, 'dgrad', 0, c1)
             tape.add_grad(x, ops.conv3x3(dz, pkd[0], None, cout, c1, pkd[3], ksplit=None))
         if x2 is not None and need_dx2:
-            pkd = _CACHE.get(layer, ('dg', 1), _ver(w), lambda: ops.pack_conv3x3_dgrad(
-                wd[:, c1:].contiguous()))
+            pkd = packs.get(layer, 'dgrad', c1, cin)
             tape.add_grad(x2, ops.conv3x3(dz, pkd[0], None, cout, cin - c1, pkd[3], ksplit=None))
     tape.record(bwd)
     return y
@@ -305,11 +258,11 @@ def resblock(tape, conv1, conv2, x):
             return
         if w2.requires_grad:
             tape.defer_wgrad(('w', id(conv2), 0), g, y1, _grad_buf(w2), 0, bias=_grad_buf(b2))
-        pk2 = _CACHE.get(conv2, ('dg', 0), _ver(w2), lambda: ops.pack_conv3x3_dgrad(w2.detach().contiguous()))
+        pk2 = packs.get(conv2, 'dgrad', 0, w2.shape[1])
         dz1 = ops.conv3x3(g, pk2[0], None, c, c, pk2[3], relu_mask=y1)
         if w1.requires_grad:
             tape.defer_wgrad(('w', id(conv1), 0), dz1, x, _grad_buf(w1), 0, bias=_grad_buf(b1))
-        pk1 = _CACHE.get(conv1, ('dg', 0), _ver(w1), lambda: ops.pack_conv3x3_dgrad(w1.detach().contiguous()))
+        pk1 = packs.get(conv1, 'dgrad', 0, w1.shape[1])
         tape.add_grad(x, ops.conv3x3(dz1, pk1[0], None, c, w1.shape[1], pk1[3], res=g))
     tape.record(bwd)
     return out
@@ -324,25 +277,13 @@ def srnet_body(tape, srnet, lr, tran):
     forward, one launch for the whole reverse sweep of these 1 + 2*nb layers; the (dZ, X) pairs of
     the weight gradients are deferred exactly as the per-layer nodes defer them."""
     from .. import _lib as L
-    conv_in = srnet.conv_in['0']
-    blocks = [(rb.conv['0'], rb.conv['2']) for rb in srnet.resblocks]
-    layers = [conv_in] + [c for pair in blocks for c in pair]
-    nb, nl = len(blocks), 1 + 2 * len(blocks)
     n, c_lr, h, w = lr.shape
+    layout = 16 if _ChainState.parts(n, h, w) == 4 else 64
+    layers, keep, dgp = packs.get(srnet, 'body', layout, c_lr)
+    conv_in, nl = layers[0], len(layers)
+    nb = (nl - 1) // 2
     c_tran, nf = tran.shape[1], conv_in.cout
     fw = (L.PackedLayer * nl)()
-    layout = 16 if _ChainState.parts(n, h, w) == 4 else 64
-    # all 2 x (1 + 2nb) packs (forward, data gradient) of the body by two launches, cached on the network
-    # until a parameter changes
-    ver = (tuple(_ver(m.weight) for m in layers), layout, c_lr)      # every layer: a partial load / freeze must re-pack too
-
-    def build():
-        ws = [m.weight.detach() for m in layers]
-        f = ops.chain_pack([(wt, 0, wt.shape[1], 0) for wt in ws], layout)
-        # (the data gradient of conv_in only reaches `tran`: input channels [c_lr, c_lr + c_tran))
-        d = ops.chain_pack([(ws[0], c_lr, c_tran, 2)] + [(wt, 0, wt.shape[1], 2) for wt in ws[1:]], layout)
-        return f, d
-    keep, dgp = _CACHE.get(srnet, ('body',), ver, build)
     for i, m in enumerate(layers):
         fw[i].w, fw[i].b = keep[i].data_ptr(), m.bias.data_ptr()
     acts = torch.empty(nl, n, nf, h, w, dtype=torch.float32, device=lr.device)
@@ -363,7 +304,6 @@ def srnet_body(tape, srnet, lr, tran):
         if g is None:
             return
         dg = (L.PackedLayer * nl)()
-        hold = dgp
         for i in range(nl):
             dg[i].w = dgp[i].data_ptr()
         if g.data_ptr() != dz[nl - 1].data_ptr():
@@ -374,7 +314,7 @@ def srnet_body(tape, srnet, lr, tran):
                                           c_tran, n, nf, h, w, fl.data_ptr(), er.data_ptr(), ep,
                                           _ChainState.poll_limit, ops._stream()),
                 'tg_srnet_body_bwd')
-        tape.keep.append(hold)
+        tape.keep.append(dgp)
         if conv_in.weight.requires_grad:
             gw = _grad_buf(conv_in.weight)
             tape.defer_wgrad(('w', id(conv_in), 0), dz[0], lr, gw, 0)
@@ -414,12 +354,10 @@ def conv3x3_small(tape, layer, x, act=NONE, up_src=None, up_mode=ops.UP_NONE, up
         fuse = id(x) in tape.relu_outputs        # x = relu(...): deliver dZ of that layer directly
         if ops.conv3x3_fewin_ok(dz, cin) and (not fuse or x.data_ptr() % 16 == 0):
             # few channels in, many out: the VALU kernel (the MFMA one pads K = 9 cout to a 72-deep chunk)
-            wd = _CACHE.get(layer, ('dgw',), _ver(w),
-                            lambda: w.detach().transpose(0, 1).flip(2, 3).contiguous())
+            wd = packs.get(layer, 'dgrad_fewin')
             tape.add_grad(x, ops.conv3x3_fewin(dz, wd, relu_mask=x if fuse else None), masked=fuse)
         else:
-            pkd = _CACHE.get(layer, ('dg', 0), _ver(w),
-                             lambda: ops.pack_conv3x3_dgrad(w.detach().contiguous()))
+            pkd = packs.get(layer, 'dgrad', 0, cin)
             tape.add_grad(x, ops.conv3x3(dz, pkd[0], None, cout, cin, pkd[3], ksplit=1,
                                          relu_mask=x if fuse else None), masked=fuse)
     tape.record(bwd)
@@ -428,44 +366,8 @@ def conv3x3_small(tape, layer, x, act=NONE, up_src=None, up_mode=ops.UP_NONE, up
 
 # ---------------------------------------------------------------------------
 # ConvTranspose2d(k3,s2,p1,op1): forward = sub-pixel phase kernel; backward via
-# the space-to-depth embedding (oy = 2*iy - 1 + ky  <=>  ky -> (phase, tap)).
+# the space-to-depth embedding (packs._convt_embed).
 # ---------------------------------------------------------------------------
-_KT = {0: (1, 0), 1: (0, 1), 2: (1, 1)}          # convT: ky -> (py, ty)
-_IDX = {}
-
-
-def _embed_index(kind, a, b, device):
-    """Flat gather indices of the space-to-depth embeddings, built once per shape:
-    `fwd` maps every element of the embedded 3x3 weight to its source element (or to a
-    trailing zero slot), `inv` maps every element of the original weight to its slot in the
-    embedded tensor.  One index_select then replaces 9 / 16 strided slice copies."""
-    key = (kind, a, b, str(device))
-    ent = _IDX.get(key)
-    if ent is None:
-        table = _KT if kind == 'convt' else _K4
-        k = len(table)
-        src = torch.arange(a * b * k * k, dtype=torch.int64).view(a, b, k, k)
-        # convt: (ci, co, 3, 3) -> (ci, 4co, 3, 3); conv4: (co, ci, 4, 4) -> (co, 4ci, 3, 3)
-        emb = torch.full((a, 4 * b, 3, 3), a * b * k * k, dtype=torch.int64)
-        for ky, (py, ty) in table.items():
-            for kx, (px, tx) in table.items():
-                ph = py * 2 + px
-                emb[:, ph * b:(ph + 1) * b, ty, tx] = src[:, :, ky, kx]
-        fwd = emb.reshape(-1)
-        inv = torch.empty(a * b * k * k, dtype=torch.int64)
-        valid = fwd < a * b * k * k
-        inv[fwd[valid]] = torch.nonzero(valid).reshape(-1)
-        ent = _IDX[key] = (fwd.to(device), inv.to(device))
-    return ent
-
-
-def _convt_embed(wt):
-    """(ci, co, 3, 3) -> conv weight (cout_op = ci, cin_op = 4*co, 3, 3) acting on s2d(dY)."""
-    ci, co = wt.shape[:2]
-    fwd, _ = _embed_index('convt', ci, co, wt.device)
-    return ops.index_gather(wt.contiguous(), fwd).view(ci, 4 * co, 3, 3)   # out-of-range slot = 0
-
-
 def convt3x3s2(tape, layer, x, act=RELU):
     w, b = layer.weight, layer.bias            # (ci, co, 3, 3)
     ci, co = w.shape[:2]
@@ -489,12 +391,12 @@ def convt3x3s2(tape, layer, x, act=RELU):
         if ops.conv3x3s2_supported(nx, co, ci, hx, wx):
             # small frames: the gradient taken directly as a stride-2 conv of dZ (K = 9 co) -- 11 us
             # instead of 27 us for the 32-chunk phased form on s2d(dZ)
-            wk = _CACHE.get(layer, ('ctd',), _ver(w), lambda: ops.pack_conv3x3(w.detach().contiguous(), ocb=64)[0])
+            wk = packs.get(layer, 'convt_dgrad_s2')
             buf = tape.reserved.get(id(x)) if tape.grad(x) is None else None
             tape.add_grad(x, ops.conv3x3s2(dz, wk, co, ci, relu_mask=x if fuse else None, out=buf), masked=fuse)
         else:
             s = ops.space_to_depth(dz, 2)                          # (n, 4co, h, w)
-            we = _CACHE.get(layer, ('cte',), _ver(w), lambda: ops.pack_conv3x3(_convt_embed(w.detach())))
+            we = packs.get(layer, 'convt_dgrad_embed')
             if co % 8 == 0:    # phase py = 1 owns tap rows {0, 1}, py = 0 only {1}: 9 of 36 taps are non-zero
                 tape.add_grad(x, ops.conv3x3_phased(s, we[0], 4 * co, ci, we[3], 1, co, ops.TAPS_1, ops.TAPS_01,
                                                     relu_mask=x if fuse else None), masked=fuse)
@@ -520,21 +422,11 @@ def convt3x3s2(tape, layer, x, act=RELU):
 
 # ---------------------------------------------------------------------------
 # Conv2d(k4, s2, p1, no bias) of the discriminator blocks through s2d:
-#   2*oy - 1 + ky = 2*(oy + ty - 1) + py
+#   2*oy - 1 + ky = 2*(oy + ty - 1) + py     (packs._conv4_embed)
 # ---------------------------------------------------------------------------
-_K4 = {0: (1, 0), 1: (0, 1), 2: (1, 1), 3: (0, 2)}   # ky -> (py, ty)
-
-
 def direct_conv4():
     """TG_CONV4_DIRECT=0: the embedded form everywhere (lab / tests).  Read per call, so a test can toggle it."""
     return os.environ.get('TG_CONV4_DIRECT', '1') != '0'
-
-
-def _conv4_embed(w4):
-    """(co, ci, 4, 4) -> (co, 4*ci, 3, 3) acting on s2d(x, 2)."""
-    co, ci = w4.shape[:2]
-    fwd, _ = _embed_index('conv4', co, ci, w4.device)
-    return ops.index_gather(w4.contiguous(), fwd).view(co, 4 * ci, 3, 3)
 
 
 def conv4x4s2(tape, holder, x, need_dx=True):
@@ -550,12 +442,12 @@ def conv4x4s2(tape, holder, x, need_dx=True):
     direct = direct_conv4() and ops.conv4x4s2_supported(n, ci, co, h_, w_)
     sparse = ci % 8 == 0 and co > 32
     if direct:
-        pk4 = _CACHE.get(holder, ('c4x',), _ver(w), lambda: ops.pack_conv4x4s2(w.detach().contiguous()))
+        pk4 = packs.get(holder, 'conv4_direct')
         y = ops.conv4x4s2(x, pk4[0], co)
         s_held = [None]
     else:
         s_held = [ops.space_to_depth(x, 2)]
-        pk = _CACHE.get(holder, ('c4f',), _ver(w), lambda: ops.pack_conv3x3(_conv4_embed(w.detach())))
+        pk = packs.get(holder, 'conv4_embed')
         # phase coordinate 1 owns tap rows {0, 1}, coordinate 0 rows {1, 2}: 4 of 9 taps per channel
         if sparse:
             y = ops.conv3x3_phased(s_held[0], pk[0], 4 * ci, co, pk[3], 1, ci, ops.TAPS_12, ops.TAPS_01)
@@ -583,8 +475,7 @@ def conv4x4s2(tape, holder, x, need_dx=True):
                 gx = ops.conv4x4s2_dgrad(g, pk4[1], ci, act_y=x if fuse else None, act=a if fuse else ops.ACT_NONE)
                 tape.add_grad(x, gx, act_applied=fuse)
                 return
-            pkd = _CACHE.get(holder, ('c4d',), _ver(w),
-                             lambda: ops.pack_conv3x3_dgrad(_conv4_embed(w.detach())))
+            pkd = packs.get(holder, 'conv4_dgrad_embed')
             if ci % 64 == 0:    # rot180 taps: coordinate 1 owns rows {1, 2}, coordinate 0 rows {0, 1}
                 ds = ops.conv3x3_phased(g, pkd[0], co, 4 * ci, pkd[3], 2, ci, ops.TAPS_01, ops.TAPS_12)
             else:

@@ -35,7 +35,7 @@
  *     constructs also gets its Python name in _lib.py;
  *   - prototypes `type tg_name(type name, ...);` or `(void)`: every parameter named; one-word scalar
  *     types from the list above by value; pointers and `type name[N]` arrays to those, to void, char,
- *     uint8_t, uint16_t and to the types declared here, `const` where it belongs.  A `T*` parameter whose T
+ *     uint8_t, uint16_t, int16_t and to the types declared here, `const` where it belongs.  A `T*` parameter whose T
  *     is a struct with fields is type-checked as that struct; every other pointer is an untyped address.
  *     A struct must be declared above its first use.
  */
@@ -636,6 +636,27 @@ int tg_downsample_bi_u8(const uint8_t* x_hwc, uint8_t* y_u8_hwc, float* y_f32_ch
                         int pad, tg_stream_t stream);
 int tg_downsample_bi_f32(const float* x_chw, uint8_t* y_u8_hwc, float* y_f32_chw, int n, int h, int w, int scale,
                          int pad, tg_stream_t stream);
+
+/* Bicubic resize of 8-bit frames to any size, the general case of the BI degradation above: one
+ * launch, exact integers, nothing in global memory between the two passes.  The weights differ per output pixel, so
+ * they are arguments: per axis two tables in device memory, made on the host by the contribution algorithm
+ * (ops.resample_tables; tests/resize_ref.py is the specification),
+ *   idx int32 [n_out][taps]: the input pixels output pixel o reads, already mirrored;
+ *   w   int16 [n_out][taps]: their weights over 2^TG_RESAMPLE_WEIGHT_BITS, every row summing to exactly that.
+ * With N = sum_r sum_c v_w[oy][r] h_w[ox][c] x[v_idx[oy][r]][h_idx[ox][c]] the byte is clamp((N + 2^27) >> 28, 0, 255),
+ * round-half-up on the exact value.  x_hwc (n, h_in, w_in, 3) and y_hwc (n, h_out, w_out, 3) uint8, any alignment; the
+ * tables 4- and 2-byte aligned.  Every index read from a table is clamped to [0, n_in - 1] and a tile of `tile`
+ * outputs stages at most tg_resample_tile_span(n_in, n_out, taps, tile) pixels along an axis (a host function: the
+ * bound (tile - 1) ceil(n_in / n_out) + taps + 2 the contribution algorithm keeps, never more than n_in; -1 for an
+ * argument < 1), so a wrong table gives wrong bytes and never an access out of range.
+ * Null pointers, n < 1, taps outside 1..TG_RESAMPLE_MAX_TAPS: TG_E_ARG; a size < 1, h_out / h_in or w_out / w_in outside
+ * [1/4, 4], a frame of 2^31 bytes or more: TG_E_SHAPE.  Nothing is launched then. */
+#define TG_RESAMPLE_MAX_TAPS 18
+#define TG_RESAMPLE_WEIGHT_BITS 14
+int tg_resample_tile_span(int n_in, int n_out, int taps, int tile);
+int tg_resample_u8(const uint8_t* x_hwc, uint8_t* y_hwc, int n, int h_in, int w_in, int h_out, int w_out,
+                   const int32_t* v_idx, const int16_t* v_w, int v_taps, const int32_t* h_idx, const int16_t* h_w,
+                   int h_taps, tg_stream_t stream);
 
 /* MetricCalculator.compute_PSNR (codes/metrics/metric_calculator.py:228-244) on uint8 HWC
  * frames resident on the device: sse[f] = sum of squared differences of frame f, exact

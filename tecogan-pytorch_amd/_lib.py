@@ -31,7 +31,7 @@ class TecoganHipError(RuntimeError):
 _SCALARS = {'int': C.c_int, 'int32_t': C.c_int32, 'int64_t': C.c_int64, 'unsigned': C.c_uint,
             'uint32_t': C.c_uint32, 'uint64_t': C.c_uint64, 'size_t': C.c_size_t,
             'float': C.c_float, 'double': C.c_double}
-_POINTEES = set(_SCALARS) | {'void', 'char', 'uint8_t', 'uint16_t'}       # may stand behind a `*`
+_POINTEES = set(_SCALARS) | {'void', 'char', 'uint8_t', 'uint16_t', 'int16_t'}       # may stand behind a `*`
 _DECLARATOR = re.compile(r'(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\s*)?)*)(\w+)?\s*(\[\s*\w*\s*\])?')
 
 Header = collections.namedtuple('Header', 'constants structs signatures')

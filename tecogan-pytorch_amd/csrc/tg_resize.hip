@@ -230,3 +230,224 @@ extern "C" int tg_downsample_bi_f32(const float* x_chw, uint8_t* y_u8_hwc, float
                                     int scale, int pad, tg_stream_t stream) {
   return tg::downsample_bi_launch("downsample_bi_f32", x_chw, true, y_u8_hwc, y_f32_chw, n, h, w, scale, pad, stream);
 }
+
+// ---- bicubic resize to any size, table-driven -------------------------------------------------
+// The general case of the kernel above: the weights differ per output pixel, so they come as tables, built on the host
+// by the contribution algorithm (tests/resize_ref.py is the specification): per axis idx[n_out][taps] (input pixel,
+// already mirrored) and w[n_out][taps] (int16 over 2^14, every row sums to 2^14).  With N the separable integer sum the
+// byte is clamp((N + 2^27) >> 28, 0, 255).
+//
+// A workgroup makes RS_TH x RS_TW output pixels of one frame.  It copies the tile's table rows into LDS, every index
+// clamped to [0, n_in - 1]; their minimum and maximum per axis are the tile's input footprint, a plain rectangle of
+// the frame (the mirroring is in the tables), at most RS_RH x RS_CW pixels at the ratio 1/4.  The host sizes the LDS by
+// what the call's ratios can ask for (resample_tile_span: 13 KB at 3/4, 39 KB at 1/4, 42 KB at most).  The rectangle is staged as
+// bytes: aligned dword loads of every row (a dword that reaches past either end of the row's bytes is put together from
+// byte loads, so nothing outside the rectangle is read), written to LDS byte by byte so that every staged row starts at
+// its first byte whatever its alignment in memory.  Vertical pass on dwords of four byte columns into int32
+// (|t| <= 255 * 18 * 2^15 < 2^28 for ANY table), horizontal pass in 64 bits, one rounding.  A table that is wrong gives wrong bytes, never an access outside the frame
+// or the staged tile: offsets into the tile are clamped to what was staged.
+namespace tg {
+
+constexpr int RS_TH = 8, RS_TW = 32, RS_T = TG_RESAMPLE_MAX_TAPS, RS_SH = 2 * TG_RESAMPLE_WEIGHT_BITS;
+constexpr int RS_RH = 50, RS_CW = 146;                // footprint of a tile at 1/4: (T - 1) * 4 + 1 + 18 = 47 and 143
+
+// Pixels along an axis that a tile of `tile` outputs can read: output o's first tap is floor(u_o - kw / 2) with
+// u_{o+1} - u_o = n_in / n_out, so two neighbours' first taps lie at most ceil(n_in / n_out) apart; the kept taps are
+// among the taps + 2 columns the contribution algorithm starts from; mirroring only folds them back into the frame.
+__host__ __device__ inline int resample_tile_span(int n_in, int n_out, int taps, int tile) {
+  const long long step = ((long long)n_in + n_out - 1) / n_out;
+  const long long v = (tile - 1) * step + taps + 2;
+  return (int)(v < n_in ? v : n_in);
+}
+static_assert((RS_TH - 1) * 4 + RS_T + 2 <= RS_RH && (RS_TW - 1) * 4 + RS_T + 2 <= RS_CW, "the ratio 1/4 fits the caps");
+
+__global__ __launch_bounds__(256) void resample_u8_kernel(const uint8_t* __restrict__ x, uint8_t* __restrict__ y,
+                                                          int h_in, int w_in, int h_out, int w_out,
+                                                          const int* __restrict__ v_idx, const int16_t* __restrict__ v_w,
+                                                          int v_taps, const int* __restrict__ h_idx,
+                                                          const int16_t* __restrict__ h_w, int h_taps, int tiles_x,
+                                                          int tiles_y, int rh_cap, int cw_cap) {
+  // LDS, sized by the host (resample_lds_bytes): the staged tile of rh_cap rows x nd_cap dwords, the vertical sums,
+  // the tile's table rows, the footprint
+  extern __shared__ __attribute__((aligned(16))) uint32_t rs_lds[];
+  const int nd_cap = (cw_cap * 3 + 3) / 4;            // dwords per staged row
+  const int vrow = nd_cap * 4;                        // vertical sums per tile row, a multiple of 4
+  uint32_t* tile = rs_lds;                            // bytes [row][px * 3 + ch]
+  int* vbuf = reinterpret_cast<int*>(rs_lds + (rh_cap * nd_cap + 3) / 4 * 4);   // vertical sums [r][px * 3 + ch], 16-byte aligned
+  int* s_vi = vbuf + RS_TH * vrow;                    // first the clamped indices, then offsets into tile / vbuf
+  int* s_vw = s_vi + RS_TH * v_taps;
+  int* s_hi = s_vw + RS_TH * v_taps;
+  int* s_hw = s_hi + RS_TW * h_taps;
+  int* s_lim = s_hw + RS_TW * h_taps;                 // row min, row max, column min, column max
+  uint8_t* tile8 = reinterpret_cast<uint8_t*>(tile);
+
+  const int tid = threadIdx.x;
+  int b = blockIdx.x;
+  const int tx = b % tiles_x; b /= tiles_x;
+  const int ty = b % tiles_y;
+  const long long f = b / tiles_y;
+  const int ox0 = tx * RS_TW, oy0 = ty * RS_TH;
+  const int th = h_out - oy0 < RS_TH ? h_out - oy0 : RS_TH;
+  const int tw = w_out - ox0 < RS_TW ? w_out - ox0 : RS_TW;
+
+  if (tid == 0) { s_lim[0] = h_in - 1; s_lim[1] = 0; s_lim[2] = w_in - 1; s_lim[3] = 0; }
+  __syncthreads();
+  int lo_v = h_in - 1, hi_v = 0, lo_h = w_in - 1, hi_h = 0;
+  for (int i = tid; i < th * v_taps; i += 256) {      // (rows oy0 .. oy0 + th - 1 of a table are contiguous)
+    int v = v_idx[(long long)oy0 * v_taps + i];
+    v = v < 0 ? 0 : (v > h_in - 1 ? h_in - 1 : v);
+    s_vi[i] = v;
+    s_vw[i] = (int)v_w[(long long)oy0 * v_taps + i];
+    lo_v = v < lo_v ? v : lo_v;
+    hi_v = v > hi_v ? v : hi_v;
+  }
+  for (int i = tid; i < tw * h_taps; i += 256) {
+    int v = h_idx[(long long)ox0 * h_taps + i];
+    v = v < 0 ? 0 : (v > w_in - 1 ? w_in - 1 : v);
+    s_hi[i] = v;
+    s_hw[i] = (int)h_w[(long long)ox0 * h_taps + i];
+    lo_h = v < lo_h ? v : lo_h;
+    hi_h = v > hi_h ? v : hi_h;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {           // the wave's extremes, then one LDS atomic each per wave
+    const int a = __shfl_xor(lo_v, off), b2 = __shfl_xor(hi_v, off), c = __shfl_xor(lo_h, off), d = __shfl_xor(hi_h, off);
+    lo_v = a < lo_v ? a : lo_v;
+    hi_v = b2 > hi_v ? b2 : hi_v;
+    lo_h = c < lo_h ? c : lo_h;
+    hi_h = d > hi_h ? d : hi_h;
+  }
+  if ((tid & 63) == 0) {
+    atomicMin(&s_lim[0], lo_v);
+    atomicMax(&s_lim[1], hi_v);
+    atomicMin(&s_lim[2], lo_h);
+    atomicMax(&s_lim[3], hi_h);
+  }
+  __syncthreads();
+  const int y_lo = s_lim[0], x_lo = s_lim[2];
+  int nr = s_lim[1] - y_lo + 1, nc = s_lim[3] - x_lo + 1;
+  nr = nr > rh_cap ? rh_cap : nr;                     // (only a wrong table asks for more)
+  nc = nc > cw_cap ? cw_cap : nc;
+  const int nc3 = 3 * nc;
+
+  const uint8_t* xf = x + f * 3LL * h_in * w_in + 3 * x_lo;
+  const long long row3 = 3LL * w_in;
+
+  // staging: a batch of independent loads into registers, then the LDS writes (as in the kernel above).  A row's
+  // shift is where its first byte sits inside its aligned dword in memory.
+  const int nd = (nc3 + 3 + 3) / 4;                   // aligned dwords of a row that can hold one of its bytes
+  const int tot = nr * nd;
+  constexpr int U = 8;
+  for (int base = tid; base < tot; base += 256 * U) {
+    uint32_t v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = base + 256 * u;
+      v[u] = 0u;
+      if (i < tot) {
+        const int q = i % nd, rr = i / nd;
+        const uint8_t* row = xf + (y_lo + rr) * row3;
+        const int first = 4 * q - (int)((uintptr_t)row & 3);             // the aligned dword's first byte in the row's nc3
+        if (first >= 0 && first + 4 <= nc3) {
+          v[u] = *reinterpret_cast<const uint32_t*>(row + first);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (first + e >= 0 && first + e < nc3) v[u] |= (uint32_t)row[first + e] << (8 * e);
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = base + 256 * u;
+      if (i < tot) {
+        const int q = i % nd, rr = i / nd;
+        const int first = 4 * q - (int)((uintptr_t)(xf + (y_lo + rr) * row3) & 3);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (first + e >= 0 && first + e < nc3) tile8[rr * vrow + first + e] = (uint8_t)(v[u] >> (8 * e));
+      }
+    }
+  }
+  // indices -> offsets: first dword of the row in the tile; first int of a column's triple in a vbuf row
+  for (int i = tid; i < th * v_taps; i += 256) {
+    int rel = s_vi[i] - y_lo;
+    rel = rel > nr - 1 ? nr - 1 : rel;
+    s_vi[i] = rel * nd_cap;
+  }
+  for (int i = tid; i < tw * h_taps; i += 256) {
+    int rel = s_hi[i] - x_lo;
+    rel = rel > nc - 1 ? nc - 1 : rel;
+    s_hi[i] = 3 * rel;
+  }
+  __syncthreads();
+
+  // vertical pass: four neighbouring byte columns of one output row per step, lanes along the staged row (the last
+  // dword of a row may hold bytes nobody staged: their sums are never read)
+  const int nd4 = (nc3 + 3) >> 2;
+  for (int i = tid; i < th * nd4; i += 256) {
+    const int q = i % nd4, r = i / nd4;
+    int acc[4] = {0, 0, 0, 0};
+    for (int k = 0; k < v_taps; ++k) {
+      const int w = s_vw[r * v_taps + k];
+      const uint32_t d = tile[s_vi[r * v_taps + k] + q];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[e] += w * (int)((d >> (8 * e)) & 255u);
+    }
+    *reinterpret_cast<int4*>(vbuf + r * vrow + 4 * q) = make_int4(acc[0], acc[1], acc[2], acc[3]);
+  }
+  __syncthreads();
+
+  // horizontal pass and the rounding: lanes along the output row's bytes
+  const int tw3 = 3 * tw;
+  for (int i = tid; i < th * tw3; i += 256) {
+    const int j = i % tw3, r = i / tw3;
+    const int oxl = j / 3, ch = j - 3 * oxl;
+    const int* v = vbuf + r * vrow + ch;
+    long long N = 0;
+    for (int k = 0; k < h_taps; ++k) N += (long long)s_hw[oxl * h_taps + k] * (long long)v[s_hi[oxl * h_taps + k]];
+    // (N + 2^27) >> 28 clamped to a byte: clamp first, then a logical shift (tg_yuv.hip's form)
+    long long a = N + (1LL << (RS_SH - 1));
+    const long long top = (256LL << RS_SH) - 1;
+    a = a < 0 ? 0 : (a > top ? top : a);
+    y[((f * h_out + (oy0 + r)) * w_out + ox0) * 3 + j] = (uint8_t)((unsigned long long)a >> RS_SH);
+  }
+}
+
+// the dynamic LDS of a launch with these caps and tap counts, as the kernel lays it out
+static size_t resample_lds_bytes(int rh_cap, int cw_cap, int v_taps, int h_taps) {
+  const int nd_cap = (cw_cap * 3 + 3) / 4;
+  return 4 * ((size_t)(rh_cap * nd_cap + 3) / 4 * 4 + (size_t)RS_TH * nd_cap * 4 + 2 * (size_t)(RS_TH * v_taps + RS_TW * h_taps) + 4);
+}
+
+}  // namespace tg
+
+extern "C" int tg_resample_tile_span(int n_in, int n_out, int taps, int tile) {
+  if (n_in < 1 || n_out < 1 || taps < 1 || tile < 1) return -1;
+  return tg::resample_tile_span(n_in, n_out, taps, tile);
+}
+
+extern "C" int tg_resample_u8(const uint8_t* x_hwc, uint8_t* y_hwc, int n, int h_in, int w_in, int h_out, int w_out,
+                              const int32_t* v_idx, const int16_t* v_w, int v_taps, const int32_t* h_idx,
+                              const int16_t* h_w, int h_taps, tg_stream_t stream) {
+  TG_REQUIRE(x_hwc && y_hwc && v_idx && v_w && h_idx && h_w, TG_E_ARG, "resample_u8: null pointer");
+  TG_REQUIRE(n >= 1, TG_E_ARG, "resample_u8: n=%d (n >= 1)", n);
+  TG_REQUIRE(v_taps >= 1 && v_taps <= TG_RESAMPLE_MAX_TAPS && h_taps >= 1 && h_taps <= TG_RESAMPLE_MAX_TAPS, TG_E_ARG,
+             "resample_u8: v_taps=%d h_taps=%d (1 .. %d)", v_taps, h_taps, TG_RESAMPLE_MAX_TAPS);
+  TG_REQUIRE(h_in >= 1 && w_in >= 1 && h_out >= 1 && w_out >= 1, TG_E_SHAPE,
+             "resample_u8: %dx%d -> %dx%d (every size >= 1)", h_in, w_in, h_out, w_out);
+  TG_REQUIRE(4LL * h_out >= h_in && h_out <= 4LL * h_in && 4LL * w_out >= w_in && w_out <= 4LL * w_in, TG_E_SHAPE,
+             "resample_u8: %dx%d -> %dx%d (the ratio of either axis lies in [1/4, 4])", h_in, w_in, h_out, w_out);
+  TG_REQUIRE(3LL * h_in * w_in < (1LL << 31) && 3LL * h_out * w_out < (1LL << 31), TG_E_SHAPE,
+             "resample_u8: %dx%d -> %dx%d (a frame has fewer than 2^31 bytes)", h_in, w_in, h_out, w_out);
+  const int tiles_x = tg::cdiv(w_out, tg::RS_TW), tiles_y = tg::cdiv(h_out, tg::RS_TH);
+  const long long blocks = (long long)tiles_x * tiles_y * n;
+  TG_REQUIRE(blocks < (1LL << 31), TG_E_SHAPE, "resample_u8: %lld workgroups", blocks);
+  // what a tile can read at these ratios, never more than the caps: a table that asks for more is clamped to them
+  const int rh = tg::resample_tile_span(h_in, h_out, v_taps, tg::RS_TH), cw = tg::resample_tile_span(w_in, w_out, h_taps, tg::RS_TW);
+  const int rh_cap = rh < tg::RS_RH ? rh : tg::RS_RH, cw_cap = cw < tg::RS_CW ? cw : tg::RS_CW;
+  const size_t lds = tg::resample_lds_bytes(rh_cap, cw_cap, v_taps, h_taps);
+  hipLaunchKernelGGL(tg::resample_u8_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, x_hwc, y_hwc,
+                     h_in, w_in, h_out, w_out, v_idx, v_w, v_taps, h_idx, h_w, h_taps, tiles_x, tiles_y, rh_cap, cw_cap);
+  return tg::check_launch("resample_u8");
+}

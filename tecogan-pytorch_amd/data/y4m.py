@@ -130,16 +130,36 @@ class Y4MReader:
         return self._buf
 
 
+def scale_aspect_tag(tag, num, den):
+    """The A tag `An:d` (pixel aspect ratio) times num / den, reduced.  A0:0 (unknown) stays as it is."""
+    import math
+    try:
+        n, d = (int(v) for v in tag[1:].split(':'))
+    except ValueError:
+        raise Y4MError(f'y4m: {tag!r}: the pixel aspect ratio is An:d') from None
+    if num < 1 or den < 1:
+        raise Y4MError(f'y4m: the pixel aspect ratio is scaled by a positive fraction, got {num}/{den}')
+    if n <= 0 or d <= 0:
+        return tag
+    n, d = n * num, d * den
+    g = math.gcd(n, d)
+    return f'A{n // g}:{d // g}'
+
+
 class Y4MWriter:
     """Writes frames of W x H after a header that carries the F, A, C and X tags of `header_of_input` (a Y4MReader's
-    .header, or None: C420jpeg and nothing else), then Ip."""
+    .header, or None: C420jpeg and nothing else), then Ip.  aspect_scale (num, den): the frames were stretched, every
+    pixel is num / den times as wide for its height as the input's, and the A tag is rewritten accordingly
+    (scale_aspect_tag); a header without an A tag gets none."""
 
-    def __init__(self, fileobj, W, H, header_of_input=None):
+    def __init__(self, fileobj, W, H, header_of_input=None, aspect_scale=None):
         if W < 2 or H < 2:
             raise Y4MError(f'y4m: W={W} H={H}')
         self.f, self.w, self.h = fileobj, W, H
         self.frame_bytes = frame_bytes(H, W)
         tags = list(header_of_input['tags']) if header_of_input else ['C420jpeg']
+        if aspect_scale is not None:
+            tags = [scale_aspect_tag(t, *aspect_scale) if t.startswith('A') else t for t in tags]
         self._write_all((' '.join(['YUV4MPEG2', f'W{W}', f'H{H}'] + tags + ['Ip']) + '\n').encode('ascii'))
 
     def _write_all(self, data):

@@ -30,6 +30,7 @@ device; the cut frames are listed on stderr at the end, never on stdout.
 import argparse
 import os
 import random
+import re
 import time
 
 import numpy as np
@@ -40,6 +41,14 @@ from .metrics.psnr import compute_psnr, compute_psnr_device  # noqa: F401
 from .models import define_model
 from .models.networks import define_generator
 from .utils import dist_utils
+
+
+def output_size_arg(text):
+    """`WxH` of --output-size -> (w, h)."""
+    m = re.fullmatch(r'([1-9][0-9]*)[xX]([1-9][0-9]*)', text.strip())
+    if not m:
+        raise argparse.ArgumentTypeError(f'{text!r}: the output size is WxH, two positive integers')
+    return int(m.group(1)), int(m.group(2))
 
 
 def parse_args(argv=None):
@@ -86,7 +95,14 @@ def parse_args(argv=None):
                    help='--mode infer into a PNG folder: pillow (default) encodes on writer threads with zlib; device '
                         'encodes on the GPU (DESIGN.md section 7i: Huffman-only deflate, larger files, no host codec on '
                         'the output side).  Not for y4m output')
+    p.add_argument('--output-size', dest='output_size', type=output_size_arg, default=None, metavar='WxH',
+                   help='--mode infer: deliver every frame at W x H, resized on the GPU behind the generator (DESIGN.md '
+                        'section 7j: antialiased bicubic, exact integers); each side within [1/4, 4] of the super-resolved '
+                        'one, both even for y4m.  A y4m header gets the new size, and a pixel aspect ratio that keeps the '
+                        'display aspect when the shape changes')
     args = p.parse_args(argv)
+    if args.output_size is not None and args.mode != 'infer':
+        p.error('--output-size belongs to --mode infer')
     if args.png_encoder == 'device' and args.input and (args.input == '-' or os.path.isfile(args.input)):
         p.error('--png-encoder device writes PNG folders; y4m input is written as y4m')
     return args
@@ -372,12 +388,21 @@ def log_scene_cuts(name, scene_cut):
           file=sys.stderr, flush=True)
 
 
-def infer(opt, input_dir, output_dir, scene_cut=None, png_encoder='pillow'):
+def resize_option(output_size):
+    """The Resize of --output-size WxH (as (w, h)), or None."""
+    if output_size is None:
+        return None
+    from .models.networks import Resize
+    return Resize(output_size[1], output_size[0])
+
+
+def infer(opt, input_dir, output_dir, scene_cut=None, png_encoder='pillow', output_size=None):
     """--mode infer: every sequence of input_dir through VSRModel.infer_stream.  Frames are decoded one by one as the
     stream asks for them; the writers copy each frame out of the yielded ring slot before the generator is advanced.
     scene_cut (a SceneCut): passed on for every sequence, its cuts logged to stderr.  png_encoder 'device': the stream
     yields finished PNG files (infer_stream(png=Png())) and a writer copies one out of the slot and writes it as it
-    is; 'pillow': the writers encode the RGB frames.  Returns {sequence: frames written}."""
+    is; 'pillow': the writers encode the RGB frames.  output_size (w, h): the frames are resized to it on the device
+    (infer_stream(resize=Resize(h, w))), whichever encoder writes them.  Returns {sequence: frames written}."""
     import threading
     from concurrent.futures import ThreadPoolExecutor
     from PIL import Image
@@ -392,6 +417,8 @@ def infer(opt, input_dir, output_dir, scene_cut=None, png_encoder='pillow'):
     if png_encoder == 'device':
         from .models.networks import Png
         kw['png'] = Png()
+    if output_size is not None:
+        kw['resize'] = resize_option(output_size)
     done = {}
     slots = threading.BoundedSemaphore(4 * INFER_WRITER_THREADS)       # frames copied out and not yet on disk
 
@@ -444,11 +471,12 @@ def infer(opt, input_dir, output_dir, scene_cut=None, png_encoder='pillow'):
     return done
 
 
-def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None):
+def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None, output_size=None):
     """--mode infer on raw video: the y4m stream `src` (a binary file object) through VSRModel.infer_stream(yuv=...)
     into the y4m stream `dst`, in order.  The output header carries the scaled size and the input's F, A, C and X tags.
-    Each chunk is written out of the ring slot before the generator is advanced; nothing is held beyond it.  Returns
-    the number of frames written."""
+    Each chunk is written out of the ring slot before the generator is advanced; nothing is held beyond it.
+    output_size (w, h): the frames are resized to it on the device; the header carries that size and, when the shape
+    changes, an A tag scaled so that the display aspect stays.  Returns the number of frames written."""
     from .data.y4m import Y4MReader, Y4MWriter
     from .models.networks import Yuv420
     reader = Y4MReader(src)
@@ -456,9 +484,21 @@ def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None):
     spec = Yuv420(reader.h, reader.w, matrix=matrix, full_range=bool(full), siting=reader.siting)
     model = define_model(opt)
     s = model.net_G.scale
-    writer = Y4MWriter(dst, s * reader.w, s * reader.h, reader.header)
+    W, H = s * reader.w, s * reader.h
+    kw = {} if scene_cut is None else {'scene_cut': scene_cut}
+    aspect = None
+    if output_size is not None:
+        ow, oh = output_size
+        if ow % 2 or oh % 2:
+            raise ValueError(f'--output-size {ow}x{oh}: a 4:2:0 frame has even sides')
+        kw['resize'] = resize_option(output_size)
+        kw['resize'].check_source(H, W)
+        if oh * W != ow * H:                        # the shape changes: every pixel becomes this much wider for its height
+            aspect = (W * oh, H * ow)
+        W, H = ow, oh
+    writer = Y4MWriter(dst, W, H, reader.header, aspect_scale=aspect)
     t0, k = time.time(), 0
-    for chunk in model.infer_stream(reader, yuv=spec, **({} if scene_cut is None else {'scene_cut': scene_cut})):
+    for chunk in model.infer_stream(reader, yuv=spec, **kw):
         for frame in chunk:
             writer.write(frame)
             k += 1
@@ -467,13 +507,13 @@ def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None):
     if scene_cut is not None:
         log_scene_cuts('y4m', scene_cut)
     dt = time.time() - t0
-    print(f'y4m: {k} frames {reader.w}x{reader.h} -> {s * reader.w}x{s * reader.h} '
+    print(f'y4m: {k} frames {reader.w}x{reader.h} -> {W}x{H} '
           f'({k / max(dt, 1e-9):.1f} frames/s, {spec.matrix} {"full" if spec.full_range else "limited"} range, '
           f'{spec.siting} siting)', flush=True)
     return k
 
 
-def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range, scene_cut=None):
+def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range, scene_cut=None, output_size=None):
     """Opens the two ends of infer_y4m.  With `--output -` the y4m bytes are the ONLY thing on stdout: the descriptor
     is set aside for them and, for the length of the run, descriptor 1 and sys.stdout lead to stderr, so that neither
     a print nor a library's message can land in the stream."""
@@ -482,7 +522,7 @@ def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range, scene_cut=Non
     try:
         if output_path != '-':
             with open(output_path, 'wb') as dst:
-                return infer_y4m(opt, src, dst, matrix, yuv_range, scene_cut)
+                return infer_y4m(opt, src, dst, matrix, yuv_range, scene_cut, output_size)
         sys.stdout.flush()
         keep = os.dup(1)
         py_stdout = sys.stdout
@@ -490,7 +530,7 @@ def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range, scene_cut=Non
         sys.stdout = sys.stderr
         try:
             with os.fdopen(os.dup(keep), 'wb') as dst:
-                return infer_y4m(opt, src, dst, matrix, yuv_range, scene_cut)
+                return infer_y4m(opt, src, dst, matrix, yuv_range, scene_cut, output_size)
         finally:
             sys.stdout = py_stdout
             os.dup2(keep, 1)
@@ -575,9 +615,10 @@ def main(argv=None):
         if not args.input or not args.output:
             raise ValueError('--mode infer needs --input DIR and --output DIR (or a y4m file / - for both)')
         if args.input == '-' or os.path.isfile(args.input):
-            infer_y4m_cli(opt, args.input, args.output, args.yuv_matrix, args.yuv_range, scene_cut_option(args))
+            infer_y4m_cli(opt, args.input, args.output, args.yuv_matrix, args.yuv_range, scene_cut_option(args),
+                          args.output_size)
         else:
-            infer(opt, args.input, args.output, scene_cut_option(args), args.png_encoder)
+            infer(opt, args.input, args.output, scene_cut_option(args), args.png_encoder, args.output_size)
     elif args.mode == 'profile':
         profile(opt, tuple(int(v) for v in args.lr_size.split('x')), args.test_speed)
     else:

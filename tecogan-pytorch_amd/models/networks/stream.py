@@ -1,7 +1,8 @@
-"""FRNet.infer_stream (DESIGN.md sections 7d, 7e, 7h, 7i): input parsing, the batch ring, the raw-video form Yuv420, the
-PNG output form Png, the scene-cut option SceneCut, one small object per input form, output form and option, and the engine
-that runs a clip of any length through rings of STREAM_SLOTS batches.  A batch's launches are frnet_infer's enqueue_batch,
-the ones infer_sequence(pipeline=True) enqueues.  Uses the network only through its attributes."""
+"""FRNet.infer_stream (DESIGN.md sections 7d, 7e, 7h, 7i, 7j): input parsing, the batch ring, the raw-video form Yuv420,
+the PNG output form Png, the scene-cut option SceneCut, the output size Resize, one small object per input form, output
+form and option, and the engine that runs a clip of any length through rings of STREAM_SLOTS batches.  A batch's launches
+are frnet_infer's enqueue_batch, the ones infer_sequence(pipeline=True) enqueues.  Uses the network only through its
+attributes."""
 import math
 from dataclasses import dataclass
 
@@ -210,6 +211,28 @@ class Png:
         return L.PNG_FILTER[self.filter]
 
 
+@dataclass(frozen=True)
+class Resize:
+    """Output size of a stream (FRNet.infer_stream(resize=...)): every super-resolved frame is
+    resized to h x w on the device, by ONE tg_resample_u8 per batch (MATLAB-style antialiased bicubic, exact integers),
+    before the output form sees it.  h / (s * LR height) and w / (s * LR width) lie in [1/4, 4].  Frozen."""
+    h: int
+    w: int
+
+    def __post_init__(self):
+        for name in ('h', 'w'):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f'Resize: {name} is an integer >= 1, got {v!r}')
+            object.__setattr__(self, name, int(v))
+
+    def check_source(self, H, W):
+        """ValueError unless H x W frames can be resized to h x w (either ratio in [1/4, 4])."""
+        for n_in, n_out in ((H, self.h), (W, self.w)):
+            if 4 * n_out < n_in or n_out > 4 * n_in:
+                raise ValueError(f'resize: {H}x{W} frames to {self.h}x{self.w}: the ratio of either axis lies in [1/4, 4]')
+
+
 class SceneCut:
     """Scene-cut option of a stream (FRNet.infer_stream(scene_cut=...)) and the caller's handle on
     what it found.  At a cut the recurrence restarts from the zero HR state, which makes the frame the frame 0 of a clip
@@ -364,8 +387,8 @@ class _RgbOut:
     """Output form: the batch's uint8 RGB frames come down as they are; the chunk is a view of the pinned slot."""
 
     def alloc(self, eng):
-        self.u8 = eng.u8
-        self.host_out = torch.empty(tuple(eng.u8.shape), dtype=torch.uint8, pin_memory=True)
+        self.u8 = eng.out_u8
+        self.host_out = torch.empty(tuple(self.u8.shape), dtype=torch.uint8, pin_memory=True)
 
     def encode(self, sl, cnt):
         pass
@@ -385,9 +408,9 @@ class _I420Out:
         self.yuv = yuv
 
     def alloc(self, eng):
-        ns, m, H, W = eng.u8.shape[:4]
-        self.lib, self.u8, self.args = eng.lib, eng.u8, (H, W, *self.yuv.codes(), eng.main.cuda_stream)
-        self.host_out = torch.empty(ns, m, self.yuv.out_frame_bytes(eng.net.scale), dtype=torch.uint8, pin_memory=True)
+        ns, m, H, W = eng.out_u8.shape[:4]
+        self.lib, self.u8, self.args = eng.lib, eng.out_u8, (H, W, *self.yuv.codes(), eng.main.cuda_stream)
+        self.host_out = torch.empty(ns, m, H * W * 3 // 2, dtype=torch.uint8, pin_memory=True)      # (H and W are even)
         self.yuv_out = torch.empty(tuple(self.host_out.shape), dtype=torch.uint8, device=eng.dev)
 
     def encode(self, sl, cnt):
@@ -416,12 +439,12 @@ class _PngOut:
         self.files_at, self.slot_bytes = 8 * m, 8 * m + m * self.png_stride
 
     def alloc(self, eng):
-        ns, m, H, W = eng.u8.shape[:4]
+        ns, m, H, W = eng.out_u8.shape[:4]
         cap, wsb = eng.lib.tg_png_capacity(H, W), eng.lib.tg_png_workspace_bytes(m, H, W)
         if cap < 0 or wsb < 0:
             L.check(L.TG_E_SHAPE, 'tg_png_capacity')
         self.layout(m, cap)
-        self.lib, self.u8, self.size, self.stream = eng.lib, eng.u8, (H, W), eng.main.cuda_stream
+        self.lib, self.u8, self.size, self.stream = eng.lib, eng.out_u8, (H, W), eng.main.cuda_stream
         self.png_out = torch.empty(ns, self.slot_bytes, dtype=torch.uint8, device=eng.dev)
         self.png_ws = torch.empty(wsb, dtype=torch.uint8, device=eng.dev)
         self.host_out = torch.empty(ns, self.slot_bytes, dtype=torch.uint8, pin_memory=True)
@@ -493,24 +516,48 @@ class _CutSlots:
                        res[self.dist_at:].view(np.uint32)[:cnt], self.n_pixels)
 
 
+class _ResizedFrames:
+    """The resized frames of a stream with a Resize: one more uint8 ring, (slots, m, h, w, 3), and
+    the two axes' tables on the device.  ONE tg_resample_u8 per batch turns the slot's HR frames into the slot's resized
+    frames; the output form reads those (eng.out_u8) in place of the HR frames."""
+
+    def __init__(self, resize):
+        self.rs = resize
+
+    def alloc(self, eng):
+        from ... import ops
+        ns, m, H, W = eng.u8.shape[:4]
+        self.lib, self.u8 = eng.lib, eng.u8
+        vi, vw, vt = ops.resample_tables_device(H, self.rs.h, eng.dev)
+        hi, hw, ht = ops.resample_tables_device(W, self.rs.w, eng.dev)
+        self.tables = (vi, vw, hi, hw)              # (kept alive: the cache may drop them)
+        self.args = (H, W, self.rs.h, self.rs.w, vi.data_ptr(), vw.data_ptr(), vt, hi.data_ptr(), hw.data_ptr(), ht,
+                     eng.main.cuda_stream)
+        self.frames = torch.empty(ns, m, self.rs.h, self.rs.w, 3, dtype=torch.uint8, device=eng.dev)
+
+    def run(self, sl, cnt):
+        L.check(self.lib.tg_resample_u8(self.u8[sl].data_ptr(), self.frames[sl].data_ptr(), cnt, *self.args),
+                'tg_resample_u8')
+
+
 class _StreamEngine:
     """State of one FRNet.infer_stream (see there): the part that is the same for every form.  Everything the device
     touches is allocated once, at the first item: STREAM_SLOTS slots of {LR batch + the frame before it, uint8 frames on
     the device, HR state snapshot, four events}, the HR ping-pong pair, the zero flow, and what the three form objects
     above allocate for themselves -- `inp` (staging and raw input), `out` (the pinned output ring and what is encoded
-    into it), `cut` (None without a SceneCut).  Per batch:
+    into it), `cut` (None without a SceneCut), `rsz` (the resized ring, None without a Resize).  Per batch:
 
     _upload, copy stream: the frame before the batch, inp.upload, cut.detect, ev_in.
     _compute, caller's stream: the HR snapshot, enqueue_batch (given cut.reset: one tg_zero_if_flag in front of every
-    frame's SRNet launch), out.encode behind the batch's last frame, ev_s.
+    frame's SRNet launch), rsz.run and then out.encode behind the batch's last frame, ev_s.
     _flush_download, copy stream, behind the NEXT batch's upload or at retire: out.download, cut.download, ev_out.
     _retire: waits for ev_out, reads the fault counter, cut.report, returns out.result.
 
     The host never waits for a scene-cut decision.  The repair path knows no form: it runs _compute again, which
-    encodes again and reads the same per-slot flags, and the snapshot it restores was taken before the batch's first
-    conditional fill."""
+    resizes and encodes again and reads the same per-slot flags, and the snapshot it restores was taken before the
+    batch's first conditional fill."""
 
-    def __init__(self, net, frames, device, on_fault, yuv=None, scene_cut=None, png=None):
+    def __init__(self, net, frames, device, on_fault, yuv=None, scene_cut=None, png=None, resize=None):
         if on_fault not in ('rerun', 'raise'):
             raise ValueError(f"on_fault must be 'rerun' or 'raise', got {on_fault!r}")
         if png is not None:
@@ -531,10 +578,20 @@ class _StreamEngine:
                 raise ValueError(f'scene_cut needs RGB frames (in_nc = 3), this network has in_nc = {net.in_nc}')
             scene_cut.cuts.clear()
             scene_cut.scores.clear()
+        if resize is not None:
+            if not isinstance(resize, Resize):
+                raise ValueError(f'resize must be a Resize or None, got {type(resize).__name__}')
+            if net.in_nc != 3:
+                raise ValueError(f'resize needs RGB frames (in_nc = 3), this network has in_nc = {net.in_nc}')
+            if yuv is not None:
+                if resize.h % 2 or resize.w % 2:
+                    raise ValueError(f'resize: an I420 frame has even sides, got {resize.h}x{resize.w}')
+                resize.check_source(net.scale * yuv.h, net.scale * yuv.w)
         # the forms: the output and the scene-cut slots follow from the options, the input from the first item as well
         self.inp, self.input_form = None, lambda piece: _input_form(piece, net.in_nc, yuv)
         self.out = _PngOut(png) if png is not None else _I420Out(yuv) if yuv is not None else _RgbOut()
         self.cut = _CutSlots(scene_cut) if scene_cut is not None else None
+        self.rsz = _ResizedFrames(resize) if resize is not None else None
         self.net, self.on_fault, self.parts = net, on_fault, stream_parts(frames, net.in_nc, yuv)
         self.dev = _norm_device(device if device is not None else next(net.parameters()).device)
         self.closed, self.warned, self.reruns = False, False, 0
@@ -549,6 +606,8 @@ class _StreamEngine:
         c, s, ns = net.in_nc, net.scale, self.ring.slots
         h, w, m = self.inp.h, self.inp.w, max(self.first, self.later)
         self.h, self.w, self.m = h, w, m
+        if self.rsz is not None:
+            self.rsz.rs.check_source(s * h, s * w)  # (the size of the first item: nothing has been allocated or enqueued)
         self.wk = net._weights_key()
         self.plan = net._get_plan(1, h, w, dev, wk=self.wk)
         self.fplans = {}
@@ -560,6 +619,10 @@ class _StreamEngine:
                    torch.empty(1, c, s * h, s * w, dtype=torch.float32, device=dev)]
         self.snap = torch.empty(ns, 1, c, s * h, s * w, dtype=torch.float32, device=dev)
         self.u8 = torch.empty(ns, m, s * h, s * w, c, dtype=torch.uint8, device=dev)
+        self.out_u8 = self.u8                       # what the output form reads
+        if self.rsz is not None:
+            self.rsz.alloc(self)
+            self.out_u8 = self.rsz.frames
         self.out.alloc(self)
         self.inp.alloc(self)
         self.zflow = torch.zeros(2 * self.plan.fh * self.plan.fw, dtype=torch.float32, device=dev)
@@ -612,6 +675,8 @@ class _StreamEngine:
                       self.u8_ptr[sl], self.u8_stride, self.zflow.data_ptr(), self.fsz, main, side, self.ev_f[sl],
                       self.ev_s[(b - 2) % ns] if b >= 2 else None,     # (flow slot b & 1 was batch b - 2's)
                       reset=self.cut.reset(sl) if self.cut is not None else None)
+        if self.rsz is not None:
+            self.rsz.run(sl, cnt)                   # behind the batch's last frame, in front of the encode
         self.out.encode(sl, cnt)                    # behind the batch's last frame
         self.ev_s[sl].record(main)
         self.pending_dl = rec
@@ -733,6 +798,6 @@ class _StreamEngine:
             if self.ring.inflight:
                 self.plan.chain_state()             # a fault in frames nobody will see: counted, the plan has fallen back
         finally:
-            self.inp = self.out = self.cut = None   # the forms' buffers go with them
-            self.lr = self.hr = self.snap = self.u8 = self.zflow = None
+            self.inp = self.out = self.cut = self.rsz = None   # the forms' buffers go with them
+            self.lr = self.hr = self.snap = self.u8 = self.out_u8 = self.zflow = None
 

@@ -21,7 +21,7 @@ from ...utils.net_utils import get_upsampling_func
 # (what is not a network: every name stays reachable as tecogan_nets.<name>)
 from .frnet_infer import (FNET_FIRST_PASS_FRAMES, _SIDE_STREAMS, _StepPlan, _norm_device, clip_batches,  # noqa: F401
                           enqueue_batch, side_stream, stream_batch_sizes)
-from .stream import (STREAM_SLOTS, Png, SceneCut, StreamFormat, StreamRing, Yuv420, _StreamEngine, stream_frames,  # noqa: F401
+from .stream import (STREAM_SLOTS, Png, Resize, SceneCut, StreamFormat, StreamRing, Yuv420, _StreamEngine, stream_frames,  # noqa: F401
                      stream_frames_yuv, stream_parts, stream_rebatch, yuv420_planes)
 
 
@@ -410,7 +410,7 @@ class FRNet(nn.Module):
         self._get_plan(k, h, w, dev).check_chain()   # (the clip has been synchronised: a 4-byte read)
         return out.transpose(1, 0, 2, 3, 4) if multi else out[:, 0]
 
-    def infer_stream(self, frames, device=None, on_fault='rerun', yuv=None, scene_cut=None, png=None):
+    def infer_stream(self, frames, device=None, on_fault='rerun', yuv=None, scene_cut=None, png=None, resize=None):
         """Super-resolve a clip of ANY length in bounded memory: a generator over `frames` (any iterable, pulled lazily)
         that yields (m, s*h, s*w, 3) uint8 numpy chunks in order, as many frames in total as it consumed.
 
@@ -470,12 +470,21 @@ class FRNet(nn.Module):
         tg_png_encode_u8 call on the caller's stream writes the batch's files and their sizes into the slot's buffer,
         which comes down in place of the RGB frames.  The generator yields, per batch, a LIST of 1-D uint8 views, one
         file each, valid until it is advanced: the bytes are ops.png_encode of the frames the stream yields without
-        `png`.  A repaired batch is encoded again with it."""
+        `png`.  A repaired batch is encoded again with it.
+
+        resize: a Resize(h, w) delivers every frame at h x w in place of s*h x s*w; without it
+        the stream enqueues exactly what it always did.  One more uint8 ring of h x w frames is allocated, and after a
+        batch's last frame ONE tg_resample_u8 on the caller's stream -- MATLAB-style antialiased bicubic in exact
+        integers, the bytes of ops.resize_u8 -- fills the slot's resized frames, in front of the output form's encode,
+        which reads them in place of the HR frames: RGB chunks are (m, h, w, 3), I420 chunks frames of h x w, PNG files
+        h x w.  It composes with scene_cut unchanged, and a repaired batch is resized again.  ValueError before an item
+        is pulled: in_nc != 3, an odd h or w together with `yuv`, h or w outside [1/4, 4] of the HR size (known then
+        with `yuv`; otherwise it is raised when the first item shows the size, before anything is allocated)."""
         import weakref
         cur = self._stream_ref() if self._stream_ref is not None else None
         if cur is not None and not cur.closed:
             raise RuntimeError('infer_stream: this network already has a live stream (one at a time: close it first)')
-        eng = _StreamEngine(self, frames, device, on_fault, yuv, scene_cut, png)
+        eng = _StreamEngine(self, frames, device, on_fault, yuv, scene_cut, png, resize)
         self._stream_ref = weakref.ref(eng)
         return eng.run()
 

@@ -93,7 +93,7 @@ class VSRModel(BaseModel):
             hr_seq = self.net_G(lr_data, self.device)
         return hr_seq[n_pad_front:]
 
-    def infer_stream(self, frames, yuv=None, scene_cut=None, png=None):
+    def infer_stream(self, frames, yuv=None, scene_cut=None, png=None, resize=None):
         """infer() for a clip of any length (FRNet.infer_stream): `frames` is an iterable of LR frames or chunks, uint8
         (h,w,3) or float32 (3,h,w); yields (m,H,W,3) uint8 chunks -- views of the generator's pinned ring, valid until
         the next one is asked for.  The temporal padding of the front (test.padding_mode / num_pad_front) is applied
@@ -103,7 +103,9 @@ class VSRModel(BaseModel):
         scene_cut (a SceneCut): the recurrence restarts at scene cuts (FRNet.infer_stream).  Its `at`, `cuts` and
         `scores` are in the numbering of `frames`: the padded stream runs a shifted copy, and what that finds inside
         the padded prefix is dropped.  Known limit: the front padding is NOT repeated after a cut -- a new shot starts
-        cold, as a clip does with num_pad_front = 0."""
+        cold, as a clip does with num_pad_front = 0.
+        resize (a Resize): every frame is delivered at resize.h x resize.w, resized on the device, in whichever of the
+        three output forms (FRNet.infer_stream)."""
         mode = self.opt['test'].get('padding_mode', 'reflect')
         skip = self.opt['test'].get('num_pad_front', 0)
         self.net_G.eval()
@@ -114,7 +116,8 @@ class VSRModel(BaseModel):
             scene_cut.scores.clear()
         gen = self.net_G.infer_stream(front_pad_stream(frames, mode, skip, self.net_G.in_nc, yuv), self.device,
                                       yuv=yuv, **({} if inner is None else {'scene_cut': inner}),
-                                      **({} if png is None else {'png': png}))
+                                      **({} if png is None else {'png': png}),
+                                      **({} if resize is None else {'resize': resize}))
         try:
             for chunk in gen:
                 if inner is not None:

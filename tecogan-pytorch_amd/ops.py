@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the C ABI.  PyTorch is plumbing here: it owns the
 device memory and the stream; every computation is a HIP kernel from
 libtecogan_hip.so.  All tensors must be CUDA(HIP) fp32 and contiguous."""
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -1302,6 +1303,107 @@ def downsample_bi(x, scale, pad=True, out='f32'):
     y8 = torch.empty(n, oh, ow, 3, dtype=torch.uint8, device=x.device) if out != 'f32' else None
     L.check(fn(x.data_ptr(), _ptr(y8), _ptr(y32), n, h, w, scale, 1 if pad else 0, _stream()), name)
     return y32 if out == 'f32' else (y8 if out == 'u8' else (y32, y8))
+
+
+# ---- bicubic resize to any size ----
+RESAMPLE_MAX_TAPS, RESAMPLE_WEIGHT_BITS = L.TG_RESAMPLE_MAX_TAPS, L.TG_RESAMPLE_WEIGHT_BITS
+_RESAMPLE_DEVICE_TABLES = {}                     # (n_in, n_out, device) -> (idx, w) on the device
+_RESAMPLE_CACHE_ENTRIES = 64
+
+
+def resample_ratio_ok(n_in, n_out):
+    """Whether tg_resample_u8 takes n_in -> n_out along an axis: both >= 1, n_out / n_in in [1/4, 4]."""
+    return n_in >= 1 and n_out >= 1 and 4 * n_out >= n_in and n_out <= 4 * n_in
+
+
+def _cubic(x):
+    ax = np.abs(x)
+    ax2, ax3 = ax * ax, ax * ax * ax
+    return (1.5 * ax3 - 2.5 * ax2 + 1) * (ax <= 1) + (-0.5 * ax3 + 2.5 * ax2 - 4 * ax + 2) * ((1 < ax) & (ax <= 2))
+
+
+def resample_tables(n_in, n_out):
+    """The tables tg_resample_u8 takes for one axis, numpy (idx int32 (n_out, P), w int16 (n_out, P)): MATLAB
+    imresize's contributions() for 'bicubic' in fp64 -- cubic kernel a = -0.5, stretched by n_in / n_out when
+    shrinking, weights normalised, indices mirrored with the edge pixel repeated, all-zero columns dropped -- then
+    w = rint(weight * 2^14) with the row's residual 2^14 - sum(w) added to its largest entry (the first on a tie), so
+    every row sums to exactly 2^14.  tests/resize_ref.py is the specification; the arithmetic here is the same, in the
+    same order."""
+    n_in, n_out = int(n_in), int(n_out)
+    if not resample_ratio_ok(n_in, n_out):
+        raise L.TecoganHipError(f'resample_tables: {n_in} -> {n_out}: both sizes are >= 1 and the ratio lies in [1/4, 4]')
+    scale = n_out / n_in
+    kernel_width = 4.0
+    if scale < 1:
+        def h(x):
+            return scale * _cubic(scale * x)
+        kernel_width = kernel_width / scale
+    else:
+        h = _cubic
+    x = np.arange(1, n_out + 1, dtype=np.float64)
+    u = x / scale + 0.5 * (1 - 1 / scale)
+    left = np.floor(u - kernel_width / 2)
+    P = int(np.ceil(kernel_width)) + 2
+    indices = left[:, None] + np.arange(P, dtype=np.float64)[None, :]
+    weights = h(u[:, None] - indices)
+    weights = weights / weights.sum(axis=1, keepdims=True)
+    aux = np.concatenate([np.arange(1, n_in + 1), np.arange(n_in, 0, -1)])
+    indices = aux[np.mod(indices.astype(np.int64) - 1, 2 * n_in)] - 1
+    keep = np.any(weights != 0, axis=0)
+    weights, indices = weights[:, keep], indices[:, keep]
+    one = 1 << RESAMPLE_WEIGHT_BITS
+    q = np.rint(weights * one).astype(np.int64)
+    q[np.arange(n_out), np.argmax(q, axis=1)] += one - q.sum(axis=1)
+    if q.shape[1] > RESAMPLE_MAX_TAPS or np.abs(q).max() >= 2 ** 15:
+        raise L.TecoganHipError(f'resample_tables: {n_in} -> {n_out}: {q.shape[1]} taps, largest weight {np.abs(q).max()}')
+    return np.ascontiguousarray(indices, dtype=np.int32), np.ascontiguousarray(q, dtype=np.int16)
+
+
+def resample_tables_device(n_in, n_out, device):
+    """resample_tables on `device`, as (idx, w, taps); cached per (n_in, n_out, device)."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    key = (int(n_in), int(n_out), device)
+    hit = _RESAMPLE_DEVICE_TABLES.get(key)
+    if hit is None:
+        idx, w = resample_tables(n_in, n_out)
+        if len(_RESAMPLE_DEVICE_TABLES) >= _RESAMPLE_CACHE_ENTRIES:
+            _RESAMPLE_DEVICE_TABLES.clear()
+        hit = _RESAMPLE_DEVICE_TABLES[key] = (torch.from_numpy(idx).to(device), torch.from_numpy(w).to(device),
+                                              idx.shape[1])
+    return hit
+
+
+def resize_u8(x, size, out=None):
+    """(n,H,W,3) uint8 frames on device -> (n,h,w,3) uint8, size = (h, w): MATLAB-style antialiased bicubic in exact
+    integers, one launch (tg_resample_u8), the bytes of tests/resize_ref.py.  Either ratio lies
+    in [1/4, 4]; at 1/2 and 1/4 of a multiple of 2 or 4 the bytes are downsample_bi's.  out: a contiguous (n,h,w,3)
+    uint8 tensor on x's device to write into."""
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise L.TecoganHipError('resize_u8: expected a CUDA/HIP tensor (no CPU path exists)')
+    _chk_u8(x, 'x')
+    if x.dim() != 4 or x.shape[3] != 3 or x.shape[0] < 1:
+        raise L.TecoganHipError(f'resize_u8: expected uint8 (n,H,W,3) with n >= 1, got shape {tuple(x.shape)}')
+    try:
+        h, w = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise L.TecoganHipError(f'resize_u8: size is (h, w), got {size!r}') from None
+    n, H, W, _ = x.shape
+    if not (resample_ratio_ok(H, h) and resample_ratio_ok(W, w)):
+        raise L.TecoganHipError(f'resize_u8: {H}x{W} -> {h}x{w}: the ratio of either axis lies in [1/4, 4]')
+    if out is None:
+        out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=x.device)
+    else:
+        _chk_u8(out, 'out')
+        if tuple(out.shape) != (n, h, w, 3) or out.device != x.device:
+            raise L.TecoganHipError(f'resize_u8: out is uint8 {(n, h, w, 3)} on {x.device}, got {tuple(out.shape)} on '
+                                    f'{out.device}')
+    vi, vw, vt = resample_tables_device(H, h, x.device)
+    hi, hw, ht = resample_tables_device(W, w, x.device)
+    L.check(L.lib().tg_resample_u8(_ptr(x), _ptr(out), n, H, W, h, w, _ptr(vi), _ptr(vw), vt, _ptr(hi), _ptr(hw), ht,
+                                   _stream()), 'tg_resample_u8')
+    return out
 
 
 # ---- SyncBatchNorm (+LeakyReLU): statistics exchanged over ranks between the halves ----

@@ -575,6 +575,25 @@ int tg_yuv420_to_rgb_f32(const uint8_t* yuv, float* rgb_chw, int n, int h, int w
 int tg_rgb_u8_to_yuv420(const uint8_t* rgb_hwc, uint8_t* yuv, int n, int H, int W, int matrix, int full_range,
                         int siting, tg_stream_t stream);
 
+/* Planar YUV 4:2:0 at 10 or 12 bits per sample (y4m C420p10 / C420p12).  A sample is a 16-bit
+ * little-endian word holding `depth` significant bits; a frame is I420's layout with 2-byte samples, 2 (h*w + 2*ch*cw)
+ * bytes.  matrix, full_range and siting are the enums above.  Limited range at depth d: yo = 16 << (d-8), ys = 219 <<
+ * (d-8), cs = 224 << (d-8), chroma mid value 128 << (d-8); full range: yo = 0, ys = cs = 2^d - 1, mid 2^(d-1).
+ * depth other than 10 or 12, a yuv pointer that is not 2-byte aligned (or an fp32 pointer that is not 4-byte aligned), a
+ * null pointer, an unknown enum value or n < 1 is TG_E_ARG, without a launch. */
+/* yuv (n frames, h x w, any h, w >= 2) -> rgb_chw (n,3,h,w) fp32 in [0,1], as tg_yuv420_to_rgb_f32: the same integer
+ * chroma up-sampling (weights sum to 16), one fp32 matrix step with the depth's yo, ys, cs and mid, clamp.  A sample
+ * above 2^depth - 1 is read as 2^depth - 1.  Within 2e-6 of the fp64 formula. */
+int tg_yuv420p16_to_rgb_f32(const uint16_t* yuv, float* rgb_chw, int n, int h, int w, int depth, int matrix,
+                            int full_range, int siting, tg_stream_t stream);
+/* rgb_chw (n,3,H,W) fp32 (the layout of the HR state) -> yuv (n frames, H x W; H and W even, else TG_E_ARG).  One
+ * float step per value, q = (int) rintf(c * 65535.0f) with c = v > 0 ? v : 0 (NaN gives 0), then c < 1 ? c : 1; then
+ * exact 64-bit integers: Q = rint(M_d * 2^24), M_d the matrix with ys/65535 and cs/65535; Y = clip((Q_Y.q + (yo << 24) +
+ * 2^23) >> 24, 0, 2^d - 1); chroma from the sum S of q over the 2x2 block (centre: shift 26) or over (1,2,1) x 2 rows
+ * around the left column, x-1 clamped (left: shift 27), plus the mid value, clipped alike. */
+int tg_rgb_f32_to_yuv420p16(const float* rgb_chw, uint16_t* yuv, int n, int H, int W, int depth, int matrix,
+                            int full_range, int siting, tg_stream_t stream);
+
 /* PNG files written on the device: what the reference's save_sequence does with cv2.imwrite
  * (codes/utils/data_utils.py), without the host's zlib.  The specification is tests/png_ref.py and the bytes are
  * equal: 8-bit RGB, no interlace, one IDAT; per row the filter type (adaptive: the one of None, Sub, Up, Average,

@@ -228,7 +228,282 @@ static bool yuv_enums_ok(int matrix, int full_range, int siting) {
          (siting == TG_YUV_CENTER || siting == TG_YUV_LEFT);
 }
 
+// ---- 10 and 12 bits per sample ---------------------------------------------------------------
+// A sample is a 16-bit little-endian word with d significant bits; the frame layout is I420's with 2-byte samples.
+//   tg_rgb_f32_to_yuv420p16: the fp32 CHW HR state -> I420 at d bits.  ONE float step per value (clamp, times 65535,
+//     round half even) gives 16-bit integers q; everything behind it is exact 64-bit integer arithmetic on Q =
+//     rint(M_d * 2^24), and tests/yuv_depth_ref.py restates it in numpy: the words must be equal.
+//   tg_yuv420p16_to_rgb_f32: the 8-bit input kernel again on 16-bit samples (one above 2^d - 1 is read as 2^d - 1).
+// The thread-to-pixel map is the 8-bit kernels': 2 rows x 4 pixels on the way out (six float4 loads, two 8-byte Y stores,
+// two 4-byte chroma stores), one row x 4 pixels on the way in (one 8-byte Y load, three float4 stores); neighbouring
+// lanes touch neighbouring 16 / 8 / 4 bytes of every plane.  The wide forms are taken only where every address is
+// aligned (width a multiple of 4, fp32 base 16-byte and sample base 8-byte aligned: all row, plane and frame strides
+// follow); every other shape or placement takes the element-wide form, whose sample stores are 2 bytes wide.
+struct yuv_q24 {        // rint(M_d * 2^24), rows Y / Cb / Cr; luma offset, chroma mid value and top code at depth d
+  int y[3], cb[3], cr[3], yo, mid, top;
+};
+
+// [depth 10, 12][bt601, bt709][limited, full]: the tables of DESIGN.md section 7k (tests/test_yuv_depth_cpu.py
+// recomputes them from Kr and Kb in fp64)
+static const yuv_q24 Q24_TABLE[2][2][2] = {
+    {{{{67054, 131640, 25566}, {-38705, -75985, 114690}, {114690, -96038, -18651}, 64, 512, 1023},
+      {{78306, 153731, 29856}, {-44191, -86755, 130946}, {130946, -109651, -21295}, 0, 512, 1023}},
+     {{{47678, 160390, 16192}, {-26280, -88409, 114690}, {114690, -104173, -10516}, 64, 512, 1023},
+      {{55678, 187305, 18909}, {-30006, -100940, 130946}, {130946, -118939, -12007}, 0, 512, 1023}}},
+    {{{{268214, 526561, 102262}, {-154818, -303941, 458759}, {458759, -384153, -74606}, 256, 2048, 4095},
+      {{313452, 615373, 119510}, {-176892, -347276, 524168}, {524168, -438925, -85243}, 0, 2048, 4095}},
+     {{{190710, 641561, 64766}, {-105122, -353637, 458759}, {458759, -416693, -42066}, 256, 2048, 4095},
+      {{222876, 749770, 75690}, {-120110, -404058, 524168}, {524168, -476105, -48063}, 0, 2048, 4095}}}};
+
+static yuv_f inverse_coefficients_deep(int matrix, int full_range, int depth) {
+  const double kr = matrix == TG_YUV_BT601 ? 0.299 : 0.2126, kb = matrix == TG_YUV_BT601 ? 0.114 : 0.0722;
+  const double kg = 1.0 - kr - kb;
+  const double top = (double)((1 << depth) - 1), up = (double)(1 << (depth - 8));
+  const double ys = full_range ? top : 219.0 * up, cs16 = 16.0 * (full_range ? top : 224.0 * up);
+  yuv_f f;
+  f.ky = (float)(1.0 / ys);
+  f.rv = (float)(2.0 * (1.0 - kr) / cs16);
+  f.bu = (float)(2.0 * (1.0 - kb) / cs16);
+  f.gu = (float)(-(2.0 * kb * (1.0 - kb) / kg) / cs16);
+  f.gv = (float)(-(2.0 * kr * (1.0 - kr) / kg) / cs16);
+  f.yo = full_range ? 0 : 16 << (depth - 8);
+  return f;
+}
+
+// the one float step of the output direction: v < 0 and NaN give 0 (both comparisons are false for a NaN, so the first
+// one decides), v > 1 gives 65535; one fp32 multiply, one round half even
+__device__ __forceinline__ int quantize16(float v) {
+  v = v > 0.f ? v : 0.f;
+  v = v < 1.f ? v : 1.f;
+  return (int)__builtin_rintf(v * 65535.0f);
+}
+// clip(acc >> sh, 0, top) of a floor shift on 64 bits, as shift_clip_u8 writes it: the clamp comes first, the shift is
+// logical, and no packed 16-bit shift can be formed from it (section 7e's compiler note)
+__device__ __forceinline__ unsigned shift_clip_top(long long acc, int sh, int top) {
+  const long long lim = ((long long)(top + 1) << sh) - 1;
+  acc = acc < 0 ? 0 : (acc > lim ? lim : acc);
+  return (unsigned)((unsigned long long)acc >> sh);
+}
+__device__ __forceinline__ long long dot3_64(const int q[3], const int p[3]) {
+  return (long long)q[0] * p[0] + (long long)q[1] * p[1] + (long long)q[2] * p[2];
+}
+
+// thread = rows 2j, 2j+1 x pixels 4*tx .. 4*tx+3 of frame k.  H and W are even, so a strip holds 2 or 4 pixels.
+template <bool VEC, bool LEFT>
+__global__ __launch_bounds__(256) void rgb_f32_to_yuv420p16_kernel(const float* __restrict__ rgb,
+                                                                   uint16_t* __restrict__ yuv, int H, int W, int strips,
+                                                                   long long total, yuv_q24 q) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int tx = (int)(i % strips);
+  const long long r = i / strips;
+  const int j = (int)(r % (H >> 1));
+  const long long k = r / (H >> 1);
+  const int x0 = 4 * tx, cw = W >> 1, ch = H >> 1;
+  const int npx = W - x0 < 4 ? W - x0 : 4;                        // 2 or 4
+  const long long plane = (long long)H * W;
+  const float* src = rgb + k * 3 * plane + (long long)(2 * j) * W + x0;
+  int p[2][4][3];
+#pragma unroll
+  for (int rr = 0; rr < 2; ++rr)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float* s = src + c * plane + (long long)rr * W;
+      if (VEC) {                                                  // 16 bytes at a 16-byte aligned address
+        const f32x4 v = *reinterpret_cast<const f32x4*>(s);
+        p[rr][0][c] = quantize16(v.x); p[rr][1][c] = quantize16(v.y);
+        p[rr][2][c] = quantize16(v.z); p[rr][3][c] = quantize16(v.w);
+      } else {
+#pragma unroll
+        for (int x = 0; x < 4; ++x) p[rr][x][c] = x < npx ? quantize16(s[x]) : 0;
+      }
+    }
+  uint16_t* yp = yuv + k * (plane + 2LL * ch * cw);
+  uint16_t* up = yp + plane;
+  uint16_t* vp = up + (long long)ch * cw;
+  const long long yround = ((long long)q.yo << 24) + (1LL << 23);
+#pragma unroll
+  for (int rr = 0; rr < 2; ++rr) {
+    unsigned yv[4];
+#pragma unroll
+    for (int x = 0; x < 4; ++x) yv[x] = shift_clip_top(dot3_64(q.y, p[rr][x]) + yround, 24, q.top);
+    uint16_t* dst = yp + (long long)(2 * j + rr) * W + x0;
+    if (VEC) {
+      *reinterpret_cast<u32x2*>(dst) = u32x2{yv[0] | (yv[1] << 16), yv[2] | (yv[3] << 16)};
+    } else {
+#pragma unroll
+      for (int x = 0; x < 4; ++x)
+        if (x < npx) dst[x] = (uint16_t)yv[x];
+    }
+  }
+  unsigned uo[2], vo[2];
+#pragma unroll
+  for (int c2 = 0; c2 < 2; ++c2) {
+    int s[3];
+    if (LEFT) {                                                   // (1, 2, 1) over x-1, x, x+1 at x = 2i, x-1 clamped to 0
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        int acc = 0;
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+          int left;
+          if (c2 == 1) left = p[rr][1][c];
+          else left = x0 == 0 ? p[rr][0][c] : quantize16(src[c * plane + (long long)rr * W - 1]);   // the strip before
+          acc += left + 2 * p[rr][2 * c2][c] + p[rr][2 * c2 + 1][c];
+        }
+        s[c] = acc;
+      }
+      const long long cround = ((long long)q.mid << 27) + (1LL << 26);
+      uo[c2] = shift_clip_top(dot3_64(q.cb, s) + cround, 27, q.top);
+      vo[c2] = shift_clip_top(dot3_64(q.cr, s) + cround, 27, q.top);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        s[c] = p[0][2 * c2][c] + p[0][2 * c2 + 1][c] + p[1][2 * c2][c] + p[1][2 * c2 + 1][c];
+      const long long cround = ((long long)q.mid << 26) + (1LL << 25);
+      uo[c2] = shift_clip_top(dot3_64(q.cb, s) + cround, 26, q.top);
+      vo[c2] = shift_clip_top(dot3_64(q.cr, s) + cround, 26, q.top);
+    }
+  }
+  const long long co = (long long)j * cw + 2 * tx;
+  if (VEC) {                                                      // cw and both plane offsets are even here
+    *reinterpret_cast<uint32_t*>(up + co) = uo[0] | (uo[1] << 16);
+    *reinterpret_cast<uint32_t*>(vp + co) = vo[0] | (vo[1] << 16);
+  } else {
+    up[co] = (uint16_t)uo[0];
+    vp[co] = (uint16_t)vo[0];
+    if (npx == 4) {
+      up[co + 1] = (uint16_t)uo[1];
+      vp[co + 1] = (uint16_t)vo[1];
+    }
+  }
+}
+
+// thread = row y x pixels 4*tx .. 4*tx+3 of frame k, as yuv420_to_rgb_f32_kernel; `top` = 2^d - 1 bounds every sample,
+// `mid16` = 16 * 2^(d-1) is the chroma mid value in sixteenths
+template <bool VEC, bool LEFT>
+__global__ __launch_bounds__(256) void yuv420p16_to_rgb_f32_kernel(const uint16_t* __restrict__ yuv,
+                                                                   float* __restrict__ rgb, int h, int w, int strips,
+                                                                   long long total, yuv_f f, int top, int mid16) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int tx = (int)(i % strips);
+  const long long r = i / strips;
+  const int y = (int)(r % h);
+  const long long k = r / h;
+  const int x0 = 4 * tx, ch = (h + 1) >> 1, cw = (w + 1) >> 1;
+  const uint16_t* yp = yuv + k * ((long long)h * w + 2LL * ch * cw);
+  const uint16_t* up = yp + (long long)h * w;
+  const uint16_t* vp = up + (long long)ch * cw;
+  int r0 = (y & 1) ? (y - 1) >> 1 : (y >> 1) - 1, r1 = r0 + 1;
+  const int w0 = (y & 1) ? 3 : 1, w1 = 4 - w0;
+  r0 = r0 < 0 ? 0 : r0;
+  r1 = r1 > ch - 1 ? ch - 1 : r1;
+  auto sample = [top](const uint16_t* p, long long at) { const int s = (int)p[at]; return s > top ? top : s; };
+  int u[4], v[4];                                                 // vertical sums of columns 2*tx-1 .. 2*tx+2, in quarters
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    int c = 2 * tx - 1 + m;
+    c = c < 0 ? 0 : (c > cw - 1 ? cw - 1 : c);
+    u[m] = w0 * sample(up, (long long)r0 * cw + c) + w1 * sample(up, (long long)r1 * cw + c);
+    v[m] = w0 * sample(vp, (long long)r0 * cw + c) + w1 * sample(vp, (long long)r1 * cw + c);
+  }
+  int u16[4], v16[4];                                             // sixteenths
+  if (LEFT) {
+    u16[0] = 4 * u[1]; u16[1] = 2 * (u[1] + u[2]); u16[2] = 4 * u[2]; u16[3] = 2 * (u[2] + u[3]);
+    v16[0] = 4 * v[1]; v16[1] = 2 * (v[1] + v[2]); v16[2] = 4 * v[2]; v16[3] = 2 * (v[2] + v[3]);
+  } else {
+    u16[0] = u[0] + 3 * u[1]; u16[1] = 3 * u[1] + u[2]; u16[2] = u[1] + 3 * u[2]; u16[3] = 3 * u[2] + u[3];
+    v16[0] = v[0] + 3 * v[1]; v16[1] = 3 * v[1] + v[2]; v16[2] = v[1] + 3 * v[2]; v16[3] = 3 * v[2] + v[3];
+  }
+  int yy[4];
+  const uint16_t* ysrc = yp + (long long)y * w + x0;
+  if (VEC) {                                                      // 8 bytes at an 8-byte aligned address
+    const u32x2 a = *reinterpret_cast<const u32x2*>(ysrc);
+    yy[0] = (int)(a.x & 65535u); yy[1] = (int)(a.x >> 16); yy[2] = (int)(a.y & 65535u); yy[3] = (int)(a.y >> 16);
+  } else {
+#pragma unroll
+    for (int x = 0; x < 4; ++x) yy[x] = x0 + x < w ? (int)ysrc[x] : 0;
+  }
+  float R[4], G[4], B[4];
+#pragma unroll
+  for (int x = 0; x < 4; ++x) {
+    const int ys = yy[x] > top ? top : yy[x];
+    const float yf = f.ky * (float)(ys - f.yo);
+    const float du = (float)(u16[x] - mid16), dv = (float)(v16[x] - mid16);
+    R[x] = clamp01(__builtin_fmaf(f.rv, dv, yf));
+    G[x] = clamp01(__builtin_fmaf(f.gv, dv, __builtin_fmaf(f.gu, du, yf)));
+    B[x] = clamp01(__builtin_fmaf(f.bu, du, yf));
+  }
+  const long long plane = (long long)h * w;
+  float* dst = rgb + k * 3 * plane + (long long)y * w + x0;
+  if (VEC) {
+    *reinterpret_cast<f32x4*>(dst) = f32x4{R[0], R[1], R[2], R[3]};
+    *reinterpret_cast<f32x4*>(dst + plane) = f32x4{G[0], G[1], G[2], G[3]};
+    *reinterpret_cast<f32x4*>(dst + 2 * plane) = f32x4{B[0], B[1], B[2], B[3]};
+  } else {
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+      if (x0 + x < w) {
+        dst[x] = R[x];
+        dst[plane + x] = G[x];
+        dst[2 * plane + x] = B[x];
+      }
+  }
+}
+
 }  // namespace tg
+
+extern "C" int tg_yuv420p16_to_rgb_f32(const uint16_t* yuv, float* rgb_chw, int n, int h, int w, int depth, int matrix,
+                                       int full_range, int siting, tg_stream_t stream) {
+  TG_REQUIRE(yuv && rgb_chw, TG_E_ARG, "yuv420p16_to_rgb_f32: null pointer");
+  TG_REQUIRE((uintptr_t)yuv % 2 == 0 && (uintptr_t)rgb_chw % 4 == 0, TG_E_ARG,
+             "yuv420p16_to_rgb_f32: yuv is 2-byte aligned and rgb_chw 4-byte aligned");
+  TG_REQUIRE(depth == 10 || depth == 12, TG_E_ARG, "yuv420p16_to_rgb_f32: depth=%d (10 or 12)", depth);
+  TG_REQUIRE(n >= 1 && h >= 2 && w >= 2, TG_E_ARG, "yuv420p16_to_rgb_f32: n=%d h=%d w=%d (n >= 1, h, w >= 2)", n, h, w);
+  TG_REQUIRE(tg::yuv_enums_ok(matrix, full_range, siting), TG_E_ARG,
+             "yuv420p16_to_rgb_f32: matrix=%d full_range=%d siting=%d", matrix, full_range, siting);
+  const int strips = (w + 3) / 4;
+  const long long total = (long long)n * h * strips;
+  TG_REQUIRE(total < (1LL << 38), TG_E_SHAPE, "yuv420p16_to_rgb_f32: %lld strips", total);
+  const bool vec = w % 4 == 0 && (uintptr_t)yuv % 8 == 0 && (uintptr_t)rgb_chw % 16 == 0;
+  const tg::yuv_f f = tg::inverse_coefficients_deep(matrix, full_range, depth);
+  const int top = (1 << depth) - 1, mid16 = 16 << (depth - 1);
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  const hipStream_t st = (hipStream_t)stream;
+#define TG_YUV_IN16(V, L)                                                                                         \
+  hipLaunchKernelGGL((tg::yuv420p16_to_rgb_f32_kernel<V, L>), grid, block, 0, st, yuv, rgb_chw, h, w, strips, total, f, \
+                     top, mid16)
+  if (vec) { if (siting == TG_YUV_LEFT) TG_YUV_IN16(true, true); else TG_YUV_IN16(true, false); }
+  else { if (siting == TG_YUV_LEFT) TG_YUV_IN16(false, true); else TG_YUV_IN16(false, false); }
+#undef TG_YUV_IN16
+  return tg::check_launch("yuv420p16_to_rgb_f32");
+}
+
+extern "C" int tg_rgb_f32_to_yuv420p16(const float* rgb_chw, uint16_t* yuv, int n, int H, int W, int depth, int matrix,
+                                       int full_range, int siting, tg_stream_t stream) {
+  TG_REQUIRE(rgb_chw && yuv, TG_E_ARG, "rgb_f32_to_yuv420p16: null pointer");
+  TG_REQUIRE((uintptr_t)yuv % 2 == 0 && (uintptr_t)rgb_chw % 4 == 0, TG_E_ARG,
+             "rgb_f32_to_yuv420p16: yuv is 2-byte aligned and rgb_chw 4-byte aligned");
+  TG_REQUIRE(depth == 10 || depth == 12, TG_E_ARG, "rgb_f32_to_yuv420p16: depth=%d (10 or 12)", depth);
+  TG_REQUIRE(n >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, TG_E_ARG,
+             "rgb_f32_to_yuv420p16: n=%d H=%d W=%d (n >= 1, H and W even)", n, H, W);
+  TG_REQUIRE(tg::yuv_enums_ok(matrix, full_range, siting), TG_E_ARG,
+             "rgb_f32_to_yuv420p16: matrix=%d full_range=%d siting=%d", matrix, full_range, siting);
+  const int strips = (W + 3) / 4;
+  const long long total = (long long)n * (H / 2) * strips;
+  TG_REQUIRE(total < (1LL << 38), TG_E_SHAPE, "rgb_f32_to_yuv420p16: %lld strips", total);
+  const bool vec = W % 4 == 0 && (uintptr_t)rgb_chw % 16 == 0 && (uintptr_t)yuv % 8 == 0;
+  const tg::yuv_q24 q = tg::Q24_TABLE[depth == 12][matrix][full_range];
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  const hipStream_t st = (hipStream_t)stream;
+#define TG_YUV_OUT16(V, L)                                                                                        \
+  hipLaunchKernelGGL((tg::rgb_f32_to_yuv420p16_kernel<V, L>), grid, block, 0, st, rgb_chw, yuv, H, W, strips, total, q)
+  if (vec) { if (siting == TG_YUV_LEFT) TG_YUV_OUT16(true, true); else TG_YUV_OUT16(true, false); }
+  else { if (siting == TG_YUV_LEFT) TG_YUV_OUT16(false, true); else TG_YUV_OUT16(false, false); }
+#undef TG_YUV_OUT16
+  return tg::check_launch("rgb_f32_to_yuv420p16");
+}
 
 extern "C" int tg_yuv420_to_rgb_f32(const uint8_t* yuv, float* rgb_chw, int n, int h, int w, int matrix,
                                     int full_range, int siting, tg_stream_t stream) {

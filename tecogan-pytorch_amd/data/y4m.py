@@ -1,14 +1,19 @@
-"""YUV4MPEG2 (y4m) streams of 8-bit 4:2:0 frames: the pipe format that joins a codec to the stream,
+"""YUV4MPEG2 (y4m) streams of 4:2:0 frames, 8 bits per sample and on request 10 or 12: the pipe format that joins a codec
+to the stream,
 `ffmpeg -i in.mp4 -f yuv4mpegpipe - | python -m tecogan_pytorch_amd.main --mode infer --input - --output - | ffmpeg -i - out.mp4`.
 
 A stream is one header line `YUV4MPEG2 W<w> H<h> F<n:d> I<p> A<n:d> C<colourspace> X<comment>...`, then per frame a line
 `FRAME[ parameters]` followed by exactly frame_bytes bytes of I420 (Y, U, V planes, tightly packed).  Only progressive
 8-bit 4:2:0 with a chroma siting the device kernels implement is taken: C420jpeg (centred), C420mpeg2
-(left), and bare C420 or no C tag, which both mean centred per the format.  Everything else is refused by name."""
+(left), and bare C420 or no C tag, which both mean centred per the format.  Everything else is refused by name.
+A reader opened with depths=(8, 10, 12) also takes C420p10 and C420p12: samples are 16-bit
+little-endian words, a frame has twice the bytes, and the tag says nothing about the siting."""
 import numpy as np
 
 MAGIC = b'YUV4MPEG2'
 SITING_OF_TAG = {'420jpeg': 'center', '420mpeg2': 'left', '420': 'center'}
+DEPTH_OF_TAG = {'420p10': 10, '420p12': 12}      # taken only by a reader that was opened for that depth; no siting
+TAG_OF_SITING = {'center': '420jpeg', 'left': '420mpeg2'}
 MAX_LINE = 4096          # a header or FRAME line longer than this is not y4m
 
 
@@ -37,14 +42,16 @@ def _read_line(f, limit=MAX_LINE):
     return line[:-1]
 
 
-def parse_header(line):
-    """The header line (bytes, without the newline) -> dict(w, h, tags, siting, full_range).  `tags` keeps the F, A, C
-    and X tags as written, for the writer; full_range is True / False from XCOLORRANGE, None when the header has none."""
+def parse_header(line, depths=(8,)):
+    """The header line (bytes, without the newline) -> dict(w, h, tags, siting, full_range, depth).  `tags` keeps the F,
+    A, C and X tags as written, for the writer; full_range is True / False from XCOLORRANGE, None when the header has
+    none.  depths: the bits per sample the caller takes; C420p10 / C420p12 are accepted only when theirs is among them,
+    and then siting is None (the tag carries none)."""
     parts = line.decode('ascii', 'replace').split(' ')
     if parts[0] != MAGIC.decode():
         raise Y4MError('y4m: the stream does not start with YUV4MPEG2')
     w = h = None
-    tags, ctag, full = [], None, None
+    tags, ctag, full, depth = [], None, None, 8
     for p in parts[1:]:
         if not p:
             continue
@@ -57,11 +64,14 @@ def parse_header(line):
             if v != 'p':
                 raise Y4MError(f'y4m: I{v}: interlaced material is not supported (progressive Ip only)')
         elif k == 'C':
-            if v not in SITING_OF_TAG:
+            if DEPTH_OF_TAG.get(v) in tuple(depths):
+                depth = DEPTH_OF_TAG[v]
+            elif v not in SITING_OF_TAG:
                 why = ('more than 8 bits per sample' if any(b in v for b in ('p10', 'p12', 'p14', 'p16')) else
                        'PAL-DV chroma siting' if v == '420paldv' else 'not 4:2:0' if not v.startswith('420') else
                        'unknown 4:2:0 variant')
-                raise Y4MError(f'y4m: C{v}: {why} (supported: C420jpeg, C420mpeg2, C420)')
+                more = ''.join(f', C{t}' for t, d in DEPTH_OF_TAG.items() if d in tuple(depths))
+                raise Y4MError(f'y4m: C{v}: {why} (supported: C420jpeg, C420mpeg2, C420{more})')
             ctag = v
             tags.append(p)
         elif k in 'FA':
@@ -77,28 +87,33 @@ def parse_header(line):
             raise Y4MError(f'y4m: unknown header tag {p!r}')
     if w is None or h is None or w < 2 or h < 2:
         raise Y4MError(f'y4m: the header needs W and H of at least 2 (got W={w} H={h})')
-    return {'w': w, 'h': h, 'tags': tags, 'siting': SITING_OF_TAG[ctag or '420'], 'full_range': full}
+    if 8 not in tuple(depths) and depth == 8:
+        raise Y4MError(f'y4m: C{ctag or "420"}: 8 bits per sample, and the reader was opened for {tuple(depths)}')
+    return {'w': w, 'h': h, 'tags': tags, 'siting': SITING_OF_TAG[ctag or '420'] if depth == 8 else None,
+            'full_range': full, 'depth': depth}
 
 
-def frame_bytes(h, w):
-    return h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)
+def frame_bytes(h, w, depth=8):
+    return (h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)) * (2 if depth > 8 else 1)
 
 
 class Y4MReader:
     """Frames of a y4m stream, lazily: iterating yields ONE reused (frame_bytes,) uint8 numpy buffer per frame (copy
     what you keep; FRNet.infer_stream copies an item when it pulls it).  fileobj: anything with read / readinto --
     a file, sys.stdin.buffer, the read end of a pipe.  Short reads are looped over; the end of the stream inside a
-    frame is an error, at a frame boundary it ends the iteration."""
+    frame is an error, at a frame boundary it ends the iteration.  depths: the bits per sample that are taken, (8,) by
+    default; with (8, 10, 12) C420p10 and C420p12 streams are read too -- .depth says which, .siting is None for them
+    and a frame is the file's bytes, two per sample."""
 
-    def __init__(self, fileobj):
+    def __init__(self, fileobj, depths=(8,)):
         self.f = fileobj
         line = _read_line(fileobj)
         if line is None:
             raise Y4MError('y4m: empty stream')
-        self.header = parse_header(line)
+        self.header = parse_header(line, depths)
         self.w, self.h = self.header['w'], self.header['h']
-        self.siting, self.full_range = self.header['siting'], self.header['full_range']
-        self.frame_bytes = frame_bytes(self.h, self.w)
+        self.siting, self.full_range, self.depth = self.header['siting'], self.header['full_range'], self.header['depth']
+        self.frame_bytes = frame_bytes(self.h, self.w, self.depth)
         self.frames_read = 0
         self._buf = np.empty(self.frame_bytes, np.uint8)
 
@@ -150,14 +165,35 @@ class Y4MWriter:
     """Writes frames of W x H after a header that carries the F, A, C and X tags of `header_of_input` (a Y4MReader's
     .header, or None: C420jpeg and nothing else), then Ip.  aspect_scale (num, den): the frames were stretched, every
     pixel is num / den times as wide for its height as the input's, and the A tag is rewritten accordingly
-    (scale_aspect_tag); a header without an A tag gets none."""
+    (scale_aspect_tag); a header without an A tag gets none.  depth 10 | 12: frames of 16-bit little-endian samples; the
+    C tag becomes C420p10 / C420p12 in place of the input's, with XYSCSS=420P10 / 420P12 (the form ffmpeg writes and
+    reads) in place of the input's XYSCSS.  depth 8 after a 10- or 12-bit input: the C tag (and an XYSCSS tag) of
+    `siting` ('center' | 'left') in place of the input's; otherwise the input's tags as they are."""
 
-    def __init__(self, fileobj, W, H, header_of_input=None, aspect_scale=None):
+    def __init__(self, fileobj, W, H, header_of_input=None, aspect_scale=None, depth=8, siting=None):
         if W < 2 or H < 2:
             raise Y4MError(f'y4m: W={W} H={H}')
-        self.f, self.w, self.h = fileobj, W, H
-        self.frame_bytes = frame_bytes(H, W)
+        if depth not in (8, 10, 12):
+            raise Y4MError(f'y4m: depth is 8, 10 or 12, got {depth!r}')
+        self.f, self.w, self.h, self.depth = fileobj, W, H, depth
+        self.frame_bytes = frame_bytes(H, W, depth)
         tags = list(header_of_input['tags']) if header_of_input else ['C420jpeg']
+        ctag = None
+        if depth > 8:
+            ctag = '420p%d' % depth
+        elif header_of_input and header_of_input.get('depth', 8) > 8:
+            if siting not in TAG_OF_SITING:
+                raise Y4MError(f'y4m: an 8-bit stream after a {header_of_input["depth"]}-bit one needs the siting for its '
+                               f'C tag (center | left), got {siting!r}')
+            ctag = TAG_OF_SITING[siting]
+        if ctag is not None:
+            had_c = any(t.startswith('C') for t in tags)
+            tags = ['C' + ctag if t.startswith('C') else 'XYSCSS=' + ctag.upper() if t.startswith('XYSCSS=') else t
+                    for t in tags]
+            if not had_c:
+                tags.append('C' + ctag)
+            if 'XYSCSS=' + ctag.upper() not in tags and depth > 8:
+                tags.insert(1 + max(i for i, t in enumerate(tags) if t.startswith('C')), 'XYSCSS=' + ctag.upper())
         if aspect_scale is not None:
             tags = [scale_aspect_tag(t, *aspect_scale) if t.startswith('A') else t for t in tags]
         self._write_all((' '.join(['YUV4MPEG2', f'W{W}', f'H{H}'] + tags + ['Ip']) + '\n').encode('ascii'))
@@ -169,7 +205,7 @@ class Y4MWriter:
             view = view[len(view) if k is None else k:]
 
     def write(self, frame):
-        """One I420 frame: any uint8 buffer of frame_bytes bytes."""
+        """One I420 frame: any contiguous buffer of frame_bytes bytes (uint8, or uint16 samples above 8 bits)."""
         view = memoryview(np.ascontiguousarray(frame)).cast('B')
         if len(view) != self.frame_bytes:
             raise Y4MError(f'y4m: a {self.w}x{self.h} frame has {self.frame_bytes} bytes, got {len(view)}')

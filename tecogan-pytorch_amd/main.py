@@ -19,6 +19,10 @@ video instead (data/y4m.py): I420 frames go up as they are, are converted on the
 
   ffmpeg -i in.mp4 -f yuv4mpegpipe - | python -m tecogan_pytorch_amd.main --mode infer --input - --output - | ffmpeg -i - out.mp4
 
+A `C420p10` / `C420p12` y4m input is taken as well (`--yuv-siting` names the chroma siting those
+headers do not carry), and `--output-depth 8|10|12` (default: the input's) sets the bits per sample of the y4m written:
+above 8 the frames are converted from the float result, not from the rounded 8-bit one.
+
 `--scene-cut` (both forms of `infer`) restarts the recurrence at scene cuts, detected on the
 device; the cut frames are listed on stderr at the end, never on stdout.
 
@@ -73,7 +77,7 @@ def parse_args(argv=None):
                         "the yml; absent = 'fp32').  Training is always fp32")
     p.add_argument('--input', type=str, default=None,
                    help='--mode infer: folder of LR frames (png | jpg), either the frames of one sequence or one '
-                        'sub-folder per sequence; no ground truth is needed.  Or a y4m file (8-bit 4:2:0), or - for '
+                        'sub-folder per sequence; no ground truth is needed.  Or a y4m file (4:2:0 at 8, 10 or 12 bits), or - for '
                         'a y4m stream on stdin')
     p.add_argument('--output', type=str, default=None,
                    help='--mode infer: folder the super-resolved PNGs are written to, under the names (and sub-folders) '
@@ -83,6 +87,12 @@ def parse_args(argv=None):
                    help='y4m input: the YCbCr matrix of the clip (y4m headers do not carry it)')
     p.add_argument('--yuv-range', dest='yuv_range', type=str, default=None, choices=['limited', 'full'],
                    help="y4m input: the range of the clip; default: the header's XCOLORRANGE, or limited without one")
+    p.add_argument('--yuv-siting', dest='yuv_siting', type=str, default='left', choices=['center', 'left'],
+                   help='y4m input: where a chroma sample sits, consulted only where the header does not decide '
+                        '(C420p10 and C420p12 carry no siting); 8-bit headers decide for themselves')
+    p.add_argument('--output-depth', dest='output_depth', type=int, default=None, choices=[8, 10, 12],
+                   help="y4m input: bits per sample of the y4m written (DESIGN.md section 7k); default: the input's.  "
+                        'Above 8 the frames are converted from the float result, not from the rounded 8-bit one')
     p.add_argument('--scene-cut', dest='scene_cut', action='store_true',
                    help='--mode infer: restart the recurrence at scene cuts, detected on the GPU (DESIGN.md section 7h); '
                         'the cut frames are listed on stderr at the end.  The default thresholds have not been '
@@ -103,6 +113,11 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.output_size is not None and args.mode != 'infer':
         p.error('--output-size belongs to --mode infer')
+    if args.output_depth is not None and not (args.mode == 'infer' and args.input and
+                                              (args.input == '-' or os.path.isfile(args.input))):
+        p.error('--output-depth belongs to --mode infer with y4m input (a y4m file, or - for stdin)')
+    if args.output_depth not in (None, 8) and args.output_size is not None:
+        p.error('--output-size resizes the 8-bit frames; it cannot be combined with --output-depth above 8')
     if args.png_encoder == 'device' and args.input and (args.input == '-' or os.path.isfile(args.input)):
         p.error('--png-encoder device writes PNG folders; y4m input is written as y4m')
     return args
@@ -471,17 +486,22 @@ def infer(opt, input_dir, output_dir, scene_cut=None, png_encoder='pillow', outp
     return done
 
 
-def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None, output_size=None):
+def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None, output_size=None, siting='left',
+              output_depth=None):
     """--mode infer on raw video: the y4m stream `src` (a binary file object) through VSRModel.infer_stream(yuv=...)
     into the y4m stream `dst`, in order.  The output header carries the scaled size and the input's F, A, C and X tags.
     Each chunk is written out of the ring slot before the generator is advanced; nothing is held beyond it.
     output_size (w, h): the frames are resized to it on the device; the header carries that size and, when the shape
-    changes, an A tag scaled so that the display aspect stays.  Returns the number of frames written."""
+    changes, an A tag scaled so that the display aspect stays.  The input may be C420p10 / C420p12 (DESIGN.md section
+    7k): `siting` stands in where the header carries none.  output_depth 8 | 10 | 12 | None (the input's): bits per
+    sample of the output; its C and XYSCSS tags follow.  Returns the number of frames written."""
     from .data.y4m import Y4MReader, Y4MWriter
     from .models.networks import Yuv420
-    reader = Y4MReader(src)
+    reader = Y4MReader(src, depths=(8, 10, 12))
     full = reader.full_range if yuv_range is None else yuv_range == 'full'
-    spec = Yuv420(reader.h, reader.w, matrix=matrix, full_range=bool(full), siting=reader.siting)
+    spec = Yuv420(reader.h, reader.w, matrix=matrix, full_range=bool(full),
+                  siting=reader.siting if reader.siting is not None else siting, depth=reader.depth,
+                  out_depth=output_depth)
     model = define_model(opt)
     s = model.net_G.scale
     W, H = s * reader.w, s * reader.h
@@ -496,7 +516,7 @@ def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None, out
         if oh * W != ow * H:                        # the shape changes: every pixel becomes this much wider for its height
             aspect = (W * oh, H * ow)
         W, H = ow, oh
-    writer = Y4MWriter(dst, W, H, reader.header, aspect_scale=aspect)
+    writer = Y4MWriter(dst, W, H, reader.header, aspect_scale=aspect, depth=spec.od, siting=spec.siting)
     t0, k = time.time(), 0
     for chunk in model.infer_stream(reader, yuv=spec, **kw):
         for frame in chunk:
@@ -509,11 +529,12 @@ def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None, out
     dt = time.time() - t0
     print(f'y4m: {k} frames {reader.w}x{reader.h} -> {W}x{H} '
           f'({k / max(dt, 1e-9):.1f} frames/s, {spec.matrix} {"full" if spec.full_range else "limited"} range, '
-          f'{spec.siting} siting)', flush=True)
+          f'{spec.siting} siting, {spec.depth} -> {spec.od} bits)', flush=True)
     return k
 
 
-def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range, scene_cut=None, output_size=None):
+def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range, scene_cut=None, output_size=None, siting='left',
+                  output_depth=None):
     """Opens the two ends of infer_y4m.  With `--output -` the y4m bytes are the ONLY thing on stdout: the descriptor
     is set aside for them and, for the length of the run, descriptor 1 and sys.stdout lead to stderr, so that neither
     a print nor a library's message can land in the stream."""
@@ -522,7 +543,7 @@ def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range, scene_cut=Non
     try:
         if output_path != '-':
             with open(output_path, 'wb') as dst:
-                return infer_y4m(opt, src, dst, matrix, yuv_range, scene_cut, output_size)
+                return infer_y4m(opt, src, dst, matrix, yuv_range, scene_cut, output_size, siting, output_depth)
         sys.stdout.flush()
         keep = os.dup(1)
         py_stdout = sys.stdout
@@ -530,7 +551,7 @@ def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range, scene_cut=Non
         sys.stdout = sys.stderr
         try:
             with os.fdopen(os.dup(keep), 'wb') as dst:
-                return infer_y4m(opt, src, dst, matrix, yuv_range, scene_cut, output_size)
+                return infer_y4m(opt, src, dst, matrix, yuv_range, scene_cut, output_size, siting, output_depth)
         finally:
             sys.stdout = py_stdout
             os.dup2(keep, 1)
@@ -616,7 +637,7 @@ def main(argv=None):
             raise ValueError('--mode infer needs --input DIR and --output DIR (or a y4m file / - for both)')
         if args.input == '-' or os.path.isfile(args.input):
             infer_y4m_cli(opt, args.input, args.output, args.yuv_matrix, args.yuv_range, scene_cut_option(args),
-                          args.output_size)
+                          args.output_size, args.yuv_siting, args.output_depth)
         else:
             infer(opt, args.input, args.output, scene_cut_option(args), args.png_encoder, args.output_size)
     elif args.mode == 'profile':

@@ -159,7 +159,7 @@ def clip_batches(tot_frm, first, later):
 
 
 def enqueue_batch(lib, plan, flow_plan, b, i0, cnt, lr_prev, lr_stride, hr, u8, u8_stride, zflow, flow_bytes,
-                  main, side, ev_flow, ev_free, *, reset=None):
+                  main, side, ev_flow, ev_free, *, reset=None, after=None):
     """Enqueue the launches of batch b = frames i0 .. i0 + cnt - 1 of a clip, and nothing else: the order both
     infer_sequence(pipeline=True) and infer_stream produce their frames in, which is why they agree bit for bit.
 
@@ -180,11 +180,18 @@ def enqueue_batch(lib, plan, flow_plan, b, i0, cnt, lr_prev, lr_stride, hr, u8, 
     reset = (flags_addr, hr_bytes) (infer_stream with a SceneCut): one int32 flag per frame of
     the batch in device memory.  Directly in front of the tg_frnet_step_srnet of every frame j of the batch but the
     stream's frame 0, tg_zero_if_flag(hr[i & 1], hr_bytes, flags_addr + 4 j) goes onto `main`: with the flag set the
-    frame warps the zero state, as a clip's frame 0 does, whatever its flow.  None: exactly the calls above."""
+    frame warps the zero state, as a clip's frame 0 does, whatever its flow.  None: exactly the calls above.
+
+    after (infer_stream with a 10- or 12-bit output): a callable invoked directly behind the
+    tg_frnet_step_srnet of every frame j of the batch, the stream's frame 0 included, with (j, the address of the HR
+    state that launch writes); what it enqueues on `main` reads the float frame before the next one replaces its
+    predecessor.  None: exactly the calls above."""
     check, step, handle, ms = L.check, lib.tg_frnet_step_srnet, plan.handle, main.cuda_stream
     lr = lr_prev + lr_stride
     if i0 == 0:
         check(step(handle, zflow, lr, hr[0], hr[1], u8, ms), 'tg_frnet_step_srnet')
+        if after is not None:
+            after(0, hr[1])
     f0 = 1 if i0 == 0 else 0                    # frame 0's flow is never used: not estimated
     npair = cnt - f0
     if npair <= 0:
@@ -203,3 +210,5 @@ def enqueue_batch(lib, plan, flow_plan, b, i0, cnt, lr_prev, lr_stride, hr, u8, 
             check(lib.tg_zero_if_flag(hr[i & 1], reset[1], reset[0] + 4 * j, ms), 'tg_zero_if_flag')
         check(step(handle, flow0 + (j - f0) * flow_bytes, lr + j * lr_stride, hr[i & 1], hr[(i + 1) & 1],
                    u8 + j * u8_stride, ms), 'tg_frnet_step_srnet')
+        if after is not None:
+            after(j, hr[(i + 1) & 1])

@@ -5,6 +5,7 @@ are frnet_infer's enqueue_batch, the ones infer_sequence(pipeline=True) enqueues
 attributes."""
 import math
 from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 import torch
@@ -67,8 +68,14 @@ class StreamFormat:
 
 def stream_frames_yuv(item, yuv):
     """One input item of a yuv stream -> (n, frame_bytes) uint8 host tensor: a 1-D item is one I420 frame, a 2-D item
-    a chunk of frames.  Anything else is a ValueError."""
+    a chunk of frames.  With yuv.depth above 8 an item is the bytes of the file (uint8, frame_bytes a frame) or its
+    samples (uint16, half that length), which are taken as their bytes.  Anything else is a ValueError."""
     x = item
+    if yuv.depth > 8:
+        if isinstance(x, np.ndarray) and x.dtype == np.uint16:
+            x = np.ascontiguousarray(x).view(np.uint8)
+        elif torch.is_tensor(x) and x.dtype == torch.uint16 and not x.is_cuda:
+            x = x.contiguous().view(torch.uint8)
     if isinstance(x, np.ndarray):
         if x.dtype != np.uint8:
             raise ValueError(f'infer_stream: I420 frames are uint8; got numpy {x.dtype}')
@@ -154,16 +161,23 @@ class StreamRing:
         return self.inflight.pop(0)
 
 
+YUV_DEPTHS = (8, 10, 12)
+
+
 @dataclass(frozen=True)
 class Yuv420:
-    """Raw-video form of a stream (FRNet.infer_stream(yuv=...)): planar 8-bit YUV 4:2:0 (I420)
+    """Raw-video form of a stream (FRNet.infer_stream(yuv=...), DESIGN.md sections 7e and 7k): planar YUV 4:2:0 (I420)
     frames of h x w on the way in and of s*h x s*w on the way out.  matrix 'bt601' | 'bt709', full_range (bool),
-    siting 'center' (y4m C420jpeg) | 'left' (y4m C420mpeg2).  Frozen."""
+    siting 'center' (y4m C420jpeg) | 'left' (y4m C420mpeg2).  depth 8 | 10 | 12: bits per sample of the input; above 8
+    a sample is a 16-bit little-endian word.  out_depth 8 | 10 | 12 | None (the input's): bits per sample of the output;
+    above 8 the frames are written from the float HR frame, not from the rounded uint8 one.  Frozen."""
     h: int
     w: int
     matrix: str = 'bt709'
     full_range: bool = False
     siting: str = 'left'
+    depth: int = 8
+    out_depth: Optional[int] = None
 
     def __post_init__(self):
         for name in ('h', 'w'):
@@ -178,16 +192,29 @@ class Yuv420:
         if not isinstance(self.full_range, (bool, np.bool_)):
             raise ValueError(f'Yuv420: full_range is a bool, got {self.full_range!r}')
         object.__setattr__(self, 'full_range', bool(self.full_range))
+        for name in ('depth', 'out_depth'):
+            v = getattr(self, name)
+            if name == 'out_depth' and v is None:
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v not in YUV_DEPTHS:
+                raise ValueError(f'Yuv420: {name} is one of {YUV_DEPTHS}, got {v!r}')
+            object.__setattr__(self, name, int(v))
+
+    @property
+    def od(self):
+        """Bits per sample of the output: out_depth, or the input's."""
+        return self.depth if self.out_depth is None else self.out_depth
 
     @property
     def frame_bytes(self):
-        return self.h * self.w + 2 * ((self.h + 1) // 2) * ((self.w + 1) // 2)
+        samples = self.h * self.w + 2 * ((self.h + 1) // 2) * ((self.w + 1) // 2)
+        return samples * (2 if self.depth > 8 else 1)
 
     def out_frame_bytes(self, scale):
         """Bytes of a super-resolved frame (s*h and s*w are even: the scale is 2 or 4)."""
         if scale < 1 or (scale * self.h) % 2 or (scale * self.w) % 2:
             raise ValueError(f'Yuv420: an output frame has even sides; scale {scale} gives {scale * self.h}x{scale * self.w}')
-        return scale * self.h * scale * self.w * 3 // 2
+        return scale * self.h * scale * self.w * 3 // 2 * (2 if self.od > 8 else 1)
 
     def codes(self):
         """(matrix, full_range, siting) as the C ABI takes them."""
@@ -299,10 +326,18 @@ class SceneCut:
         return len(inner.cuts), len(inner.scores)
 
 
-def yuv420_planes(chunk, H, W):
+def yuv420_planes(chunk, H, W, depth=8):
     """(Y, U, V) views of I420 frames: chunk (m, frame_bytes) -> (m,H,W), (m,ch,cw), (m,ch,cw); a single frame
-    (frame_bytes,) -> (H,W), (ch,cw), (ch,cw).  numpy or torch; nothing is copied."""
+    (frame_bytes,) -> (H,W), (ch,cw), (ch,cw).  numpy or torch; nothing is copied.  depth above 8: the chunk holds
+    2-byte samples (uint8 as the stream yields it, or uint16 already) and the views are uint16."""
     ch, cw = (H + 1) // 2, (W + 1) // 2
+    if depth not in YUV_DEPTHS:
+        raise ValueError(f'yuv420_planes: depth is one of {YUV_DEPTHS}, got {depth!r}')
+    if depth > 8 and chunk.dtype == (np.uint8 if isinstance(chunk, np.ndarray) else torch.uint8):
+        if chunk.shape[-1] != 2 * (H * W + 2 * ch * cw):
+            raise ValueError(f'yuv420_planes: {H}x{W} frames at {depth} bits have {2 * (H * W + 2 * ch * cw)} bytes; '
+                             f'got shape {tuple(chunk.shape)}')
+        chunk = chunk.view(np.uint16 if isinstance(chunk, np.ndarray) else torch.uint16)
     if chunk.shape[-1] != H * W + 2 * ch * cw:
         raise ValueError(f'yuv420_planes: {H}x{W} frames have {H * W + 2 * ch * cw} bytes; got shape {tuple(chunk.shape)}')
     lead = tuple(chunk.shape[:-1])
@@ -375,6 +410,9 @@ class _HostBytes:
 
 def _input_form(piece, c, yuv):
     """The input form of a stream, from its options and its first item (as stream_parts hands it out)."""
+    if yuv is not None and yuv.depth > 8:
+        return _HostBytes(yuv.h, yuv.w, (yuv.frame_bytes,), 'tg_yuv420p16_to_rgb_f32',
+                          (yuv.h, yuv.w, yuv.depth, *yuv.codes()))
     if yuv is not None:
         return _HostBytes(yuv.h, yuv.w, (yuv.frame_bytes,), 'tg_yuv420_to_rgb_f32', (yuv.h, yuv.w, *yuv.codes()))
     if piece.dtype == torch.uint8:
@@ -416,6 +454,40 @@ class _I420Out:
     def encode(self, sl, cnt):
         L.check(self.lib.tg_rgb_u8_to_yuv420(self.u8[sl].data_ptr(), self.yuv_out[sl].data_ptr(), cnt, *self.args),
                 'tg_rgb_u8_to_yuv420')
+
+    def download(self, sl, cnt):
+        self.host_out[sl, :cnt].copy_(self.yuv_out[sl, :cnt], non_blocking=True)
+
+    def result(self, sl, cnt):
+        return self.host_out[sl, :cnt].numpy()
+
+
+class _I420DeepOut:
+    """Output form I420 at 10 or 12 bits: directly behind every frame's SRNet launch ONE
+    tg_rgb_f32_to_yuv420p16 (n = 1, on the caller's stream) converts the float HR frame just written into the slot's
+    device buffer at that frame -- `after(sl)` is the hook enqueue_batch calls -- so nothing is left to encode behind
+    the batch.  The slot's uint8 frames are still written by the HR tail and are not downloaded."""
+
+    def __init__(self, yuv):
+        self.yuv = yuv
+
+    def alloc(self, eng):
+        ns, m, H, W = eng.u8.shape[:4]
+        self.fb = self.yuv.out_frame_bytes(eng.net.scale)
+        self.fn = eng.lib.tg_rgb_f32_to_yuv420p16
+        self.args = (1, H, W, self.yuv.od, *self.yuv.codes(), eng.main.cuda_stream)
+        self.host_out = torch.empty(ns, m, self.fb, dtype=torch.uint8, pin_memory=True)
+        self.yuv_out = torch.empty(ns, m, self.fb, dtype=torch.uint8, device=eng.dev)
+
+    def after(self, sl):
+        base, fb, fn, args = self.yuv_out[sl].data_ptr(), self.fb, self.fn, self.args
+
+        def convert(j, hr_addr):
+            L.check(fn(hr_addr, base + j * fb, *args), 'tg_rgb_f32_to_yuv420p16')
+        return convert
+
+    def encode(self, sl, cnt):
+        pass
 
     def download(self, sl, cnt):
         self.host_out[sl, :cnt].copy_(self.yuv_out[sl, :cnt], non_blocking=True)
@@ -549,7 +621,8 @@ class _StreamEngine:
 
     _upload, copy stream: the frame before the batch, inp.upload, cut.detect, ev_in.
     _compute, caller's stream: the HR snapshot, enqueue_batch (given cut.reset: one tg_zero_if_flag in front of every
-    frame's SRNet launch), rsz.run and then out.encode behind the batch's last frame, ev_s.
+    frame's SRNet launch; given deep.after, 10- and 12-bit output only: one conversion behind it), rsz.run and then
+    out.encode behind the batch's last frame, ev_s.
     _flush_download, copy stream, behind the NEXT batch's upload or at retire: out.download, cut.download, ev_out.
     _retire: waits for ev_out, reads the fault counter, cut.report, returns out.result.
 
@@ -586,10 +659,15 @@ class _StreamEngine:
             if yuv is not None:
                 if resize.h % 2 or resize.w % 2:
                     raise ValueError(f'resize: an I420 frame has even sides, got {resize.h}x{resize.w}')
+                if yuv.od > 8:
+                    raise ValueError(f'infer_stream: resize works on the 8-bit frames and cannot be combined with '
+                                     f'out_depth = {yuv.od}; resize needs an 8-bit output')
                 resize.check_source(net.scale * yuv.h, net.scale * yuv.w)
         # the forms: the output and the scene-cut slots follow from the options, the input from the first item as well
         self.inp, self.input_form = None, lambda piece: _input_form(piece, net.in_nc, yuv)
-        self.out = _PngOut(png) if png is not None else _I420Out(yuv) if yuv is not None else _RgbOut()
+        self.deep = _I420DeepOut(yuv) if yuv is not None and yuv.od > 8 else None    # (the one form with a per-frame hook)
+        self.out = _PngOut(png) if png is not None else self.deep if self.deep is not None else \
+            _I420Out(yuv) if yuv is not None else _RgbOut()
         self.cut = _CutSlots(scene_cut) if scene_cut is not None else None
         self.rsz = _ResizedFrames(resize) if resize is not None else None
         self.net, self.on_fault, self.parts = net, on_fault, stream_parts(frames, net.in_nc, yuv)
@@ -674,7 +752,8 @@ class _StreamEngine:
         enqueue_batch(self.lib, self.plan, self._fplan, b, i0, cnt, self.lr_ptr[sl], self.lr_stride, self.hr_ptr,
                       self.u8_ptr[sl], self.u8_stride, self.zflow.data_ptr(), self.fsz, main, side, self.ev_f[sl],
                       self.ev_s[(b - 2) % ns] if b >= 2 else None,     # (flow slot b & 1 was batch b - 2's)
-                      reset=self.cut.reset(sl) if self.cut is not None else None)
+                      reset=self.cut.reset(sl) if self.cut is not None else None,
+                      after=self.deep.after(sl) if self.deep is not None else None)
         if self.rsz is not None:
             self.rsz.run(sl, cnt)                   # behind the batch's last frame, in front of the encode
         self.out.encode(sl, cnt)                    # behind the batch's last frame
@@ -798,6 +877,6 @@ class _StreamEngine:
             if self.ring.inflight:
                 self.plan.chain_state()             # a fault in frames nobody will see: counted, the plan has fallen back
         finally:
-            self.inp = self.out = self.cut = self.rsz = None   # the forms' buffers go with them
+            self.inp = self.out = self.deep = self.cut = self.rsz = None   # the forms' buffers go with them
             self.lr = self.hr = self.snap = self.u8 = self.out_u8 = self.zflow = None
 

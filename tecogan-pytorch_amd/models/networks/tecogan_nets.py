@@ -456,6 +456,15 @@ class FRNet(nn.Module):
         stream yields without `yuv` for the same LR input, bit for bit.  Both launches sit inside the per-batch
         enqueue functions, so a repaired batch has its I420 bytes derived again.
 
+        Yuv420(..., depth=10 | 12) takes frames of 16-bit little-endian samples: items are host
+        uint8 arrays of frame_bytes (the bytes of the file) or uint16 arrays of half that length, and
+        tg_yuv420p16_to_rgb_f32 is the input launch.  Yuv420(..., out_depth=10 | 12) writes the output from the FLOAT
+        HR frame: directly behind every frame's tg_frnet_step_srnet ONE tg_rgb_f32_to_yuv420p16 on the caller's stream
+        converts the state just written into the slot's buffer, nothing is encoded behind the batch, and the yielded
+        uint8 views hold 2-byte samples (yuv420_planes(chunk, H, W, depth) views them as uint16): the bytes are
+        ops.rgb_f32_to_yuv420p of the float frames.  The two depths combine freely; at 8 and 8 the stream enqueues
+        exactly what it always did.  `resize` together with an output above 8 bits is a ValueError.
+
         scene_cut: a SceneCut(mad, hist, detect, at, keep_scores) restarts the recurrence at scene cuts, decided on the
         device; without one the stream enqueues exactly what it always did.  For every batch
         tg_scene_cut_flags compares each LR frame with the one before it on the copy stream, behind whatever wrote the

@@ -522,6 +522,57 @@ def rgb_to_yuv420(rgb_hwc, matrix='bt709', full_range=False, siting='left'):
     return out
 
 
+def yuv420p_frame_samples(h, w):
+    """16-bit samples of one 10- or 12-bit I420 frame (2 bytes each)."""
+    return yuv420_frame_bytes(h, w)
+
+
+def _chk_depth(depth, what):
+    if isinstance(depth, bool) or not isinstance(depth, int):
+        raise L.TecoganHipError(f'{what}: depth is 10 or 12, got {depth!r}')
+    return depth
+
+
+def yuv420p_to_rgb(yuv_u16, h, w, depth, matrix='bt709', full_range=False, siting='left', out=None):
+    """(n, frame_samples) / (frame_samples,) uint16 I420 frames at `depth` (10 | 12) bits on device -> (n,3,h,w) fp32
+    RGB in [0,1]; a sample above 2^depth - 1 is read as 2^depth - 1 (tg_yuv420p16_to_rgb_f32).
+    out: a contiguous CUDA float32 (n,3,h,w) tensor to write into."""
+    _chk(yuv_u16, 'yuv', torch.uint16)
+    if yuv_u16.dim() == 1:
+        yuv_u16 = yuv_u16.unsqueeze(0)
+    if yuv_u16.dim() != 2 or yuv_u16.shape[1] != yuv420p_frame_samples(h, w):
+        raise L.TecoganHipError(f'yuv420p_to_rgb: {h}x{w} frames have {yuv420p_frame_samples(h, w)} samples; '
+                                f'got shape {tuple(yuv_u16.shape)}')
+    m, r, s = _yuv_codes(matrix, full_range, siting, 'yuv420p_to_rgb')
+    n = yuv_u16.shape[0]
+    if out is None:
+        out = torch.empty(n, 3, h, w, dtype=torch.float32, device=yuv_u16.device)
+    elif _chk(out, 'out').shape != (n, 3, h, w):
+        raise L.TecoganHipError(f'yuv420p_to_rgb: out is ({n},3,{h},{w}), got shape {tuple(out.shape)}')
+    L.check(L.lib().tg_yuv420p16_to_rgb_f32(_ptr(yuv_u16), _ptr(out), n, h, w, _chk_depth(depth, 'yuv420p_to_rgb'), m, r,
+                                            s, _stream()), 'tg_yuv420p16_to_rgb_f32')
+    return out
+
+
+def rgb_f32_to_yuv420p(rgb_chw, depth, matrix='bt709', full_range=False, siting='left', out=None):
+    """(n,3,H,W) float32 RGB on device -> (n, frame_samples) uint16 I420 frames at `depth` (10 | 12) bits: one fp32
+    step to 16-bit integers, then exact integer arithmetic; H and W even (tg_rgb_f32_to_yuv420p16; DESIGN.md section
+    7k).  out: a contiguous CUDA uint16 (n, frame_samples) tensor to write into."""
+    _chk(rgb_chw, 'rgb')
+    if rgb_chw.dim() != 4 or rgb_chw.shape[1] != 3:
+        raise L.TecoganHipError(f'rgb_f32_to_yuv420p: expected (n,3,H,W), got shape {tuple(rgb_chw.shape)}')
+    m, r, s = _yuv_codes(matrix, full_range, siting, 'rgb_f32_to_yuv420p')
+    n, _, H, W = rgb_chw.shape
+    if out is None:
+        out = torch.empty(n, yuv420p_frame_samples(H, W), dtype=torch.uint16, device=rgb_chw.device)
+    elif _chk(out, 'out', torch.uint16).shape != (n, yuv420p_frame_samples(H, W)):
+        raise L.TecoganHipError(f'rgb_f32_to_yuv420p: out is ({n}, {yuv420p_frame_samples(H, W)}), got shape '
+                                f'{tuple(out.shape)}')
+    L.check(L.lib().tg_rgb_f32_to_yuv420p16(_ptr(rgb_chw), _ptr(out), n, H, W, _chk_depth(depth, 'rgb_f32_to_yuv420p'),
+                                            m, r, s, _stream()), 'tg_rgb_f32_to_yuv420p16')
+    return out
+
+
 def png_encode(rgb_hwc, filter='adaptive'):
     """(n,H,W,3) / (H,W,3) uint8 RGB on device -> a list of n host `bytes`, each one complete PNG file, encoded on
     the device (tg_png_encode_u8): filter 'adaptive' | 'none', Huffman-only deflate in segments

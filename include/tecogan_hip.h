@@ -594,6 +594,39 @@ int tg_yuv420p16_to_rgb_f32(const uint16_t* yuv, float* rgb_chw, int n, int h, i
 int tg_rgb_f32_to_yuv420p16(const float* rgb_chw, uint16_t* yuv, int n, int H, int W, int depth, int matrix,
                             int full_range, int siting, tg_stream_t stream);
 
+/* Planar YUV 4:2:0, 4:2:2 and 4:4:4 at 8, 10 or 12 bits per sample, and the BT.2020 matrix.  A
+ * frame is the Y plane h*w, then U, then V, each ceil(h/sy) x ceil(w/sx) with (sx, sy) = (2,2) (420), (2,1) (422),
+ * (1,1) (444), tightly packed; a sample is a byte at depth 8 and a 16-bit little-endian word above it (one above
+ * 2^depth - 1 is read as 2^depth - 1).  matrix, full_range and siting are the enums above, plus TG_YUV_BT2020
+ * (non-constant luminance: Kr, Kb = 0.2627, 0.0593), which ONLY the three functions below accept.  The arithmetic is
+ * the one of the six functions above with a subsampled axis switched on or off, and at chroma 420 with BT601 / BT709
+ * the results are theirs bit for bit.  The integer tables rint(M * 2^16) / rint(M_d * 2^24) are computed on the host in
+ * fp64 from (Kr, Kb).  Samples carry whatever transfer function the material has (PQ and HLG included): code values
+ * pass through, nothing is linearised.
+ *   in:  chroma to sixteenths in exact integers -- a subsampled axis by its rule above ((1,3)/(3,1) vertically, the
+ *        siting's rule horizontally), an axis that is not subsampled times 4 (a 4:4:4 sample is 16 c) -- every index
+ *        clamped into the plane, then the one fp32 matrix step and the clamp.
+ *   out: Y as above.  A chroma sample is dot(Q row, tap-weighted RGB sum) + (mid << sh) + (1 << (sh-1)), clamped and
+ *        then shifted by sh = 16 + t (8 bit) or 24 + t (10 | 12 bit), 2^t the total tap weight: 444 the pixel itself
+ *        (t = 0, the siting is not looked at); 422 centre the two pixels of the pair (t = 1), 422 left (1,2,1) over
+ *        x-1, x, x+1 of the row with x-1 clamped to 0 (t = 2); 420 as above (t = 2 centre, 3 left).
+ * A null pointer, an unknown enum value, a depth other than 8 | 10 | 12 (8 | 10 | 12 in, 10 | 12 for the 16-bit
+ * output), n < 1, an fp32 pointer that is not 4-byte aligned, a pointer to 16-bit samples that is not 2-byte aligned,
+ * or a shape outside the lines below is TG_E_ARG, without a launch. */
+enum { TG_YUV_BT2020 = 2 };
+enum { TG_YUV_420 = 0, TG_YUV_422 = 1, TG_YUV_444 = 2 };
+/* yuv (n frames, h x w, any h, w >= 2; uint8_t samples at depth 8, uint16_t at 10 | 12) -> rgb_chw (n,3,h,w) fp32 in
+ * [0,1] */
+int tg_yuv_planar_to_rgb_f32(const void* yuv, float* rgb_chw, int n, int h, int w, int chroma, int depth, int matrix,
+                             int full_range, int siting, tg_stream_t stream);
+/* rgb_hwc (n,H,W,3) uint8 -> yuv (n frames of bytes, H x W).  420: H and W even; 422: W even; 444: any H, W >= 1. */
+int tg_rgb_u8_to_yuv_planar(const uint8_t* rgb_hwc, uint8_t* yuv, int n, int H, int W, int chroma, int matrix,
+                            int full_range, int siting, tg_stream_t stream);
+/* rgb_chw (n,3,H,W) fp32 -> yuv (n frames of 16-bit samples at depth 10 | 12, H x W; the shapes of the line above),
+ * through the one float step q = (int) rintf(clamp(v) * 65535.0f) of tg_rgb_f32_to_yuv420p16. */
+int tg_rgb_f32_to_yuv_planar16(const float* rgb_chw, uint16_t* yuv, int n, int H, int W, int chroma, int depth,
+                               int matrix, int full_range, int siting, tg_stream_t stream);
+
 /* PNG files written on the device: what the reference's save_sequence does with cv2.imwrite
  * (codes/utils/data_utils.py), without the host's zlib.  The specification is tests/png_ref.py and the bytes are
  * equal: 8-bit RGB, no interlace, one IDAT; per row the filter type (adaptive: the one of None, Sub, Up, Average,

@@ -155,6 +155,9 @@ UP_NONE, UP_BICUBIC, UP_BILINEAR = (_K['TG_UP_' + k] for k in ('NONE', 'BICUBIC'
 PREC_F32, PREC_F16 = _K['TG_PREC_F32'], _K['TG_PREC_F16']
 YUV_MATRIX = {'bt601': _K['TG_YUV_BT601'], 'bt709': _K['TG_YUV_BT709']}
 YUV_SITING = {'center': _K['TG_YUV_CENTER'], 'left': _K['TG_YUV_LEFT']}
+# what the three tg_*yuv_planar* entry points take on top; YUV_MATRIX stays the 4:2:0 functions'
+YUV_PLANAR_MATRIX = dict(YUV_MATRIX, bt2020=_K['TG_YUV_BT2020'])
+YUV_CHROMA = {'420': _K['TG_YUV_420'], '422': _K['TG_YUV_422'], '444': _K['TG_YUV_444']}
 PNG_FILTER = {'none': _K['TG_PNG_FILTER_NONE'], 'adaptive': _K['TG_PNG_FILTER_ADAPTIVE']}
 
 STRUCTS = _HEADER.structs                           # C name -> Structure class

@@ -452,7 +452,452 @@ __global__ __launch_bounds__(256) void yuv420p16_to_rgb_f32_kernel(const uint16_
   }
 }
 
+// ---- 4:2:0, 4:2:2 and 4:4:4 at 8, 10 and 12 bits, any (Kr, Kb) -------------------------------
+// One kernel template per direction over (sample type T, SX, SY, VEC, LEFT): T = uint8_t is the 8-bit arithmetic of
+// section 7e (32-bit accumulators, shift 16, uint8 HWC RGB on the way out), T = uint16_t the one of section 7k (64-bit
+// accumulators, shift 24, fp32 CHW RGB); (SX, SY) is the chroma sub-sampling, (2,2) | (2,1) | (1,1).  The arithmetic is
+// the four kernels' above with a sub-sampled axis switched on or off, through the same helpers, so (2,2) gives their
+// floats, bytes and words.  The integer tables are computed on the host from (Kr, Kb) and passed as a kernel argument.
+//
+// Thread map: one row x 4 pixels on the way in; SY rows x 4 pixels on the way out, so that a thread owns whole chroma
+// samples (4 / SX per plane).
+//
+// Alignment of the wide form (VEC), taken only when W % 4 == 0 and the bases are aligned as the entry points above
+// test (samples: 4 bytes at 8 bit, 8 bytes at 16 bit; fp32: 16 bytes; uint8 RGB: 4 bytes).  In samples, with W = 4 m:
+//   row stride W, and a strip's x0 = 4 tx: multiples of 4.  Y plane H W: a multiple of 4.
+//   chroma plane ch cw -- 4:2:0 (on the way in ch = ceil(H/2)): ch 2m, even, and two planes ch W, a multiple of 4;
+//   4:2:2: H 2m, even, two planes H W; 4:4:4: H W, a multiple of 4 already.
+//   So every frame starts a multiple of 4 samples behind the base, U starts a multiple of 4 behind the frame, and V an
+//   even number of samples (a multiple of 4 at 4:4:4) behind U.  A strip's chroma run starts at j cw + x0 / SX: even
+//   for SX = 2 (cw = 2m, a run of 2 samples), a multiple of 4 for SX = 1 (cw = 4m, a run of 4).
+//   Hence: Y runs of 4 samples and 4:4:4 chroma runs of 4 are aligned to 4 samples (a dword at 8 bit, 8 bytes at 16
+//   bit), chroma runs of 2 to 2 samples (a 16-bit word / a dword).  fp32 CHW: plane H W and row W are multiples of 4
+//   floats, so every float4 is 16-byte aligned; uint8 HWC: row 3W = 12m and 3 x0 = 12 tx, so the three dwords are.
+// Every other shape or placement takes the element-wide form of the same kernel.
+struct yuv_qp {         // rint(M * 2^16) (8 bit) or rint(M_d * 2^24), rows Y / Cb / Cr; luma offset, chroma mid, top code
+  int y[3], cb[3], cr[3], yo, mid, top;
+};
+
+static bool yuv_kr_kb(int matrix, double* kr, double* kb) {
+  switch (matrix) {
+    case TG_YUV_BT601: *kr = 0.299; *kb = 0.114; return true;
+    case TG_YUV_BT709: *kr = 0.2126; *kb = 0.0722; return true;
+    case TG_YUV_BT2020: *kr = 0.2627; *kb = 0.0593; return true;      // non-constant luminance
+  }
+  return false;
+}
+
+// yo, ys, cs, mid at `depth` bits (8: section 7e's, above: section 7k's)
+static void yuv_scales(int depth, int full_range, int* yo, double* ys, double* cs, int* mid) {
+  const int up = depth - 8;
+  const double top = (double)((1 << depth) - 1);
+  *yo = full_range ? 0 : 16 << up;
+  *ys = full_range ? top : (double)(219 << up);
+  *cs = full_range ? top : (double)(224 << up);
+  *mid = 128 << up;
+}
+
+// Q in fp64, rounded half even (the default rounding mode): from RGB levels 0..255 times 2^16 at depth 8, from 16-bit
+// codes 0..65535 times 2^24 above.  For BT601 / BT709 these are Q_TABLE / Q24_TABLE entry for entry.
+static yuv_qp forward_table(int matrix, int full_range, int depth) {
+  double kr = 0, kb = 0, ys, cs;
+  yuv_qp q;
+  yuv_kr_kb(matrix, &kr, &kb);
+  yuv_scales(depth, full_range, &q.yo, &ys, &cs, &q.mid);
+  q.top = (1 << depth) - 1;
+  const double kg = 1.0 - kr - kb;
+  const double in = depth == 8 ? 255.0 : 65535.0, one = depth == 8 ? 65536.0 : 16777216.0;
+  const double m[3][3] = {{kr * ys / in, kg * ys / in, kb * ys / in},
+                          {-kr / (2 * (1 - kb)) * cs / in, -kg / (2 * (1 - kb)) * cs / in, 0.5 * cs / in},
+                          {0.5 * cs / in, -kg / (2 * (1 - kr)) * cs / in, -kb / (2 * (1 - kr)) * cs / in}};
+  for (int c = 0; c < 3; ++c) {
+    q.y[c] = (int)__builtin_rint(m[0][c] * one);
+    q.cb[c] = (int)__builtin_rint(m[1][c] * one);
+    q.cr[c] = (int)__builtin_rint(m[2][c] * one);
+  }
+  return q;
+}
+
+static yuv_f inverse_table(int matrix, int full_range, int depth) {       // inverse_coefficients(_deep) for any (Kr, Kb)
+  double kr = 0, kb = 0, ys, cs;
+  int mid;
+  yuv_f f;
+  yuv_kr_kb(matrix, &kr, &kb);
+  yuv_scales(depth, full_range, &f.yo, &ys, &cs, &mid);
+  const double kg = 1.0 - kr - kb, cs16 = 16.0 * cs;
+  f.ky = (float)(1.0 / ys);
+  f.rv = (float)(2.0 * (1.0 - kr) / cs16);
+  f.bu = (float)(2.0 * (1.0 - kb) / cs16);
+  f.gu = (float)(-(2.0 * kb * (1.0 - kb) / kg) / cs16);
+  f.gv = (float)(-(2.0 * kr * (1.0 - kr) / kg) / cs16);
+  return f;
+}
+
+// what differs between the two sample types on the way out: the RGB source, the accumulator and the base shift
+template <typename T> struct yuv_out;
+template <> struct yuv_out<uint8_t> {
+  typedef uint8_t src_t;
+  typedef int acc_t;
+  static constexpr int BASE = 16;
+  static __device__ __forceinline__ acc_t dot(const int q[3], const int p[3]) { return dot3(q, p); }
+  static __device__ __forceinline__ unsigned clip(acc_t acc, int sh, int) { return (unsigned)shift_clip_u8(acc, sh); }
+  // pixels x0 .. x0+3 of row `row` of frame k (HWC bytes); the ones from npx on are 0
+  template <bool VEC>
+  static __device__ __forceinline__ void load(const src_t* rgb, long long k, int H, int W, int row, int x0, int npx,
+                                              int p[4][3]) {
+    const uint8_t* s = rgb + (k * H + row) * (3LL * W) + 3 * x0;
+    if (VEC) {                                                    // 12 bytes at a 4-byte aligned address
+      const uint32_t* s4 = reinterpret_cast<const uint32_t*>(s);
+      const uint32_t a = s4[0], b = s4[1], c = s4[2];
+      const uint32_t by[12] = {a & 255, (a >> 8) & 255, (a >> 16) & 255, a >> 24, b & 255, (b >> 8) & 255,
+                               (b >> 16) & 255, b >> 24, c & 255, (c >> 8) & 255, (c >> 16) & 255, c >> 24};
+#pragma unroll
+      for (int e = 0; e < 12; ++e) p[e / 3][e % 3] = (int)by[e];
+    } else {
+#pragma unroll
+      for (int e = 0; e < 12; ++e) p[e / 3][e % 3] = e < 3 * npx ? (int)s[e] : 0;
+    }
+  }
+  // pixel x0 - 1 of that row (x0 >= 4): the strip before's last column
+  static __device__ __forceinline__ void left(const src_t* rgb, long long k, int H, int W, int row, int x0, int l[3]) {
+    const uint8_t* s = rgb + (k * H + row) * (3LL * W) + 3 * x0 - 3;
+    l[0] = (int)s[0]; l[1] = (int)s[1]; l[2] = (int)s[2];
+  }
+};
+template <> struct yuv_out<uint16_t> {
+  typedef float src_t;
+  typedef long long acc_t;
+  static constexpr int BASE = 24;
+  static __device__ __forceinline__ acc_t dot(const int q[3], const int p[3]) { return dot3_64(q, p); }
+  static __device__ __forceinline__ unsigned clip(acc_t acc, int sh, int top) { return shift_clip_top(acc, sh, top); }
+  template <bool VEC>
+  static __device__ __forceinline__ void load(const src_t* rgb, long long k, int H, int W, int row, int x0, int npx,
+                                              int p[4][3]) {
+    const long long plane = (long long)H * W;
+    const float* s = rgb + k * 3 * plane + (long long)row * W + x0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (VEC) {                                                  // 16 bytes at a 16-byte aligned address
+        const f32x4 v = *reinterpret_cast<const f32x4*>(s + c * plane);
+        p[0][c] = quantize16(v.x); p[1][c] = quantize16(v.y); p[2][c] = quantize16(v.z); p[3][c] = quantize16(v.w);
+      } else {
+#pragma unroll
+        for (int x = 0; x < 4; ++x) p[x][c] = x < npx ? quantize16(s[c * plane + x]) : 0;
+      }
+    }
+  }
+  static __device__ __forceinline__ void left(const src_t* rgb, long long k, int H, int W, int row, int x0, int l[3]) {
+    const long long plane = (long long)H * W;
+    const float* s = rgb + k * 3 * plane + (long long)row * W + x0 - 1;
+    l[0] = quantize16(s[0]); l[1] = quantize16(s[plane]); l[2] = quantize16(s[2 * plane]);
+  }
+};
+
+// N = 4 | 2 samples to dst; the wide form is one store of N samples (dst aligned to N samples), the other one writes
+// the first cnt of them one by one
+template <bool VEC, int N>
+__device__ __forceinline__ void store_samples(uint8_t* dst, const unsigned v[N], int cnt) {
+  if (VEC) {
+    if (N == 4) *reinterpret_cast<uint32_t*>(dst) = v[0] | (v[1] << 8) | (v[2 % N] << 16) | (v[3 % N] << 24);
+    else *reinterpret_cast<uint16_t*>(dst) = (uint16_t)(v[0] | (v[1] << 8));
+  } else {
+#pragma unroll
+    for (int x = 0; x < N; ++x)
+      if (x < cnt) dst[x] = (uint8_t)v[x];
+  }
+}
+template <bool VEC, int N>
+__device__ __forceinline__ void store_samples(uint16_t* dst, const unsigned v[N], int cnt) {
+  if (VEC) {
+    if (N == 4) *reinterpret_cast<u32x2*>(dst) = u32x2{v[0] | (v[1] << 16), v[2 % N] | (v[3 % N] << 16)};
+    else *reinterpret_cast<uint32_t*>(dst) = v[0] | (v[1] << 16);
+  } else {
+#pragma unroll
+    for (int x = 0; x < N; ++x)
+      if (x < cnt) dst[x] = (uint16_t)v[x];
+  }
+}
+
+// thread = rows SY*j .. SY*j + SY-1 x pixels 4*tx .. 4*tx+3 of frame k.  H is a multiple of SY and W one of SX (the
+// entry points test it), so a strip holds whole chroma samples: npx is 2 or 4 for SX = 2, 1 .. 4 for SX = 1.
+template <typename T, int SX, int SY, bool VEC, bool LEFT>
+__global__ __launch_bounds__(256) void rgb_to_yuv_planar_kernel(const typename yuv_out<T>::src_t* __restrict__ rgb,
+                                                                T* __restrict__ yuv, int H, int W, int strips,
+                                                                long long total, yuv_qp q) {
+  typedef yuv_out<T> O;
+  typedef typename O::acc_t acc_t;
+  static_assert((SX == 2 || SX == 1) && (SY == 2 || SY == 1) && SY <= SX, "4:2:0, 4:2:2 or 4:4:4");
+  static_assert(SX == 2 || !LEFT, "the siting matters along a sub-sampled axis only");
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int tx = (int)(i % strips);
+  const long long r = i / strips;
+  const int ch = H / SY, cw = W / SX;
+  const int j = (int)(r % ch);
+  const long long k = r / ch;
+  const int x0 = 4 * tx;
+  const int npx = W - x0 < 4 ? W - x0 : 4;
+  const long long plane = (long long)H * W, cplane = (long long)ch * cw;
+  int p[SY][4][3];
+#pragma unroll
+  for (int rr = 0; rr < SY; ++rr) O::template load<VEC>(rgb, k, H, W, SY * j + rr, x0, npx, p[rr]);
+  T* yp = yuv + k * (plane + 2 * cplane);
+  T* up = yp + plane;
+  T* vp = up + cplane;
+  const acc_t yround = ((acc_t)q.yo << O::BASE) + ((acc_t)1 << (O::BASE - 1));
+#pragma unroll
+  for (int rr = 0; rr < SY; ++rr) {
+    unsigned yv[4];
+#pragma unroll
+    for (int x = 0; x < 4; ++x) yv[x] = O::clip(O::dot(q.y, p[rr][x]) + yround, O::BASE, q.top);
+    store_samples<VEC, 4>(yp + (long long)(SY * j + rr) * W + x0, yv, npx);
+  }
+  constexpr int NC = 4 / SX;                                      // chroma samples of the strip, per plane
+  constexpr int T2 = (SX == 2 ? (LEFT ? 2 : 1) : 0) + (SY - 1);   // log2 of the total tap weight
+  constexpr int SH = O::BASE + T2;
+  const acc_t cround = ((acc_t)q.mid << SH) + ((acc_t)1 << (SH - 1));
+  unsigned uo[NC], vo[NC];
+#pragma unroll
+  for (int c2 = 0; c2 < NC; ++c2) {
+    int s[3] = {0, 0, 0};
+#pragma unroll
+    for (int rr = 0; rr < SY; ++rr) {
+      if (SX == 1) {                                              // the pixel itself
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s[c] += p[rr][c2][c];
+      } else if (LEFT) {                                          // (1, 2, 1) over x-1, x, x+1 at x = 2i, x-1 clamped to 0
+        int l[3] = {p[rr][(2 * c2 + 3) % 4][0], p[rr][(2 * c2 + 3) % 4][1], p[rr][(2 * c2 + 3) % 4][2]};
+        if (c2 == 0) {
+          if (x0 == 0) { l[0] = p[rr][0][0]; l[1] = p[rr][0][1]; l[2] = p[rr][0][2]; }
+          else O::left(rgb, k, H, W, SY * j + rr, x0, l);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s[c] += l[c] + 2 * p[rr][(2 * c2) % 4][c] + p[rr][(2 * c2 + 1) % 4][c];
+      } else {                                                    // the pair
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s[c] += p[rr][(2 * c2) % 4][c] + p[rr][(2 * c2 + 1) % 4][c];
+      }
+    }
+    uo[c2] = O::clip(O::dot(q.cb, s) + cround, SH, q.top);
+    vo[c2] = O::clip(O::dot(q.cr, s) + cround, SH, q.top);
+  }
+  const long long co = (long long)j * cw + NC * tx;
+  const int ncs = npx / SX;                                       // chroma samples inside the frame
+  store_samples<VEC, NC>(up + co, uo, ncs);
+  store_samples<VEC, NC>(vp + co, vo, ncs);
+}
+
+// thread = row y x pixels 4*tx .. 4*tx+3 of frame k, as yuv420_to_rgb_f32_kernel.  `top` = 2^d - 1 bounds every 16-bit
+// sample, `mid16` = 16 * mid.  Along a sub-sampled axis the taps are the ones above; along one that is not, the sample
+// of the pixel itself times 4.  Every chroma index is clamped into the plane, so the loads of the pixels past the
+// width are in bounds too.
+template <typename T, int SX, int SY, bool VEC, bool LEFT>
+__global__ __launch_bounds__(256) void yuv_planar_to_rgb_f32_kernel(const T* __restrict__ yuv, float* __restrict__ rgb,
+                                                                    int h, int w, int strips, long long total, yuv_f f,
+                                                                    int top, int mid16) {
+  static_assert((SX == 2 || SX == 1) && (SY == 2 || SY == 1) && SY <= SX, "4:2:0, 4:2:2 or 4:4:4");
+  static_assert(SX == 2 || !LEFT, "the siting matters along a sub-sampled axis only");
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int tx = (int)(i % strips);
+  const long long r = i / strips;
+  const int y = (int)(r % h);
+  const long long k = r / h;
+  const int x0 = 4 * tx, ch = (h + SY - 1) / SY, cw = (w + SX - 1) / SX;
+  const T* yp = yuv + k * ((long long)h * w + 2LL * ch * cw);
+  const T* up = yp + (long long)h * w;
+  const T* vp = up + (long long)ch * cw;
+  auto sample = [top](const T* p, long long at) {
+    const int s = (int)p[at];
+    return sizeof(T) == 1 ? s : (s > top ? top : s);
+  };
+  int r0, r1, w0, w1;                                             // two chroma rows and their weights, in quarters
+  if (SY == 2) {                                                  // even y -> (y/2 - 1, y/2) x (1, 3); odd y -> (3, 1)
+    r0 = (y & 1) ? (y - 1) >> 1 : (y >> 1) - 1;
+    r1 = r0 + 1;
+    w0 = (y & 1) ? 3 : 1;
+    w1 = 4 - w0;
+    r0 = r0 < 0 ? 0 : r0;
+    r1 = r1 > ch - 1 ? ch - 1 : r1;
+  } else {
+    r0 = r1 = y;
+    w0 = 4;
+    w1 = 0;
+  }
+  int u[4], v[4];                                                 // vertical sums in quarters: columns 2*tx-1 .. 2*tx+2, or x0 .. x0+3
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    int c = SX == 2 ? 2 * tx - 1 + m : x0 + m;
+    c = c < 0 ? 0 : (c > cw - 1 ? cw - 1 : c);
+    if (SY == 2) {
+      u[m] = w0 * sample(up, (long long)r0 * cw + c) + w1 * sample(up, (long long)r1 * cw + c);
+      v[m] = w0 * sample(vp, (long long)r0 * cw + c) + w1 * sample(vp, (long long)r1 * cw + c);
+    } else {
+      u[m] = 4 * sample(up, (long long)r0 * cw + c);
+      v[m] = 4 * sample(vp, (long long)r0 * cw + c);
+    }
+  }
+  int u16[4], v16[4];                                             // sixteenths
+  if (SX == 1) {
+#pragma unroll
+    for (int x = 0; x < 4; ++x) { u16[x] = 4 * u[x]; v16[x] = 4 * v[x]; }
+  } else if (LEFT) {                                              // even x: its own column; odd x: the two around it
+    u16[0] = 4 * u[1]; u16[1] = 2 * (u[1] + u[2]); u16[2] = 4 * u[2]; u16[3] = 2 * (u[2] + u[3]);
+    v16[0] = 4 * v[1]; v16[1] = 2 * (v[1] + v[2]); v16[2] = 4 * v[2]; v16[3] = 2 * (v[2] + v[3]);
+  } else {                                                        // the row rule again
+    u16[0] = u[0] + 3 * u[1]; u16[1] = 3 * u[1] + u[2]; u16[2] = u[1] + 3 * u[2]; u16[3] = 3 * u[2] + u[3];
+    v16[0] = v[0] + 3 * v[1]; v16[1] = 3 * v[1] + v[2]; v16[2] = v[1] + 3 * v[2]; v16[3] = 3 * v[2] + v[3];
+  }
+  int yy[4];
+  const T* ysrc = yp + (long long)y * w + x0;
+  if (VEC && sizeof(T) == 1) {                                    // 4 bytes at a 4-byte aligned address
+    const uint32_t a = *reinterpret_cast<const uint32_t*>(ysrc);
+    yy[0] = (int)(a & 255); yy[1] = (int)((a >> 8) & 255); yy[2] = (int)((a >> 16) & 255); yy[3] = (int)(a >> 24);
+  } else if (VEC) {                                               // 8 bytes at an 8-byte aligned address
+    const u32x2 a = *reinterpret_cast<const u32x2*>(ysrc);
+    yy[0] = (int)(a.x & 65535u); yy[1] = (int)(a.x >> 16); yy[2] = (int)(a.y & 65535u); yy[3] = (int)(a.y >> 16);
+  } else {
+#pragma unroll
+    for (int x = 0; x < 4; ++x) yy[x] = x0 + x < w ? (int)ysrc[x] : 0;
+  }
+  float R[4], G[4], B[4];
+#pragma unroll
+  for (int x = 0; x < 4; ++x) {
+    const int ys = sizeof(T) == 1 ? yy[x] : (yy[x] > top ? top : yy[x]);
+    const float yf = f.ky * (float)(ys - f.yo);
+    const float du = (float)(u16[x] - mid16), dv = (float)(v16[x] - mid16);
+    R[x] = clamp01(__builtin_fmaf(f.rv, dv, yf));
+    G[x] = clamp01(__builtin_fmaf(f.gv, dv, __builtin_fmaf(f.gu, du, yf)));
+    B[x] = clamp01(__builtin_fmaf(f.bu, du, yf));
+  }
+  const long long plane = (long long)h * w;
+  float* dst = rgb + k * 3 * plane + (long long)y * w + x0;
+  if (VEC) {
+    *reinterpret_cast<f32x4*>(dst) = f32x4{R[0], R[1], R[2], R[3]};
+    *reinterpret_cast<f32x4*>(dst + plane) = f32x4{G[0], G[1], G[2], G[3]};
+    *reinterpret_cast<f32x4*>(dst + 2 * plane) = f32x4{B[0], B[1], B[2], B[3]};
+  } else {
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+      if (x0 + x < w) {
+        dst[x] = R[x];
+        dst[plane + x] = G[x];
+        dst[2 * plane + x] = B[x];
+      }
+  }
+}
+
+static bool yuv_planar_enums_ok(int chroma, int matrix, int full_range, int siting) {
+  return (chroma == TG_YUV_420 || chroma == TG_YUV_422 || chroma == TG_YUV_444) &&
+         (matrix == TG_YUV_BT601 || matrix == TG_YUV_BT709 || matrix == TG_YUV_BT2020) &&
+         (full_range == 0 || full_range == 1) && (siting == TG_YUV_CENTER || siting == TG_YUV_LEFT);
+}
+
+template <typename T, int SX, int SY>
+static void launch_planar_out(bool vec, bool left, dim3 grid, hipStream_t st, const typename yuv_out<T>::src_t* rgb,
+                              T* yuv, int H, int W, int strips, long long total, const yuv_qp& q) {
+  constexpr bool L = SX == 2;                                     // (4:4:4 has the one form: the siting is not looked at)
+  const dim3 block(256);
+  if (vec) {
+    if (left) hipLaunchKernelGGL((rgb_to_yuv_planar_kernel<T, SX, SY, true, L>), grid, block, 0, st, rgb, yuv, H, W, strips, total, q);
+    else hipLaunchKernelGGL((rgb_to_yuv_planar_kernel<T, SX, SY, true, false>), grid, block, 0, st, rgb, yuv, H, W, strips, total, q);
+  } else {
+    if (left) hipLaunchKernelGGL((rgb_to_yuv_planar_kernel<T, SX, SY, false, L>), grid, block, 0, st, rgb, yuv, H, W, strips, total, q);
+    else hipLaunchKernelGGL((rgb_to_yuv_planar_kernel<T, SX, SY, false, false>), grid, block, 0, st, rgb, yuv, H, W, strips, total, q);
+  }
+}
+
+template <typename T, int SX, int SY>
+static void launch_planar_in(bool vec, bool left, dim3 grid, hipStream_t st, const T* yuv, float* rgb, int h, int w,
+                             int strips, long long total, const yuv_f& f, int top, int mid16) {
+  constexpr bool L = SX == 2;
+  const dim3 block(256);
+  if (vec) {
+    if (left) hipLaunchKernelGGL((yuv_planar_to_rgb_f32_kernel<T, SX, SY, true, L>), grid, block, 0, st, yuv, rgb, h, w, strips, total, f, top, mid16);
+    else hipLaunchKernelGGL((yuv_planar_to_rgb_f32_kernel<T, SX, SY, true, false>), grid, block, 0, st, yuv, rgb, h, w, strips, total, f, top, mid16);
+  } else {
+    if (left) hipLaunchKernelGGL((yuv_planar_to_rgb_f32_kernel<T, SX, SY, false, L>), grid, block, 0, st, yuv, rgb, h, w, strips, total, f, top, mid16);
+    else hipLaunchKernelGGL((yuv_planar_to_rgb_f32_kernel<T, SX, SY, false, false>), grid, block, 0, st, yuv, rgb, h, w, strips, total, f, top, mid16);
+  }
+}
+
+// the checks and the launch of the output direction for one sample type; `base_ok` = the wide form's base alignments
+template <typename T>
+static int rgb_to_yuv_planar(const char* name, const typename yuv_out<T>::src_t* rgb, T* yuv, int n, int H, int W,
+                             int chroma, int depth, int matrix, int full_range, int siting, bool base_ok,
+                             tg_stream_t stream) {
+  TG_REQUIRE(yuv_planar_enums_ok(chroma, matrix, full_range, siting), TG_E_ARG,
+             "%s: chroma=%d matrix=%d full_range=%d siting=%d", name, chroma, matrix, full_range, siting);
+  const int sx = chroma == TG_YUV_444 ? 1 : 2, sy = chroma == TG_YUV_420 ? 2 : 1;
+  TG_REQUIRE(n >= 1 && H >= sy && W >= sx && H % sy == 0 && W % sx == 0, TG_E_ARG,
+             "%s: n=%d H=%d W=%d (n >= 1; 4:2:0: H and W even, 4:2:2: W even)", name, n, H, W);
+  const int strips = (W + 3) / 4;
+  const long long total = (long long)n * (H / sy) * strips;
+  TG_REQUIRE(total < (1LL << 38), TG_E_SHAPE, "%s: %lld strips", name, total);
+  const bool vec = W % 4 == 0 && base_ok, left = siting == TG_YUV_LEFT && sx == 2;
+  const yuv_qp q = forward_table(matrix, full_range, depth);
+  const dim3 grid((unsigned)((total + 255) / 256));
+  const hipStream_t st = (hipStream_t)stream;
+  if (chroma == TG_YUV_420) launch_planar_out<T, 2, 2>(vec, left, grid, st, rgb, yuv, H, W, strips, total, q);
+  else if (chroma == TG_YUV_422) launch_planar_out<T, 2, 1>(vec, left, grid, st, rgb, yuv, H, W, strips, total, q);
+  else launch_planar_out<T, 1, 1>(vec, left, grid, st, rgb, yuv, H, W, strips, total, q);
+  return check_launch(name);
+}
+
+template <typename T>
+static int yuv_planar_to_rgb(const T* yuv, float* rgb, int n, int h, int w, int chroma, int depth, int matrix,
+                             int full_range, int siting, bool base_ok, tg_stream_t stream) {
+  const int sx = chroma == TG_YUV_444 ? 1 : 2;
+  const int strips = (w + 3) / 4;
+  const long long total = (long long)n * h * strips;
+  TG_REQUIRE(total < (1LL << 38), TG_E_SHAPE, "yuv_planar_to_rgb_f32: %lld strips", total);
+  const bool vec = w % 4 == 0 && base_ok, left = siting == TG_YUV_LEFT && sx == 2;
+  const yuv_f f = inverse_table(matrix, full_range, depth);
+  const int top = (1 << depth) - 1, mid16 = 16 << (depth - 1);
+  const dim3 grid((unsigned)((total + 255) / 256));
+  const hipStream_t st = (hipStream_t)stream;
+  if (chroma == TG_YUV_420) launch_planar_in<T, 2, 2>(vec, left, grid, st, yuv, rgb, h, w, strips, total, f, top, mid16);
+  else if (chroma == TG_YUV_422) launch_planar_in<T, 2, 1>(vec, left, grid, st, yuv, rgb, h, w, strips, total, f, top, mid16);
+  else launch_planar_in<T, 1, 1>(vec, left, grid, st, yuv, rgb, h, w, strips, total, f, top, mid16);
+  return check_launch("yuv_planar_to_rgb_f32");
+}
+
 }  // namespace tg
+
+extern "C" int tg_yuv_planar_to_rgb_f32(const void* yuv, float* rgb_chw, int n, int h, int w, int chroma, int depth,
+                                        int matrix, int full_range, int siting, tg_stream_t stream) {
+  TG_REQUIRE(yuv && rgb_chw, TG_E_ARG, "yuv_planar_to_rgb_f32: null pointer");
+  TG_REQUIRE(depth == 8 || depth == 10 || depth == 12, TG_E_ARG, "yuv_planar_to_rgb_f32: depth=%d (8, 10 or 12)", depth);
+  TG_REQUIRE((depth == 8 || (uintptr_t)yuv % 2 == 0) && (uintptr_t)rgb_chw % 4 == 0, TG_E_ARG,
+             "yuv_planar_to_rgb_f32: 16-bit samples are 2-byte aligned and rgb_chw 4-byte aligned");
+  TG_REQUIRE(n >= 1 && h >= 2 && w >= 2, TG_E_ARG, "yuv_planar_to_rgb_f32: n=%d h=%d w=%d (n >= 1, h, w >= 2)", n, h, w);
+  TG_REQUIRE(tg::yuv_planar_enums_ok(chroma, matrix, full_range, siting), TG_E_ARG,
+             "yuv_planar_to_rgb_f32: chroma=%d matrix=%d full_range=%d siting=%d", chroma, matrix, full_range, siting);
+  const bool f16 = (uintptr_t)rgb_chw % 16 == 0;
+  if (depth == 8)
+    return tg::yuv_planar_to_rgb<uint8_t>((const uint8_t*)yuv, rgb_chw, n, h, w, chroma, depth, matrix, full_range,
+                                          siting, f16 && (uintptr_t)yuv % 4 == 0, stream);
+  return tg::yuv_planar_to_rgb<uint16_t>((const uint16_t*)yuv, rgb_chw, n, h, w, chroma, depth, matrix, full_range,
+                                         siting, f16 && (uintptr_t)yuv % 8 == 0, stream);
+}
+
+extern "C" int tg_rgb_u8_to_yuv_planar(const uint8_t* rgb_hwc, uint8_t* yuv, int n, int H, int W, int chroma,
+                                       int matrix, int full_range, int siting, tg_stream_t stream) {
+  TG_REQUIRE(rgb_hwc && yuv, TG_E_ARG, "rgb_u8_to_yuv_planar: null pointer");
+  return tg::rgb_to_yuv_planar<uint8_t>("rgb_u8_to_yuv_planar", rgb_hwc, yuv, n, H, W, chroma, 8, matrix, full_range,
+                                        siting, (uintptr_t)rgb_hwc % 4 == 0 && (uintptr_t)yuv % 4 == 0, stream);
+}
+
+extern "C" int tg_rgb_f32_to_yuv_planar16(const float* rgb_chw, uint16_t* yuv, int n, int H, int W, int chroma,
+                                          int depth, int matrix, int full_range, int siting, tg_stream_t stream) {
+  TG_REQUIRE(rgb_chw && yuv, TG_E_ARG, "rgb_f32_to_yuv_planar16: null pointer");
+  TG_REQUIRE((uintptr_t)yuv % 2 == 0 && (uintptr_t)rgb_chw % 4 == 0, TG_E_ARG,
+             "rgb_f32_to_yuv_planar16: yuv is 2-byte aligned and rgb_chw 4-byte aligned");
+  TG_REQUIRE(depth == 10 || depth == 12, TG_E_ARG, "rgb_f32_to_yuv_planar16: depth=%d (10 or 12)", depth);
+  return tg::rgb_to_yuv_planar<uint16_t>("rgb_f32_to_yuv_planar16", rgb_chw, yuv, n, H, W, chroma, depth, matrix,
+                                         full_range, siting, (uintptr_t)rgb_chw % 16 == 0 && (uintptr_t)yuv % 8 == 0,
+                                         stream);
+}
 
 extern "C" int tg_yuv420p16_to_rgb_f32(const uint16_t* yuv, float* rgb_chw, int n, int h, int w, int depth, int matrix,
                                        int full_range, int siting, tg_stream_t stream) {

@@ -21,7 +21,9 @@ video instead (data/y4m.py): I420 frames go up as they are, are converted on the
 
 A `C420p10` / `C420p12` y4m input is taken as well (`--yuv-siting` names the chroma siting those
 headers do not carry), and `--output-depth 8|10|12` (default: the input's) sets the bits per sample of the y4m written:
-above 8 the frames are converted from the float result, not from the rounded 8-bit one.
+above 8 the frames are converted from the float result, not from the rounded 8-bit one.  `C422*` and `C444*` inputs are
+taken too, `--output-chroma 420|422|444` (default: the input's) sets the layout written -- 444 keeps every chroma sample
+the network computed -- and `--yuv-matrix bt2020` is the non-constant-luminance BT.2020 matrix.
 
 `--scene-cut` (both forms of `infer`) restarts the recurrence at scene cuts, detected on the
 device; the cut frames are listed on stderr at the end, never on stdout.
@@ -83,16 +85,21 @@ def parse_args(argv=None):
                    help='--mode infer: folder the super-resolved PNGs are written to, under the names (and sub-folders) '
                         'of the input.  With y4m input: the y4m file to write, or - for stdout (logging then goes to '
                         'stderr)')
-    p.add_argument('--yuv-matrix', dest='yuv_matrix', type=str, default='bt709', choices=['bt601', 'bt709'],
-                   help='y4m input: the YCbCr matrix of the clip (y4m headers do not carry it)')
+    p.add_argument('--yuv-matrix', dest='yuv_matrix', type=str, default='bt709', choices=['bt601', 'bt709', 'bt2020'],
+                   help='y4m input: the YCbCr matrix of the clip (y4m headers do not carry it); bt2020 is the '
+                        'non-constant-luminance one (DESIGN.md section 7l)')
     p.add_argument('--yuv-range', dest='yuv_range', type=str, default=None, choices=['limited', 'full'],
                    help="y4m input: the range of the clip; default: the header's XCOLORRANGE, or limited without one")
     p.add_argument('--yuv-siting', dest='yuv_siting', type=str, default='left', choices=['center', 'left'],
                    help='y4m input: where a chroma sample sits, consulted only where the header does not decide '
-                        '(C420p10 and C420p12 carry no siting); 8-bit headers decide for themselves')
+                        '(C420p10, C420p12 and every C422 / C444 tag carry no siting); 8-bit 4:2:0 headers decide for '
+                        'themselves')
     p.add_argument('--output-depth', dest='output_depth', type=int, default=None, choices=[8, 10, 12],
                    help="y4m input: bits per sample of the y4m written (DESIGN.md section 7k); default: the input's.  "
                         'Above 8 the frames are converted from the float result, not from the rounded 8-bit one')
+    p.add_argument('--output-chroma', dest='output_chroma', type=str, default=None, choices=['420', '422', '444'],
+                   help="y4m input: chroma layout of the y4m written (DESIGN.md section 7l); default: the input's.  444 "
+                        'keeps every chroma sample the network computed')
     p.add_argument('--scene-cut', dest='scene_cut', action='store_true',
                    help='--mode infer: restart the recurrence at scene cuts, detected on the GPU (DESIGN.md section 7h); '
                         'the cut frames are listed on stderr at the end.  The default thresholds have not been '
@@ -116,6 +123,9 @@ def parse_args(argv=None):
     if args.output_depth is not None and not (args.mode == 'infer' and args.input and
                                               (args.input == '-' or os.path.isfile(args.input))):
         p.error('--output-depth belongs to --mode infer with y4m input (a y4m file, or - for stdin)')
+    if args.output_chroma is not None and not (args.mode == 'infer' and args.input and
+                                               (args.input == '-' or os.path.isfile(args.input))):
+        p.error('--output-chroma belongs to --mode infer with y4m input (a y4m file, or - for stdin)')
     if args.output_depth not in (None, 8) and args.output_size is not None:
         p.error('--output-size resizes the 8-bit frames; it cannot be combined with --output-depth above 8')
     if args.png_encoder == 'device' and args.input and (args.input == '-' or os.path.isfile(args.input)):
@@ -487,21 +497,28 @@ def infer(opt, input_dir, output_dir, scene_cut=None, png_encoder='pillow', outp
 
 
 def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None, output_size=None, siting='left',
-              output_depth=None):
+              output_depth=None, output_chroma=None):
     """--mode infer on raw video: the y4m stream `src` (a binary file object) through VSRModel.infer_stream(yuv=...)
     into the y4m stream `dst`, in order.  The output header carries the scaled size and the input's F, A, C and X tags.
     Each chunk is written out of the ring slot before the generator is advanced; nothing is held beyond it.
     output_size (w, h): the frames are resized to it on the device; the header carries that size and, when the shape
     changes, an A tag scaled so that the display aspect stays.  The input may be C420p10 / C420p12 (DESIGN.md section
     7k): `siting` stands in where the header carries none.  output_depth 8 | 10 | 12 | None (the input's): bits per
-    sample of the output; its C and XYSCSS tags follow.  Returns the number of frames written."""
+    sample of the output; its C and XYSCSS tags follow.  The input may be C422 / C444 at any of the three depths, and
+    output_chroma '420' | '422' | '444' | None (the input's) is the layout written; matrix may be
+    'bt2020'.  A 4:2:0 clip with a 4:2:0 output and BT.601 / BT.709 runs as a Yuv420, everything else as a Yuv.  Returns
+    the number of frames written."""
     from .data.y4m import Y4MReader, Y4MWriter
-    from .models.networks import Yuv420
-    reader = Y4MReader(src, depths=(8, 10, 12))
+    from .models.networks import Yuv, Yuv420
+    reader = Y4MReader(src, depths=(8, 10, 12), chromas=('420', '422', '444'))
     full = reader.full_range if yuv_range is None else yuv_range == 'full'
-    spec = Yuv420(reader.h, reader.w, matrix=matrix, full_range=bool(full),
-                  siting=reader.siting if reader.siting is not None else siting, depth=reader.depth,
-                  out_depth=output_depth)
+    common = dict(matrix=matrix, full_range=bool(full), siting=reader.siting if reader.siting is not None else siting,
+                  depth=reader.depth, out_depth=output_depth)
+    if reader.chroma == '420' and output_chroma in (None, '420') and matrix != 'bt2020':
+        spec, oc = Yuv420(reader.h, reader.w, **common), '420'
+    else:
+        spec = Yuv(reader.h, reader.w, chroma=reader.chroma, out_chroma=output_chroma, **common)
+        oc = spec.oc
     model = define_model(opt)
     s = model.net_G.scale
     W, H = s * reader.w, s * reader.h
@@ -509,14 +526,16 @@ def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None, out
     aspect = None
     if output_size is not None:
         ow, oh = output_size
-        if ow % 2 or oh % 2:
+        if oc == '420' and (ow % 2 or oh % 2):
             raise ValueError(f'--output-size {ow}x{oh}: a 4:2:0 frame has even sides')
+        if oc == '422' and ow % 2:
+            raise ValueError(f'--output-size {ow}x{oh}: a 4:2:2 frame has an even width')
         kw['resize'] = resize_option(output_size)
         kw['resize'].check_source(H, W)
         if oh * W != ow * H:                        # the shape changes: every pixel becomes this much wider for its height
             aspect = (W * oh, H * ow)
         W, H = ow, oh
-    writer = Y4MWriter(dst, W, H, reader.header, aspect_scale=aspect, depth=spec.od, siting=spec.siting)
+    writer = Y4MWriter(dst, W, H, reader.header, aspect_scale=aspect, depth=spec.od, siting=spec.siting, chroma=oc)
     t0, k = time.time(), 0
     for chunk in model.infer_stream(reader, yuv=spec, **kw):
         for frame in chunk:
@@ -529,12 +548,12 @@ def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None, out
     dt = time.time() - t0
     print(f'y4m: {k} frames {reader.w}x{reader.h} -> {W}x{H} '
           f'({k / max(dt, 1e-9):.1f} frames/s, {spec.matrix} {"full" if spec.full_range else "limited"} range, '
-          f'{spec.siting} siting, {spec.depth} -> {spec.od} bits)', flush=True)
+          f'{spec.siting} siting, {spec.depth} -> {spec.od} bits, {reader.chroma} -> {oc})', flush=True)
     return k
 
 
 def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range, scene_cut=None, output_size=None, siting='left',
-                  output_depth=None):
+                  output_depth=None, output_chroma=None):
     """Opens the two ends of infer_y4m.  With `--output -` the y4m bytes are the ONLY thing on stdout: the descriptor
     is set aside for them and, for the length of the run, descriptor 1 and sys.stdout lead to stderr, so that neither
     a print nor a library's message can land in the stream."""
@@ -543,7 +562,8 @@ def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range, scene_cut=Non
     try:
         if output_path != '-':
             with open(output_path, 'wb') as dst:
-                return infer_y4m(opt, src, dst, matrix, yuv_range, scene_cut, output_size, siting, output_depth)
+                return infer_y4m(opt, src, dst, matrix, yuv_range, scene_cut, output_size, siting, output_depth,
+                                 output_chroma)
         sys.stdout.flush()
         keep = os.dup(1)
         py_stdout = sys.stdout
@@ -551,7 +571,8 @@ def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range, scene_cut=Non
         sys.stdout = sys.stderr
         try:
             with os.fdopen(os.dup(keep), 'wb') as dst:
-                return infer_y4m(opt, src, dst, matrix, yuv_range, scene_cut, output_size, siting, output_depth)
+                return infer_y4m(opt, src, dst, matrix, yuv_range, scene_cut, output_size, siting, output_depth,
+                                 output_chroma)
         finally:
             sys.stdout = py_stdout
             os.dup2(keep, 1)
@@ -637,7 +658,7 @@ def main(argv=None):
             raise ValueError('--mode infer needs --input DIR and --output DIR (or a y4m file / - for both)')
         if args.input == '-' or os.path.isfile(args.input):
             infer_y4m_cli(opt, args.input, args.output, args.yuv_matrix, args.yuv_range, scene_cut_option(args),
-                          args.output_size, args.yuv_siting, args.output_depth)
+                          args.output_size, args.yuv_siting, args.output_depth, args.output_chroma)
         else:
             infer(opt, args.input, args.output, scene_cut_option(args), args.png_encoder, args.output_size)
     elif args.mode == 'profile':

@@ -14,8 +14,8 @@ from ..utils.data_utils import gaussian_kernel2d
 def front_pad_stream(frames, mode, n_pad, in_nc=3, yuv=None):
     """pad_sequence for a stream whose length is not known: buffers the first n_pad + 1 frames of `frames` (items as
     FRNet.infer_stream takes them), yields the reflected / replicated prefix, the buffered frames, then the rest of the
-    stream as it comes.  A stream shorter than n_pad + 1 frames is refused (pad_sequence's assert).  yuv (a Yuv420):
-    the items are I420 frames -- 1-D: one frame, 2-D: a chunk -- and so is what is yielded."""
+    stream as it comes.  A stream shorter than n_pad + 1 frames is refused (pad_sequence's assert).  yuv (a Yuv420 or a Yuv):
+    the items are planar YUV frames -- 1-D: one frame, 2-D: a chunk -- and so is what is yielded."""
     from .networks.tecogan_nets import stream_parts
     if mode not in ('reflect', 'replicate'):
         raise ValueError(f'Unrecognized padding mode: {mode}')

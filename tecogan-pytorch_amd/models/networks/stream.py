@@ -221,6 +221,95 @@ class Yuv420:
         return L.YUV_MATRIX[self.matrix], int(self.full_range), L.YUV_SITING[self.siting]
 
 
+YUV_SUBSAMPLING = {'420': (2, 2), '422': (2, 1), '444': (1, 1)}     # chroma -> (sx, sy): luma samples per chroma sample
+
+
+def yuv_frame_samples(h, w, chroma):
+    """Samples of one planar frame: Y h*w, then U and V of ceil(h/sy) x ceil(w/sx)."""
+    sx, sy = YUV_SUBSAMPLING[chroma]
+    return h * w + 2 * ((h + sy - 1) // sy) * ((w + sx - 1) // sx)
+
+
+@dataclass(frozen=True)
+class Yuv:
+    """Raw-video form of a stream in any of the three planar layouts (FRNet.infer_stream(yuv=...), DESIGN.md section
+    7l): frames of h x w on the way in and of s*h x s*w on the way out.  chroma '420' | '422' | '444': the layout of
+    the input; out_chroma the same | None (the input's): the layout of the output.  matrix 'bt601' | 'bt709' | 'bt2020'
+    (non-constant luminance), full_range (bool), siting 'center' | 'left': where a chroma sample sits along a
+    sub-sampled horizontal axis (not looked at for 4:4:4).  depth and out_depth as Yuv420's.  Samples pass through as
+    code values whatever their transfer function (PQ and HLG included).  A Yuv always takes the planar launches
+    (tg_yuv_planar_to_rgb_f32, tg_rgb_u8_to_yuv_planar, tg_rgb_f32_to_yuv_planar16), at '420' as well.  Frozen."""
+    h: int
+    w: int
+    chroma: str = '420'
+    out_chroma: Optional[str] = None
+    matrix: str = 'bt709'
+    full_range: bool = False
+    siting: str = 'left'
+    depth: int = 8
+    out_depth: Optional[int] = None
+
+    def __post_init__(self):
+        for name in ('h', 'w'):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 2:
+                raise ValueError(f'Yuv: {name} is an integer >= 2, got {v!r}')
+            object.__setattr__(self, name, int(v))
+        for name in ('chroma', 'out_chroma'):
+            v = getattr(self, name)
+            if name == 'out_chroma' and v is None:
+                continue
+            if not isinstance(v, str) or v not in L.YUV_CHROMA:
+                raise ValueError(f'Yuv: {name} is one of {sorted(L.YUV_CHROMA)}, got {v!r}')
+        if not isinstance(self.matrix, str) or self.matrix not in L.YUV_PLANAR_MATRIX:
+            raise ValueError(f'Yuv: matrix is one of {sorted(L.YUV_PLANAR_MATRIX)}, got {self.matrix!r}')
+        if not isinstance(self.siting, str) or self.siting not in L.YUV_SITING:
+            raise ValueError(f'Yuv: siting is one of {sorted(L.YUV_SITING)}, got {self.siting!r}')
+        if not isinstance(self.full_range, (bool, np.bool_)):
+            raise ValueError(f'Yuv: full_range is a bool, got {self.full_range!r}')
+        object.__setattr__(self, 'full_range', bool(self.full_range))
+        for name in ('depth', 'out_depth'):
+            v = getattr(self, name)
+            if name == 'out_depth' and v is None:
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v not in YUV_DEPTHS:
+                raise ValueError(f'Yuv: {name} is one of {YUV_DEPTHS}, got {v!r}')
+            object.__setattr__(self, name, int(v))
+
+    @property
+    def od(self):
+        """Bits per sample of the output: out_depth, or the input's."""
+        return self.depth if self.out_depth is None else self.out_depth
+
+    @property
+    def oc(self):
+        """Layout of the output: out_chroma, or the input's."""
+        return self.chroma if self.out_chroma is None else self.out_chroma
+
+    @property
+    def frame_bytes(self):
+        return yuv_frame_samples(self.h, self.w, self.chroma) * (2 if self.depth > 8 else 1)
+
+    def out_size_bytes(self, H, W):
+        """Bytes of an H x W output frame; ValueError where the output layout cannot hold that size (4:2:0: even sides,
+        4:2:2: an even width)."""
+        sx, sy = YUV_SUBSAMPLING[self.oc]
+        if H < 1 or W < 1 or H % sy or W % sx:
+            raise ValueError(f'Yuv: a 4:{self.oc[1]}:{self.oc[2]} output frame has '
+                             f'{"even sides" if sy == 2 else "an even width"}, got {H}x{W}')
+        return yuv_frame_samples(H, W, self.oc) * (2 if self.od > 8 else 1)
+
+    def out_frame_bytes(self, scale):
+        """Bytes of a super-resolved frame."""
+        if scale < 1:
+            raise ValueError(f'Yuv: scale {scale}')
+        return self.out_size_bytes(scale * self.h, scale * self.w)
+
+    def codes(self):
+        """(matrix, full_range, siting) as the C ABI takes them."""
+        return L.YUV_PLANAR_MATRIX[self.matrix], int(self.full_range), L.YUV_SITING[self.siting]
+
+
 @dataclass(frozen=True)
 class Png:
     """PNG output form of a stream (FRNet.infer_stream(png=...)): every super-resolved frame
@@ -346,6 +435,31 @@ def yuv420_planes(chunk, H, W, depth=8):
             chunk[..., H * W + ch * cw:].reshape(lead + (ch, cw)))
 
 
+def yuv_planes(chunk, H, W, chroma='420', depth=8):
+    """yuv420_planes for any of the three layouts: (Y, U, V) views of planar frames, U and V of ceil(H/sy) x ceil(W/sx)
+    with (sx, sy) = (2,2) '420', (2,1) '422', (1,1) '444'.  chunk (m, frame_bytes) or a single frame (frame_bytes,),
+    numpy or torch; nothing is copied.  depth above 8: the chunk holds 2-byte samples (uint8 as the stream yields it, or
+    uint16 already) and the views are uint16."""
+    if chroma not in YUV_SUBSAMPLING:
+        raise ValueError(f'yuv_planes: chroma is one of {sorted(YUV_SUBSAMPLING)}, got {chroma!r}')
+    if depth not in YUV_DEPTHS:
+        raise ValueError(f'yuv_planes: depth is one of {YUV_DEPTHS}, got {depth!r}')
+    sx, sy = YUV_SUBSAMPLING[chroma]
+    ch, cw = (H + sy - 1) // sy, (W + sx - 1) // sx
+    ns = H * W + 2 * ch * cw
+    if depth > 8 and chunk.dtype == (np.uint8 if isinstance(chunk, np.ndarray) else torch.uint8):
+        if chunk.shape[-1] != 2 * ns:
+            raise ValueError(f'yuv_planes: {H}x{W} {chroma} frames at {depth} bits have {2 * ns} bytes; '
+                             f'got shape {tuple(chunk.shape)}')
+        chunk = chunk.view(np.uint16 if isinstance(chunk, np.ndarray) else torch.uint16)
+    if chunk.shape[-1] != ns:
+        raise ValueError(f'yuv_planes: {H}x{W} {chroma} frames have {ns} samples; got shape {tuple(chunk.shape)}')
+    lead = tuple(chunk.shape[:-1])
+    return (chunk[..., :H * W].reshape(lead + (H, W)),
+            chunk[..., H * W:H * W + ch * cw].reshape(lead + (ch, cw)),
+            chunk[..., H * W + ch * cw:].reshape(lead + (ch, cw)))
+
+
 # -- the forms of a stream: each object owns its buffers and is the only place that knows their layout.  alloc(eng) runs
 # once, inside the engine's _open; the engine decides when every other method runs, and on which stream (see there).
 class _DeviceF32:
@@ -410,6 +524,9 @@ class _HostBytes:
 
 def _input_form(piece, c, yuv):
     """The input form of a stream, from its options and its first item (as stream_parts hands it out)."""
+    if isinstance(yuv, Yuv):
+        return _HostBytes(yuv.h, yuv.w, (yuv.frame_bytes,), 'tg_yuv_planar_to_rgb_f32',
+                          (yuv.h, yuv.w, L.YUV_CHROMA[yuv.chroma], yuv.depth, *yuv.codes()))
     if yuv is not None and yuv.depth > 8:
         return _HostBytes(yuv.h, yuv.w, (yuv.frame_bytes,), 'tg_yuv420p16_to_rgb_f32',
                           (yuv.h, yuv.w, yuv.depth, *yuv.codes()))
@@ -494,6 +611,42 @@ class _I420DeepOut:
 
     def result(self, sl, cnt):
         return self.host_out[sl, :cnt].numpy()
+
+
+class _YuvOut(_I420Out):
+    """Output form planar YUV at 8 bits in the layout yuv.oc: _I420Out with ONE
+    tg_rgb_u8_to_yuv_planar per batch and the layout's frame size."""
+
+    def alloc(self, eng):
+        ns, m, H, W = eng.out_u8.shape[:4]
+        self.lib, self.u8 = eng.lib, eng.out_u8
+        self.args = (H, W, L.YUV_CHROMA[self.yuv.oc], *self.yuv.codes(), eng.main.cuda_stream)
+        self.host_out = torch.empty(ns, m, self.yuv.out_size_bytes(H, W), dtype=torch.uint8, pin_memory=True)
+        self.yuv_out = torch.empty(tuple(self.host_out.shape), dtype=torch.uint8, device=eng.dev)
+
+    def encode(self, sl, cnt):
+        L.check(self.lib.tg_rgb_u8_to_yuv_planar(self.u8[sl].data_ptr(), self.yuv_out[sl].data_ptr(), cnt, *self.args),
+                'tg_rgb_u8_to_yuv_planar')
+
+
+class _YuvDeepOut(_I420DeepOut):
+    """Output form planar YUV at 10 or 12 bits in the layout yuv.oc: _I420DeepOut with ONE
+    tg_rgb_f32_to_yuv_planar16 behind every frame's SRNet launch."""
+
+    def alloc(self, eng):
+        ns, m, H, W = eng.u8.shape[:4]
+        self.fb = self.yuv.out_frame_bytes(eng.net.scale)
+        self.fn = eng.lib.tg_rgb_f32_to_yuv_planar16
+        self.args = (1, H, W, L.YUV_CHROMA[self.yuv.oc], self.yuv.od, *self.yuv.codes(), eng.main.cuda_stream)
+        self.host_out = torch.empty(ns, m, self.fb, dtype=torch.uint8, pin_memory=True)
+        self.yuv_out = torch.empty(ns, m, self.fb, dtype=torch.uint8, device=eng.dev)
+
+    def after(self, sl):
+        base, fb, fn, args = self.yuv_out[sl].data_ptr(), self.fb, self.fn, self.args
+
+        def convert(j, hr_addr):
+            L.check(fn(hr_addr, base + j * fb, *args), 'tg_rgb_f32_to_yuv_planar16')
+        return convert
 
 
 class _PngOut:
@@ -641,8 +794,8 @@ class _StreamEngine:
             if net.in_nc != 3:
                 raise ValueError(f'png needs RGB frames (in_nc = 3), this network has in_nc = {net.in_nc}')
         if yuv is not None:
-            if not isinstance(yuv, Yuv420):
-                raise ValueError(f'yuv must be a Yuv420 or None, got {type(yuv).__name__}')
+            if not isinstance(yuv, (Yuv420, Yuv)):
+                raise ValueError(f'yuv must be a Yuv420, a Yuv or None, got {type(yuv).__name__}')
             yuv.out_frame_bytes(net.scale)
         if scene_cut is not None:
             if not isinstance(scene_cut, SceneCut):
@@ -656,18 +809,23 @@ class _StreamEngine:
                 raise ValueError(f'resize must be a Resize or None, got {type(resize).__name__}')
             if net.in_nc != 3:
                 raise ValueError(f'resize needs RGB frames (in_nc = 3), this network has in_nc = {net.in_nc}')
-            if yuv is not None:
+            if isinstance(yuv, Yuv):
+                if yuv.od == 8:
+                    yuv.out_size_bytes(resize.h, resize.w)          # (per layout: 4:2:2 an even width, 4:4:4 any size)
+            elif yuv is not None:
                 if resize.h % 2 or resize.w % 2:
                     raise ValueError(f'resize: an I420 frame has even sides, got {resize.h}x{resize.w}')
+            if yuv is not None:
                 if yuv.od > 8:
                     raise ValueError(f'infer_stream: resize works on the 8-bit frames and cannot be combined with '
                                      f'out_depth = {yuv.od}; resize needs an 8-bit output')
                 resize.check_source(net.scale * yuv.h, net.scale * yuv.w)
         # the forms: the output and the scene-cut slots follow from the options, the input from the first item as well
         self.inp, self.input_form = None, lambda piece: _input_form(piece, net.in_nc, yuv)
-        self.deep = _I420DeepOut(yuv) if yuv is not None and yuv.od > 8 else None    # (the one form with a per-frame hook)
+        planar = isinstance(yuv, Yuv)               # (a Yuv420 keeps its own launches)
+        self.deep = None if yuv is None or yuv.od == 8 else _YuvDeepOut(yuv) if planar else _I420DeepOut(yuv)   # (per-frame hook)
         self.out = _PngOut(png) if png is not None else self.deep if self.deep is not None else \
-            _I420Out(yuv) if yuv is not None else _RgbOut()
+            _YuvOut(yuv) if planar else _I420Out(yuv) if yuv is not None else _RgbOut()
         self.cut = _CutSlots(scene_cut) if scene_cut is not None else None
         self.rsz = _ResizedFrames(resize) if resize is not None else None
         self.net, self.on_fault, self.parts = net, on_fault, stream_parts(frames, net.in_nc, yuv)

@@ -22,7 +22,7 @@ from ...utils.net_utils import get_upsampling_func
 from .frnet_infer import (FNET_FIRST_PASS_FRAMES, _SIDE_STREAMS, _StepPlan, _norm_device, clip_batches,  # noqa: F401
                           enqueue_batch, side_stream, stream_batch_sizes)
 from .stream import (STREAM_SLOTS, Png, Resize, SceneCut, StreamFormat, StreamRing, Yuv420, _StreamEngine, stream_frames,  # noqa: F401
-                     stream_frames_yuv, stream_parts, stream_rebatch, yuv420_planes)
+                     stream_frames_yuv, stream_parts, stream_rebatch, yuv420_planes, Yuv, yuv_planes)
 
 
 class _Conv(nn.Module):
@@ -464,6 +464,16 @@ class FRNet(nn.Module):
         uint8 views hold 2-byte samples (yuv420_planes(chunk, H, W, depth) views them as uint16): the bytes are
         ops.rgb_f32_to_yuv420p of the float frames.  The two depths combine freely; at 8 and 8 the stream enqueues
         exactly what it always did.  `resize` together with an output above 8 bits is a ValueError.
+
+        yuv: a Yuv(h, w, chroma, out_chroma, matrix, full_range, siting, depth, out_depth) is raw video in any of the
+        three planar layouts '420' | '422' | '444' each way, with the matrices 'bt601' | 'bt709' | 'bt2020' (DESIGN.md
+        section 7l); a Yuv420 enqueues exactly what it always did.  A Yuv always takes the planar launches, in the same
+        places: tg_yuv_planar_to_rgb_f32 writes the LR slot; an 8-bit output is ONE tg_rgb_u8_to_yuv_planar per batch,
+        the bytes of ops.rgb_to_yuv of the RGB frames; an output above 8 bits is ONE tg_rgb_f32_to_yuv_planar16 behind
+        every frame's SRNet launch, the words of ops.rgb_f32_to_yuv of the float frames.  yuv_planes(chunk, H, W, chroma,
+        depth) splits a chunk.  The layouts and depths of the two sides combine freely: a 4:2:0 clip can leave as 4:4:4,
+        which keeps the chroma the network computed.  `resize` with an 8-bit 4:2:2 output needs an even width, with
+        4:2:0 even sides, with 4:4:4 nothing; with an output above 8 bits it stays a ValueError.
 
         scene_cut: a SceneCut(mad, hist, detect, at, keep_scores) restarts the recurrence at scene cuts, decided on the
         device; without one the stream enqueues exactly what it always did.  For every batch

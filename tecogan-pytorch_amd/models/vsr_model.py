@@ -98,7 +98,8 @@ class VSRModel(BaseModel):
         (h,w,3) or float32 (3,h,w); yields (m,H,W,3) uint8 chunks -- views of the generator's pinned ring, valid until
         the next one is asked for.  The temporal padding of the front (test.padding_mode / num_pad_front) is applied
         lazily: the first n_pad + 1 frames are buffered, the padded prefix runs first, its n_pad outputs are dropped.
-        yuv (a Yuv420): the items are I420 frames or chunks of them and (m, out_frame_bytes) I420 chunks are yielded.
+        yuv (a Yuv420, or a Yuv for 4:2:2 / 4:4:4 / BT.2020): the items are planar YUV frames or chunks of them and
+        (m, out_frame_bytes) chunks of such frames are yielded.
         png (a Png): lists of 1-D uint8 views are yielded, each view one complete PNG file (not together with yuv).
         scene_cut (a SceneCut): the recurrence restarts at scene cuts (FRNet.infer_stream).  Its `at`, `cuts` and
         `scores` are in the numbering of `frames`: the padded stream runs a shifted copy, and what that finds inside

@@ -573,6 +573,90 @@ def rgb_f32_to_yuv420p(rgb_chw, depth, matrix='bt709', full_range=False, siting=
     return out
 
 
+# -- planar YUV 4:2:0 | 4:2:2 | 4:4:4 at 8 | 10 | 12 bits, BT.601 | BT.709 | BT.2020 ----------------
+YUV_SUBSAMPLING = {'420': (2, 2), '422': (2, 1), '444': (1, 1)}     # chroma -> (sx, sy)
+
+
+def _yuv_planar_codes(chroma, matrix, full_range, siting, what):
+    """Names -> the C enums of the planar entry points; integers pass through (the library refuses an unknown one)."""
+    for name, val, table in (('chroma', chroma, L.YUV_CHROMA), ('matrix', matrix, L.YUV_PLANAR_MATRIX),
+                             ('siting', siting, L.YUV_SITING)):
+        if isinstance(val, str) and val not in table:
+            raise L.TecoganHipError(f'{what}: {name} is one of {sorted(table)}, got {val!r}')
+    return (L.YUV_CHROMA[chroma] if isinstance(chroma, str) else int(chroma),
+            L.YUV_PLANAR_MATRIX[matrix] if isinstance(matrix, str) else int(matrix), int(full_range),
+            L.YUV_SITING[siting] if isinstance(siting, str) else int(siting))
+
+
+def yuv_frame_samples(h, w, chroma='420'):
+    """Samples of one planar frame: Y h*w, then U and V of ceil(h/sy) x ceil(w/sx); chroma '420' | '422' | '444'."""
+    if chroma not in YUV_SUBSAMPLING:
+        raise L.TecoganHipError(f'yuv_frame_samples: chroma is one of {sorted(YUV_SUBSAMPLING)}, got {chroma!r}')
+    sx, sy = YUV_SUBSAMPLING[chroma]
+    return h * w + 2 * ((h + sy - 1) // sy) * ((w + sx - 1) // sx)
+
+
+def yuv_to_rgb(yuv, h, w, chroma='420', depth=8, matrix='bt709', full_range=False, siting='left', out=None):
+    """(n, frame_samples) / (frame_samples,) planar YUV frames on device -- uint8 at depth 8, uint16 at 10 | 12 --
+    -> (n,3,h,w) fp32 RGB in [0,1] (tg_yuv_planar_to_rgb_f32).  chroma '420' | '422' | '444',
+    matrix 'bt601' | 'bt709' | 'bt2020'.  out: a contiguous CUDA float32 (n,3,h,w) tensor to write into."""
+    if isinstance(depth, bool) or not isinstance(depth, int):
+        raise L.TecoganHipError(f'yuv_to_rgb: depth is 8, 10 or 12, got {depth!r}')
+    _chk(yuv, 'yuv', torch.uint8 if depth == 8 else torch.uint16)
+    c, m, r, s = _yuv_planar_codes(chroma, matrix, full_range, siting, 'yuv_to_rgb')
+    if yuv.dim() == 1:
+        yuv = yuv.unsqueeze(0)
+    chroma = {v: k for k, v in L.YUV_CHROMA.items()}.get(c)          # (None: the library refuses it before any access)
+    if chroma is not None and (yuv.dim() != 2 or yuv.shape[1] != yuv_frame_samples(h, w, chroma)):
+        raise L.TecoganHipError(f'yuv_to_rgb: {h}x{w} {chroma} frames have {yuv_frame_samples(h, w, chroma)} samples; '
+                                f'got shape {tuple(yuv.shape)}')
+    n = yuv.shape[0]
+    if out is None:
+        out = torch.empty(n, 3, h, w, dtype=torch.float32, device=yuv.device)
+    elif _chk(out, 'out').shape != (n, 3, h, w):
+        raise L.TecoganHipError(f'yuv_to_rgb: out is ({n},3,{h},{w}), got shape {tuple(out.shape)}')
+    L.check(L.lib().tg_yuv_planar_to_rgb_f32(_ptr(yuv), _ptr(out), n, h, w, c, depth, m, r, s, _stream()),
+            'tg_yuv_planar_to_rgb_f32')
+    return out
+
+
+def rgb_to_yuv(rgb_hwc, chroma='420', matrix='bt709', full_range=False, siting='left'):
+    """(n,H,W,3) uint8 RGB on device -> (n, frame_samples) uint8 planar YUV frames, exact integer arithmetic
+    (tg_rgb_u8_to_yuv_planar).  '420': H and W even; '422': W even; '444': any size."""
+    _chk_u8(rgb_hwc, 'rgb')
+    if rgb_hwc.dim() != 4 or rgb_hwc.shape[3] != 3:
+        raise L.TecoganHipError(f'rgb_to_yuv: expected (n,H,W,3), got shape {tuple(rgb_hwc.shape)}')
+    c, m, r, s = _yuv_planar_codes(chroma, matrix, full_range, siting, 'rgb_to_yuv')
+    if not isinstance(chroma, str):
+        raise L.TecoganHipError(f'rgb_to_yuv: chroma is one of {sorted(L.YUV_CHROMA)}, got {chroma!r}')
+    n, H, W, _ = rgb_hwc.shape
+    out = torch.empty(n, yuv_frame_samples(H, W, chroma), dtype=torch.uint8, device=rgb_hwc.device)
+    L.check(L.lib().tg_rgb_u8_to_yuv_planar(_ptr(rgb_hwc), _ptr(out), n, H, W, c, m, r, s, _stream()),
+            'tg_rgb_u8_to_yuv_planar')
+    return out
+
+
+def rgb_f32_to_yuv(rgb_chw, chroma='420', depth=10, matrix='bt709', full_range=False, siting='left', out=None):
+    """(n,3,H,W) float32 RGB on device -> (n, frame_samples) uint16 planar YUV frames at `depth` (10 | 12) bits: one
+    fp32 step to 16-bit integers, then exact integer arithmetic (tg_rgb_f32_to_yuv_planar16).
+    The sizes of rgb_to_yuv.  out: a contiguous CUDA uint16 (n, frame_samples) tensor to write into."""
+    _chk(rgb_chw, 'rgb')
+    if rgb_chw.dim() != 4 or rgb_chw.shape[1] != 3:
+        raise L.TecoganHipError(f'rgb_f32_to_yuv: expected (n,3,H,W), got shape {tuple(rgb_chw.shape)}')
+    c, m, r, s = _yuv_planar_codes(chroma, matrix, full_range, siting, 'rgb_f32_to_yuv')
+    if not isinstance(chroma, str):
+        raise L.TecoganHipError(f'rgb_f32_to_yuv: chroma is one of {sorted(L.YUV_CHROMA)}, got {chroma!r}')
+    n, _, H, W = rgb_chw.shape
+    ns = yuv_frame_samples(H, W, chroma)
+    if out is None:
+        out = torch.empty(n, ns, dtype=torch.uint16, device=rgb_chw.device)
+    elif _chk(out, 'out', torch.uint16).shape != (n, ns):
+        raise L.TecoganHipError(f'rgb_f32_to_yuv: out is ({n}, {ns}), got shape {tuple(out.shape)}')
+    L.check(L.lib().tg_rgb_f32_to_yuv_planar16(_ptr(rgb_chw), _ptr(out), n, H, W, c, _chk_depth(depth, 'rgb_f32_to_yuv'),
+                                               m, r, s, _stream()), 'tg_rgb_f32_to_yuv_planar16')
+    return out
+
+
 def png_encode(rgb_hwc, filter='adaptive'):
     """(n,H,W,3) / (H,W,3) uint8 RGB on device -> a list of n host `bytes`, each one complete PNG file, encoded on
     the device (tg_png_encode_u8): filter 'adaptive' | 'none', Huffman-only deflate in segments

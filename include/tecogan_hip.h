@@ -1155,8 +1155,11 @@ int tg_frnet_plan_chain_rearms(const tg_frnet_plan* plan, int* rearms, int* curr
  * are being repaired.  hold = 0 resumes the count where it stood.  No effect on a plan whose body is in use. */
 int tg_frnet_plan_hold_chain_rearm(tg_frnet_plan* plan, int hold);
 /* hr_out may alias nothing else; lr_curr/lr_prev (n,c,h,w), hr_prev/hr_out (n,c,s*h,s*w).
- * u8_out (optional): (n, s*h, s*w, c) uint8 quantised frames (n > 1 needs the fused HR stage:
- * out_nc <= 3, nf <= 64). */
+ * c = in_nc = out_nc = 3: the frame is the next call's hr_prev, and the output conv adds the up-sampled lr_curr
+ * channel by channel, so tg_frnet_workspace_floats returns 0 and tg_frnet_plan_create TG_E_SHAPE for out_nc != in_nc.
+ * u8_out (optional): (n, s*h, s*w, c) uint8 quantised frames (n > 1 needs the fused HR stage, which every
+ * fp32 plan runs unless the lab switch TG_HR_FUSE=0 selects the unfused launches; the fp16 body at 2x ends in
+ * the unfused one and takes n == 1 only). */
 int tg_frnet_step(tg_frnet_plan* plan, const float* lr_curr, const float* lr_prev,
                   const float* hr_prev, float* hr_out, uint8_t* u8_out,
                   tg_stream_t stream);

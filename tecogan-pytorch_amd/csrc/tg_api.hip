@@ -168,8 +168,11 @@ static void carve(const tg_frnet_cfg* c, size_t off[15]) {
   off[1] = o; o += sr * align64(n * 64 * hw);                  // B
   off[2] = o; o += align64(n * 2 * hw);                        // FLOW
   off[3] = o; o += sr * align64(n * c->scale * c->scale * c->in_nc * hw);  // S2D
-  off[4] = o; o += sr * align64(n * c->nf * 4 * hw);           // U1
-  off[5] = o; o += (c->scale == 4) ? sr * align64(n * c->nf * 16 * hw) : 0;  // U2
+  // the fused HR stage never writes the last nf-channel tensor: its region (U2 at 4x, U1 at 2x) holds the 9 * out_nc tap
+  // planes of conv_out at a batch stride of 32 planes, whatever nf is
+  const size_t zc = c->nf < 32 ? 32 : c->nf;
+  off[4] = o; o += sr * align64(n * (c->scale == 4 ? c->nf : zc) * 4 * hw);  // U1
+  off[5] = o; o += (c->scale == 4) ? sr * align64(n * zc * 16 * hw) : 0;  // U2
   off[6] = o; o += sr * align64(fnet_partial_floats(c));       // PART (split-K partial sums, SRNet)
   off[7] = o; o += align64(n * 64 * hw);                       // FA   (FNet ping)
   off[8] = o; o += align64(n * 64 * hw);                       // FB   (FNet pong)
@@ -186,8 +189,11 @@ static void carve(const tg_frnet_cfg* c, size_t off[15]) {
   off[14] = o;
 }
 
+// out_nc == in_nc: the frame is fed back as hr_prev (read as in_nc channels), and the output conv adds the up-sampled
+// lr_curr, which the small-cout kernel and the tail index with out_nc channels per image (tecogan_nets.py:145, :250
+// need the same) -- out_nc = 4 would read past lr_curr, out_nc < 3 the wrong image of a batch.
 static int cfg_ok(const tg_frnet_cfg* c) {
-  return c && c->in_nc == 3 && c->out_nc >= 1 && c->out_nc <= 4 && c->nf >= 1 && c->nf <= 64 &&
+  return c && c->in_nc == 3 && c->out_nc == c->in_nc && c->nf >= 1 && c->nf <= 64 &&
          c->nb >= 0 && (c->scale == 2 || c->scale == 4) &&
          (c->up_mode == TG_UP_BICUBIC || c->up_mode == TG_UP_BILINEAR) && c->n >= 1 &&
          c->h >= 8 && c->w >= 8;
@@ -204,7 +210,7 @@ extern "C" int tg_frnet_plan_create(const tg_frnet_cfg* cfg, const tg_layer_weig
                                     int n_layers, float* workspace, tg_frnet_plan** out) {
   TG_REQUIRE(cfg && layers && workspace && out, TG_E_ARG, "frnet_plan_create: null pointer");
   TG_REQUIRE(cfg_ok(cfg), TG_E_SHAPE,
-             "frnet_plan_create: unsupported cfg (in_nc=3, out_nc<=4, nf<=64, scale 2|4, h,w>=8)");
+             "frnet_plan_create: unsupported cfg (in_nc=3, out_nc=in_nc, nf<=64, scale 2|4, h,w>=8)");
   int nup = cfg->scale == 4 ? 2 : 1;
   int need = 14 + 1 + 2 * cfg->nb + nup + 1;
   TG_REQUIRE(n_layers == need, TG_E_ARG, "frnet_plan_create: %d layers given, %d expected",
@@ -314,7 +320,7 @@ static bool resident_wanted(bool layer_prefers_wino) {
 // the fused tail writes (n, H, W, c) uint8 frames for any n; the unfused quantise pass only n == 1
 static bool plan_u8_ok(const tg_frnet_plan* p) {
   if (p->f16 && p->cfg.scale == 2) return p->cfg.n == 1;      // (the fp16 body ends in the unfused HR stage at 2x)
-  return p->cfg.n == 1 || (hr_fuse_enabled() && p->cfg.out_nc <= 3 && p->cfg.nf <= 64);
+  return p->cfg.n == 1 || hr_fuse_enabled();                  // (cfg_ok: out_nc == 3, nf <= 64)
 }
 
 static int step_impl(tg_frnet_plan* p, const float* lr_curr, const float* lr_prev,
@@ -580,7 +586,7 @@ static int step_impl(tg_frnet_plan* p, const float* lr_curr, const float* lr_pre
     }
   }
   // (at 2x the fused HR stage IS the first up-sampling layer: the fp16 body then ends in the unfused output conv)
-  const bool fuse = hr_fuse_enabled() && c.out_nc <= 3 && nf <= 64 && !(p->f16 && s == 2);
+  const bool fuse = hr_fuse_enabled() && !(p->f16 && s == 2);  // (cfg_ok: out_nc == 3, nf <= 64)
   const tg_layer_weights lw_up1 = p->L[li++];
   const tg_layer_weights lw_up2 = s == 4 ? p->L[li++] : tg_layer_weights{nullptr, nullptr, nullptr};
   const tg_layer_weights lw_out = p->L[li++];

@@ -164,6 +164,24 @@ def test_error_codes_not_exceptions():
     assert lib.tg_frnet_workspace_floats(ctypes.byref(ok)) > 64 * 16 * 134 * 320
 
 
+@pytest.mark.parametrize('out_nc', [1, 2, 4])
+def test_frame_plan_refuses_out_nc_other_than_in_nc(out_nc):
+    """The frame is fed back as hr_prev (in_nc channels) and the output conv adds the up-sampled lr_curr with out_nc
+    channels per image: neither the size query nor plan creation admits out_nc != in_nc (nothing is allocated or run)."""
+    lib = L.lib()
+    bad = L.FrnetCfg(3, out_nc, 64, 10, 4, 1, 1, 134, 320)
+    assert lib.tg_frnet_workspace_floats(ctypes.byref(bad)) == 0
+    assert lib.tg_frnet_f16_workspace_bytes(ctypes.byref(bad)) == 0
+    nl = 14 + 1 + 20 + 2 + 1
+    dummy = (ctypes.c_float * 16)()
+    arr = (L.LayerWeights * nl)()
+    for i in range(nl):
+        arr[i].w = arr[i].b = ctypes.addressof(dummy)
+    hnd = ctypes.c_void_p()
+    rc = lib.tg_frnet_plan_create(ctypes.byref(bad), arr, nl, ctypes.addressof(dummy), ctypes.byref(hnd))
+    assert rc == -1 and b'out_nc=in_nc' in lib.tg_last_error_string() and not hnd.value          # TG_E_SHAPE
+
+
 def test_ops_refuse_cpu_tensors():
     from tecogan_pytorch_amd import ops
     with pytest.raises(L.TecoganHipError):

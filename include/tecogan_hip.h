@@ -632,7 +632,8 @@ int tg_rgb_f32_to_yuv_planar16(const float* rgb_chw, uint16_t* yuv, int n, int H
  * equal: 8-bit RGB, no interlace, one IDAT; per row the filter type (adaptive: the one of None, Sub, Up, Average,
  * Paeth with the smallest sum of |int8(byte)|, the lowest on a tie; none: type 0); the filtered stream in segments of
  * 32768 bytes, each deflated on its own with Huffman codes only (a dynamic block and an empty stored block, or one
- * stored block when that is not larger).  No LZ77 matches, so files are larger than zlib's.
+ * stored block when that is not larger).  No LZ77 matches, so files are larger than zlib's (tg_png_encode_lz_u8 below
+ * adds them).
  *   rgb_hwc (n,h,w,3) uint8.  Frame k's complete file starts at out + k * out_stride (any alignment), its length goes
  *   to sizes[k] (8-byte aligned); bytes past it inside the stride are unspecified, bytes outside
  *   [out, out + n * out_stride) are never written.  out_stride is at least tg_png_capacity(h, w), the bytes a frame
@@ -645,6 +646,22 @@ int64_t tg_png_capacity(int h, int w);
 int64_t tg_png_workspace_bytes(int n, int h, int w);
 int tg_png_encode_u8(const uint8_t* rgb_hwc, int n, int h, int w, int filter, uint8_t* out, int64_t out_stride,
                      int64_t* sizes, void* workspace, tg_stream_t stream);
+
+/* The same files with LZ77 matches; the specification is tests/png_lz_ref.py and the bytes are
+ * equal.  File layout, filtering, segments, checksums and tg_png_capacity are tg_png_encode_u8's; only a segment's
+ * deflate differs.  The segment is its own window: per position the up to 4 nearest earlier positions with the same
+ * 16-bit hash of their four bytes are compared, the longest match (at most 258 bytes, the nearest on a tie) is taken
+ * if it has 4 bytes or more (exactly 4 only up to distance 4096), the parse is greedy, and the segment is written as
+ * the smallest of one stored block, tg_png_encode_u8's Huffman-only block and the LZ block (a dynamic block with
+ * literal/length and distance codes plus the empty stored block), the earlier one on a tie.  So no file is longer
+ * than tg_png_encode_u8's, and a frame without a match is the same file.
+ *   Arguments, placement rules and error codes are tg_png_encode_u8's; workspace: at least
+ *   tg_png_lz_workspace_bytes(n, h, w) bytes, any alignment: 256 KiB more per segment (the sorted keys, later the
+ *   tokens, and the matches), about 5 times tg_png_workspace_bytes -- 165 MB against 33 MB for 8 frames of 536x1280.
+ *   Eight launches on `stream`, ordered by the stream alone. */
+int64_t tg_png_lz_workspace_bytes(int n, int h, int w);
+int tg_png_encode_lz_u8(const uint8_t* rgb_hwc, int n, int h, int w, int filter, uint8_t* out, int64_t out_stride,
+                        int64_t* sizes, void* workspace, tg_stream_t stream);
 
 /* Scene cuts of FRNet.infer_stream, decided on the device; the reference has no counterpart (its
  * test sets are single-shot clips).  The formula is the specification, tests/scene_cut_ref.py restates it in numpy and

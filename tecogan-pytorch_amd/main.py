@@ -112,6 +112,9 @@ def parse_args(argv=None):
                    help='--mode infer into a PNG folder: pillow (default) encodes on writer threads with zlib; device '
                         'encodes on the GPU (DESIGN.md section 7i: Huffman-only deflate, larger files, no host codec on '
                         'the output side).  Not for y4m output')
+    p.add_argument('--png-lz77', dest='png_lz77', action='store_true',
+                   help='--png-encoder device: LZ77 matches inside every 32 KiB segment (DESIGN.md section 7n): smaller '
+                        'files, never larger than without it, at a lower frame rate')
     p.add_argument('--output-size', dest='output_size', type=output_size_arg, default=None, metavar='WxH',
                    help='--mode infer: deliver every frame at W x H, resized on the GPU behind the generator (DESIGN.md '
                         'section 7j: antialiased bicubic, exact integers); each side within [1/4, 4] of the super-resolved '
@@ -130,6 +133,8 @@ def parse_args(argv=None):
         p.error('--output-size resizes the 8-bit frames; it cannot be combined with --output-depth above 8')
     if args.png_encoder == 'device' and args.input and (args.input == '-' or os.path.isfile(args.input)):
         p.error('--png-encoder device writes PNG folders; y4m input is written as y4m')
+    if args.png_lz77 and args.png_encoder != 'device':
+        p.error('--png-lz77 belongs to --png-encoder device')
     return args
 
 
@@ -421,19 +426,22 @@ def resize_option(output_size):
     return Resize(output_size[1], output_size[0])
 
 
-def infer(opt, input_dir, output_dir, scene_cut=None, png_encoder='pillow', output_size=None):
+def infer(opt, input_dir, output_dir, scene_cut=None, png_encoder='pillow', output_size=None, png_lz77=False):
     """--mode infer: every sequence of input_dir through VSRModel.infer_stream.  Frames are decoded one by one as the
     stream asks for them; the writers copy each frame out of the yielded ring slot before the generator is advanced.
     scene_cut (a SceneCut): passed on for every sequence, its cuts logged to stderr.  png_encoder 'device': the stream
     yields finished PNG files (infer_stream(png=Png())) and a writer copies one out of the slot and writes it as it
     is; 'pillow': the writers encode the RGB frames.  output_size (w, h): the frames are resized to it on the device
-    (infer_stream(resize=Resize(h, w))), whichever encoder writes them.  Returns {sequence: frames written}."""
+    (infer_stream(resize=Resize(h, w))), whichever encoder writes them.  png_lz77: the device encoder's LZ77 mode
+    (Png(lz77=True)).  Returns {sequence: frames written}."""
     import threading
     from concurrent.futures import ThreadPoolExecutor
     from PIL import Image
     from .data.folder_dataset import read_rgb
     if png_encoder not in ('pillow', 'device'):
         raise ValueError(f"png_encoder is 'pillow' or 'device', got {png_encoder!r}")
+    if png_lz77 and png_encoder != 'device':
+        raise ValueError("png_lz77 belongs to png_encoder 'device'")
     seqs = infer_sequences(input_dir)
     if not seqs:
         raise ValueError(f'--input {input_dir}: no png | jpg frames, directly or one level down')
@@ -441,7 +449,7 @@ def infer(opt, input_dir, output_dir, scene_cut=None, png_encoder='pillow', outp
     kw = {} if scene_cut is None else {'scene_cut': scene_cut}
     if png_encoder == 'device':
         from .models.networks import Png
-        kw['png'] = Png()
+        kw['png'] = Png(lz77=bool(png_lz77))
     if output_size is not None:
         kw['resize'] = resize_option(output_size)
     done = {}
@@ -660,7 +668,7 @@ def main(argv=None):
             infer_y4m_cli(opt, args.input, args.output, args.yuv_matrix, args.yuv_range, scene_cut_option(args),
                           args.output_size, args.yuv_siting, args.output_depth, args.output_chroma)
         else:
-            infer(opt, args.input, args.output, scene_cut_option(args), args.png_encoder, args.output_size)
+            infer(opt, args.input, args.output, scene_cut_option(args), args.png_encoder, args.output_size, args.png_lz77)
     elif args.mode == 'profile':
         profile(opt, tuple(int(v) for v in args.lr_size.split('x')), args.test_speed)
     else:

@@ -315,12 +315,22 @@ class Png:
     """PNG output form of a stream (FRNet.infer_stream(png=...)): every super-resolved frame
     leaves the device as one complete 8-bit RGB PNG file, encoded there by tg_png_encode_u8.  filter 'adaptive' (per
     row the type with the smallest sum of |int8(byte)|) | 'none' (type 0 on every row).  Huffman-only deflate: the
-    files are larger than zlib's.  Frozen."""
+    files are larger than zlib's.  lz77=True: tg_png_encode_lz_u8 instead, LZ77 matches inside
+    every 32 KiB segment; no file is larger than without it, and the encoder takes longer.  Frozen."""
     filter: str = 'adaptive'
+    lz77: bool = False
 
     def __post_init__(self):
         if not isinstance(self.filter, str) or self.filter not in L.PNG_FILTER:
             raise ValueError(f'Png: filter is one of {sorted(L.PNG_FILTER)}, got {self.filter!r}')
+        if not isinstance(self.lz77, (bool, np.bool_)):
+            raise ValueError(f'Png: lz77 is True or False, got {self.lz77!r}')
+        object.__setattr__(self, 'lz77', bool(self.lz77))
+
+    def entry(self):
+        """(encoder, its workspace query) as the C ABI names them."""
+        return ('tg_png_encode_lz_u8', 'tg_png_lz_workspace_bytes') if self.lz77 else \
+            ('tg_png_encode_u8', 'tg_png_workspace_bytes')
 
     def code(self):
         """The filter as the C ABI takes it."""
@@ -652,7 +662,8 @@ class _YuvDeepOut(_I420DeepOut):
 class _PngOut:
     """Output form PNG.  A slot, on the device and pinned, is m int64 file sizes followed by m
     regions of png_stride bytes (tg_png_capacity rounded up to 8), file k from the first byte of region k: the layout is
-    defined here and nowhere else.  ONE tg_png_encode_u8 writes a batch's files and sizes; the sizes and the first cnt
+    defined here and nowhere else.  ONE tg_png_encode_u8 (tg_png_encode_lz_u8 for Png(lz77=True), section 7n, with its own
+    workspace size) writes a batch's files and sizes; the sizes and the first cnt
     regions come down; the chunk is a list of views cut from the pinned slot by the sizes.  The encoder's workspace is
     one for all slots: every call is on the caller's stream."""
 
@@ -665,7 +676,9 @@ class _PngOut:
 
     def alloc(self, eng):
         ns, m, H, W = eng.out_u8.shape[:4]
-        cap, wsb = eng.lib.tg_png_capacity(H, W), eng.lib.tg_png_workspace_bytes(m, H, W)
+        self.fn_name, ws_name = self.png.entry()
+        self.fn = getattr(eng.lib, self.fn_name)
+        cap, wsb = eng.lib.tg_png_capacity(H, W), getattr(eng.lib, ws_name)(m, H, W)
         if cap < 0 or wsb < 0:
             L.check(L.TG_E_SHAPE, 'tg_png_capacity')
         self.layout(m, cap)
@@ -676,8 +689,8 @@ class _PngOut:
 
     def encode(self, sl, cnt):
         base = self.png_out[sl].data_ptr()
-        L.check(self.lib.tg_png_encode_u8(self.u8[sl].data_ptr(), cnt, *self.size, self.png.code(), base + self.files_at,
-                                          self.png_stride, base, self.png_ws.data_ptr(), self.stream), 'tg_png_encode_u8')
+        L.check(self.fn(self.u8[sl].data_ptr(), cnt, *self.size, self.png.code(), base + self.files_at, self.png_stride,
+                        base, self.png_ws.data_ptr(), self.stream), self.fn_name)
 
     def download(self, sl, cnt):
         used = self.files_at + cnt * self.png_stride

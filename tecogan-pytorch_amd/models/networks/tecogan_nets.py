@@ -489,7 +489,8 @@ class FRNet(nn.Module):
         tg_png_encode_u8 call on the caller's stream writes the batch's files and their sizes into the slot's buffer,
         which comes down in place of the RGB frames.  The generator yields, per batch, a LIST of 1-D uint8 views, one
         file each, valid until it is advanced: the bytes are ops.png_encode of the frames the stream yields without
-        `png`.  A repaired batch is encoded again with it.
+        `png`.  A repaired batch is encoded again with it.  Png(filter, lz77=True) calls tg_png_encode_lz_u8 instead
+        (section 7n): LZ77 matches inside a segment, the bytes of ops.png_encode(..., lz77=True), no file larger.
 
         resize: a Resize(h, w) delivers every frame at h x w in place of s*h x s*w; without it
         the stream enqueues exactly what it always did.  One more uint8 ring of h x w frames is allocated, and after a

@@ -100,7 +100,8 @@ class VSRModel(BaseModel):
         lazily: the first n_pad + 1 frames are buffered, the padded prefix runs first, its n_pad outputs are dropped.
         yuv (a Yuv420, or a Yuv for 4:2:2 / 4:4:4 / BT.2020): the items are planar YUV frames or chunks of them and
         (m, out_frame_bytes) chunks of such frames are yielded.
-        png (a Png): lists of 1-D uint8 views are yielded, each view one complete PNG file (not together with yuv).
+        png (a Png): lists of 1-D uint8 views are yielded, each view one complete PNG file (not together with yuv);
+        Png(lz77=True) makes them smaller and the stream slower.
         scene_cut (a SceneCut): the recurrence restarts at scene cuts (FRNet.infer_stream).  Its `at`, `cuts` and
         `scores` are in the numbering of `frames`: the padded stream runs a shifted copy, and what that finds inside
         the padded prefix is dropped.  Known limit: the front padding is NOT repeated after a cut -- a new shot starts

@@ -657,11 +657,14 @@ def rgb_f32_to_yuv(rgb_chw, chroma='420', depth=10, matrix='bt709', full_range=F
     return out
 
 
-def png_encode(rgb_hwc, filter='adaptive'):
+def png_encode(rgb_hwc, filter='adaptive', lz77=False):
     """(n,H,W,3) / (H,W,3) uint8 RGB on device -> a list of n host `bytes`, each one complete PNG file, encoded on
     the device (tg_png_encode_u8): filter 'adaptive' | 'none', Huffman-only deflate in segments
-    of 32768 bytes, the bytes of tests/png_ref.py.  Synchronises: for tools and tests; a stream writes files through
-    FRNet.infer_stream(png=...)."""
+    of 32768 bytes, the bytes of tests/png_ref.py.  lz77=True: tg_png_encode_lz_u8 (section 7n), LZ77 matches inside a
+    segment, the bytes of tests/png_lz_ref.py, never more than without it.  Synchronises: for tools and tests; a
+    stream writes files through FRNet.infer_stream(png=...)."""
+    if not isinstance(lz77, bool):
+        raise L.TecoganHipError(f'png_encode: lz77 is True or False, got {lz77!r}')
     _chk_u8(rgb_hwc, 'rgb')
     if rgb_hwc.dim() == 3:
         rgb_hwc = rgb_hwc.unsqueeze(0)
@@ -672,14 +675,15 @@ def png_encode(rgb_hwc, filter='adaptive'):
     code = L.PNG_FILTER[filter] if isinstance(filter, str) else int(filter)
     n, H, W, _ = rgb_hwc.shape
     lib, dev = L.lib(), rgb_hwc.device
-    cap, wsb = lib.tg_png_capacity(H, W), lib.tg_png_workspace_bytes(n, H, W)
+    name, ws_name = ('tg_png_encode_lz_u8', 'tg_png_lz_workspace_bytes') if lz77 else \
+        ('tg_png_encode_u8', 'tg_png_workspace_bytes')
+    cap, wsb = lib.tg_png_capacity(H, W), getattr(lib, ws_name)(n, H, W)
     if cap < 0 or wsb < 0:
         L.check(L.TG_E_SHAPE, 'tg_png_capacity')
     out = torch.empty(n, cap, dtype=torch.uint8, device=dev)
     sizes = torch.empty(n, dtype=torch.int64, device=dev)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    L.check(lib.tg_png_encode_u8(_ptr(rgb_hwc), n, H, W, code, _ptr(out), cap, _ptr(sizes), _ptr(ws), _stream()),
-            'tg_png_encode_u8')
+    L.check(getattr(lib, name)(_ptr(rgb_hwc), n, H, W, code, _ptr(out), cap, _ptr(sizes), _ptr(ws), _stream()), name)
     sizes, out = sizes.cpu().tolist(), out.cpu().numpy()
     return [out[k, :sizes[k]].tobytes() for k in range(n)]
 

@@ -599,8 +599,9 @@ int tg_rgb_f32_to_yuv420p16(const float* rgb_chw, uint16_t* yuv, int n, int H, i
  * (1,1) (444), tightly packed; a sample is a byte at depth 8 and a 16-bit little-endian word above it (one above
  * 2^depth - 1 is read as 2^depth - 1).  matrix, full_range and siting are the enums above, plus TG_YUV_BT2020
  * (non-constant luminance: Kr, Kb = 0.2627, 0.0593), which ONLY the three functions below accept.  The arithmetic is
- * the one of the six functions above with a subsampled axis switched on or off, and at chroma 420 with BT601 / BT709
- * the results are theirs bit for bit.  The integer tables rint(M * 2^16) / rint(M_d * 2^24) are computed on the host in
+ * the one of the four 4:2:0 functions above with a subsampled axis switched on or off, and at chroma 420 with BT601 /
+ * BT709 the results are theirs bit for bit: those four run their own argument checks and then the same kernels (one
+ * template per direction, these are the only yuv kernels).  The integer tables rint(M * 2^16) / rint(M_d * 2^24) are computed on the host in
  * fp64 from (Kr, Kb).  Samples carry whatever transfer function the material has (PQ and HLG included): code values
  * pass through, nothing is linearised.
  *   in:  chroma to sixteenths in exact integers -- a subsampled axis by its rule above ((1,3)/(3,1) vertically, the
@@ -626,6 +627,12 @@ int tg_rgb_u8_to_yuv_planar(const uint8_t* rgb_hwc, uint8_t* yuv, int n, int H, 
  * through the one float step q = (int) rintf(clamp(v) * 65535.0f) of tg_rgb_f32_to_yuv420p16. */
 int tg_rgb_f32_to_yuv_planar16(const float* rgb_chw, uint16_t* yuv, int n, int H, int W, int chroma, int depth,
                                int matrix, int full_range, int siting, tg_stream_t stream);
+/* Host query, no device call: the tables that all seven functions above hand to their kernels (one kernel template
+ * per direction; the four 4:2:0 functions launch its 420 forms).  depth 8 | 10 | 12, matrix and full_range as above
+ * (TG_YUV_BT2020 included); anything else, or a null pointer, is TG_E_ARG.
+ *   q: rint(M * 2^16) (depth 8) or rint(M_d * 2^24), rows Y, Cb, Cr (q[0..8]); then yo, the chroma mid value, 2^depth - 1
+ *   f: the fp32 gains of the input direction's matrix step: ky = 1/ys, then rv, gu, gv, bu per sixteenth of a code */
+int tg_yuv_tables(int depth, int matrix, int full_range, int q[12], float f[5]);
 
 /* PNG files written on the device: what the reference's save_sequence does with cv2.imwrite
  * (codes/utils/data_utils.py), without the host's zlib.  The specification is tests/png_ref.py and the bytes are

@@ -1,8 +1,8 @@
-"""FRNet.infer_stream (DESIGN.md sections 7d, 7e, 7h, 7i, 7j): input parsing, the batch ring, the raw-video form Yuv420,
-the PNG output form Png, the scene-cut option SceneCut, the output size Resize, one small object per input form, output
-form and option, and the engine that runs a clip of any length through rings of STREAM_SLOTS batches.  A batch's launches
-are frnet_infer's enqueue_batch, the ones infer_sequence(pipeline=True) enqueues.  Uses the network only through its
-attributes."""
+"""FRNet.infer_stream (DESIGN.md sections 7d, 7e, 7h, 7i, 7j, 7l): input parsing, the batch ring, the raw-video forms
+Yuv420 and Yuv, the PNG output form Png, the scene-cut option SceneCut, the output size Resize, one small object per input
+form, output form and option, and the engine that runs a clip of any length through rings of STREAM_SLOTS batches.  A
+batch's launches are frnet_infer's enqueue_batch, the ones infer_sequence(pipeline=True) enqueues.  Uses the network
+only through its attributes."""
 import math
 from dataclasses import dataclass
 from typing import Optional
@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from ... import _lib as L
+from ...ops import YUV_SUBSAMPLING, yuv_frame_samples
 from .frnet_infer import _norm_device, enqueue_batch, stream_batch_sizes
 
 
@@ -164,116 +165,33 @@ class StreamRing:
 YUV_DEPTHS = (8, 10, 12)
 
 
-@dataclass(frozen=True)
-class Yuv420:
-    """Raw-video form of a stream (FRNet.infer_stream(yuv=...), DESIGN.md sections 7e and 7k): planar YUV 4:2:0 (I420)
-    frames of h x w on the way in and of s*h x s*w on the way out.  matrix 'bt601' | 'bt709', full_range (bool),
-    siting 'center' (y4m C420jpeg) | 'left' (y4m C420mpeg2).  depth 8 | 10 | 12: bits per sample of the input; above 8
-    a sample is a 16-bit little-endian word.  out_depth 8 | 10 | 12 | None (the input's): bits per sample of the output;
-    above 8 the frames are written from the float HR frame, not from the rounded uint8 one.  Frozen."""
-    h: int
-    w: int
-    matrix: str = 'bt709'
-    full_range: bool = False
-    siting: str = 'left'
-    depth: int = 8
-    out_depth: Optional[int] = None
+class _YuvSpec:
+    """What Yuv420 and Yuv share: the validation of the fields (the messages carry the class's name), the derived sizes,
+    and the C ABI's view of the spec.  A subclass names its matrices and its three launches -- input_launch(),
+    out_launch(H, W) at 8 bits and deep_launch(H, W) above -- each as (entry point, the arguments between the frame
+    count and the stream)."""
 
     def __post_init__(self):
+        who = type(self).__name__
         for name in ('h', 'w'):
             v = getattr(self, name)
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 2:
-                raise ValueError(f'Yuv420: {name} is an integer >= 2, got {v!r}')
+                raise ValueError(f'{who}: {name} is an integer >= 2, got {v!r}')
             object.__setattr__(self, name, int(v))
-        if self.matrix not in L.YUV_MATRIX:
-            raise ValueError(f'Yuv420: matrix is one of {sorted(L.YUV_MATRIX)}, got {self.matrix!r}')
-        if self.siting not in L.YUV_SITING:
-            raise ValueError(f'Yuv420: siting is one of {sorted(L.YUV_SITING)}, got {self.siting!r}')
+        for name, table in (('chroma', L.YUV_CHROMA), ('out_chroma', L.YUV_CHROMA), ('matrix', self.MATRICES),
+                            ('siting', L.YUV_SITING)):
+            v = getattr(self, name)
+            if not (name == 'out_chroma' and v is None) and (not isinstance(v, str) or v not in table):
+                raise ValueError(f'{who}: {name} is one of {sorted(table)}, got {v!r}')
         if not isinstance(self.full_range, (bool, np.bool_)):
-            raise ValueError(f'Yuv420: full_range is a bool, got {self.full_range!r}')
+            raise ValueError(f'{who}: full_range is a bool, got {self.full_range!r}')
         object.__setattr__(self, 'full_range', bool(self.full_range))
         for name in ('depth', 'out_depth'):
             v = getattr(self, name)
             if name == 'out_depth' and v is None:
                 continue
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v not in YUV_DEPTHS:
-                raise ValueError(f'Yuv420: {name} is one of {YUV_DEPTHS}, got {v!r}')
-            object.__setattr__(self, name, int(v))
-
-    @property
-    def od(self):
-        """Bits per sample of the output: out_depth, or the input's."""
-        return self.depth if self.out_depth is None else self.out_depth
-
-    @property
-    def frame_bytes(self):
-        samples = self.h * self.w + 2 * ((self.h + 1) // 2) * ((self.w + 1) // 2)
-        return samples * (2 if self.depth > 8 else 1)
-
-    def out_frame_bytes(self, scale):
-        """Bytes of a super-resolved frame (s*h and s*w are even: the scale is 2 or 4)."""
-        if scale < 1 or (scale * self.h) % 2 or (scale * self.w) % 2:
-            raise ValueError(f'Yuv420: an output frame has even sides; scale {scale} gives {scale * self.h}x{scale * self.w}')
-        return scale * self.h * scale * self.w * 3 // 2 * (2 if self.od > 8 else 1)
-
-    def codes(self):
-        """(matrix, full_range, siting) as the C ABI takes them."""
-        return L.YUV_MATRIX[self.matrix], int(self.full_range), L.YUV_SITING[self.siting]
-
-
-YUV_SUBSAMPLING = {'420': (2, 2), '422': (2, 1), '444': (1, 1)}     # chroma -> (sx, sy): luma samples per chroma sample
-
-
-def yuv_frame_samples(h, w, chroma):
-    """Samples of one planar frame: Y h*w, then U and V of ceil(h/sy) x ceil(w/sx)."""
-    sx, sy = YUV_SUBSAMPLING[chroma]
-    return h * w + 2 * ((h + sy - 1) // sy) * ((w + sx - 1) // sx)
-
-
-@dataclass(frozen=True)
-class Yuv:
-    """Raw-video form of a stream in any of the three planar layouts (FRNet.infer_stream(yuv=...), DESIGN.md section
-    7l): frames of h x w on the way in and of s*h x s*w on the way out.  chroma '420' | '422' | '444': the layout of
-    the input; out_chroma the same | None (the input's): the layout of the output.  matrix 'bt601' | 'bt709' | 'bt2020'
-    (non-constant luminance), full_range (bool), siting 'center' | 'left': where a chroma sample sits along a
-    sub-sampled horizontal axis (not looked at for 4:4:4).  depth and out_depth as Yuv420's.  Samples pass through as
-    code values whatever their transfer function (PQ and HLG included).  A Yuv always takes the planar launches
-    (tg_yuv_planar_to_rgb_f32, tg_rgb_u8_to_yuv_planar, tg_rgb_f32_to_yuv_planar16), at '420' as well.  Frozen."""
-    h: int
-    w: int
-    chroma: str = '420'
-    out_chroma: Optional[str] = None
-    matrix: str = 'bt709'
-    full_range: bool = False
-    siting: str = 'left'
-    depth: int = 8
-    out_depth: Optional[int] = None
-
-    def __post_init__(self):
-        for name in ('h', 'w'):
-            v = getattr(self, name)
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 2:
-                raise ValueError(f'Yuv: {name} is an integer >= 2, got {v!r}')
-            object.__setattr__(self, name, int(v))
-        for name in ('chroma', 'out_chroma'):
-            v = getattr(self, name)
-            if name == 'out_chroma' and v is None:
-                continue
-            if not isinstance(v, str) or v not in L.YUV_CHROMA:
-                raise ValueError(f'Yuv: {name} is one of {sorted(L.YUV_CHROMA)}, got {v!r}')
-        if not isinstance(self.matrix, str) or self.matrix not in L.YUV_PLANAR_MATRIX:
-            raise ValueError(f'Yuv: matrix is one of {sorted(L.YUV_PLANAR_MATRIX)}, got {self.matrix!r}')
-        if not isinstance(self.siting, str) or self.siting not in L.YUV_SITING:
-            raise ValueError(f'Yuv: siting is one of {sorted(L.YUV_SITING)}, got {self.siting!r}')
-        if not isinstance(self.full_range, (bool, np.bool_)):
-            raise ValueError(f'Yuv: full_range is a bool, got {self.full_range!r}')
-        object.__setattr__(self, 'full_range', bool(self.full_range))
-        for name in ('depth', 'out_depth'):
-            v = getattr(self, name)
-            if name == 'out_depth' and v is None:
-                continue
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v not in YUV_DEPTHS:
-                raise ValueError(f'Yuv: {name} is one of {YUV_DEPTHS}, got {v!r}')
+                raise ValueError(f'{who}: {name} is one of {YUV_DEPTHS}, got {v!r}')
             object.__setattr__(self, name, int(v))
 
     @property
@@ -295,9 +213,70 @@ class Yuv:
         4:2:2: an even width)."""
         sx, sy = YUV_SUBSAMPLING[self.oc]
         if H < 1 or W < 1 or H % sy or W % sx:
-            raise ValueError(f'Yuv: a 4:{self.oc[1]}:{self.oc[2]} output frame has '
+            raise ValueError(f'{type(self).__name__}: a 4:{self.oc[1]}:{self.oc[2]} output frame has '
                              f'{"even sides" if sy == 2 else "an even width"}, got {H}x{W}')
         return yuv_frame_samples(H, W, self.oc) * (2 if self.od > 8 else 1)
+
+    def codes(self):
+        """(matrix, full_range, siting) as the C ABI takes them."""
+        return self.MATRICES[self.matrix], int(self.full_range), L.YUV_SITING[self.siting]
+
+
+@dataclass(frozen=True)
+class Yuv420(_YuvSpec):
+    """Raw-video form of a stream (FRNet.infer_stream(yuv=...), DESIGN.md sections 7e and 7k): planar YUV 4:2:0 (I420)
+    frames of h x w on the way in and of s*h x s*w on the way out.  matrix 'bt601' | 'bt709', full_range (bool),
+    siting 'center' (y4m C420jpeg) | 'left' (y4m C420mpeg2).  depth 8 | 10 | 12: bits per sample of the input; above 8
+    a sample is a 16-bit little-endian word.  out_depth 8 | 10 | 12 | None (the input's): bits per sample of the output;
+    above 8 the frames are written from the float HR frame, not from the rounded uint8 one.  A Yuv420 takes the four
+    4:2:0 entry points (tg_yuv420_to_rgb_f32, tg_yuv420p16_to_rgb_f32, tg_rgb_u8_to_yuv420, tg_rgb_f32_to_yuv420p16).
+    Frozen."""
+    h: int
+    w: int
+    matrix: str = 'bt709'
+    full_range: bool = False
+    siting: str = 'left'
+    depth: int = 8
+    out_depth: Optional[int] = None
+    MATRICES, chroma, out_chroma = L.YUV_MATRIX, '420', None         # (no fields: the one layout, BT.601 / BT.709 only)
+
+    def out_frame_bytes(self, scale):
+        """Bytes of a super-resolved frame (s*h and s*w are even: the scale is 2 or 4)."""
+        if scale < 1 or (scale * self.h) % 2 or (scale * self.w) % 2:
+            raise ValueError(f'Yuv420: an output frame has even sides; scale {scale} gives {scale * self.h}x{scale * self.w}')
+        return self.out_size_bytes(scale * self.h, scale * self.w)
+
+    def input_launch(self):
+        if self.depth > 8:
+            return 'tg_yuv420p16_to_rgb_f32', (self.h, self.w, self.depth, *self.codes())
+        return 'tg_yuv420_to_rgb_f32', (self.h, self.w, *self.codes())
+
+    def out_launch(self, H, W):
+        return 'tg_rgb_u8_to_yuv420', (H, W, *self.codes())
+
+    def deep_launch(self, H, W):
+        return 'tg_rgb_f32_to_yuv420p16', (H, W, self.od, *self.codes())
+
+
+@dataclass(frozen=True)
+class Yuv(_YuvSpec):
+    """Raw-video form of a stream in any of the three planar layouts (FRNet.infer_stream(yuv=...), DESIGN.md section
+    7l): frames of h x w on the way in and of s*h x s*w on the way out.  chroma '420' | '422' | '444': the layout of
+    the input; out_chroma the same | None (the input's): the layout of the output.  matrix 'bt601' | 'bt709' | 'bt2020'
+    (non-constant luminance), full_range (bool), siting 'center' | 'left': where a chroma sample sits along a
+    sub-sampled horizontal axis (not looked at for 4:4:4).  depth and out_depth as Yuv420's.  Samples pass through as
+    code values whatever their transfer function (PQ and HLG included).  A Yuv always takes the planar launches
+    (tg_yuv_planar_to_rgb_f32, tg_rgb_u8_to_yuv_planar, tg_rgb_f32_to_yuv_planar16), at '420' as well.  Frozen."""
+    h: int
+    w: int
+    chroma: str = '420'
+    out_chroma: Optional[str] = None
+    matrix: str = 'bt709'
+    full_range: bool = False
+    siting: str = 'left'
+    depth: int = 8
+    out_depth: Optional[int] = None
+    MATRICES = L.YUV_PLANAR_MATRIX
 
     def out_frame_bytes(self, scale):
         """Bytes of a super-resolved frame."""
@@ -305,9 +284,14 @@ class Yuv:
             raise ValueError(f'Yuv: scale {scale}')
         return self.out_size_bytes(scale * self.h, scale * self.w)
 
-    def codes(self):
-        """(matrix, full_range, siting) as the C ABI takes them."""
-        return L.YUV_PLANAR_MATRIX[self.matrix], int(self.full_range), L.YUV_SITING[self.siting]
+    def input_launch(self):
+        return 'tg_yuv_planar_to_rgb_f32', (self.h, self.w, L.YUV_CHROMA[self.chroma], self.depth, *self.codes())
+
+    def out_launch(self, H, W):
+        return 'tg_rgb_u8_to_yuv_planar', (H, W, L.YUV_CHROMA[self.oc], *self.codes())
+
+    def deep_launch(self, H, W):
+        return 'tg_rgb_f32_to_yuv_planar16', (H, W, L.YUV_CHROMA[self.oc], self.od, *self.codes())
 
 
 @dataclass(frozen=True)
@@ -426,44 +410,30 @@ class SceneCut:
 
 
 def yuv420_planes(chunk, H, W, depth=8):
-    """(Y, U, V) views of I420 frames: chunk (m, frame_bytes) -> (m,H,W), (m,ch,cw), (m,ch,cw); a single frame
-    (frame_bytes,) -> (H,W), (ch,cw), (ch,cw).  numpy or torch; nothing is copied.  depth above 8: the chunk holds
-    2-byte samples (uint8 as the stream yields it, or uint16 already) and the views are uint16."""
-    ch, cw = (H + 1) // 2, (W + 1) // 2
-    if depth not in YUV_DEPTHS:
-        raise ValueError(f'yuv420_planes: depth is one of {YUV_DEPTHS}, got {depth!r}')
-    if depth > 8 and chunk.dtype == (np.uint8 if isinstance(chunk, np.ndarray) else torch.uint8):
-        if chunk.shape[-1] != 2 * (H * W + 2 * ch * cw):
-            raise ValueError(f'yuv420_planes: {H}x{W} frames at {depth} bits have {2 * (H * W + 2 * ch * cw)} bytes; '
-                             f'got shape {tuple(chunk.shape)}')
-        chunk = chunk.view(np.uint16 if isinstance(chunk, np.ndarray) else torch.uint16)
-    if chunk.shape[-1] != H * W + 2 * ch * cw:
-        raise ValueError(f'yuv420_planes: {H}x{W} frames have {H * W + 2 * ch * cw} bytes; got shape {tuple(chunk.shape)}')
-    lead = tuple(chunk.shape[:-1])
-    return (chunk[..., :H * W].reshape(lead + (H, W)),
-            chunk[..., H * W:H * W + ch * cw].reshape(lead + (ch, cw)),
-            chunk[..., H * W + ch * cw:].reshape(lead + (ch, cw)))
+    """yuv_planes of I420 frames: chunk (m, frame_bytes) -> (m,H,W), (m,ch,cw), (m,ch,cw); a single frame
+    (frame_bytes,) -> (H,W), (ch,cw), (ch,cw)."""
+    return yuv_planes(chunk, H, W, '420', depth, who='yuv420_planes')
 
 
-def yuv_planes(chunk, H, W, chroma='420', depth=8):
-    """yuv420_planes for any of the three layouts: (Y, U, V) views of planar frames, U and V of ceil(H/sy) x ceil(W/sx)
+def yuv_planes(chunk, H, W, chroma='420', depth=8, who='yuv_planes'):
+    """(Y, U, V) views of planar frames in any of the three layouts, U and V of ceil(H/sy) x ceil(W/sx)
     with (sx, sy) = (2,2) '420', (2,1) '422', (1,1) '444'.  chunk (m, frame_bytes) or a single frame (frame_bytes,),
     numpy or torch; nothing is copied.  depth above 8: the chunk holds 2-byte samples (uint8 as the stream yields it, or
     uint16 already) and the views are uint16."""
     if chroma not in YUV_SUBSAMPLING:
-        raise ValueError(f'yuv_planes: chroma is one of {sorted(YUV_SUBSAMPLING)}, got {chroma!r}')
+        raise ValueError(f'{who}: chroma is one of {sorted(YUV_SUBSAMPLING)}, got {chroma!r}')
     if depth not in YUV_DEPTHS:
-        raise ValueError(f'yuv_planes: depth is one of {YUV_DEPTHS}, got {depth!r}')
+        raise ValueError(f'{who}: depth is one of {YUV_DEPTHS}, got {depth!r}')
     sx, sy = YUV_SUBSAMPLING[chroma]
     ch, cw = (H + sy - 1) // sy, (W + sx - 1) // sx
     ns = H * W + 2 * ch * cw
     if depth > 8 and chunk.dtype == (np.uint8 if isinstance(chunk, np.ndarray) else torch.uint8):
         if chunk.shape[-1] != 2 * ns:
-            raise ValueError(f'yuv_planes: {H}x{W} {chroma} frames at {depth} bits have {2 * ns} bytes; '
+            raise ValueError(f'{who}: {H}x{W} {chroma} frames at {depth} bits have {2 * ns} bytes; '
                              f'got shape {tuple(chunk.shape)}')
         chunk = chunk.view(np.uint16 if isinstance(chunk, np.ndarray) else torch.uint16)
     if chunk.shape[-1] != ns:
-        raise ValueError(f'yuv_planes: {H}x{W} {chroma} frames have {ns} samples; got shape {tuple(chunk.shape)}')
+        raise ValueError(f'{who}: {H}x{W} {chroma} frames have {ns} samples; got shape {tuple(chunk.shape)}')
     lead = tuple(chunk.shape[:-1])
     return (chunk[..., :H * W].reshape(lead + (H, W)),
             chunk[..., H * W:H * W + ch * cw].reshape(lead + (ch, cw)),
@@ -534,14 +504,8 @@ class _HostBytes:
 
 def _input_form(piece, c, yuv):
     """The input form of a stream, from its options and its first item (as stream_parts hands it out)."""
-    if isinstance(yuv, Yuv):
-        return _HostBytes(yuv.h, yuv.w, (yuv.frame_bytes,), 'tg_yuv_planar_to_rgb_f32',
-                          (yuv.h, yuv.w, L.YUV_CHROMA[yuv.chroma], yuv.depth, *yuv.codes()))
-    if yuv is not None and yuv.depth > 8:
-        return _HostBytes(yuv.h, yuv.w, (yuv.frame_bytes,), 'tg_yuv420p16_to_rgb_f32',
-                          (yuv.h, yuv.w, yuv.depth, *yuv.codes()))
     if yuv is not None:
-        return _HostBytes(yuv.h, yuv.w, (yuv.frame_bytes,), 'tg_yuv420_to_rgb_f32', (yuv.h, yuv.w, *yuv.codes()))
+        return _HostBytes(yuv.h, yuv.w, (yuv.frame_bytes,), *yuv.input_launch())
     if piece.dtype == torch.uint8:
         h, w = piece.shape[1:3]
         return _HostBytes(h, w, (h, w, c), 'tg_dequantize_u8_hwc', (c, h, w))
@@ -565,22 +529,23 @@ class _RgbOut:
         return self.host_out[sl, :cnt].numpy()
 
 
-class _I420Out:
-    """Output form I420: ONE tg_rgb_u8_to_yuv420 turns the batch's RGB frames into the slot's
-    I420 frames on the device, and those come down: out_frame_bytes per frame, on the device and pinned."""
+class _YuvOut:
+    """Output form planar YUV at 8 bits (DESIGN.md sections 7e and 7l): ONE launch of the spec's out_launch
+    (tg_rgb_u8_to_yuv420 for a Yuv420, tg_rgb_u8_to_yuv_planar for a Yuv) turns the batch's RGB frames into the slot's
+    YUV frames on the device, and those come down: out_size_bytes per frame, on the device and pinned."""
 
     def __init__(self, yuv):
         self.yuv = yuv
 
     def alloc(self, eng):
         ns, m, H, W = eng.out_u8.shape[:4]
-        self.lib, self.u8, self.args = eng.lib, eng.out_u8, (H, W, *self.yuv.codes(), eng.main.cuda_stream)
-        self.host_out = torch.empty(ns, m, H * W * 3 // 2, dtype=torch.uint8, pin_memory=True)      # (H and W are even)
+        self.u8, (self.launch, args) = eng.out_u8, self.yuv.out_launch(H, W)
+        self.fn, self.args = getattr(eng.lib, self.launch), (*args, eng.main.cuda_stream)
+        self.host_out = torch.empty(ns, m, self.yuv.out_size_bytes(H, W), dtype=torch.uint8, pin_memory=True)
         self.yuv_out = torch.empty(tuple(self.host_out.shape), dtype=torch.uint8, device=eng.dev)
 
     def encode(self, sl, cnt):
-        L.check(self.lib.tg_rgb_u8_to_yuv420(self.u8[sl].data_ptr(), self.yuv_out[sl].data_ptr(), cnt, *self.args),
-                'tg_rgb_u8_to_yuv420')
+        L.check(self.fn(self.u8[sl].data_ptr(), self.yuv_out[sl].data_ptr(), cnt, *self.args), self.launch)
 
     def download(self, sl, cnt):
         self.host_out[sl, :cnt].copy_(self.yuv_out[sl, :cnt], non_blocking=True)
@@ -589,11 +554,12 @@ class _I420Out:
         return self.host_out[sl, :cnt].numpy()
 
 
-class _I420DeepOut:
-    """Output form I420 at 10 or 12 bits: directly behind every frame's SRNet launch ONE
-    tg_rgb_f32_to_yuv420p16 (n = 1, on the caller's stream) converts the float HR frame just written into the slot's
-    device buffer at that frame -- `after(sl)` is the hook enqueue_batch calls -- so nothing is left to encode behind
-    the batch.  The slot's uint8 frames are still written by the HR tail and are not downloaded."""
+class _YuvDeepOut:
+    """Output form planar YUV at 10 or 12 bits (DESIGN.md sections 7k and 7l): directly behind every frame's SRNet
+    launch ONE launch of the spec's deep_launch (tg_rgb_f32_to_yuv420p16 for a Yuv420, tg_rgb_f32_to_yuv_planar16 for a
+    Yuv; n = 1, on the caller's stream) converts the float HR frame just written into the slot's device buffer at that
+    frame -- `after(sl)` is the hook enqueue_batch calls -- so nothing is left to encode behind the batch.  The slot's
+    uint8 frames are still written by the HR tail and are not downloaded."""
 
     def __init__(self, yuv):
         self.yuv = yuv
@@ -601,16 +567,16 @@ class _I420DeepOut:
     def alloc(self, eng):
         ns, m, H, W = eng.u8.shape[:4]
         self.fb = self.yuv.out_frame_bytes(eng.net.scale)
-        self.fn = eng.lib.tg_rgb_f32_to_yuv420p16
-        self.args = (1, H, W, self.yuv.od, *self.yuv.codes(), eng.main.cuda_stream)
+        self.launch, args = self.yuv.deep_launch(H, W)
+        self.fn, self.args = getattr(eng.lib, self.launch), (1, *args, eng.main.cuda_stream)
         self.host_out = torch.empty(ns, m, self.fb, dtype=torch.uint8, pin_memory=True)
         self.yuv_out = torch.empty(ns, m, self.fb, dtype=torch.uint8, device=eng.dev)
 
     def after(self, sl):
-        base, fb, fn, args = self.yuv_out[sl].data_ptr(), self.fb, self.fn, self.args
+        base, fb, fn, args, launch = self.yuv_out[sl].data_ptr(), self.fb, self.fn, self.args, self.launch
 
         def convert(j, hr_addr):
-            L.check(fn(hr_addr, base + j * fb, *args), 'tg_rgb_f32_to_yuv420p16')
+            L.check(fn(hr_addr, base + j * fb, *args), launch)
         return convert
 
     def encode(self, sl, cnt):
@@ -621,42 +587,6 @@ class _I420DeepOut:
 
     def result(self, sl, cnt):
         return self.host_out[sl, :cnt].numpy()
-
-
-class _YuvOut(_I420Out):
-    """Output form planar YUV at 8 bits in the layout yuv.oc: _I420Out with ONE
-    tg_rgb_u8_to_yuv_planar per batch and the layout's frame size."""
-
-    def alloc(self, eng):
-        ns, m, H, W = eng.out_u8.shape[:4]
-        self.lib, self.u8 = eng.lib, eng.out_u8
-        self.args = (H, W, L.YUV_CHROMA[self.yuv.oc], *self.yuv.codes(), eng.main.cuda_stream)
-        self.host_out = torch.empty(ns, m, self.yuv.out_size_bytes(H, W), dtype=torch.uint8, pin_memory=True)
-        self.yuv_out = torch.empty(tuple(self.host_out.shape), dtype=torch.uint8, device=eng.dev)
-
-    def encode(self, sl, cnt):
-        L.check(self.lib.tg_rgb_u8_to_yuv_planar(self.u8[sl].data_ptr(), self.yuv_out[sl].data_ptr(), cnt, *self.args),
-                'tg_rgb_u8_to_yuv_planar')
-
-
-class _YuvDeepOut(_I420DeepOut):
-    """Output form planar YUV at 10 or 12 bits in the layout yuv.oc: _I420DeepOut with ONE
-    tg_rgb_f32_to_yuv_planar16 behind every frame's SRNet launch."""
-
-    def alloc(self, eng):
-        ns, m, H, W = eng.u8.shape[:4]
-        self.fb = self.yuv.out_frame_bytes(eng.net.scale)
-        self.fn = eng.lib.tg_rgb_f32_to_yuv_planar16
-        self.args = (1, H, W, L.YUV_CHROMA[self.yuv.oc], self.yuv.od, *self.yuv.codes(), eng.main.cuda_stream)
-        self.host_out = torch.empty(ns, m, self.fb, dtype=torch.uint8, pin_memory=True)
-        self.yuv_out = torch.empty(ns, m, self.fb, dtype=torch.uint8, device=eng.dev)
-
-    def after(self, sl):
-        base, fb, fn, args = self.yuv_out[sl].data_ptr(), self.fb, self.fn, self.args
-
-        def convert(j, hr_addr):
-            L.check(fn(hr_addr, base + j * fb, *args), 'tg_rgb_f32_to_yuv_planar16')
-        return convert
 
 
 class _PngOut:
@@ -835,10 +765,9 @@ class _StreamEngine:
                 resize.check_source(net.scale * yuv.h, net.scale * yuv.w)
         # the forms: the output and the scene-cut slots follow from the options, the input from the first item as well
         self.inp, self.input_form = None, lambda piece: _input_form(piece, net.in_nc, yuv)
-        planar = isinstance(yuv, Yuv)               # (a Yuv420 keeps its own launches)
-        self.deep = None if yuv is None or yuv.od == 8 else _YuvDeepOut(yuv) if planar else _I420DeepOut(yuv)   # (per-frame hook)
+        self.deep = None if yuv is None or yuv.od == 8 else _YuvDeepOut(yuv)        # (per-frame hook)
         self.out = _PngOut(png) if png is not None else self.deep if self.deep is not None else \
-            _YuvOut(yuv) if planar else _I420Out(yuv) if yuv is not None else _RgbOut()
+            _YuvOut(yuv) if yuv is not None else _RgbOut()
         self.cut = _CutSlots(scene_cut) if scene_cut is not None else None
         self.rsz = _ResizedFrames(resize) if resize is not None else None
         self.net, self.on_fault, self.parts = net, on_fault, stream_parts(frames, net.in_nc, yuv)

@@ -479,113 +479,9 @@ def dequantize_u8_hwc(x):
     return out
 
 
-def _yuv_codes(matrix, full_range, siting, what):
-    """Names -> the C enums; integers pass through (the library refuses an unknown value with TG_E_ARG)."""
-    for name, val, table in (('matrix', matrix, L.YUV_MATRIX), ('siting', siting, L.YUV_SITING)):
-        if isinstance(val, str) and val not in table:
-            raise L.TecoganHipError(f'{what}: {name} is one of {sorted(table)}, got {val!r}')
-    return (L.YUV_MATRIX[matrix] if isinstance(matrix, str) else int(matrix), int(full_range),
-            L.YUV_SITING[siting] if isinstance(siting, str) else int(siting))
-
-
-def yuv420_frame_bytes(h, w):
-    """Bytes of one I420 frame: Y h*w, then U and V of ceil(h/2) x ceil(w/2)."""
-    return h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)
-
-
-def yuv420_to_rgb(yuv, h, w, matrix='bt709', full_range=False, siting='left'):
-    """(n, frame_bytes) / (frame_bytes,) uint8 I420 frames on device -> (n,3,h,w) fp32 RGB in [0,1]: integer bilinear
-    chroma up-sampling, one fp32 matrix step, clamp (tg_yuv420_to_rgb_f32; DESIGN.md section 7e)."""
-    _chk_u8(yuv, 'yuv')
-    if yuv.dim() == 1:
-        yuv = yuv.unsqueeze(0)
-    if yuv.dim() != 2 or yuv.shape[1] != yuv420_frame_bytes(h, w):
-        raise L.TecoganHipError(f'yuv420_to_rgb: {h}x{w} frames have {yuv420_frame_bytes(h, w)} bytes; '
-                                f'got shape {tuple(yuv.shape)}')
-    m, r, s = _yuv_codes(matrix, full_range, siting, 'yuv420_to_rgb')
-    n = yuv.shape[0]
-    out = torch.empty(n, 3, h, w, dtype=torch.float32, device=yuv.device)
-    L.check(L.lib().tg_yuv420_to_rgb_f32(_ptr(yuv), _ptr(out), n, h, w, m, r, s, _stream()), 'tg_yuv420_to_rgb_f32')
-    return out
-
-
-def rgb_to_yuv420(rgb_hwc, matrix='bt709', full_range=False, siting='left'):
-    """(n,H,W,3) uint8 RGB on device -> (n, frame_bytes) uint8 I420 frames, exact integer arithmetic; H and W even
-    (tg_rgb_u8_to_yuv420; DESIGN.md section 7e)."""
-    _chk_u8(rgb_hwc, 'rgb')
-    if rgb_hwc.dim() != 4 or rgb_hwc.shape[3] != 3:
-        raise L.TecoganHipError(f'rgb_to_yuv420: expected (n,H,W,3), got shape {tuple(rgb_hwc.shape)}')
-    m, r, s = _yuv_codes(matrix, full_range, siting, 'rgb_to_yuv420')
-    n, H, W, _ = rgb_hwc.shape
-    out = torch.empty(n, yuv420_frame_bytes(H, W), dtype=torch.uint8, device=rgb_hwc.device)
-    L.check(L.lib().tg_rgb_u8_to_yuv420(_ptr(rgb_hwc), _ptr(out), n, H, W, m, r, s, _stream()), 'tg_rgb_u8_to_yuv420')
-    return out
-
-
-def yuv420p_frame_samples(h, w):
-    """16-bit samples of one 10- or 12-bit I420 frame (2 bytes each)."""
-    return yuv420_frame_bytes(h, w)
-
-
-def _chk_depth(depth, what):
-    if isinstance(depth, bool) or not isinstance(depth, int):
-        raise L.TecoganHipError(f'{what}: depth is 10 or 12, got {depth!r}')
-    return depth
-
-
-def yuv420p_to_rgb(yuv_u16, h, w, depth, matrix='bt709', full_range=False, siting='left', out=None):
-    """(n, frame_samples) / (frame_samples,) uint16 I420 frames at `depth` (10 | 12) bits on device -> (n,3,h,w) fp32
-    RGB in [0,1]; a sample above 2^depth - 1 is read as 2^depth - 1 (tg_yuv420p16_to_rgb_f32; DESIGN.md section 7k).
-    out: a contiguous CUDA float32 (n,3,h,w) tensor to write into."""
-    _chk(yuv_u16, 'yuv', torch.uint16)
-    if yuv_u16.dim() == 1:
-        yuv_u16 = yuv_u16.unsqueeze(0)
-    if yuv_u16.dim() != 2 or yuv_u16.shape[1] != yuv420p_frame_samples(h, w):
-        raise L.TecoganHipError(f'yuv420p_to_rgb: {h}x{w} frames have {yuv420p_frame_samples(h, w)} samples; '
-                                f'got shape {tuple(yuv_u16.shape)}')
-    m, r, s = _yuv_codes(matrix, full_range, siting, 'yuv420p_to_rgb')
-    n = yuv_u16.shape[0]
-    if out is None:
-        out = torch.empty(n, 3, h, w, dtype=torch.float32, device=yuv_u16.device)
-    elif _chk(out, 'out').shape != (n, 3, h, w):
-        raise L.TecoganHipError(f'yuv420p_to_rgb: out is ({n},3,{h},{w}), got shape {tuple(out.shape)}')
-    L.check(L.lib().tg_yuv420p16_to_rgb_f32(_ptr(yuv_u16), _ptr(out), n, h, w, _chk_depth(depth, 'yuv420p_to_rgb'), m, r,
-                                            s, _stream()), 'tg_yuv420p16_to_rgb_f32')
-    return out
-
-
-def rgb_f32_to_yuv420p(rgb_chw, depth, matrix='bt709', full_range=False, siting='left', out=None):
-    """(n,3,H,W) float32 RGB on device -> (n, frame_samples) uint16 I420 frames at `depth` (10 | 12) bits: one fp32
-    step to 16-bit integers, then exact integer arithmetic; H and W even (tg_rgb_f32_to_yuv420p16; DESIGN.md section
-    7k).  out: a contiguous CUDA uint16 (n, frame_samples) tensor to write into."""
-    _chk(rgb_chw, 'rgb')
-    if rgb_chw.dim() != 4 or rgb_chw.shape[1] != 3:
-        raise L.TecoganHipError(f'rgb_f32_to_yuv420p: expected (n,3,H,W), got shape {tuple(rgb_chw.shape)}')
-    m, r, s = _yuv_codes(matrix, full_range, siting, 'rgb_f32_to_yuv420p')
-    n, _, H, W = rgb_chw.shape
-    if out is None:
-        out = torch.empty(n, yuv420p_frame_samples(H, W), dtype=torch.uint16, device=rgb_chw.device)
-    elif _chk(out, 'out', torch.uint16).shape != (n, yuv420p_frame_samples(H, W)):
-        raise L.TecoganHipError(f'rgb_f32_to_yuv420p: out is ({n}, {yuv420p_frame_samples(H, W)}), got shape '
-                                f'{tuple(out.shape)}')
-    L.check(L.lib().tg_rgb_f32_to_yuv420p16(_ptr(rgb_chw), _ptr(out), n, H, W, _chk_depth(depth, 'rgb_f32_to_yuv420p'),
-                                            m, r, s, _stream()), 'tg_rgb_f32_to_yuv420p16')
-    return out
-
-
-# -- planar YUV 4:2:0 | 4:2:2 | 4:4:4 at 8 | 10 | 12 bits, BT.601 | BT.709 | BT.2020 (DESIGN.md section 7l) ----------------
-YUV_SUBSAMPLING = {'420': (2, 2), '422': (2, 1), '444': (1, 1)}     # chroma -> (sx, sy)
-
-
-def _yuv_planar_codes(chroma, matrix, full_range, siting, what):
-    """Names -> the C enums of the planar entry points; integers pass through (the library refuses an unknown one)."""
-    for name, val, table in (('chroma', chroma, L.YUV_CHROMA), ('matrix', matrix, L.YUV_PLANAR_MATRIX),
-                             ('siting', siting, L.YUV_SITING)):
-        if isinstance(val, str) and val not in table:
-            raise L.TecoganHipError(f'{what}: {name} is one of {sorted(table)}, got {val!r}')
-    return (L.YUV_CHROMA[chroma] if isinstance(chroma, str) else int(chroma),
-            L.YUV_PLANAR_MATRIX[matrix] if isinstance(matrix, str) else int(matrix), int(full_range),
-            L.YUV_SITING[siting] if isinstance(siting, str) else int(siting))
+# -- planar YUV 4:2:0 | 4:2:2 | 4:4:4 at 8 | 10 | 12 bits, BT.601 | BT.709 | BT.2020 (DESIGN.md sections 7e, 7k, 7l): seven
+# wrappers over seven entry points, one body per direction --------------------------------------------------------------
+YUV_SUBSAMPLING = {'420': (2, 2), '422': (2, 1), '444': (1, 1)}     # chroma -> (sx, sy): luma samples per chroma sample
 
 
 def yuv_frame_samples(h, w, chroma='420'):
@@ -596,65 +492,130 @@ def yuv_frame_samples(h, w, chroma='420'):
     return h * w + 2 * ((h + sy - 1) // sy) * ((w + sx - 1) // sx)
 
 
-def yuv_to_rgb(yuv, h, w, chroma='420', depth=8, matrix='bt709', full_range=False, siting='left', out=None):
-    """(n, frame_samples) / (frame_samples,) planar YUV frames on device -- uint8 at depth 8, uint16 at 10 | 12 --
-    -> (n,3,h,w) fp32 RGB in [0,1] (tg_yuv_planar_to_rgb_f32; DESIGN.md section 7l).  chroma '420' | '422' | '444',
-    matrix 'bt601' | 'bt709' | 'bt2020'.  out: a contiguous CUDA float32 (n,3,h,w) tensor to write into."""
+def yuv420_frame_bytes(h, w):
+    """Bytes of one I420 frame, and 16-bit samples of one 10- or 12-bit I420 frame (2 bytes each)."""
+    return yuv_frame_samples(h, w, '420')
+
+
+yuv420p_frame_samples = yuv420_frame_bytes
+
+
+def _yuv_codes(what, matrices, matrix, full_range, siting, chroma=None):
+    """Names -> the C enums, (matrix, full_range, siting) with the chroma code in front if one is given; integers pass
+    through (the library refuses an unknown value with TG_E_ARG)."""
+    codes = []
+    for name, val, table in (('chroma', chroma, L.YUV_CHROMA), ('matrix', matrix, matrices), ('siting', siting, L.YUV_SITING)):
+        if isinstance(val, str) and val not in table:
+            raise L.TecoganHipError(f'{what}: {name} is one of {sorted(table)}, got {val!r}')
+        if val is not None:
+            codes.append(table[val] if isinstance(val, str) else int(val))
+    return (*codes[:-1], int(full_range), codes[-1])
+
+
+def _chk_depth(depth, what, depths='10 or 12'):
     if isinstance(depth, bool) or not isinstance(depth, int):
-        raise L.TecoganHipError(f'yuv_to_rgb: depth is 8, 10 or 12, got {depth!r}')
-    _chk(yuv, 'yuv', torch.uint8 if depth == 8 else torch.uint16)
-    c, m, r, s = _yuv_planar_codes(chroma, matrix, full_range, siting, 'yuv_to_rgb')
+        raise L.TecoganHipError(f'{what}: depth is {depths}, got {depth!r}')
+    return depth
+
+
+def _yuv_in(what, launch, yuv, dtype, h, w, ns, frames, lead, out=None):
+    """The input direction's one body: (n, ns) / (ns,) samples of `dtype` on device -> (n,3,h,w) fp32 through
+    `launch`(yuv, out, n, h, w, *lead, stream).  ns None: a layout the wrapper does not know, which the library refuses
+    before any access."""
+    _chk(yuv, 'yuv', dtype)
     if yuv.dim() == 1:
         yuv = yuv.unsqueeze(0)
-    chroma = {v: k for k, v in L.YUV_CHROMA.items()}.get(c)          # (None: the library refuses it before any access)
-    if chroma is not None and (yuv.dim() != 2 or yuv.shape[1] != yuv_frame_samples(h, w, chroma)):
-        raise L.TecoganHipError(f'yuv_to_rgb: {h}x{w} {chroma} frames have {yuv_frame_samples(h, w, chroma)} samples; '
-                                f'got shape {tuple(yuv.shape)}')
+    if ns is not None and (yuv.dim() != 2 or yuv.shape[1] != ns):
+        raise L.TecoganHipError(f'{what}: {h}x{w} {frames}; got shape {tuple(yuv.shape)}')
     n = yuv.shape[0]
     if out is None:
         out = torch.empty(n, 3, h, w, dtype=torch.float32, device=yuv.device)
     elif _chk(out, 'out').shape != (n, 3, h, w):
-        raise L.TecoganHipError(f'yuv_to_rgb: out is ({n},3,{h},{w}), got shape {tuple(out.shape)}')
-    L.check(L.lib().tg_yuv_planar_to_rgb_f32(_ptr(yuv), _ptr(out), n, h, w, c, depth, m, r, s, _stream()),
-            'tg_yuv_planar_to_rgb_f32')
+        raise L.TecoganHipError(f'{what}: out is ({n},3,{h},{w}), got shape {tuple(out.shape)}')
+    L.check(getattr(L.lib(), launch)(_ptr(yuv), _ptr(out), n, h, w, *lead, _stream()), launch)
     return out
+
+
+def _yuv_out(what, launch, rgb, deep, chroma, lead, out=None):
+    """The output direction's one body: (n,H,W,3) uint8 RGB -> (n, frame_samples) uint8, or with `deep` (n,3,H,W) float32
+    RGB -> uint16, through `launch`(rgb, out, n, H, W, *lead, stream)."""
+    _chk(rgb, 'rgb', torch.float32 if deep else torch.uint8)
+    if rgb.dim() != 4 or rgb.shape[1 if deep else 3] != 3:
+        raise L.TecoganHipError(f'{what}: expected {"(n,3,H,W)" if deep else "(n,H,W,3)"}, got shape {tuple(rgb.shape)}')
+    n, H, W = (rgb.shape[0], *rgb.shape[2:]) if deep else rgb.shape[:3]
+    ns, dtype = yuv_frame_samples(H, W, chroma), torch.uint16 if deep else torch.uint8
+    if out is None:
+        out = torch.empty(n, ns, dtype=dtype, device=rgb.device)
+    elif _chk(out, 'out', dtype).shape != (n, ns):
+        raise L.TecoganHipError(f'{what}: out is ({n}, {ns}), got shape {tuple(out.shape)}')
+    L.check(getattr(L.lib(), launch)(_ptr(rgb), _ptr(out), n, H, W, *lead, _stream()), launch)
+    return out
+
+
+def yuv420_to_rgb(yuv, h, w, matrix='bt709', full_range=False, siting='left'):
+    """(n, frame_bytes) / (frame_bytes,) uint8 I420 frames on device -> (n,3,h,w) fp32 RGB in [0,1]: integer bilinear
+    chroma up-sampling, one fp32 matrix step, clamp (tg_yuv420_to_rgb_f32; DESIGN.md section 7e)."""
+    ns = yuv420_frame_bytes(h, w)
+    return _yuv_in('yuv420_to_rgb', 'tg_yuv420_to_rgb_f32', yuv, torch.uint8, h, w, ns, f'frames have {ns} bytes',
+                   _yuv_codes('yuv420_to_rgb', L.YUV_MATRIX, matrix, full_range, siting))
+
+
+def rgb_to_yuv420(rgb_hwc, matrix='bt709', full_range=False, siting='left'):
+    """(n,H,W,3) uint8 RGB on device -> (n, frame_bytes) uint8 I420 frames, exact integer arithmetic; H and W even
+    (tg_rgb_u8_to_yuv420; DESIGN.md section 7e)."""
+    return _yuv_out('rgb_to_yuv420', 'tg_rgb_u8_to_yuv420', rgb_hwc, False, '420',
+                    _yuv_codes('rgb_to_yuv420', L.YUV_MATRIX, matrix, full_range, siting))
+
+
+def yuv420p_to_rgb(yuv_u16, h, w, depth, matrix='bt709', full_range=False, siting='left', out=None):
+    """(n, frame_samples) / (frame_samples,) uint16 I420 frames at `depth` (10 | 12) bits on device -> (n,3,h,w) fp32
+    RGB in [0,1]; a sample above 2^depth - 1 is read as 2^depth - 1 (tg_yuv420p16_to_rgb_f32; DESIGN.md section 7k).
+    out: a contiguous CUDA float32 (n,3,h,w) tensor to write into."""
+    ns = yuv420p_frame_samples(h, w)
+    return _yuv_in('yuv420p_to_rgb', 'tg_yuv420p16_to_rgb_f32', yuv_u16, torch.uint16, h, w, ns, f'frames have {ns} samples',
+                   (_chk_depth(depth, 'yuv420p_to_rgb'), *_yuv_codes('yuv420p_to_rgb', L.YUV_MATRIX, matrix, full_range, siting)),
+                   out)
+
+
+def rgb_f32_to_yuv420p(rgb_chw, depth, matrix='bt709', full_range=False, siting='left', out=None):
+    """(n,3,H,W) float32 RGB on device -> (n, frame_samples) uint16 I420 frames at `depth` (10 | 12) bits: one fp32
+    step to 16-bit integers, then exact integer arithmetic; H and W even (tg_rgb_f32_to_yuv420p16; DESIGN.md section
+    7k).  out: a contiguous CUDA uint16 (n, frame_samples) tensor to write into."""
+    return _yuv_out('rgb_f32_to_yuv420p', 'tg_rgb_f32_to_yuv420p16', rgb_chw, True, '420',
+                    (_chk_depth(depth, 'rgb_f32_to_yuv420p'),
+                     *_yuv_codes('rgb_f32_to_yuv420p', L.YUV_MATRIX, matrix, full_range, siting)), out)
+
+
+def yuv_to_rgb(yuv, h, w, chroma='420', depth=8, matrix='bt709', full_range=False, siting='left', out=None):
+    """(n, frame_samples) / (frame_samples,) planar YUV frames on device -- uint8 at depth 8, uint16 at 10 | 12 --
+    -> (n,3,h,w) fp32 RGB in [0,1] (tg_yuv_planar_to_rgb_f32; DESIGN.md section 7l).  chroma '420' | '422' | '444',
+    matrix 'bt601' | 'bt709' | 'bt2020'.  out: a contiguous CUDA float32 (n,3,h,w) tensor to write into."""
+    _chk_depth(depth, 'yuv_to_rgb', '8, 10 or 12')
+    c, m, r, s = _yuv_codes('yuv_to_rgb', L.YUV_PLANAR_MATRIX, matrix, full_range, siting, chroma)
+    chroma = {v: k for k, v in L.YUV_CHROMA.items()}.get(c)          # (None: the library refuses it before any access)
+    ns = None if chroma is None else yuv_frame_samples(h, w, chroma)
+    return _yuv_in('yuv_to_rgb', 'tg_yuv_planar_to_rgb_f32', yuv, torch.uint8 if depth == 8 else torch.uint16, h, w, ns,
+                   f'{chroma} frames have {ns} samples', (c, depth, m, r, s), out)
 
 
 def rgb_to_yuv(rgb_hwc, chroma='420', matrix='bt709', full_range=False, siting='left'):
     """(n,H,W,3) uint8 RGB on device -> (n, frame_samples) uint8 planar YUV frames, exact integer arithmetic
     (tg_rgb_u8_to_yuv_planar).  '420': H and W even; '422': W even; '444': any size."""
-    _chk_u8(rgb_hwc, 'rgb')
-    if rgb_hwc.dim() != 4 or rgb_hwc.shape[3] != 3:
-        raise L.TecoganHipError(f'rgb_to_yuv: expected (n,H,W,3), got shape {tuple(rgb_hwc.shape)}')
-    c, m, r, s = _yuv_planar_codes(chroma, matrix, full_range, siting, 'rgb_to_yuv')
     if not isinstance(chroma, str):
         raise L.TecoganHipError(f'rgb_to_yuv: chroma is one of {sorted(L.YUV_CHROMA)}, got {chroma!r}')
-    n, H, W, _ = rgb_hwc.shape
-    out = torch.empty(n, yuv_frame_samples(H, W, chroma), dtype=torch.uint8, device=rgb_hwc.device)
-    L.check(L.lib().tg_rgb_u8_to_yuv_planar(_ptr(rgb_hwc), _ptr(out), n, H, W, c, m, r, s, _stream()),
-            'tg_rgb_u8_to_yuv_planar')
-    return out
+    return _yuv_out('rgb_to_yuv', 'tg_rgb_u8_to_yuv_planar', rgb_hwc, False, chroma,
+                    _yuv_codes('rgb_to_yuv', L.YUV_PLANAR_MATRIX, matrix, full_range, siting, chroma))
 
 
 def rgb_f32_to_yuv(rgb_chw, chroma='420', depth=10, matrix='bt709', full_range=False, siting='left', out=None):
     """(n,3,H,W) float32 RGB on device -> (n, frame_samples) uint16 planar YUV frames at `depth` (10 | 12) bits: one
     fp32 step to 16-bit integers, then exact integer arithmetic (tg_rgb_f32_to_yuv_planar16).
     The sizes of rgb_to_yuv.  out: a contiguous CUDA uint16 (n, frame_samples) tensor to write into."""
-    _chk(rgb_chw, 'rgb')
-    if rgb_chw.dim() != 4 or rgb_chw.shape[1] != 3:
-        raise L.TecoganHipError(f'rgb_f32_to_yuv: expected (n,3,H,W), got shape {tuple(rgb_chw.shape)}')
-    c, m, r, s = _yuv_planar_codes(chroma, matrix, full_range, siting, 'rgb_f32_to_yuv')
     if not isinstance(chroma, str):
         raise L.TecoganHipError(f'rgb_f32_to_yuv: chroma is one of {sorted(L.YUV_CHROMA)}, got {chroma!r}')
-    n, _, H, W = rgb_chw.shape
-    ns = yuv_frame_samples(H, W, chroma)
-    if out is None:
-        out = torch.empty(n, ns, dtype=torch.uint16, device=rgb_chw.device)
-    elif _chk(out, 'out', torch.uint16).shape != (n, ns):
-        raise L.TecoganHipError(f'rgb_f32_to_yuv: out is ({n}, {ns}), got shape {tuple(out.shape)}')
-    L.check(L.lib().tg_rgb_f32_to_yuv_planar16(_ptr(rgb_chw), _ptr(out), n, H, W, c, _chk_depth(depth, 'rgb_f32_to_yuv'),
-                                               m, r, s, _stream()), 'tg_rgb_f32_to_yuv_planar16')
-    return out
+    c, m, r, s = _yuv_codes('rgb_f32_to_yuv', L.YUV_PLANAR_MATRIX, matrix, full_range, siting, chroma)
+    return _yuv_out('rgb_f32_to_yuv', 'tg_rgb_f32_to_yuv_planar16', rgb_chw, True, chroma,
+                    (c, _chk_depth(depth, 'rgb_f32_to_yuv'), m, r, s), out)
 
 
 def png_encode(rgb_hwc, filter='adaptive', lz77=False):

@@ -89,7 +89,7 @@ def _rgb_inputs(n, H, W, seed):
 
 
 @pytest.mark.parametrize('n', [1, 3])
-@pytest.mark.parametrize('H,W', [(2, 2), (4, 6), (18, 18), (16, 34), (18, 258), (64, 96)])
+@pytest.mark.parametrize('H,W', [(2, 2), (4, 6), (18, 18), (16, 34), (18, 258), (64, 96), (6, 8)])
 def test_rgb_to_yuv420_is_bit_identical_to_the_integer_specification(H, W, n):
     inputs = _rgb_inputs(n, H, W, seed=H * 1000 + W + n)
     for cfg in ALL_CONFIGS:
@@ -128,7 +128,7 @@ def _yuv_inputs(n, h, w, seed):
 
 
 @pytest.mark.parametrize('n', [1, 3])
-@pytest.mark.parametrize('h,w', [(2, 2), (8, 8), (9, 11), (13, 34), (9, 9), (16, 258)])
+@pytest.mark.parametrize('h,w', [(2, 2), (8, 8), (9, 11), (13, 34), (9, 9), (16, 258), (3, 5), (4, 6), (6, 8)])
 def test_yuv420_to_rgb_is_within_tolerance_of_fp64_and_inside_the_unit_range(h, w, n):
     inputs = _yuv_inputs(n, h, w, seed=h * 1000 + w + n)
     worst = 0.0

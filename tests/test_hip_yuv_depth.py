@@ -157,7 +157,7 @@ def _yuv16_inputs(n, h, w, depth, seed):
 
 
 @pytest.mark.parametrize('n', [1, 3])
-@pytest.mark.parametrize('h,w', [(2, 2), (3, 5), (9, 11), (16, 24)])
+@pytest.mark.parametrize('h,w', [(2, 2), (3, 5), (9, 11), (16, 24), (4, 6), (6, 8)])
 def test_yuv420p_to_rgb_is_within_the_derived_bound_of_fp64_and_inside_the_unit_range(h, w, n):
     worst = 0.0
     for depth, siting, matrix, full in R.CASES:
@@ -213,6 +213,36 @@ def test_both_entry_points_return_tg_e_arg_without_a_launch():
     assert in_fn(yuv.data_ptr(), rgb.data_ptr(), 1, 1, 6, 10, 1, 0, 1, st) == E_ARG
     torch.cuda.synchronize()
     assert bool((yuv == GUARD).all()) and bool((rgb == 7.0).all()), 'a refused call launched'
+
+
+def test_the_four_420_entry_points_refuse_under_their_own_names_without_a_launch():
+    """The four 4:2:0 entry points forward to the launches of the planar ones, which take BT.2020 and depth 8: their own
+    checks still come first.  Every refused call is TG_E_ARG, the message names the entry point that was CALLED, and
+    nothing is written."""
+    from tecogan_pytorch_amd import _lib as L
+    lib = L.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    f32 = torch.full((3 * 6 * 6,), 7.0, device=DEV)                  # fp32 RGB, either direction
+    u8 = torch.full((6 * 6 * 3,), GUARD, dtype=torch.uint8, device=DEV)             # uint8 RGB
+    yuv = torch.full((2 * R.frame_samples(6, 6) + 2,), GUARD, dtype=torch.uint8, device=DEV)
+    y, f, u = yuv.data_ptr(), f32.data_ptr(), u8.data_ptr()
+    calls = {      # name -> call(src / dst offset of the samples, n, H, W, depth, matrix); out: the output direction
+        'tg_rgb_u8_to_yuv420': (True, None, lambda o, n, H, W, d, m: lib.tg_rgb_u8_to_yuv420(u, y + o, n, H, W, m, 0, 1, st)),
+        'tg_yuv420_to_rgb_f32': (False, None, lambda o, n, H, W, d, m: lib.tg_yuv420_to_rgb_f32(y + o, f, n, H, W, m, 0, 1, st)),
+        'tg_rgb_f32_to_yuv420p16': (True, 10, lambda o, n, H, W, d, m: lib.tg_rgb_f32_to_yuv420p16(f, y + o, n, H, W, d, m, 0, 1, st)),
+        'tg_yuv420p16_to_rgb_f32': (False, 10, lambda o, n, H, W, d, m: lib.tg_yuv420p16_to_rgb_f32(y + o, f, n, H, W, d, m, 0, 1, st)),
+    }
+    for name, (out, depth, call) in calls.items():
+        refused = [(0, 1, 6, 6, depth, 2), (0, 0, 6, 6, depth, 1)]                  # BT.2020; n = 0
+        if out:
+            refused += [(0, 1, 5, 6, depth, 1), (0, 1, 6, 5, depth, 1)]             # odd H, odd W on the way out
+        if depth is not None:
+            refused += [(0, 1, 6, 6, 8, 1), (1, 1, 6, 6, depth, 1)]                 # depth 8; a sample pointer on an odd byte
+        for args in refused:
+            assert call(*args) == E_ARG, (name, args)
+            assert lib.tg_last_error_string().startswith(name[3:].encode() + b':'), (name, args, lib.tg_last_error_string())
+    torch.cuda.synchronize()
+    assert bool((yuv == GUARD).all()) and bool((u8 == GUARD).all()) and bool((f32 == 7.0).all()), 'a refused call launched'
 
 
 def test_ops_wrappers_equal_the_c_abi_and_refuse_what_the_8_bit_ones_refuse():

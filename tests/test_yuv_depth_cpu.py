@@ -9,8 +9,8 @@ trip's bound is derived from that: a Y, Cb or Cr code is within 1 + 0.5 codes of
 comes back through the fp64 inverse is off by at most 1.5 (1/ys + k/cs) of full scale, k the inverse's largest chroma
 gain row sum: B with 2(1-Kb) = 1.8556 under BT.709.  In 8-bit RGB levels, limited range: 255 * 1.5 * (1/219 + 1.8556/224)
 / 2^(d-8) = 4.92 / 2^(d-8): 1.23 at 10 bits, 0.31 at 12 (the full-range figures are smaller)."""
+import ctypes as C
 import io
-import os
 from types import SimpleNamespace
 
 import numpy as np
@@ -18,7 +18,10 @@ import pytest
 import torch
 
 from tests import yuv_depth_ref as R
+from tests import yuv_planar_ref as P
 from tests import yuv_ref as R8
+from tests.test_yuv_cpu import TABLES as TABLES_8
+from tecogan_pytorch_amd import _lib as L
 from tecogan_pytorch_amd.data.y4m import Y4MError, Y4MReader, Y4MWriter, frame_bytes
 from tecogan_pytorch_amd.models.base_model import front_pad_stream
 from tecogan_pytorch_amd.models.networks import Yuv420, yuv420_planes
@@ -26,8 +29,8 @@ from tecogan_pytorch_amd.models.networks import frnet_infer as F
 from tecogan_pytorch_amd.models.networks import tecogan_nets as N
 from tecogan_pytorch_amd.models.networks.stream import Resize
 
-ROOT_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEPTH_CONFIGS = [(d, m, fr) for d in R.DEPTHS for (m, fr) in R.CONFIGS]
+ALL_CONFIGS = [(d, m, fr) for d in P.DEPTHS for (m, fr) in P.CONFIGS]           # 3 depths x 3 matrices x 2 ranges
 
 
 def round_trip_bound(depth):
@@ -36,16 +39,48 @@ def round_trip_bound(depth):
 
 
 # ---------------------------------------------------------------- tables
-@pytest.mark.parametrize('depth,matrix,full', DEPTH_CONFIGS)
+def _reference_table(depth, matrix, full):
+    """(computed from Kr and Kb, pinned) by the specification that owns the combination: section 7e's at 8 bits, section
+    7k's at 10 and 12, section 7l's for BT.2020."""
+    if matrix == 'bt2020':
+        return P.q_table(depth, matrix, full), P.BT2020_TABLES[(depth, full)]
+    if depth == 8:
+        return R8.q_table(matrix, full), TABLES_8[(matrix, full)]
+    return R.q_table(depth, matrix, full), R.TABLES[(depth, matrix, full)]
+
+
+@pytest.mark.parametrize('depth,matrix,full', ALL_CONFIGS)
 def test_q_tables_follow_from_kr_and_kb_and_are_the_kernels(depth, matrix, full):
-    t = R.q_table(depth, matrix, full)
-    assert t.tolist() == R.TABLES[(depth, matrix, full)]
-    src = open(os.path.join(ROOT_DIR, 'tecogan-pytorch_amd', 'csrc', 'tg_yuv.hip')).read()
-    for row in t.tolist():
-        assert '{%d, %d, %d}' % tuple(row) in src, row
-    # every sum fits the 64-bit accumulator with room to spare, and not a 32-bit one
-    assert int(np.abs(t).sum(1).max()) * 8 * 65535 + (4096 << 27) < 2 ** 62
-    assert int(t[0].sum()) * 65535 > 2 ** 31
+    """What the library hands to its kernels (tg_yuv_tables: forward_table and inverse_table, no device call) against the
+    three specifications, all 18 combinations."""
+    t, pinned = _reference_table(depth, matrix, full)
+    assert t.tolist() == pinned
+    q, f = (C.c_int * 12)(), (C.c_float * 5)()
+    L.check(L.lib().tg_yuv_tables(depth, L.YUV_PLANAR_MATRIX[matrix], int(full), q, f), 'tg_yuv_tables')
+    yo, ys, cs, mid = P.scales(depth, full)
+    assert [list(q[0:3]), list(q[3:6]), list(q[6:9])] == t.tolist()
+    assert list(q[9:12]) == [yo, mid, (1 << depth) - 1]
+    # the five gains of the input direction: the fp64 expressions, rounded once to fp32
+    kr, kb = P.KR_KB[matrix]
+    kg, cs16 = 1.0 - kr - kb, 16.0 * cs
+    want = np.array([1.0 / ys, 2.0 * (1.0 - kr) / cs16, -(2.0 * kb * (1.0 - kb) / kg) / cs16,
+                     -(2.0 * kr * (1.0 - kr) / kg) / cs16, 2.0 * (1.0 - kb) / cs16], np.float64).astype(np.float32)
+    assert np.array_equal(np.array(list(f), np.float32), want)      # ky, rv, gu, gv, bu
+    if depth == 8:
+        # 8 taps of 255 at most (4:2:0, left) and the rounding term fit the 32-bit accumulator
+        assert int(np.abs(t).sum(1).max()) * 8 * 255 + (128 << 19) + (1 << 18) < 2 ** 31
+    else:
+        # every sum fits the 64-bit accumulator with room to spare, and not a 32-bit one
+        assert int(np.abs(t).sum(1).max()) * 8 * 65535 + (4096 << 27) < 2 ** 62
+        assert int(t[0].sum()) * 65535 > 2 ** 31
+
+
+@pytest.mark.parametrize('bad', [(9, 0, 0), (16, 1, 1), (8, 3, 0), (10, -1, 0), (12, 2, 2), (8, 0, -1)])
+def test_the_table_query_refuses_what_no_kernel_takes(bad):
+    q, f = (C.c_int * 12)(), (C.c_float * 5)()
+    assert L.lib().tg_yuv_tables(*bad, q, f) == L.lib().tg_yuv_tables(8, 0, 0, None, f) == \
+        L.lib().tg_yuv_tables(8, 0, 0, q, None) == L.TG_E_ARG
+    assert list(q) == [0] * 12 and list(f) == [0.0] * 5
 
 
 def test_scales_at_depth_8_are_section_7e_s():

@@ -7,13 +7,16 @@ there is no fallback.
 1. kernels: every form of the three entry points alone -- layout x siting x wide / element-wide (the base one sample
    off), 8 and 10 bits -- n = 1 at 536x1280 (the output direction) and at 134x320 (the input direction), --launches
    launches back to back, against a device copy that moves the same bytes (half of read + written each way).
-2. templates against the kernels they restate: the 4:2:0 instantiations and the four existing entry points alternate in
-   the same regions; reported: whether the new median lies inside the old min-max.  Nothing is asserted.
-3. stream: FRNet.infer_stream fed host frames one by one, every chunk copied: 420 -> 420 with a Yuv420, 420 -> 444,
-   422p10 -> 422p10 and 444 -> 444 with a Yuv.
-4. untouched (with --parent-root DIR, a built checkout of the parent commit): the uint8 RGB stream and the Yuv420 stream
-   on this tree and on the parent's, in child processes that alternate.  Acceptance is section 7d's rule: the new median
-   lies inside the parent's min-max.
+2. the four 4:2:0 entry points (`old_*`: their own host path over the same kernels), wide and element-wide, alternate
+   with the planar ones in the same regions; reported: whether the planar median lies inside the old min-max.  With
+   --parent-root the parent's library is loaded beside this one and its four entry points (`parent_old_*`) alternate in
+   the same regions too; reported per form: whether this tree's median lies inside the parent's min-max.  Nothing is
+   asserted.
+3. stream: FRNet.infer_stream fed host frames one by one, every chunk copied: 420 -> 420 with a Yuv420 at 8 bits and
+   with out_depth = 10, 420 -> 444, 422p10 -> 422p10 and 444 -> 444 with a Yuv.
+4. against the parent (with --parent-root DIR, a built checkout of the parent commit): the uint8 RGB stream (the control)
+   and the two Yuv420 streams on this tree and on the parent's, in child processes that alternate.  Acceptance is section
+   7d's rule: the new median lies inside the parent's min-max.
 
     python tools/time_yuv_planar.py [--repeats 7] [--parent-root DIR] [--out profiles/yuv_planar.json]
 """
@@ -68,7 +71,8 @@ def make_net(root):
 
 
 def child(root, steps, regions):
-    """The two untouched streams on the tree at `root`: prints one JSON line with the seconds of every region."""
+    """The control and the two Yuv420 streams on the tree at `root`: prints one JSON line with the seconds of every
+    region."""
     import numpy as np
     import torch
     net = make_net(root)
@@ -88,7 +92,8 @@ def child(root, steps, regions):
                 n += chunk.copy().shape[0]
             assert n == steps
         return go
-    forms = (('rgb_u8', run(rgb_clip)), ('yuv420', run(yuv_clip, yuv=spec)))
+    forms = (('rgb_u8', run(rgb_clip)), ('yuv420', run(yuv_clip, yuv=spec)),
+             ('yuv420_out10', run(yuv_clip, yuv=Yuv420(H, W, out_depth=10))))
     for _ in range(2):
         for _, fn in forms:
             fn()
@@ -175,15 +180,26 @@ def main():
                 add('in10_' + tag, lambda c=K[chroma], s=sc, o=o2: lib.tg_yuv_planar_to_rgb_f32(
                     yuv_b.data_ptr() + o, rgb_f.data_ptr(), 1, H, W, c, 10, 1, 0, s, st), 2 * ns_i, 12 * H * W)
     ns_o, ns_i = samples(HH, WW, '420'), samples(H, W, '420')
-    for siting, sc in (('center', 0), ('left', 1)):                  # the four existing entry points, wide
-        add(f'old_out8_420_{siting}_wide', lambda s=sc: lib.tg_rgb_u8_to_yuv420(
-            rgb_8.data_ptr(), yuv_b.data_ptr(), 1, HH, WW, 1, 0, s, st), 3 * HH * WW, ns_o)
-        add(f'old_out10_420_{siting}_wide', lambda s=sc: lib.tg_rgb_f32_to_yuv420p16(
-            rgb_f.data_ptr(), yuv_b.data_ptr(), 1, HH, WW, 10, 1, 0, s, st), 12 * HH * WW, 2 * ns_o)
-        add(f'old_in8_420_{siting}_wide', lambda s=sc: lib.tg_yuv420_to_rgb_f32(
-            yuv_b.data_ptr(), rgb_f.data_ptr(), 1, H, W, 1, 0, s, st), ns_i, 12 * H * W)
-        add(f'old_in10_420_{siting}_wide', lambda s=sc: lib.tg_yuv420p16_to_rgb_f32(
-            yuv_b.data_ptr(), rgb_f.data_ptr(), 1, H, W, 10, 1, 0, s, st), 2 * ns_i, 12 * H * W)
+    libs = {'old_': lib}
+    if args.parent_root:                                             # the parent's library beside this one, same process
+        import ctypes
+        plib = ctypes.CDLL(os.path.join(os.path.abspath(args.parent_root), 'tecogan-pytorch_amd', 'libtecogan_hip.so'))
+        for fn in ('tg_rgb_u8_to_yuv420', 'tg_rgb_f32_to_yuv420p16', 'tg_yuv420_to_rgb_f32', 'tg_yuv420p16_to_rgb_f32'):
+            getattr(plib, fn).restype, getattr(plib, fn).argtypes = L.SIGNATURES[fn]
+        libs['parent_old_'] = plib
+    for pre, lb in libs.items():                                     # the four 4:2:0 entry points, wide and element-wide
+        for siting, sc in (('center', 0), ('left', 1)):
+            for wide in (True, False):
+                tag = f'420_{siting}_{"wide" if wide else "elem"}'
+                o1, o2 = (0, 0) if wide else (1, 2)
+                add(f'{pre}out8_{tag}', lambda s=sc, o=o1, lb=lb: lb.tg_rgb_u8_to_yuv420(
+                    rgb_8.data_ptr(), yuv_b.data_ptr() + o, 1, HH, WW, 1, 0, s, st), 3 * HH * WW, ns_o)
+                add(f'{pre}out10_{tag}', lambda s=sc, o=o2, lb=lb: lb.tg_rgb_f32_to_yuv420p16(
+                    rgb_f.data_ptr(), yuv_b.data_ptr() + o, 1, HH, WW, 10, 1, 0, s, st), 12 * HH * WW, 2 * ns_o)
+                add(f'{pre}in8_{tag}', lambda s=sc, o=o1, lb=lb: lb.tg_yuv420_to_rgb_f32(
+                    yuv_b.data_ptr() + o, rgb_f.data_ptr(), 1, H, W, 1, 0, s, st), ns_i, 12 * H * W)
+                add(f'{pre}in10_{tag}', lambda s=sc, o=o2, lb=lb: lb.tg_yuv420p16_to_rgb_f32(
+                    yuv_b.data_ptr() + o, rgb_f.data_ptr(), 1, H, W, 10, 1, 0, s, st), 2 * ns_i, 12 * H * W)
     copies = {}
     for name, m in meta.items():
         half = (m['bytes_read'] + m['bytes_written']) // 2
@@ -214,13 +230,22 @@ def main():
                            'new_median_inside_old_min_max': bool(ks[name]['min'] <= ks[new]['median'] <= ks[name]['max']),
                            'ratio_new_over_old': ks[new]['median'] / ks[name]['median']}
     result['templates_against_existing_kernels'] = versus
+    fold = {name[7:]: {'this_us': ks[name[7:]], 'parent_us': ks[name],
+                       'this_median_inside_parent_min_max': bool(ks[name]['min'] <= ks[name[7:]]['median'] <= ks[name]['max']),
+                       'ratio_this_over_parent': ks[name[7:]]['median'] / ks[name]['median']}
+            for name in meta if name.startswith('parent_')}
+    if fold:
+        result['old_entry_points_against_parent'] = fold
+        print(json.dumps({k: (v['this_median_inside_parent_min_max'], round(v['ratio_this_over_parent'], 3))
+                          for k, v in fold.items()}), flush=True)
     print(json.dumps({k: (round(v['us_per_launch']['median'], 3), round(v['ratio_over_copy'], 3)) for k, v in meta.items()}), flush=True)
     print(json.dumps(versus), flush=True)
     del rgb_f, rgb_8, yuv_b, copies
 
     # -- 3. the stream -----------------------------------------------------------------------------------------------------
     rng = np.random.default_rng(1234)
-    specs = {'yuv420_to_420_Yuv420': Yuv420(H, W), 'yuv_420_to_444': Yuv(H, W, out_chroma='444'),
+    specs = {'yuv420_to_420_Yuv420': Yuv420(H, W), 'yuv420_to_420p10_Yuv420': Yuv420(H, W, out_depth=10),
+             'yuv_420_to_444': Yuv(H, W, out_chroma='444'),
              'yuv_422p10_to_422p10': Yuv(H, W, chroma='422', depth=10), 'yuv_444_to_444': Yuv(H, W, chroma='444')}
     clips = {k: (rng.integers(0, 256, (args.steps, s.frame_bytes), dtype=np.uint8) if s.depth == 8 else
                  rng.integers(0, 1024, (args.steps, s.frame_bytes // 2), dtype=np.uint16).view(np.uint8))
@@ -244,10 +269,10 @@ def main():
     result['stream']['bytes_per_hr_frame'] = {k: s.out_frame_bytes(SCALE) for k, s in specs.items()}
     print(json.dumps({k: result['stream'][k] for k in ('fps_median', 'fps_min', 'fps_max')}), flush=True)
 
-    # -- 4. the untouched paths, this tree against the parent's ---------------------------------------------------------------
+    # -- 4. the streams, this tree against the parent's -------------------------------------------------------------------------
     if args.parent_root:
         roots = {'parent': os.path.abspath(args.parent_root), 'this': HERE}
-        secs = {'rgb_u8': {k: [] for k in roots}, 'yuv420': {k: [] for k in roots}}
+        secs = {path: {k: [] for k in roots} for path in ('rgb_u8', 'yuv420', 'yuv420_out10')}
         del net
         torch.cuda.empty_cache()
         for _ in range(args.child_rounds):
@@ -260,17 +285,17 @@ def main():
                     sys.exit('time_yuv_planar.py: the %s child failed (%d): %s' % (k, r.returncode, r.stderr[-2000:]))
                 for path, ts in json.loads(line[0][6:]).items():
                     secs[path][k] += ts
-        result['untouched'] = {}
+        result['against_parent'] = {}
         for path, by_tree in secs.items():
             un = fps_summary(by_tree, args.steps)
             un['this_median_inside_parent_min_max'] = bool(un['fps_min']['parent'] <= un['fps_median']['this'] <= un['fps_max']['parent'])
             un['ratio_this_over_parent'] = un['fps_median']['this'] / un['fps_median']['parent']
-            result['untouched'][path] = un
-        result['untouched']['protocol'] = ('%d child processes per tree, alternating parent / this, each warmed and timing %d '
-                                           'alternating regions of the uint8 RGB stream and of the Yuv420 stream'
+            result['against_parent'][path] = un
+        result['against_parent']['protocol'] = ('%d child processes per tree, alternating parent / this, each warmed and timing %d '
+                                           'alternating regions of the uint8 RGB stream and of the two Yuv420 streams'
                                            % (args.child_rounds, args.child_regions))
         print(json.dumps({p: {k: u[k] for k in ('fps_median', 'fps_min', 'fps_max', 'this_median_inside_parent_min_max')}
-                          for p, u in result['untouched'].items() if p != 'protocol'}), flush=True)
+                          for p, u in result['against_parent'].items() if p != 'protocol'}), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as f:
         json.dump(result, f, indent=1)

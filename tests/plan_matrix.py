@@ -1,5 +1,6 @@
 """The case table of the frame-plan matrix (tests/test_plan_matrix_cpu.py, tests/test_hip_plan_matrix.py): one case per
-launch-list decision of `step_impl` (csrc/tg_api.hip), each as small as the branch allows.  Importable without a GPU.
+launch-list decision of the frame plan (`choose` and `Emit::conv`, csrc/tg_api.hip), each as small as the branch allows.
+Importable without a GPU.
 
 A case is (name, nf, nb, scale, degradation, n, h, w, precision, env, expect) plus `extra`:
 
@@ -72,7 +73,7 @@ def body_tiles(c):
 
 
 def body_layers(c):
-    """Layers of a one-launch body (nchain of step_impl)."""
+    """Layers of a one-launch body (Choices::nchain of csrc/tg_api.hip)."""
     return 1 + 2 * c.nb if c.scale == 4 else 2 * c.nb
 
 

@@ -15,6 +15,9 @@ Per case, on a fresh plan:
              the project's own (top of tests/test_hip_parity.py), 1e-4 for the frame, 2e-4 for the flow -- not fitted to
              this run; tests/test_plan_matrix_cpu.py shows what they catch.
   uint8      the bytes equal oracle.float32_to_uint8 of the fp32 frame the same call wrote.
+  digest     SHA-256 over the bytes of both fp32 frames, both flows (a flow-only case: its flows and frames) and the uint8
+             frames where the case asks for them: recorded, not asserted -- two libraries compute the same when a run
+             of each gives the same digests (profiles/frame_plan_refactor.json is such a comparison).
   phases     (flagged cases) tg_frnet_step_phase(1, slot) + (2, slot), both slots, and tg_frnet_step_srnet fed from a
              flow-only plan of one pair, equal tg_frnet_step bit for bit; the flow-only cases feed tg_frnet_step_srnet
              from a batched flow pass, every frame within the bounds above.
@@ -26,6 +29,7 @@ Every figure is printed before anything is asserted; TG_PLAN_MATRIX_JSON=<path> 
 """
 import contextlib
 import ctypes
+import hashlib
 import json
 import os
 import subprocess
@@ -168,6 +172,15 @@ def err(a, b):
     return (a.detach().cpu().double() - b.detach().cpu().double()).abs().max().item()
 
 
+def digest(*tensors):
+    """SHA-256 over the bytes of the tensors, in this order (None: not asked for)."""
+    h = hashlib.sha256()
+    for t in tensors:
+        if t is not None:
+            h.update(t.detach().cpu().contiguous().numpy().tobytes())
+    return h.hexdigest()
+
+
 def clips(c, frames):
     return [smooth_clip(frames, 3, c.h, c.w, seed=11 + i) for i in range(c.n)]
 
@@ -215,6 +228,7 @@ def run_frames(c):
     rec['payload_words'] = payload_words(out0) + payload_words(out1) + payload_words(flow0) + payload_words(flow1)
     rec['repeat_equal'] = bool(torch.equal(out0.view(torch.int32), again.view(torch.int32)) and
                                (not want_u8 or torch.equal(b0, b0b)))
+    rec['digest'] = digest(out0, out1, flow0, flow1, b0, b1)
     if want_u8:
         rec['u8_mismatches'] = u8_mismatches(b0, out0) + u8_mismatches(b1, out1)
     if c.precision == 'fp32':
@@ -277,6 +291,7 @@ def run_flow_only(c):
     rec['finite'] = bool(torch.isfinite(flows).all().item() and all(torch.isfinite(o).all().item() for o in outs))
     rec['payload_words'] = payload_words(flows) + sum(payload_words(o) for o in outs)
     rec['repeat_equal'] = bool(torch.equal(flows.view(torch.int32), again.view(torch.int32)))
+    rec['digest'] = digest(flows, *outs)
     fe, ee = [], []
     with torch.no_grad():
         for j in range(k):
@@ -297,6 +312,7 @@ def check_record(c, rec):
         c.name, rec['wall_s'], ' '.join('%.2e' % e for e in rec.get('frame_err', [])),
         ' '.join('%.2e' % e for e in rec.get('flow_err', [])), rec['chain_state']))
     print('    launches: ' + ', '.join('%s=%d' % kv for kv in rec['stats'].items() if kv[1]))
+    print('    digest: ' + rec['digest'])
     got = {k: rec['stats'][k] for k in c.expect}
     assert got == c.expect, (c.name, 'launch kinds', got, c.expect)
     body = c.extra['frame_body'] if c.extra.get('fnet_only') else c.extra['body']
@@ -396,7 +412,7 @@ def records():
     yield get
     path = os.environ.get('TG_PLAN_MATRIX_JSON')
     if path:
-        keep = ('stats', 'chain_state', 'frame_err', 'flow_err', 'wall_s', 'workspace_floats')
+        keep = ('stats', 'chain_state', 'frame_err', 'flow_err', 'wall_s', 'workspace_floats', 'digest')
         rows = {}
         for c in M.CASES:
             if c.name in done and 'error' not in done[c.name]:

@@ -634,6 +634,28 @@ int tg_rgb_f32_to_yuv_planar16(const float* rgb_chw, uint16_t* yuv, int n, int H
  *   f: the fp32 gains of the input direction's matrix step: ky = 1/ys, then rv, gu, gv, bu per sixteenth of a code */
 int tg_yuv_tables(int depth, int matrix, int full_range, int q[12], float f[5]);
 
+/* Motion-adaptive deinterlacing of planar YUV (the reference has no counterpart): interlaced
+ * frames in, progressive frames out, same layout and sample type as tg_yuv_planar_to_rgb_f32 takes.  The
+ * specification is tests/deinterlace_ref.py and the samples are equal: an edge-directed line average over three
+ * directions, bounded by a three-field motion measure; exact integers, no parameters, causal (only the frame before).
+ *   A frame holds two fields, p = 0 the earlier.  tff = 1: the earlier field owns the even rows.  par = p ^ (tff ? 0 : 1).
+ *   Every plane alike (ph x pw).  Row r with r % 2 == par: cur[r].  A missing row r: a = cur[r-1] (cur[r+1] at the top),
+ *   b = cur[r+1] (cur[r-1] at the bottom), x indices clamped into the row; for d = 0, -1, +1:
+ *   score_d = sum_{e=-1..1} |a[x+d+e] - b[x-d+e]|, candidate (a[x+d] + b[x-d] + 1) >> 1, sp = the candidate of the
+ *   smallest score (a later d only when strictly smaller).  Without a frame before: sp.  Else tp = (r, x) of the field
+ *   one back (cur for p = 1, the frame before for p = 0), m = max(|a[x] - prev a-row[x]|, |b[x] - prev b-row[x]|),
+ *   out = min(max(sp, tp - m), tp + m).  A 16-bit word above 2^depth - 1 is read as 2^depth - 1.
+ * frames: k + 1 frames, the frame before and then the k frames (with has_prev == 0 the first is never read and the
+ * outputs of frames[1] are spatial only); out: cnt frames.  Output j is field f = first_field + j * step counted from
+ * frames[1]: frame 1 + f / 2, p = f % 2.  step 1 (field rate) | 2 (one output per frame); first_field 0 | 1; the last
+ * field lies inside the k frames.  h even and >= 4 (a multiple of 4 at 420), w >= 2.  ONE launch for all planes and
+ * frames; 16-byte accesses per plane where its width, its place in a frame and both bases are multiples of 16 bytes,
+ * sample by sample otherwise, with equal results.  A null pointer, an unknown enum, a flag that is not 0 | 1, a
+ * 16-bit pointer that is not 2-byte aligned, k or cnt < 1 or a field window outside the frames is TG_E_ARG, without a
+ * launch; more than 2 GiB on either side, or cnt above 65535, is TG_E_SHAPE. */
+int tg_deinterlace_planar(const void* frames, void* out, int k, int h, int w, int chroma, int depth, int tff,
+                          int has_prev, int first_field, int step, int cnt, tg_stream_t stream);
+
 /* PNG files written on the device: what the reference's save_sequence does with cv2.imwrite
  * (codes/utils/data_utils.py), without the host's zlib.  The specification is tests/png_ref.py and the bytes are
  * equal: 8-bit RGB, no interlace, one IDAT; per row the filter type (adaptive: the one of None, Sub, Up, Average,

@@ -61,14 +61,17 @@ def _refusal(v, depths, chromas):
     return Y4MError(f'y4m: C{v}: {why} (supported: {", ".join(ok)})')
 
 
-def parse_header(line, depths=(8,), chromas=('420',)):
-    """The header line (bytes, without the newline) -> dict(w, h, tags, siting, full_range, depth, chroma).  `tags` keeps the F,
+def parse_header(line, depths=(8,), chromas=('420',), interlaced=False):
+    """The header line (bytes, without the newline) -> dict(w, h, tags, siting, full_range, depth, chroma, interlace).  `tags` keeps the F,
     A, C and X tags as written, for the writer; full_range is True / False from XCOLORRANGE, None when the header has
     none.  depths: the bits per sample the caller takes; C420p10 / C420p12 are accepted only when theirs is among them,
     and then siting is None (the tag carries none).  chromas: the layouts the caller takes; with '422' / '444' among
     them C422 / C444 and their p10 / p12 forms (per allowed depth) are accepted, chroma says which, siting is None.  With
-    the default every header is accepted or refused as a 4:2:0-only reader does."""
+    the default every header is accepted or refused as a 4:2:0-only reader does.  interlaced=True: It (top field first)
+    and Ib (bottom field first) are taken as well and `interlace` is 't' | 'b' | 'p' (DESIGN.md section 7o); Im (mixed)
+    stays refused.  With the default anything but Ip is refused and `interlace` is 'p'."""
     depths, chromas = tuple(depths), tuple(chromas)
+    interlace = 'p'
     parts = line.decode('ascii', 'replace').split(' ')
     if parts[0] != MAGIC.decode():
         raise Y4MError('y4m: the stream does not start with YUV4MPEG2')
@@ -83,7 +86,11 @@ def parse_header(line, depths=(8,), chromas=('420',)):
         elif k == 'H':
             h = int(v)
         elif k == 'I':
-            if v != 'p':
+            if interlaced and v in ('t', 'b'):
+                interlace = v
+            elif interlaced and v == 'm':
+                raise Y4MError('y4m: Im: mixed progressive and interlaced material is not supported (Ip, It or Ib)')
+            elif v != 'p':
                 raise Y4MError(f'y4m: I{v}: interlaced material is not supported (progressive Ip only)')
         elif k == 'C':
             planar = PLANAR_OF_TAG.get(v)
@@ -120,7 +127,7 @@ def parse_header(line, depths=(8,), chromas=('420',)):
         raise Y4MError(f'y4m: C{ctag or "420"}: 4:2:0, and the reader was opened for {chromas}')
     return {'w': w, 'h': h, 'tags': tags,
             'siting': SITING_OF_TAG[ctag or '420'] if depth == 8 and chroma == '420' else None,
-            'full_range': full, 'depth': depth, 'chroma': chroma}
+            'full_range': full, 'depth': depth, 'chroma': chroma, 'interlace': interlace}
 
 
 def frame_bytes(h, w, depth=8, chroma='420'):
@@ -136,17 +143,18 @@ class Y4MReader:
     default; with (8, 10, 12) C420p10 and C420p12 streams are read too -- .depth says which, .siting is None for them
     and a frame is the file's bytes, two per sample.  chromas: the layouts that are taken, ('420',) by default; with
     ('420', '422', '444') C422 / C444 streams (and their p10 / p12 forms, per depth) are read too -- .chroma says which,
-    .siting is None for them."""
+    .siting is None for them.  interlaced=True: It and Ib streams are read too -- .interlace is 't' | 'b' | 'p', and a
+    frame holds two fields (FRNet.infer_stream(deinterlace=...) takes them); by default they are refused."""
 
-    def __init__(self, fileobj, depths=(8,), chromas=('420',)):
+    def __init__(self, fileobj, depths=(8,), chromas=('420',), interlaced=False):
         self.f = fileobj
         line = _read_line(fileobj)
         if line is None:
             raise Y4MError('y4m: empty stream')
-        self.header = parse_header(line, depths, chromas)
+        self.header = parse_header(line, depths, chromas, interlaced)
         self.w, self.h = self.header['w'], self.header['h']
         self.siting, self.full_range, self.depth = self.header['siting'], self.header['full_range'], self.header['depth']
-        self.chroma = self.header['chroma']
+        self.chroma, self.interlace = self.header['chroma'], self.header['interlace']
         self.frame_bytes = frame_bytes(self.h, self.w, self.depth, self.chroma)
         self.frames_read = 0
         self._buf = np.empty(self.frame_bytes, np.uint8)
@@ -179,6 +187,22 @@ class Y4MReader:
         return self._buf
 
 
+def scale_rate_tag(tag, num, den):
+    """The F tag `Fn:d` (frames per second) times num / den, reduced.  F0:0 (unknown) stays as it is."""
+    import math
+    try:
+        n, d = (int(v) for v in tag[1:].split(':'))
+    except ValueError:
+        raise Y4MError(f'y4m: {tag!r}: the frame rate is Fn:d') from None
+    if num < 1 or den < 1:
+        raise Y4MError(f'y4m: the frame rate is scaled by a positive fraction, got {num}/{den}')
+    if n <= 0 or d <= 0:
+        return tag
+    n, d = n * num, d * den
+    g = math.gcd(n, d)
+    return f'F{n // g}:{d // g}'
+
+
 def scale_aspect_tag(tag, num, den):
     """The A tag `An:d` (pixel aspect ratio) times num / den, reduced.  A0:0 (unknown) stays as it is."""
     import math
@@ -205,9 +229,13 @@ class Y4MWriter:
     `siting` ('center' | 'left') in place of the input's; otherwise the input's tags as they are.  chroma '422' | '444':
     frames of that layout; the C tag becomes C422 / C444 (C422p10 ... above 8 bits) with its upper-cased XYSCSS twin
     (XYSCSS=422, 444P10, ...: the form ffmpeg is remembered to write; not verified against an ffmpeg build).  chroma
-    None | '420' after a 4:2:2 or 4:4:4 input: the 8-bit C tag is the one of `siting`, as after a 10- or 12-bit input."""
+    None | '420' after a 4:2:2 or 4:4:4 input: the 8-bit C tag is the one of `siting`, as after a 10- or 12-bit input.
+    rate_scale (num, den): the stream has num / den times the input's frames per second (2, 1 after deinterlacing at
+    field rate) and the F tag is rewritten accordingly (scale_rate_tag); a header without an F tag gets none.  The
+    writer writes Ip whatever the input was: deinterlaced frames are progressive."""
 
-    def __init__(self, fileobj, W, H, header_of_input=None, aspect_scale=None, depth=8, siting=None, chroma=None):
+    def __init__(self, fileobj, W, H, header_of_input=None, aspect_scale=None, depth=8, siting=None, chroma=None,
+                 rate_scale=None):
         if W < 2 or H < 2:
             raise Y4MError(f'y4m: W={W} H={H}')
         if depth not in (8, 10, 12):
@@ -243,6 +271,8 @@ class Y4MWriter:
                 tags.insert(1 + max(i for i, t in enumerate(tags) if t.startswith('C')), 'XYSCSS=' + ctag.upper())
         if aspect_scale is not None:
             tags = [scale_aspect_tag(t, *aspect_scale) if t.startswith('A') else t for t in tags]
+        if rate_scale is not None:
+            tags = [scale_rate_tag(t, *rate_scale) if t.startswith('F') else t for t in tags]
         self._write_all((' '.join(['YUV4MPEG2', f'W{W}', f'H{H}'] + tags + ['Ip']) + '\n').encode('ascii'))
 
     def _write_all(self, data):

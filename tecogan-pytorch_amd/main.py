@@ -25,6 +25,10 @@ above 8 the frames are converted from the float result, not from the rounded 8-b
 taken too, `--output-chroma 420|422|444` (default: the input's) sets the layout written -- 444 keeps every chroma sample
 the network computed -- and `--yuv-matrix bt2020` is the non-constant-luminance BT.2020 matrix.
 
+`--deinterlace auto|tff|bff` (y4m input) takes `It` / `Ib` streams and deinterlaces them on the
+GPU in front of the generator, at field rate (the header's `F` doubled) or with `--deinterlace-rate frame` at the
+input's; without it an interlaced header is refused.  The header written says `Ip`.
+
 `--scene-cut` (both forms of `infer`) restarts the recurrence at scene cuts, detected on the
 device; the cut frames are listed on stderr at the end, never on stdout.
 
@@ -120,7 +124,20 @@ def parse_args(argv=None):
                         'section 7j: antialiased bicubic, exact integers); each side within [1/4, 4] of the super-resolved '
                         'one, both even for y4m.  A y4m header gets the new size, and a pixel aspect ratio that keeps the '
                         'display aspect when the shape changes')
+    p.add_argument('--deinterlace', dest='deinterlace', type=str, default='off', choices=['auto', 'off', 'tff', 'bff'],
+                   help='y4m input: deinterlace on the GPU in front of the generator (DESIGN.md section 7o: edge-directed '
+                        'line average bounded by a three-field motion measure; not compared with yadif or bwdif).  off: an '
+                        "interlaced header is refused; auto: the header's field order, a progressive stream is left alone; "
+                        'tff | bff: that field order whatever the header says')
+    p.add_argument('--deinterlace-rate', dest='deinterlace_rate', type=str, default=None, choices=['field', 'frame'],
+                   help='--deinterlace: field (default): two output frames per input frame and twice the frame rate in the '
+                        "header; frame: the input's rate, the earlier field's frame only")
     args = p.parse_args(argv)
+    y4m_input = bool(args.mode == 'infer' and args.input and (args.input == '-' or os.path.isfile(args.input)))
+    if args.deinterlace != 'off' and not y4m_input:
+        p.error('--deinterlace belongs to --mode infer with y4m input (a y4m file, or - for stdin)')
+    if args.deinterlace_rate is not None and args.deinterlace == 'off':
+        p.error('--deinterlace-rate belongs to --deinterlace auto|tff|bff')
     if args.output_size is not None and args.mode != 'infer':
         p.error('--output-size belongs to --mode infer')
     if args.output_depth is not None and not (args.mode == 'infer' and args.input and
@@ -505,7 +522,7 @@ def infer(opt, input_dir, output_dir, scene_cut=None, png_encoder='pillow', outp
 
 
 def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None, output_size=None, siting='left',
-              output_depth=None, output_chroma=None):
+              output_depth=None, output_chroma=None, deinterlace='off', deinterlace_rate=None):
     """--mode infer on raw video: the y4m stream `src` (a binary file object) through VSRModel.infer_stream(yuv=...)
     into the y4m stream `dst`, in order.  The output header carries the scaled size and the input's F, A, C and X tags.
     Each chunk is written out of the ring slot before the generator is advanced; nothing is held beyond it.
@@ -514,11 +531,21 @@ def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None, out
     7k): `siting` stands in where the header carries none.  output_depth 8 | 10 | 12 | None (the input's): bits per
     sample of the output; its C and XYSCSS tags follow.  The input may be C422 / C444 at any of the three depths, and
     output_chroma '420' | '422' | '444' | None (the input's) is the layout written; matrix may be
-    'bt2020'.  A 4:2:0 clip with a 4:2:0 output and BT.601 / BT.709 runs as a Yuv420, everything else as a Yuv.  Returns
+    'bt2020'.  A 4:2:0 clip with a 4:2:0 output and BT.601 / BT.709 runs as a Yuv420, everything else as a Yuv.
+    deinterlace 'off' | 'auto' | 'tff' | 'bff' (DESIGN.md section 7o): with 'off' an It / Ib header is refused by the
+    reader; 'auto' deinterlaces an It / Ib stream in the header's field order and leaves an Ip stream alone; 'tff' / 'bff'
+    deinterlace in that order whatever the header says.  deinterlace_rate 'field' (None: the same) | 'frame': at field
+    rate two frames are written per frame read and the header's F tag is doubled.  The header written says Ip.  Returns
     the number of frames written."""
+    import sys
     from .data.y4m import Y4MReader, Y4MWriter
-    from .models.networks import Yuv, Yuv420
-    reader = Y4MReader(src, depths=(8, 10, 12), chromas=('420', '422', '444'))
+    from .models.networks import Deinterlace, Yuv, Yuv420
+    if deinterlace not in ('off', 'auto', 'tff', 'bff'):
+        raise ValueError(f'deinterlace is off, auto, tff or bff, got {deinterlace!r}')
+    reader = Y4MReader(src, depths=(8, 10, 12), chromas=('420', '422', '444'), interlaced=deinterlace != 'off')
+    order = {'t': 'tff', 'b': 'bff', 'p': None}[reader.interlace] if deinterlace == 'auto' else \
+        None if deinterlace == 'off' else deinterlace
+    deint = None if order is None else Deinterlace(tff=order == 'tff', rate=deinterlace_rate or 'field')
     full = reader.full_range if yuv_range is None else yuv_range == 'full'
     common = dict(matrix=matrix, full_range=bool(full), siting=reader.siting if reader.siting is not None else siting,
                   depth=reader.depth, out_depth=output_depth)
@@ -531,6 +558,9 @@ def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None, out
     s = model.net_G.scale
     W, H = s * reader.w, s * reader.h
     kw = {} if scene_cut is None else {'scene_cut': scene_cut}
+    if deint is not None:
+        deint.check_source(spec)
+        kw['deinterlace'] = deint
     aspect = None
     if output_size is not None:
         ow, oh = output_size
@@ -543,7 +573,8 @@ def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None, out
         if oh * W != ow * H:                        # the shape changes: every pixel becomes this much wider for its height
             aspect = (W * oh, H * ow)
         W, H = ow, oh
-    writer = Y4MWriter(dst, W, H, reader.header, aspect_scale=aspect, depth=spec.od, siting=spec.siting, chroma=oc)
+    writer = Y4MWriter(dst, W, H, reader.header, aspect_scale=aspect, depth=spec.od, siting=spec.siting, chroma=oc,
+                       rate_scale=(2, 1) if deint is not None and deint.rate == 'field' else None)
     t0, k = time.time(), 0
     for chunk in model.infer_stream(reader, yuv=spec, **kw):
         for frame in chunk:
@@ -557,11 +588,15 @@ def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None, out
     print(f'y4m: {k} frames {reader.w}x{reader.h} -> {W}x{H} '
           f'({k / max(dt, 1e-9):.1f} frames/s, {spec.matrix} {"full" if spec.full_range else "limited"} range, '
           f'{spec.siting} siting, {spec.depth} -> {spec.od} bits, {reader.chroma} -> {oc})', flush=True)
+    if deinterlace != 'off':
+        print(f'y4m: deinterlace {deinterlace}: {reader.frames_read} frames in, {k} frames out, '
+              + ('progressive input left alone' if deint is None else f'{order} at {deint.rate} rate'),
+              file=sys.stderr, flush=True)
     return k
 
 
 def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range, scene_cut=None, output_size=None, siting='left',
-                  output_depth=None, output_chroma=None):
+                  output_depth=None, output_chroma=None, deinterlace='off', deinterlace_rate=None):
     """Opens the two ends of infer_y4m.  With `--output -` the y4m bytes are the ONLY thing on stdout: the descriptor
     is set aside for them and, for the length of the run, descriptor 1 and sys.stdout lead to stderr, so that neither
     a print nor a library's message can land in the stream."""
@@ -571,7 +606,7 @@ def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range, scene_cut=Non
         if output_path != '-':
             with open(output_path, 'wb') as dst:
                 return infer_y4m(opt, src, dst, matrix, yuv_range, scene_cut, output_size, siting, output_depth,
-                                 output_chroma)
+                                 output_chroma, deinterlace, deinterlace_rate)
         sys.stdout.flush()
         keep = os.dup(1)
         py_stdout = sys.stdout
@@ -580,7 +615,7 @@ def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range, scene_cut=Non
         try:
             with os.fdopen(os.dup(keep), 'wb') as dst:
                 return infer_y4m(opt, src, dst, matrix, yuv_range, scene_cut, output_size, siting, output_depth,
-                                 output_chroma)
+                                 output_chroma, deinterlace, deinterlace_rate)
         finally:
             sys.stdout = py_stdout
             os.dup2(keep, 1)
@@ -666,7 +701,8 @@ def main(argv=None):
             raise ValueError('--mode infer needs --input DIR and --output DIR (or a y4m file / - for both)')
         if args.input == '-' or os.path.isfile(args.input):
             infer_y4m_cli(opt, args.input, args.output, args.yuv_matrix, args.yuv_range, scene_cut_option(args),
-                          args.output_size, args.yuv_siting, args.output_depth, args.output_chroma)
+                          args.output_size, args.yuv_siting, args.output_depth, args.output_chroma, args.deinterlace,
+                          args.deinterlace_rate)
         else:
             infer(opt, args.input, args.output, scene_cut_option(args), args.png_encoder, args.output_size, args.png_lz77)
     elif args.mode == 'profile':

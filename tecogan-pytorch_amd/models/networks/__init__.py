@@ -1,5 +1,5 @@
 from .tecogan_nets import (FRNet, FNet, SRNet, SpatioTemporalDiscriminator,
-                           SpatialDiscriminator, Png, Resize, SceneCut, Yuv420, yuv420_planes, Yuv, yuv_planes)
+                           SpatialDiscriminator, Deinterlace, Png, Resize, SceneCut, Yuv420, yuv420_planes, Yuv, yuv_planes)
 
 
 def define_generator(opt):

@@ -1,5 +1,6 @@
-"""FRNet.infer_stream (DESIGN.md sections 7d, 7e, 7h, 7i, 7j, 7l): input parsing, the batch ring, the raw-video forms
-Yuv420 and Yuv, the PNG output form Png, the scene-cut option SceneCut, the output size Resize, one small object per input
+"""FRNet.infer_stream (DESIGN.md sections 7d, 7e, 7h, 7i, 7j, 7l, 7o): input parsing, the batch ring, the raw-video forms
+Yuv420 and Yuv, the PNG output form Png, the scene-cut option SceneCut, the output size Resize, the interlaced-input
+option Deinterlace with its batch-to-window mapping, one small object per input
 form, output form and option, and the engine that runs a clip of any length through rings of STREAM_SLOTS batches.  A
 batch's launches are frnet_infer's enqueue_batch, the ones infer_sequence(pipeline=True) enqueues.  Uses the network
 only through its attributes."""
@@ -131,6 +132,27 @@ def stream_rebatch(parts, first, later):
                 yield nb, off, piece, True
             else:
                 yield b, off, piece, False
+
+
+def stream_rebatch_sizes(parts, sizes):
+    """stream_rebatch for batches that take sizes[0], sizes[1], ... input frames (an iterable that does not end).  A batch
+    that takes none -- every frame it needs has arrived with the one before -- is handed out as (batch index, 0, None,
+    True), directly behind the batch that completed it."""
+    sizes = iter(sizes)
+    b, fill, size = 0, 0, next(sizes)
+    for _, x in parts:
+        pos, n = 0, x.shape[0]
+        while pos < n:
+            m = min(size - fill, n - pos)
+            piece, off = x[pos:pos + m], fill
+            pos, fill = pos + m, fill + m
+            full = fill == size
+            yield b, off, piece, full
+            if full:
+                b, fill, size = b + 1, 0, next(sizes)
+                while size == 0:
+                    yield b, 0, None, True
+                    b, size = b + 1, next(sizes)
 
 
 class StreamRing:
@@ -343,6 +365,65 @@ class Resize:
                 raise ValueError(f'resize: {H}x{W} frames to {self.h}x{self.w}: the ratio of either axis lies in [1/4, 4]')
 
 
+DEINTERLACE_RATES = ('field', 'frame')
+
+
+@dataclass(frozen=True)
+class Deinterlace:
+    """Interlaced input of a raw-video stream (FRNet.infer_stream(yuv=..., deinterlace=...)): the
+    items are interlaced frames, and ONE tg_deinterlace_planar per batch, on the copy stream in front of the yuv
+    launch, turns them into progressive frames -- an edge-directed line average bounded by a three-field motion measure,
+    exact integers, the samples of tests/deinterlace_ref.py.  tff: the earlier field owns the even rows (top field
+    first), else the odd ones.  rate 'field': two output frames per input frame, one per field, in time order;
+    'frame': the input's rate, the earlier field's frame only.  **Not compared with ffmpeg's yadif or bwdif; the
+    quarter-line vertical chroma offset of interlaced 4:2:0 is not modelled** (a deinterlaced frame is handed on as
+    progressive).  Frozen."""
+    tff: bool = True
+    rate: str = 'field'
+
+    def __post_init__(self):
+        if not isinstance(self.tff, (bool, np.bool_)):
+            raise ValueError(f'Deinterlace: tff is True or False, got {self.tff!r}')
+        object.__setattr__(self, 'tff', bool(self.tff))
+        if not isinstance(self.rate, str) or self.rate not in DEINTERLACE_RATES:
+            raise ValueError(f'Deinterlace: rate is one of {sorted(DEINTERLACE_RATES)}, got {self.rate!r}')
+
+    @property
+    def per_frame(self):
+        """Output frames per input frame."""
+        return 2 if self.rate == 'field' else 1
+
+    def check_source(self, yuv):
+        """ValueError unless every plane of the spec's frames has both row parities: an even h, h % 4 == 0 at 4:2:0."""
+        need = 4 if yuv.chroma == '420' else 2
+        if yuv.h % need or yuv.h < 4:
+            raise ValueError(f'Deinterlace: a 4:{yuv.chroma[1]}:{yuv.chroma[2]} frame needs a height that is a multiple of '
+                             f'{need} and at least 4, got {yuv.h}')
+
+
+def deinterlace_window(i0, cnt, rate='field'):
+    """The input frames a batch of output frames i0 .. i0 + cnt - 1 of a deinterlaced stream is made from: (lo, hi,
+    first_field).  lo is the frame BEFORE the first one that has a field in the batch (-1: there is none, the stream
+    starts), hi the last one, first_field the field of frame lo + 1 the batch starts with.  At rate 'field' output i is
+    field i % 2 of frame i // 2, so a frame's two fields may lie in two batches; at 'frame' output i is field 0 of frame
+    i.  tg_deinterlace_planar takes frames lo .. hi as its k + 1 = hi - lo + 1 frames."""
+    if rate == 'field':
+        return i0 // 2 - 1, (i0 + cnt - 1) // 2, i0 & 1
+    if rate == 'frame':
+        return i0 - 1, i0 + cnt - 1, 0
+    raise ValueError(f'deinterlace_window: rate is one of {sorted(DEINTERLACE_RATES)}, got {rate!r}')
+
+
+def deinterlace_input_sizes(first, later, rate='field'):
+    """Endlessly: the input frames that complete batch 0, 1, ... of a deinterlaced stream whose batches are `first`, then
+    `later` output frames -- those up to the batch's hi that no batch before it took."""
+    i0, cnt, have = 0, first, 0
+    while True:
+        need = deinterlace_window(i0, cnt, rate)[1] + 1 - have
+        yield need
+        i0, cnt, have = i0 + cnt, later, have + need
+
+
 class SceneCut:
     """Scene-cut option of a stream (FRNet.infer_stream(scene_cut=...)) and the caller's handle on
     what it found.  At a cut the recurrence restarts from the zero HR state, which makes the frame the frame 0 of a clip
@@ -459,7 +540,7 @@ class _DeviceF32:
             self.lr[sl, 1 + off:1 + off + piece.shape[0]].copy_(piece, non_blocking=True)
         piece.record_stream(self.copy)
 
-    def upload(self, sl, cnt):
+    def upload(self, sl, i0, cnt):
         pass
 
 
@@ -477,7 +558,7 @@ class _HostF32:
     def take(self, sl, off, piece):
         self.stage[sl, off:off + piece.shape[0]].copy_(piece)
 
-    def upload(self, sl, cnt):
+    def upload(self, sl, i0, cnt):
         self.lr[sl, 1:1 + cnt].copy_(self.stage[sl, :cnt], non_blocking=True)
 
 
@@ -497,13 +578,57 @@ class _HostBytes:
     def take(self, sl, off, piece):
         self.stage[sl, off:off + piece.shape[0]].copy_(piece)
 
-    def upload(self, sl, cnt):
+    def upload(self, sl, i0, cnt):
         self.dev_in[sl, :cnt].copy_(self.stage[sl, :cnt], non_blocking=True)
         L.check(self.fn(self.dev_in[sl].data_ptr(), self.lr[sl, 1].data_ptr(), cnt, *self.args, self.stream), self.launch)
 
 
-def _input_form(piece, c, yuv):
+class _InterlacedBytes:
+    """Input form: interlaced planar YUV frames on the host.  A batch of cnt OUTPUT frames takes
+    the input frames deinterlace_window names; the ones no earlier batch took go up as bytes through pinned staging into
+    entries 2.. of the slot's raw frames, and entries 0 and 1 are the two frames before them, copied on the device from
+    the slot of the batch before (entry e of a slot is input frame `first new frame - 2 + e`: the layout is defined here
+    and nowhere else).  Then ONE tg_deinterlace_planar writes the slot's cnt progressive frames and the spec's own
+    input launch converts those into the LR slot, all on the copy stream."""
+
+    def __init__(self, yuv, deint):
+        self.h, self.w, self.yuv, self.deint = yuv.h, yuv.w, yuv, deint
+        self.launch, self.args = yuv.input_launch()
+
+    def alloc(self, eng):
+        ns, m, fb = eng.ring.slots, eng.m, self.yuv.frame_bytes
+        self.lr, self.fn, self.stream = eng.lr, getattr(eng.lib, self.launch), eng.copy.cuda_stream
+        self.fn_deint = eng.lib.tg_deinterlace_planar
+        self.deint_args = (self.h, self.w, L.YUV_CHROMA[self.yuv.chroma], self.yuv.depth, 1 if self.deint.tff else 0)
+        self.stage = torch.empty(ns, m, fb, dtype=torch.uint8, pin_memory=True)
+        self.raw = torch.empty(ns, m + 2, fb, dtype=torch.uint8, device=eng.dev)
+        self.prog = torch.empty(ns, m, fb, dtype=torch.uint8, device=eng.dev)
+        self.fb, self.taken, self.prev_slot = fb, 0, None       # taken: input frames uploaded so far
+
+    def take(self, sl, off, piece):
+        self.stage[sl, off:off + piece.shape[0]].copy_(piece)
+
+    def upload(self, sl, i0, cnt):
+        lo, hi, first_field = deinterlace_window(i0, cnt, self.deint.rate)
+        new, at = hi + 1 - self.taken, lo - (self.taken - 2)    # at: the slot's entry of frame lo
+        if new < 0 or new > self.stage.shape[1] or at not in (0, 1):
+            raise RuntimeError(f'infer_stream: batch {i0}+{cnt} needs frames {lo}..{hi} with {self.taken} taken')
+        if self.prev_slot is not None:
+            psl, pnew = self.prev_slot
+            self.raw[sl, :2].copy_(self.raw[psl, pnew:pnew + 2], non_blocking=True)
+        if new:
+            self.raw[sl, 2:2 + new].copy_(self.stage[sl, :new], non_blocking=True)
+        step = 1 if self.deint.rate == 'field' else 2
+        L.check(self.fn_deint(self.raw[sl, at].data_ptr(), self.prog[sl].data_ptr(), hi - lo, *self.deint_args,
+                              1 if lo >= 0 else 0, first_field, step, cnt, self.stream), 'tg_deinterlace_planar')
+        L.check(self.fn(self.prog[sl].data_ptr(), self.lr[sl, 1].data_ptr(), cnt, *self.args, self.stream), self.launch)
+        self.taken, self.prev_slot = hi + 1, (sl, new)
+
+
+def _input_form(piece, c, yuv, deint=None):
     """The input form of a stream, from its options and its first item (as stream_parts hands it out)."""
+    if deint is not None:
+        return _InterlacedBytes(yuv, deint)
     if yuv is not None:
         return _HostBytes(yuv.h, yuv.w, (yuv.frame_bytes,), *yuv.input_launch())
     if piece.dtype == torch.uint8:
@@ -726,7 +851,7 @@ class _StreamEngine:
     resizes and encodes again and reads the same per-slot flags, and the snapshot it restores was taken before the
     batch's first conditional fill."""
 
-    def __init__(self, net, frames, device, on_fault, yuv=None, scene_cut=None, png=None, resize=None):
+    def __init__(self, net, frames, device, on_fault, yuv=None, scene_cut=None, png=None, resize=None, deinterlace=None):
         if on_fault not in ('rerun', 'raise'):
             raise ValueError(f"on_fault must be 'rerun' or 'raise', got {on_fault!r}")
         if png is not None:
@@ -740,6 +865,12 @@ class _StreamEngine:
             if not isinstance(yuv, (Yuv420, Yuv)):
                 raise ValueError(f'yuv must be a Yuv420, a Yuv or None, got {type(yuv).__name__}')
             yuv.out_frame_bytes(net.scale)
+        if deinterlace is not None:
+            if not isinstance(deinterlace, Deinterlace):
+                raise ValueError(f'deinterlace must be a Deinterlace or None, got {type(deinterlace).__name__}')
+            if yuv is None:
+                raise ValueError('infer_stream: deinterlace works on planar YUV frames; pass yuv (a Yuv420 or a Yuv) with it')
+            deinterlace.check_source(yuv)
         if scene_cut is not None:
             if not isinstance(scene_cut, SceneCut):
                 raise ValueError(f'scene_cut must be a SceneCut or None, got {type(scene_cut).__name__}')
@@ -764,7 +895,8 @@ class _StreamEngine:
                                      f'out_depth = {yuv.od}; resize needs an 8-bit output')
                 resize.check_source(net.scale * yuv.h, net.scale * yuv.w)
         # the forms: the output and the scene-cut slots follow from the options, the input from the first item as well
-        self.inp, self.input_form = None, lambda piece: _input_form(piece, net.in_nc, yuv)
+        self.inp, self.input_form = None, lambda piece: _input_form(piece, net.in_nc, yuv, deinterlace)
+        self.deint, self.n_in = deinterlace, 0
         self.deep = None if yuv is None or yuv.od == 8 else _YuvDeepOut(yuv)        # (per-frame hook)
         self.out = _PngOut(png) if png is not None else self.deep if self.deep is not None else \
             _YuvOut(yuv) if yuv is not None else _RgbOut()
@@ -834,7 +966,7 @@ class _StreamEngine:
             else:
                 pb, _, pcnt = self.prev_rec
                 self.lr[sl, 0].copy_(self.lr[self.ring.slot(pb), pcnt], non_blocking=True)
-            self.inp.upload(sl, cnt)
+            self.inp.upload(sl, i0, cnt)
             if self.cut is not None:
                 self.cut.detect(sl, b, i0, cnt)     # behind whatever wrote the slot's LR frames
             self.ev_in[sl].record(self.copy)
@@ -941,24 +1073,42 @@ class _StreamEngine:
         return self.out.result(sl, cnt)
 
     # -- the generator -------------------------------------------------------------------------------------------
+    def _rebatch(self):
+        """The input cut into batches: a batch's own frames, or with a Deinterlace the input frames its window adds."""
+        if self.deint is None:
+            return stream_rebatch(self.parts, self.first, self.later)
+        return stream_rebatch_sizes(self.parts, deinterlace_input_sizes(self.first, self.later, self.deint.rate))
+
+    def _batch_frames(self, pending, full):
+        """Output frames of the batch that holds `pending` input frames: as many -- or with a Deinterlace a full batch's
+        size, and at the end of the input every output frame that is still owed."""
+        if self.deint is None:
+            return pending
+        if full:
+            return self.later if self.ring.next_batch else self.first
+        return self.n_in * self.deint.per_frame - self.ring.next_frame
+
     def run(self):
         # (no torch.no_grad() around the yields: it would leak into the caller between them; nothing here records a graph)
         try:
             pending = 0                             # frames taken into the batch being filled
-            for b, off, piece, full in stream_rebatch(self.parts, self.first, self.later):
+            for b, off, piece, full in self._rebatch():
                 if self.plan is None:
                     self.net.check_faults()         # a fault of an EARLIER clip is never this stream's to repair
                     self._open(piece)
-                self.inp.take(self.ring.slot(b), off, piece)
-                pending = off + piece.shape[0]
+                if piece is not None:               # (None: a deinterlaced batch whose frames all arrived before)
+                    self.inp.take(self.ring.slot(b), off, piece)
+                    pending = off + piece.shape[0]
+                    self.n_in += piece.shape[0]
                 if not full:
                     continue
-                self._submit(pending)
+                self._submit(self._batch_frames(pending, True))
                 pending = 0
                 if self.ring.full():
                     yield self._retire()
-            if pending:
-                self._submit(pending)               # the last batch: whatever is left
+            tail = self._batch_frames(pending, False)
+            if tail:
+                self._submit(tail)                  # the last batch: whatever is left
             while self.ring.inflight:
                 yield self._retire()
         finally:

@@ -21,7 +21,7 @@ from ...utils.net_utils import get_upsampling_func
 # (what is not a network: every name stays reachable as tecogan_nets.<name>)
 from .frnet_infer import (FNET_FIRST_PASS_FRAMES, _SIDE_STREAMS, _StepPlan, _norm_device, clip_batches,  # noqa: F401
                           enqueue_batch, side_stream, stream_batch_sizes)
-from .stream import (STREAM_SLOTS, Png, Resize, SceneCut, StreamFormat, StreamRing, Yuv420, _StreamEngine, stream_frames,  # noqa: F401
+from .stream import (STREAM_SLOTS, Deinterlace, Png, Resize, SceneCut, StreamFormat, StreamRing, Yuv420, _StreamEngine, stream_frames,  # noqa: F401
                      stream_frames_yuv, stream_parts, stream_rebatch, yuv420_planes, Yuv, yuv_planes)
 
 
@@ -410,7 +410,8 @@ class FRNet(nn.Module):
         self._get_plan(k, h, w, dev).check_chain()   # (the clip has been synchronised: a 4-byte read)
         return out.transpose(1, 0, 2, 3, 4) if multi else out[:, 0]
 
-    def infer_stream(self, frames, device=None, on_fault='rerun', yuv=None, scene_cut=None, png=None, resize=None):
+    def infer_stream(self, frames, device=None, on_fault='rerun', yuv=None, scene_cut=None, png=None, resize=None,
+                     deinterlace=None):
         """Super-resolve a clip of ANY length in bounded memory: a generator over `frames` (any iterable, pulled lazily)
         that yields (m, s*h, s*w, 3) uint8 numpy chunks in order, as many frames in total as it consumed.
 
@@ -499,12 +500,25 @@ class FRNet(nn.Module):
         which reads them in place of the HR frames: RGB chunks are (m, h, w, 3), I420 chunks frames of h x w, PNG files
         h x w.  It composes with scene_cut unchanged, and a repaired batch is resized again.  ValueError before an item
         is pulled: in_nc != 3, an odd h or w together with `yuv`, h or w outside [1/4, 4] of the HR size (known then
-        with `yuv`; otherwise it is raised when the first item shows the size, before anything is allocated)."""
+        with `yuv`; otherwise it is raised when the first item shows the size, before anything is allocated).
+
+        deinterlace: a Deinterlace(tff, rate) together with `yuv` takes INTERLACED frames; without
+        it the stream enqueues exactly what it always did.  The items are what `yuv` takes, each frame holding two fields,
+        and the stream yields two output frames per input frame (rate 'field', one per field in time order) or one
+        ('frame', the earlier field's).  Per batch the copy stream carries the upload of the input frames no earlier
+        batch took, ONE tg_deinterlace_planar into the slot's progressive frames -- an edge-directed line average bounded
+        by a three-field motion measure, exact integers, tests/deinterlace_ref.py -- and then the spec's own input
+        launch on those; a frame's two fields may lie in two batches, and the frame before a batch's first stays on the
+        device.  The yielded bytes are those of the stream WITHOUT the option fed the specification's progressive
+        frames, bit for bit, however the input is chunked.  scene_cut and resize compose unchanged: they see progressive
+        frames, and cut indices are in output-frame numbering.  Not compared with ffmpeg's yadif or bwdif, and the
+        quarter-line vertical chroma offset of interlaced 4:2:0 is not modelled.  ValueError before an item is pulled:
+        no `yuv`, an odd yuv.h, 4:2:0 with yuv.h % 4 != 0."""
         import weakref
         cur = self._stream_ref() if self._stream_ref is not None else None
         if cur is not None and not cur.closed:
             raise RuntimeError('infer_stream: this network already has a live stream (one at a time: close it first)')
-        eng = _StreamEngine(self, frames, device, on_fault, yuv, scene_cut, png, resize)
+        eng = _StreamEngine(self, frames, device, on_fault, yuv, scene_cut, png, resize, deinterlace)
         self._stream_ref = weakref.ref(eng)
         return eng.run()
 

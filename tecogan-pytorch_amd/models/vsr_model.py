@@ -93,7 +93,7 @@ class VSRModel(BaseModel):
             hr_seq = self.net_G(lr_data, self.device)
         return hr_seq[n_pad_front:]
 
-    def infer_stream(self, frames, yuv=None, scene_cut=None, png=None, resize=None):
+    def infer_stream(self, frames, yuv=None, scene_cut=None, png=None, resize=None, deinterlace=None):
         """infer() for a clip of any length (FRNet.infer_stream): `frames` is an iterable of LR frames or chunks, uint8
         (h,w,3) or float32 (3,h,w); yields (m,H,W,3) uint8 chunks -- views of the generator's pinned ring, valid until
         the next one is asked for.  The temporal padding of the front (test.padding_mode / num_pad_front) is applied
@@ -107,9 +107,19 @@ class VSRModel(BaseModel):
         the padded prefix is dropped.  Known limit: the front padding is NOT repeated after a cut -- a new shot starts
         cold, as a clip does with num_pad_front = 0.
         resize (a Resize): every frame is delivered at resize.h x resize.w, resized on the device, in whichever of the
-        three output forms (FRNet.infer_stream)."""
+        three output forms (FRNet.infer_stream).
+        deinterlace (a Deinterlace, with yuv): the items are INTERLACED frames and two progressive frames per item are
+        yielded (one at rate 'frame'), deinterlaced on the device (FRNet.infer_stream).  Interlaced
+        frames reflected in time are not a sequence of real fields, so with deinterlace the FRONT PADDING IS SKIPPED
+        whatever test.num_pad_front says: the stream starts cold, as FRNet.infer_stream does, one log line says so, and
+        scene_cut behaves as scene_cut.shifted(0) -- its indices are output frames."""
         mode = self.opt['test'].get('padding_mode', 'reflect')
         skip = self.opt['test'].get('num_pad_front', 0)
+        if deinterlace is not None and skip:
+            import logging
+            logging.getLogger('tecogan_pytorch_amd').info(
+                'infer_stream: deinterlace: the front padding (num_pad_front = %d) is skipped, the stream starts cold', skip)
+            skip = 0
         self.net_G.eval()
         n_pad, inner, seen = skip, None, (0, 0)
         if scene_cut is not None:
@@ -119,7 +129,8 @@ class VSRModel(BaseModel):
         gen = self.net_G.infer_stream(front_pad_stream(frames, mode, skip, self.net_G.in_nc, yuv), self.device,
                                       yuv=yuv, **({} if inner is None else {'scene_cut': inner}),
                                       **({} if png is None else {'png': png}),
-                                      **({} if resize is None else {'resize': resize}))
+                                      **({} if resize is None else {'resize': resize}),
+                                      **({} if deinterlace is None else {'deinterlace': deinterlace}))
         try:
             for chunk in gen:
                 if inner is not None:

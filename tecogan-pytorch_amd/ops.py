@@ -618,6 +618,45 @@ def rgb_f32_to_yuv(rgb_chw, chroma='420', depth=10, matrix='bt709', full_range=F
                     (c, _chk_depth(depth, 'rgb_f32_to_yuv'), m, r, s), out)
 
 
+DEINTERLACE_RATES = {'field': 1, 'frame': 2}       # rate -> the field step of tg_deinterlace_planar
+
+
+def deinterlace(frames, h, w, chroma='420', depth=8, tff=True, rate='field', prev=None, out=None):
+    """(k, frame_samples) interlaced planar YUV frames on device -- uint8 at depth 8, uint16 at 10 | 12 -- -> progressive
+    frames of the same layout: (2k, frame_samples) at rate 'field' (both fields of every frame, in time order), (k,
+    frame_samples) at rate 'frame' (the earlier field's frame only).  Edge-directed line average bounded by a three-field
+    motion measure, exact integers (tg_deinterlace_planar; the specification is
+    tests/deinterlace_ref.py).  tff: the earlier field owns the even rows.  prev: the frame before frames[0], (frame_samples,)
+    or (1, frame_samples), or None: the two outputs of frames[0] are then spatial only.  h is even (a multiple of 4 at
+    '420').  out: a contiguous CUDA tensor of the result's shape and type to write into."""
+    _chk_depth(depth, 'deinterlace', '8, 10 or 12')
+    if not isinstance(chroma, str) or chroma not in L.YUV_CHROMA:
+        raise L.TecoganHipError(f'deinterlace: chroma is one of {sorted(L.YUV_CHROMA)}, got {chroma!r}')
+    if rate not in DEINTERLACE_RATES:
+        raise L.TecoganHipError(f'deinterlace: rate is one of {sorted(DEINTERLACE_RATES)}, got {rate!r}')
+    dtype = torch.uint8 if depth == 8 else torch.uint16
+    ns = yuv_frame_samples(h, w, chroma)
+    _chk(frames, 'frames', dtype)
+    if frames.dim() != 2 or frames.shape[0] < 1 or frames.shape[1] != ns:
+        raise L.TecoganHipError(f'deinterlace: {h}x{w} {chroma} frames are (k, {ns}); got shape {tuple(frames.shape)}')
+    k, step = frames.shape[0], DEINTERLACE_RATES[rate]
+    cnt = 2 * k // step
+    if prev is not None and _chk(prev, 'prev', dtype).numel() != ns:
+        raise L.TecoganHipError(f'deinterlace: prev is one frame of {ns} samples; got shape {tuple(prev.shape)}')
+    # the entry point takes the frame before and the k frames as one run of memory
+    run = torch.empty(k + 1, ns, dtype=dtype, device=frames.device)
+    run[1:].view(torch.uint8).copy_(frames.view(torch.uint8))
+    if prev is not None:
+        run[0].view(torch.uint8).copy_(prev.reshape(ns).view(torch.uint8))
+    if out is None:
+        out = torch.empty(cnt, ns, dtype=dtype, device=frames.device)
+    elif _chk(out, 'out', dtype).shape != (cnt, ns):
+        raise L.TecoganHipError(f'deinterlace: out is ({cnt}, {ns}), got shape {tuple(out.shape)}')
+    L.check(L.lib().tg_deinterlace_planar(_ptr(run), _ptr(out), k, h, w, L.YUV_CHROMA[chroma], depth, 1 if tff else 0,
+                                          0 if prev is None else 1, 0, step, cnt, _stream()), 'tg_deinterlace_planar')
+    return out
+
+
 def png_encode(rgb_hwc, filter='adaptive', lz77=False):
     """(n,H,W,3) / (H,W,3) uint8 RGB on device -> a list of n host `bytes`, each one complete PNG file, encoded on
     the device (tg_png_encode_u8): filter 'adaptive' | 'none', Huffman-only deflate in segments

@@ -40,7 +40,7 @@ OBJS=()
 PIDS=()
 for f in tg_*.hip; do
   o="$OBJDIR/${f%.hip}.o"
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ tg_common.h -nt "$o" ] || [ ../../include/tecogan_hip.h -nt "$o" ] || [ build.sh -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ tg_common.h -nt "$o" ] || [ tg_launch.h -nt "$o" ] || [ ../../include/tecogan_hip.h -nt "$o" ] || [ build.sh -nt "$o" ]; then
     ff=$(sed -n 's/^\/\/ TG_FILE_FLAGS: *//p' "$f" | head -1)
     echo "hipcc $f $ff"
     rm -f "$o"                       # a failed compile must not leave a stale object to link

@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "tg_common.h"
+#include "tg_launch.h"
 
 namespace tg {
 
@@ -472,35 +473,11 @@ template <int KG> static size_t rc_lds_bytes() {
 
 // workgroups of conv3x3_rowchain_kernel<KG> the device can hold at once (0 on error)
 template <int KG> static int rc_capacity() {
-  static int cap = -1;
-  if (cap >= 0) return cap;
-  const void* fn = reinterpret_cast<const void*>(conv3x3_rowchain_kernel<KG>);
-  const size_t lds = rc_lds_bytes<KG>();
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { (void)hipGetLastError(); return cap = 0; }
-  int per_cu = 0, dev = 0, ncu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 512, lds) != hipSuccess ||
-      hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
-    (void)hipGetLastError();
-    return cap = 0;
-  }
-  return cap = per_cu * ncu;
+  return resident_capacity<conv3x3_rowchain_kernel<KG>>(512, rc_lds_bytes<KG>());
 }
 
 static size_t rc16_lds_bytes() { return (size_t)(8 * R16_CH_FLOATS + 8 * 32 * 16) * sizeof(float); }
-static int rc16_capacity() {
-  static int cap = -1;
-  if (cap >= 0) return cap;
-  const void* fn = reinterpret_cast<const void*>(conv3x3_rowchain16_kernel);
-  int per_cu = 0, dev = 0, ncu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 512, rc16_lds_bytes()) != hipSuccess ||
-      hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
-    (void)hipGetLastError();
-    return cap = 0;
-  }
-  return cap = per_cu * ncu;
-}
+static int rc16_capacity() { return resident_capacity<conv3x3_rowchain16_kernel>(512, rc16_lds_bytes()); }
 
 }  // namespace tg
 
@@ -583,13 +560,8 @@ extern "C" int tg_conv3x3_chain_pack(const tg_pack_item* items, int n_items, int
 extern "C" int tg_conv3x3_chain_supported(int n, int h, int w, int cmax) {
   if (n <= 0 || h <= 0 || w <= 0 || cmax <= 0 || cmax > 64) return 0;
   const long long ntile = (long long)n * h * cdiv(w, RC_TW);
-  int ncu = 0, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
-    (void)hipGetLastError();
-    return 0;
-  }
   // four workgroups per tile while that is at most one workgroup per CU (and resident twice over)
-  if (4 * ntile <= ncu && 2 * 4 * ntile <= rc16_capacity()) return 4;
+  if (4 * ntile <= device_cus() && 2 * 4 * ntile <= rc16_capacity()) return 4;
   if (2 * ntile * 2 <= rc_capacity<8>()) return 2;
   if (2 * ntile <= rc_capacity<4>()) return 1;
   return 0;

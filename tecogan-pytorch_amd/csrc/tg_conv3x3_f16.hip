@@ -18,6 +18,7 @@
 // so that the 16 pixels of a ds_read_b128 do not share banks) live in LDS; a workgroup loads the weights once and
 // walks over tiles with a grid stride.  No workgroup waits for another one.
 #include "tg_common.h"
+#include "tg_launch.h"
 
 namespace tg {
 
@@ -219,11 +220,7 @@ __global__ __launch_bounds__(256) void pack_weights_f16_kernel(const float* __re
 template <bool CONVT>
 static int launch_f16(const _Float16* x, const _Float16* wp, const float* bias, const _Float16* res, _Float16* yh,
                       float* yf, int64_t yf_ns, int n, int h, int w, int act, tg_stream_t st, const char* what) {
-  static const bool attr_ok = [] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_f16_kernel<CONVT>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, f16_geo<CONVT>::LDS_BYTES) == hipSuccess;
-  }();
-  if (!attr_ok) { (void)hipGetLastError(); set_error("%s: cannot reserve %d bytes of LDS", what, f16_geo<CONVT>::LDS_BYTES); return TG_E_HIP; }
+  if (const int rc = ensure_dynamic_lds<conv3x3_f16_kernel<CONVT>>(f16_geo<CONVT>::LDS_BYTES, what)) return rc;
   const int64_t ntile = (int64_t)n * cdiv(h, f16_geo<CONVT>::TR) * cdiv(w, HTC);
   const int grid = (int)(ntile < 256 ? ntile : 256);       // one workgroup per CU (LDS), grid stride over the tiles
   hipLaunchKernelGGL(conv3x3_f16_kernel<CONVT>, dim3(grid), dim3(256), f16_geo<CONVT>::LDS_BYTES, (hipStream_t)st,

@@ -27,6 +27,7 @@
 // codes/models/networks/tecogan_nets.py:23-65, 92-98, 111-113, 367-369 and the
 // torch.cat at :71 / :141 (two-source input).
 #include "tg_common.h"
+#include "tg_launch.h"
 #include <cstdlib>
 
 namespace tg {
@@ -746,12 +747,17 @@ __global__ __launch_bounds__(512) void conv3x3s2_oneshot_kernel(Conv3x3Args a) {
 }
 
 
+// w % 4 == 0 and 16-byte aligned y / res / mask planes: the float4 epilogue is allowed
+static int conv3x3_vec_ok(const Conv3x3Args& a) {
+  return (a.w % 4 == 0) && ((uintptr_t)a.y % 16 == 0) && (a.y_ns % 4 == 0) &&
+         (!a.res || (((uintptr_t)a.res % 16 == 0) && (a.res_ns % 4 == 0))) &&
+         (!a.mask || (((uintptr_t)a.mask % 16 == 0) && (a.mask_ns % 4 == 0)));
+}
+
 template <int WM, int WN, int NT, int KS = 1>
 static int launch_conv(const Conv3x3Args& a0, int n, hipStream_t stream) {
   Conv3x3Args a = a0;
-  a.vec_ok = (a.w % 4 == 0) && ((uintptr_t)a.y % 16 == 0) && (a.y_ns % 4 == 0) &&
-             (!a.res || (((uintptr_t)a.res % 16 == 0) && (a.res_ns % 4 == 0))) &&
-             (!a.mask || (((uintptr_t)a.mask % 16 == 0) && (a.mask_ns % 4 == 0)));
+  a.vec_ok = conv3x3_vec_ok(a);
   constexpr int OCB = WN * NT * 32;
   a.tiles_x = cdiv(a.w, TW);
   a.tiles_y = cdiv(a.h, WM);
@@ -761,16 +767,9 @@ static int launch_conv(const Conv3x3Args& a0, int n, hipStream_t stream) {
   if (a.ksplit < 1) a.ksplit = 1;
   TG_REQUIRE(KS == 1 || a.ksplit == 1, TG_E_ARG, "conv3x3: in-workgroup K split excludes ksplit");
   if (KS > 1) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(
-                              conv3x3_mfma_kernel<WM, WN, NT, true, 0, KS>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(
-                              conv3x3_mfma_kernel<WM, WN, NT, false, 0, KS>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
+    const int rc = a.x2 ? ensure_dynamic_lds<conv3x3_mfma_kernel<WM, WN, NT, true, 0, KS>>(lds, "conv3x3_mfma")
+                        : ensure_dynamic_lds<conv3x3_mfma_kernel<WM, WN, NT, false, 0, KS>>(lds, "conv3x3_mfma");
+    if (rc != TG_OK) return rc;
   }
   long long blocks = (long long)a.tiles_x * a.tiles_y * a.nocg * n * a.ksplit;
   TG_REQUIRE(blocks > 0 && blocks < (1ll << 31), TG_E_SHAPE, "conv3x3: grid %lld", blocks);
@@ -939,19 +938,12 @@ static int conv3x3_impl(const float* x, int64_t x_nstride, int c1, const float* 
   // At most half as many 2-row tiles as CUs (e.g. a training batch of 2 x 64 x 64): 1-row tiles
   // with the channel chunks split over two wave groups keep every SIMD busy in ONE launch.
   if (a.ksplit <= 1 && !tapsel && conv3x3_uses_oneshot(n, cin, cout, h, w)) {
-    a.vec_ok = (a.w % 4 == 0) && ((uintptr_t)a.y % 16 == 0) && (a.y_ns % 4 == 0) &&
-               (!a.res || (((uintptr_t)a.res % 16 == 0) && (a.res_ns % 4 == 0))) &&
-               (!a.mask || (((uintptr_t)a.mask % 16 == 0) && (a.mask_ns % 4 == 0)));
+    a.vec_ok = conv3x3_vec_ok(a);
     a.tiles_x = cdiv(a.w, TW); a.tiles_y = a.h; a.nocg = 1; a.nchunk = cdiv(a.cin, CK);
     const size_t lds = (size_t)(8 * 3 * 2 * RS * 4 + 2 * 3 * 16 * 64) * sizeof(float);    // 50.7 KB
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_oneshot_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_oneshot_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
+    const int rc = a.x2 ? ensure_dynamic_lds<conv3x3_oneshot_kernel<true>>(lds, "conv3x3_oneshot")
+                        : ensure_dynamic_lds<conv3x3_oneshot_kernel<false>>(lds, "conv3x3_oneshot");
+    if (rc != TG_OK) return rc;
     const unsigned grid = (unsigned)(a.tiles_x * a.tiles_y * n);
     if (a.x2) hipLaunchKernelGGL(conv3x3_oneshot_kernel<true>, dim3(grid), dim3(512), lds, s, a);
     else hipLaunchKernelGGL(conv3x3_oneshot_kernel<false>, dim3(grid), dim3(512), lds, s, a);
@@ -1046,12 +1038,7 @@ extern "C" int tg_conv3x3s2_fwd(const float* x, int64_t x_nstride, const float* 
   a.c1 = cin; a.cin = cin; a.cout = cout; a.h = h_out; a.w = w_out; a.act = act;
   a.tiles_x = cdiv(w_out, TW); a.tiles_y = h_out; a.nocg = 1; a.nchunk = cdiv(cin, CK);
   const size_t lds = (size_t)(8 * 3 * 2 * RS2 * 4 + 2 * 3 * 16 * 64) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3s2_oneshot_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
+  if (const int rc = ensure_dynamic_lds<conv3x3s2_oneshot_kernel>(lds, "conv3x3s2_oneshot")) return rc;
   hipLaunchKernelGGL(conv3x3s2_oneshot_kernel, dim3((unsigned)(a.tiles_x * a.tiles_y * n)), dim3(512), lds,
                      (hipStream_t)stream, a);
   return check_launch("conv3x3s2_oneshot");

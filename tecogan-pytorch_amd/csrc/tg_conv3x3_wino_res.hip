@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "tg_common.h"
+#include "tg_launch.h"
 
 // ---- the one build switch.  WR_UASM = 1 is what ships: hand-written weight requests + exact vmcnt waits (round 5).
 // WR_UASM = 0 is the round-4 form of the same kernel -- compiler-visible weight loads behind a branch, the compiler's own
@@ -703,31 +704,13 @@ __global__ void wres_ct_pack_kernel(const float* __restrict__ w, float* __restri
   }
 }
 
-static int wres_capacity() {
-  static int cap = -1;
-  if (cap >= 0) return cap;
-  const void* fn = reinterpret_cast<const void*>(conv3x3_wino_resident_kernel);
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WR_LDS_BYTES) != hipSuccess) {
-    (void)hipGetLastError();
-    return cap = 0;
-  }
-  int per_cu = 0, dev = 0, ncu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, WR_THREADS, WR_LDS_BYTES) != hipSuccess ||
-      hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
-    (void)hipGetLastError();
-    return cap = 0;
-  }
-  return cap = per_cu * ncu;
-}
-
 static long long wres_blocks(int h, int w) { return (long long)cdiv(h, WR_BH) * cdiv(w, WR_BW); }
 
 // one workgroup per CU, and a few CUs left free so that a co-running launch (the flow estimator on
 // its own stream) cannot keep the last workgroups of this one from ever starting
 bool conv3x3_wino_resident_ok(int n, int cout, int h, int w) {
   if (n != 1 || cout != WR_NC || h < 2 || w < 2 || (h & 1) || (w & 1)) return false;
-  const int cap = wres_capacity();
+  const int cap = resident_capacity<conv3x3_wino_resident_kernel>(WR_THREADS, WR_LDS_BYTES);
   return cap > 0 && wres_blocks(h, w) <= cap - 8 && wres_blocks(h, w) <= 1023;   // (1023: the ring table's 16-bit owner field)
 }
 

@@ -18,6 +18,7 @@
 //   stores and (optionally) multiplies by act'(x) of the layer below (what tg_depth_to_space_act_bwd did on the way
 //   out of the embedding).
 #include "tg_common.h"
+#include "tg_launch.h"
 #include <cstdlib>
 
 namespace tg {
@@ -636,22 +637,15 @@ template <int W> static constexpr int d4s_lds_bytes() {
   return (2 * ((2 * (64 / W) + 2) * 2 * ((W / 2 + 2) * 4 + 4)) + 2 * D4_WCH) * 4;
 }
 
-static bool c4_attr_done = false;
-static void c4_set_attrs() {
-  if (c4_attr_done) return;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv4x4s2_mfma_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                      c4_lds_bytes<1>());
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv4x4s2_mfma_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                      c4_lds_bytes<2>());
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv4x4s2_dgrad_mfma_kernel<false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, d4_lds_bytes());
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv4x4s2_dgrad_mfma_kernel<true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, d4_lds_bytes());
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv4x4s2_dgrad_small_kernel<32>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, d4s_lds_bytes<32>());
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv4x4s2_dgrad_small_kernel<16>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, d4s_lds_bytes<16>());
-  c4_attr_done = true;
+// the six kernels of this file that need more than 64 KB of LDS, under one call
+static int c4_ensure_lds() {
+  int rc = ensure_dynamic_lds<conv4x4s2_mfma_kernel<1>>(c4_lds_bytes<1>(), "conv4x4s2_mfma");
+  if (!rc) rc = ensure_dynamic_lds<conv4x4s2_mfma_kernel<2>>(c4_lds_bytes<2>(), "conv4x4s2_mfma");
+  if (!rc) rc = ensure_dynamic_lds<conv4x4s2_dgrad_mfma_kernel<false>>(d4_lds_bytes(), "conv4x4s2_dgrad_mfma");
+  if (!rc) rc = ensure_dynamic_lds<conv4x4s2_dgrad_mfma_kernel<true>>(d4_lds_bytes(), "conv4x4s2_dgrad_mfma");
+  if (!rc) rc = ensure_dynamic_lds<conv4x4s2_dgrad_small_kernel<32>>(d4s_lds_bytes<32>(), "conv4x4s2_dgrad_small");
+  if (!rc) rc = ensure_dynamic_lds<conv4x4s2_dgrad_small_kernel<16>>(d4s_lds_bytes<16>(), "conv4x4s2_dgrad_small");
+  return rc;
 }
 
 }  // namespace tg
@@ -715,7 +709,6 @@ extern "C" int tg_conv4x4s2_fwd(const float* x, const float* w_fwd, float* y, fl
   if (w % 64 != 0 && c4_fwd_ksplit(n, ci, co, h, w) > 1)
     TG_REQUIRE(workspace && (((uintptr_t)y | (uintptr_t)workspace) & 15) == 0, TG_E_ARG,
                "conv4x4s2_fwd: the split form of this shape needs a workspace, and y and the workspace 16-byte aligned");
-  c4_set_attrs();
   if (w % 64 != 0) {
     Conv4SmallArgs sa;
     const int ks = c4_fwd_ksplit(n, ci, co, h, w);
@@ -741,6 +734,7 @@ extern "C" int tg_conv4x4s2_fwd(const float* x, const float* w_fwd, float* y, fl
     }
     return check_launch("conv4x4s2_fwd (small maps)");
   }
+  if (const int rc = c4_ensure_lds()) return rc;
   Conv4Args a;
   a.x = x; a.wpk = w_fwd; a.y = y;
   a.x_ns = (long long)ci * h * w; a.y_ns = (long long)co * (h / 2) * (w / 2);
@@ -773,12 +767,12 @@ extern "C" int tg_conv4x4s2_dgrad(const float* g, const float* w_dgrad, const fl
     TG_REQUIRE(!(split || act_y) || (((uintptr_t)dx | (uintptr_t)(split ? workspace : nullptr) | (uintptr_t)act_y) & 15) == 0,
                TG_E_ARG, "conv4x4s2_dgrad: the two-pass form of this shape needs 16-byte aligned dx, workspace and act_y");
   }
-  c4_set_attrs();
   if (w % 64 != 0) {
     Conv4DgradSmallArgs sa;
     const int ks = c4_dgrad_ksplit(n, ci, co, h, w);
     const bool two_pass = ks > 1 || act_y;      // act'(.) rides on the summing pass
     TG_REQUIRE(ks == 1 || workspace, TG_E_ARG, "conv4x4s2_dgrad: this shape needs tg_conv4x4s2_workspace_floats of workspace");
+    if (const int rc = c4_ensure_lds()) return rc;
     const long long out_floats = (long long)n * ci * h * w;
     sa.g = g; sa.wpk = w_dgrad; sa.dx = ks == 1 ? dx : workspace;
     sa.g_ns = (long long)co * (h / 2) * (w / 2); sa.dx_ns = (long long)ci * h * w; sa.part_ss = out_floats;
@@ -800,6 +794,7 @@ extern "C" int tg_conv4x4s2_dgrad(const float* g, const float* w_dgrad, const fl
     }
     return check_launch("conv4x4s2_dgrad (small maps)");
   }
+  if (const int rc = c4_ensure_lds()) return rc;
   Conv4DgradArgs a;
   a.g = g; a.wpk = w_dgrad; a.act_y = act_y; a.dx = dx;
   a.g_ns = (long long)co * (h / 2) * (w / 2); a.dx_ns = (long long)ci * h * w; a.act_ns = a.dx_ns;

@@ -18,6 +18,7 @@
 //
 // Replaces SRNet.conv_up (codes/models/networks/tecogan_nets.py:119-126).
 #include "tg_common.h"
+#include "tg_launch.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -653,15 +654,6 @@ __global__ __launch_bounds__(256) void convout_tail4_kernel(const float* __restr
 // The Z-mode launcher's split-tail rule (also asked by the frame plan's launch accounting): 4-row workgroups, one image,
 // at least one whole round of the 2-per-CU resident slots, and a last round between a quarter and 95 % full (form 3: always
 // when a whole round exists; form 0: never).
-static int convt_z_cu_count() {                      // of the calling thread's current device (256 where the runtime does not say)
-  int dev = 0, ncu = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1) {
-    (void)hipGetLastError();
-    ncu = 256;
-  }
-  return ncu;
-}
-
 // The rule and the launch it governs share this one answer: the tile rows that the first launch of the split covers with
 // 4-row workgroups (the 2-row tail takes the input rows below them), 0 for a single launch.
 static int convt_z_split_rows(int n, int h, int w, int form) {
@@ -669,7 +661,7 @@ static int convt_z_split_rows(int n, int h, int w, int form) {
   const long long tiles_x = cdiv(w, TTW);
   const long long wg4 = tiles_x * cdiv(h, 4) * n;
   if (wg4 < 512) return 0;                           // (the launcher uses 2-row workgroups there)
-  const long long slots = 2ll * convt_z_cu_count(), rem = wg4 % slots;
+  const long long slots = 2ll * device_cus(), rem = wg4 % slots;
   if (wg4 < slots) return 0;
   const long long ty4 = (wg4 / slots) * slots / tiles_x;
   if (ty4 < 1 || ty4 >= cdiv(h, 4)) return 0;
@@ -707,12 +699,7 @@ extern "C" int tg_convt3x3s2_fwd(const float* x, int64_t x_nstride, const float*
   if (cin <= 64 && cout <= 64 && (long long)a.tiles_x * h * n <= 256) {
     a.tiles_y = h;
     const size_t lds1 = (size_t)(8 * TOS_CH_FLOATS + 2 * 4 * 4 * 16 * 64) * sizeof(float);      // 148 KB
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(convt3x3s2_oneshot_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-      attr_set = true;
-    }
+    if (const int rc = ensure_dynamic_lds<convt3x3s2_oneshot_kernel>(lds1, "convt3x3s2_oneshot")) return rc;
     hipLaunchKernelGGL(convt3x3s2_oneshot_kernel, dim3((unsigned)(a.tiles_x * h * n)), dim3(512), lds1,
                        (hipStream_t)stream, a);
     return check_launch("convt3x3s2_oneshot");

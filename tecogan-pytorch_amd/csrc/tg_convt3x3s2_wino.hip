@@ -30,6 +30,7 @@
 // (Built with -fno-slp-vectorize, the configuration measured in EXPERIMENTS.md.)
 // TG_FILE_FLAGS: -fno-slp-vectorize
 #include "tg_common.h"
+#include "tg_launch.h"
 
 namespace tg {
 
@@ -332,16 +333,24 @@ __global__ void convt_pack_wino_kernel(const float* __restrict__ wpk, float* __r
 }
 
 // The split of a launch into whole rounds of resident workgroups (2 per CU) and a remainder launch: one image, at least
-// one whole round, a remainder (split = 1: whenever a whole round exists; 0: never; -1: the rule = 1).
-bool convt_z_wino_split_rule(int n, int h, int w, int split) {
-  if (n != 1 || split == 0) return false;
+// one whole round, a remainder (split = 1: whenever a whole round exists; 0: never; -1: the rule = 1).  The rule and the
+// launch it governs share this one answer: the strip rows of the first launch, 0 for a single launch.
+static int convt_z_wino_split_rows(int n, int h, int w, int split) {
+  if (n != 1 || split == 0) return 0;
   const long long tiles_x = cdiv(w, 32), rows = cdiv(h, 2), strips = tiles_x * rows;
-  static int ncu_s = 0;
-  if (!ncu_s) { int dev = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu_s, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); ncu_s = 256; } }
-  const long long slots = 2ll * ncu_s;
-  if (strips < slots) return false;
+  const long long slots = 2ll * device_cus();
+  if (strips < slots) return 0;
   const long long rows1 = (strips / slots) * slots / tiles_x;
-  return rows1 >= 1 && rows1 < rows;
+  return rows1 >= 1 && rows1 < rows ? (int)rows1 : 0;
+}
+
+bool convt_z_wino_split_rule(int n, int h, int w, int split) { return convt_z_wino_split_rows(n, h, w, split) > 0; }
+
+template <bool RELU, bool TWO>
+static int convt_z_wino_launch(unsigned grid, const ConvTWinoArgs& a, hipStream_t s) {
+  if (const int rc = ensure_dynamic_lds<convt3x3s2_wino_z_kernel<RELU, TWO>>(WZ_LDS_BYTES, "convt3x3s2_wino_z")) return rc;
+  hipLaunchKernelGGL((convt3x3s2_wino_z_kernel<RELU, TWO>), dim3(grid), dim3(256), WZ_LDS_BYTES, s, a);
+  return TG_OK;
 }
 
 }  // namespace tg
@@ -372,17 +381,6 @@ extern "C" int tg_convt3x3s2_z_wino_fwd(const float* x, int64_t x_nstride, const
   TG_REQUIRE((z_nstride % 2) == 0 && ((uintptr_t)z % 8) == 0, TG_E_ARG, "convt3x3s2_z_wino_fwd: z must be 8-byte aligned");
   TG_REQUIRE_NSTRIDE("convt3x3s2_z_wino_fwd", "x", x, x_nstride, n, (long long)cin * h * w);
   TG_REQUIRE_NSTRIDE("convt3x3s2_z_wino_fwd", "z", z, z_nstride, n, 9ll * cz * 4 * h * w);      // the planes it writes
-  static bool attr_set = false;
-  if (!attr_set) {
-    const void* fns[4] = {reinterpret_cast<const void*>(convt3x3s2_wino_z_kernel<false, false>),
-                          reinterpret_cast<const void*>(convt3x3s2_wino_z_kernel<false, true>),
-                          reinterpret_cast<const void*>(convt3x3s2_wino_z_kernel<true, false>),
-                          reinterpret_cast<const void*>(convt3x3s2_wino_z_kernel<true, true>)};
-    for (const void* f : fns)
-      if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WZ_LDS_BYTES) != hipSuccess)
-        return check_launch("convt3x3s2_wino_z (LDS attribute)");
-    attr_set = true;
-  }
   ConvTWinoArgs a{};
   a.x = x; a.wa = w_wino; a.bias = bias; a.wz = wz; a.z = z; a.x_ns = x_nstride; a.z_ns = z_nstride;
   a.cin = cin; a.cout = cout; a.h = h; a.w = w; a.act = act; a.zrows = 9 * cz;
@@ -392,23 +390,19 @@ extern "C" int tg_convt3x3s2_z_wino_fwd(const float* x, int64_t x_nstride, const
   hipStream_t s = (hipStream_t)stream;
   const bool relu = act == TG_ACT_RELU, two = cz >= 2;
   auto launch = [&](unsigned grid, const ConvTWinoArgs& args) {
-    if (relu && two) hipLaunchKernelGGL((convt3x3s2_wino_z_kernel<true, true>), dim3(grid), dim3(256), WZ_LDS_BYTES, s, args);
-    else if (relu) hipLaunchKernelGGL((convt3x3s2_wino_z_kernel<true, false>), dim3(grid), dim3(256), WZ_LDS_BYTES, s, args);
-    else if (two) hipLaunchKernelGGL((convt3x3s2_wino_z_kernel<false, true>), dim3(grid), dim3(256), WZ_LDS_BYTES, s, args);
-    else hipLaunchKernelGGL((convt3x3s2_wino_z_kernel<false, false>), dim3(grid), dim3(256), WZ_LDS_BYTES, s, args);
+    if (!relu && !two) return convt_z_wino_launch<false, false>(grid, args, s);
+    if (!relu) return convt_z_wino_launch<false, true>(grid, args, s);
+    if (!two) return convt_z_wino_launch<true, false>(grid, args, s);
+    return convt_z_wino_launch<true, true>(grid, args, s);
   };
-  if (convt_z_wino_split_rule(n, h, w, split)) {
-    int ncu = 256;
-    { int dev = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); ncu = 256; } }
-    const long long slots = 2ll * ncu, strips = (long long)a.tiles_x * rows;
-    const int rows1 = (int)((strips / slots) * slots / a.tiles_x);
+  if (const int rows1 = convt_z_wino_split_rows(n, h, w, split)) {
     ConvTWinoArgs a1 = a; a1.strips_y = rows1; a1.strip_base = 0;
-    launch((unsigned)(a.tiles_x * rows1), a1);
+    if (const int rc = launch((unsigned)(a.tiles_x * rows1), a1)) return rc;
     ConvTWinoArgs a2 = a; a2.strips_y = rows - rows1; a2.strip_base = rows1;
-    launch((unsigned)(a.tiles_x * a2.strips_y), a2);
+    if (const int rc = launch((unsigned)(a.tiles_x * a2.strips_y), a2)) return rc;
     return check_launch("convt3x3s2_wino_z(split)");
   }
   a.strips_y = rows; a.strip_base = 0;
-  launch((unsigned)(a.tiles_x * rows * n), a);
+  if (const int rc = launch((unsigned)(a.tiles_x * rows * n), a)) return rc;
   return check_launch("convt3x3s2_wino_z");
 }

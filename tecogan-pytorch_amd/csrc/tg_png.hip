@@ -17,6 +17,7 @@
 //   png_finish_kernel   workgroup = one frame: signature, IHDR, IDAT header, Adler-32 in segment order, the IDAT CRC
 //                       (the XOR of the segments' terms: a CRC from a zero register is linear), IEND, the file's size
 #include "tg_common.h"
+#include "tg_launch.h"
 
 namespace tg {
 
@@ -935,17 +936,7 @@ extern "C" int tg_png_encode_u8(const uint8_t* rgb_hwc, int n, int h, int w, int
   TG_REQUIRE((uintptr_t)sizes % 8 == 0, TG_E_ARG, "png_encode_u8: sizes is not 8-byte aligned");
   tg::png_ws ws;
   tg::png_ws_layout(n, h, w, static_cast<uint8_t*>(workspace), &ws);
-  static bool lds_ok = false;
-  if (!lds_ok) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tg::png_segment_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, tg::PNG_SEG_LDS);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      tg::set_error("png_encode_u8: %d bytes of LDS per workgroup: %s", tg::PNG_SEG_LDS, hipGetErrorString(e));
-      return TG_E_HIP;
-    }
-    lds_ok = true;
-  }
+  if (const int rc = tg::ensure_dynamic_lds<tg::png_segment_kernel>(tg::PNG_SEG_LDS, "png_segment")) return rc;
   const hipStream_t st = (hipStream_t)stream;
   const dim3 block(tg::PNG_T), rows((unsigned)h, (unsigned)n), segs((unsigned)ws.nseg, (unsigned)n);
   if (filter == TG_PNG_FILTER_ADAPTIVE)
@@ -986,22 +977,9 @@ extern "C" int tg_png_encode_lz_u8(const uint8_t* rgb_hwc, int n, int h, int w, 
   tg::png_ws ws;
   tg::png_lz_ws lz;
   tg::png_lz_ws_layout(n, h, w, static_cast<uint8_t*>(workspace), &ws, &lz);
-  static bool lds_ok = false;
-  if (!lds_ok) {
-    const struct { const void* fn; int bytes; } need[3] = {
-        {reinterpret_cast<const void*>(tg::png_segment_kernel), tg::PNG_SEG_LDS},
-        {reinterpret_cast<const void*>(tg::png_lz_sort_kernel), tg::PNG_LZ_SORT_LDS},
-        {reinterpret_cast<const void*>(tg::png_lz_parse_kernel), tg::PNG_LZ_PARSE_LDS}};
-    for (int i = 0; i < 3; ++i) {
-      const hipError_t e = hipFuncSetAttribute(need[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, need[i].bytes);
-      if (e != hipSuccess) {
-        (void)hipGetLastError();
-        tg::set_error("png_encode_lz_u8: %d bytes of LDS per workgroup: %s", need[i].bytes, hipGetErrorString(e));
-        return TG_E_HIP;
-      }
-    }
-    lds_ok = true;
-  }
+  if (const int rc = tg::ensure_dynamic_lds<tg::png_segment_kernel>(tg::PNG_SEG_LDS, "png_segment")) return rc;
+  if (const int rc = tg::ensure_dynamic_lds<tg::png_lz_sort_kernel>(tg::PNG_LZ_SORT_LDS, "png_lz_sort")) return rc;
+  if (const int rc = tg::ensure_dynamic_lds<tg::png_lz_parse_kernel>(tg::PNG_LZ_PARSE_LDS, "png_lz_parse")) return rc;
   const hipStream_t st = (hipStream_t)stream;
   const dim3 block(tg::PNG_T), wide(tg::PNG_LZ_T), rows((unsigned)h, (unsigned)n), segs((unsigned)ws.nseg, (unsigned)n);
   if (filter == TG_PNG_FILTER_ADAPTIVE)

@@ -19,6 +19,7 @@
 // (K split) and write raw partial sums; wgrad_reduce_kernel adds the splits in
 // a fixed order (deterministic) and accumulates into the gradient tensor.
 #include "tg_common.h"
+#include "tg_launch.h"
 
 namespace tg {
 
@@ -754,43 +755,29 @@ extern "C" size_t tg_wgrad3x3_convt_workspace_floats(int n, int ci, int co, int 
   return ns * ci * co * 9 + ns * co;                 // + the bias-gradient partials
 }
 
-template <class G, bool VEC>
-static void launch_geo2(const WgradArgs& a, unsigned blocks, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad3x3_mfma_geo_kernel<G, VEC>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((wgrad3x3_mfma_geo_kernel<G, VEC>), dim3(blocks), dim3(256), G::LDS_BYTES, s, a);
+// one weight-gradient kernel, opted into its LDS on this device; TG_OK or the opt-in's error (the launch itself is
+// checked by the caller's check_launch)
+template <auto Kernel>
+static int launch_wgrad(const WgradArgs& a, unsigned blocks, size_t lds, hipStream_t s) {
+  if (const int rc = ensure_dynamic_lds<Kernel>(lds, "wgrad3x3_mfma")) return rc;
+  hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(256), lds, s, a);
+  return TG_OK;
 }
 template <class G>
-static void launch_geo(const WgradArgs& a, unsigned blocks, hipStream_t s, bool vec) {
-  if (vec) launch_geo2<G, true>(a, blocks, s); else launch_geo2<G, false>(a, blocks, s);
+static int launch_geo(const WgradArgs& a, unsigned blocks, hipStream_t s, bool vec) {
+  return vec ? launch_wgrad<wgrad3x3_mfma_geo_kernel<G, true>>(a, blocks, G::LDS_BYTES, s)
+             : launch_wgrad<wgrad3x3_mfma_geo_kernel<G, false>>(a, blocks, G::LDS_BYTES, s);
 }
-template <bool VEC, int KS>
-static void launch_ks(const WgradArgs& a, unsigned blocks, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad3x3_mfma_ks_kernel<VEC, KS>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)WgGeoStd::LDS_BYTES);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((wgrad3x3_mfma_ks_kernel<VEC, KS>), dim3(blocks), dim3(256), WgGeoStd::LDS_BYTES, s, a);
+template <int KS>
+static int launch_ks(const WgradArgs& a, unsigned blocks, hipStream_t s, bool vec) {
+  return vec ? launch_wgrad<wgrad3x3_mfma_ks_kernel<true, KS>>(a, blocks, WgGeoStd::LDS_BYTES, s)
+             : launch_wgrad<wgrad3x3_mfma_ks_kernel<false, KS>>(a, blocks, WgGeoStd::LDS_BYTES, s);
 }
-static void launch_std(const WgradArgs& a, unsigned blocks, hipStream_t s, bool vec) {
-  if (a.kmode == 3) { if (vec) launch_ks<true, 4>(a, blocks, s); else launch_ks<false, 4>(a, blocks, s); return; }
-  if (a.kmode) { if (vec) launch_ks<true, 2>(a, blocks, s); else launch_ks<false, 2>(a, blocks, s); return; }
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad3x3_mfma_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)WgGeoStd::LDS_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad3x3_mfma_vec_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)WgGeoStd::LDS_BYTES);
-    attr_set = true;
-  }
-  if (vec) hipLaunchKernelGGL(wgrad3x3_mfma_vec_kernel, dim3(blocks), dim3(256), WgGeoStd::LDS_BYTES, s, a);
-  else hipLaunchKernelGGL(wgrad3x3_mfma_kernel, dim3(blocks), dim3(256), WgGeoStd::LDS_BYTES, s, a);
+static int launch_std(const WgradArgs& a, unsigned blocks, hipStream_t s, bool vec) {
+  if (a.kmode == 3) return launch_ks<4>(a, blocks, s, vec);
+  if (a.kmode) return launch_ks<2>(a, blocks, s, vec);
+  return vec ? launch_wgrad<wgrad3x3_mfma_vec_kernel>(a, blocks, WgGeoStd::LDS_BYTES, s)
+             : launch_wgrad<wgrad3x3_mfma_kernel>(a, blocks, WgGeoStd::LDS_BYTES, s);
 }
 static void launch_smallca(const WgradSmallArgs& sa, int nseg, hipStream_t s) {
   bool vec = sa.w % 4 == 0 && sa.p_ns % 4 == 0 && sa.q_ns % 4 == 0;
@@ -915,25 +902,26 @@ static int wgrad_launch(const float* const* p_list, const float* const* q_list, 
   // bias gradient (db = sum of P = dZ over images and pixels): out of the P values the vector form stages
   const bool fuse_a = bias_grad && !stride2 && vec && !cphase;
   if (fuse_a) a.bias_part = workspace + (size_t)a.nsplit * ks * ca * cb_total * 9;
+  int rc;
   if (geo == 0) {
-    launch_std(a, blocks, s, vec);
+    rc = launch_std(a, blocks, s, vec);
   } else if (geo == 1) {
-    launch_geo<WgGeo<4, 16, 0>>(a, blocks, s, vec);
+    rc = launch_geo<WgGeo<4, 16, 0>>(a, blocks, s, vec);
   } else if (geo == 2) {
-    launch_geo<WgGeo<8, 8, 0>>(a, blocks, s, vec);
+    rc = launch_geo<WgGeo<8, 8, 0>>(a, blocks, s, vec);
   } else {
     // bias gradient of the transposed conv: out of the staged dZ when the vector form runs (and cb fits one block)
     const bool fuse_b = bias_grad && vec && a.nbb == 1;
     a.bias_part = fuse_b ? workspace + (size_t)a.nsplit * ca * cb_total * 9 : nullptr;
-    launch_geo<WgGeo<1, 32, 1>>(a, blocks, s, vec);
-    if (bias_grad && !fuse_b) {      // element-wise staging / several channel blocks: the stand-alone reduction over the HR tensors
+    rc = launch_geo<WgGeo<1, 32, 1>>(a, blocks, s, vec);
+    if (rc == TG_OK && bias_grad && !fuse_b) {      // element-wise staging / several channel blocks: the stand-alone reduction over the HR tensors
       int rb_ = check_launch("wgrad3x3_convt");
       if (rb_ != TG_OK) return rb_;
       rb_ = tg_bias_grad_multi(q_list, nseg, bias_grad, n_per_seg, cb, 4 * h * w, accumulate, stream);
       if (rb_ != TG_OK) return rb_;
     }
   }
-  int rc = check_launch("wgrad3x3_mfma");
+  if (rc == TG_OK) rc = check_launch("wgrad3x3_mfma");
   if (rc != TG_OK) return rc;
   long long total = (long long)ca * cb * 9;
   // the bias partials of the launch (db over ca: P = dZ; stride-2 form: over cb, Q = dZ) are added by the tail
@@ -1005,8 +993,8 @@ static int wgrad_body_impl(const float* const* dz_bases, const float* const* act
     }
     if (vec) a.bias_part = workspace + (size_t)nlayers * a.nsplit * c * c * 9;
   }
-  launch_std(a, (unsigned)(nlayers * a.nab * a.nbb * a.nsplit), s, vec);
-  int rc = check_launch("wgrad3x3_body");
+  int rc = launch_std(a, (unsigned)(nlayers * a.nab * a.nbb * a.nsplit), s, vec);
+  if (rc == TG_OK) rc = check_launch("wgrad3x3_body");
   if (rc != TG_OK) return rc;
   const long long total = (long long)c * c * 9;
   hipLaunchKernelGGL(wgrad_reduce_layers_kernel, dim3((unsigned)((total + 63) / 64), (unsigned)nlayers), dim3(256), 0, s,

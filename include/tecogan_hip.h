@@ -223,6 +223,33 @@ int tg_conv3x3_wino_fused_fwd(const float* x, int64_t x_nstride, const float* u_
                               float* y, int64_t y_nstride, int n, int cin, int cout, int h, int w, int act,
                               int fuse, tg_stream_t stream);
 
+/* y = act(conv3x3(bilinear_x2(x)) + bias) with the matrix work at the LOW resolution (tg_upconv.hip): FNet's three
+ * readers of a decoder block's up-sampling (tecogan_nets.py:44-64).  Up-sampling acts per channel and a tap's channel
+ * mix per pixel, so they commute: a tap GEMM z[img][tap][o][pixel] = sum_c W[o][c][tap] x[img][c][pixel] on the
+ * (h, w) source map (a quarter of the direct form's multiplies, fp32 MFMA), then a streaming combine
+ * y[o][Y][X] = act(bias[o] + sum over taps of inside(Y+ky-1, X+kx-1) * bilinear_x2(z[tap][o])[Y+ky-1][X+kx-1]).
+ * Equal to tg_upsample_fwd + tg_conv3x3_fwd up to fp32 summation order; two launches give identical bits.
+ *   x (n, cin, h, w) -> z (n, 9 cout, h, w) scratch -> y (n, cout, 2h, 2w); h, w: the SOURCE map.
+ *   supported: cin 64 | 128 | 256 with cout = cin / 2, 9 cout h w below 2^29; anything else is TG_E_ARG.
+ *   a_packed: tg_upconv_pack of the layer's weights, tg_upconv_packed_floats(cin, cout) floats (0: unsupported),
+ *             16-byte aligned; ocb 0: w is OIHW (cout, cin, 3, 3), 32 | 64: w is tg_conv3x3_pack(transposed = 0) with that ocb.
+ *   16-byte accesses run where the operands are 16-byte aligned with strides and map sizes that keep them so, else
+ *   element by element: same results.
+ * tg_upconv_prefers: 1 where the frame plan runs a reader this way (n images, SOURCE map h x w).  TG_UPCONV=0 never,
+ * 1 wherever supported, unset the measured rule; always 0 with TG_CONV_WINO=1 (the up-sampling then rides in the
+ * Winograd kernel's staging).  Whatever it says, the plan keeps a reader whose conv is a split-K pair
+ * (tg_conv3x3_pick_ksplit > 1: conv + finalize), so that its launch counts per kind do not depend on the form. */
+size_t tg_upconv_packed_floats(int cin, int cout);
+int tg_upconv_pack(const float* w, float* a_packed, int cin, int cout, int ocb, tg_stream_t stream);
+int tg_upconv_tap_gemm(const float* x, int64_t x_nstride, const float* a_packed, float* z, int64_t z_nstride,
+                       int n, int cin, int cout, int h, int w, tg_stream_t stream);
+int tg_upconv_combine(const float* z, int64_t z_nstride, const float* bias, float* y, int64_t y_nstride, int n,
+                      int cout, int h, int w, int act, tg_stream_t stream);
+int tg_upconv3x3_fwd(const float* x, int64_t x_nstride, const float* a_packed, const float* bias, float* z,
+                     int64_t z_nstride, float* y, int64_t y_nstride, int n, int cin, int cout, int h, int w,
+                     int act, tg_stream_t stream);
+int tg_upconv_prefers(int n, int cin, int cout, int h, int w);
+
 /* Several DEPENDENT 3x3 layers (layer i+1 reads what layer i writes: SRNet's conv_in and residual
  * blocks, tecogan_nets.py:108-116,141-143) in ONE launch.  Every separate launch of the Winograd
  * kernel pays ~10 us that nothing overlaps (launch, first loads, final stores); here the workgroups

@@ -87,6 +87,9 @@ struct tg_frnet_plan {
   float* WZ = nullptr;              // packed output-conv weights for the fused HR stage
   float* WA = nullptr;              // Winograd-domain weights of the Z-mode layer (tg_convt_pack_wino)
   bool wz_ready = false, wa_ready = false;
+  // the up-sampling readers at the low resolution (tg_upconv.hip): z of the reader that runs, the three tap packs
+  float *UPZ = nullptr, *UPA = nullptr;
+  bool upa_ready[3] = {false, false, false};
   int32_t* CHAINF = nullptr;        // per-tile flags of the chained SRNet launch (tg_conv3x3_wino_chain)
   bool chain_ready = false;         // flags zeroed
   unsigned epoch = 0;               // one per chained launch
@@ -184,9 +187,16 @@ static size_t fnet_partial_floats(const tg_frnet_cfg* c) {
   return best;
 }
 
+// tap packs of the three readers of a decoder block's up-sampling (decoder2.0, decoder3.0, flow.0), back to back
+static size_t fnet_upa_offset(int k) {
+  size_t o = 0;
+  for (int i = 0; i < k; ++i) o += tg_upconv_packed_floats(FNET_DEC[i], i < 2 ? FNET_DEC[i + 1] : FNET_HEAD);
+  return o;
+}
+
 static const int CHAIN_MAX_LAYERS = 24;
 // The regions in workspace order; tg_frnet_workspace_floats and tg_frnet_plan_create both walk them (carve).
-enum { R_A, R_B, R_FLOW, R_S2D, R_U1, R_U2, R_PART, R_FA, R_FB, R_FPART, R_FLOW2, R_WZ_WA, R_CHAINF, R_RESWS, R_COUNT };
+enum { R_A, R_B, R_FLOW, R_S2D, R_U1, R_U2, R_PART, R_FA, R_FB, R_FPART, R_FLOW2, R_WZ_WA, R_CHAINF, R_RESWS, R_UPZ, R_UPA, R_COUNT };
 static size_t region_floats(const tg_frnet_cfg* c, int region) {
   const size_t hw = (size_t)c->h * c->w, n = c->n;
   const size_t sr = c->fnet_only ? 0 : 1;                      // an FNet-only plan has no SRNet regions
@@ -208,6 +218,10 @@ static size_t region_floats(const tg_frnet_cfg* c, int region) {
     case R_CHAINF: return sr * align64((size_t)CHAIN_MAX_LAYERS * n * ((c->h + 1) / 2) * ((c->w + 31) / 32) + 16);
     // tg_conv3x3_wino_res.hip: exchange buffer + flags; n == 1 only
     case R_RESWS: return align64((size_t)(((sr && n == 1) ? tg::conv3x3_wino_resident_ws_bytes(c->h, c->w) : 0) + 3) / 4);
+    // z of an up-sampling reader (tg_upconv.hip): 9 cout planes of its source map; flow.0's is the largest of the three,
+    // 288 planes of the half map -- more than the 64-plane ping-pong regions hold
+    case R_UPZ: return align64(n * 9 * FNET_HEAD * 16 * (size_t)(c->h / 8) * (c->w / 8));
+    case R_UPA: return align64(fnet_upa_offset(3));
   }
   return 0;
 }
@@ -367,6 +381,41 @@ struct Emit {
     return fpool;
   }
 
+  // The kind of the ONE launch that conv() makes of a plain layer (no pool, no residual) on the (hh, ww) map, or -1
+  // where it makes two (split-K + finalize).
+  int conv_single_kind(int layer, int cin, int cout, int hh, int ww) const {
+    if (p->L[layer].u && tg_conv3x3_prefers_wino(n, cin, cout, hh, ww)) return K_CONV_WINO;
+    if (tg_conv3x3_pick_ksplit(n, cin, cout, hh, ww) > 1) return -1;
+    const int ocb = tg_conv3x3_pick_ocb(cout);
+    const int kind = ocb == 32 ? K_CONV32 : tg::conv3x3_rows_per_wg(ocb, (long long)n * hh * ww) == 4 ? K_CONV64_R4 : K_CONV64_R2;
+    if (kind == K_CONV64_R2 && tg::conv3x3_uses_wg_ksplit(n, cin, cout, hh, ww))
+      return tg::conv3x3_uses_oneshot(n, cin, cout, hh, ww) ? K_CONV_ONESHOT : K_CONV64_KS;
+    return kind;
+  }
+  // Whether reader k (0: decoder2.0, 1: decoder3.0, 2: flow.0) of the (sh, sw) source map runs at the low resolution
+  // (tg_upconv.hip): where tg_upconv_prefers says so and the conv it replaces is one launch, so that the launch counts
+  // per kind stay what they are.
+  bool upconv_wanted(int layer, int cin, int cout, int sh, int sw) const {
+    return tg_upconv_prefers(n, cin, cout, sh, sw) && conv_single_kind(layer, cin, cout, 2 * sh, 2 * sw) >= 0;
+  }
+  // conv3x3(bilinear_x2(x)) + bias + act of reader k from its (cin, sh, sw) source: tap GEMM into UPZ, then the combine.
+  // No kind of their own: the GEMM is accounted as the conv launch it replaces, with that layer's algorithmic 3x3 flops
+  // (as the Winograd Z layer is), the combine as the up-sampling launch it replaces.
+  void upconv(int layer, int k, const float* x, int cin, int cout, int sh, int sw, int act, float* y) {
+    const tg_layer_weights lw = p->L[layer];
+    const double spx = (double)n * sh * sw;
+    const int64_t zns = (int64_t)9 * cout * sh * sw;
+    float* const a = p->UPA + fnet_upa_offset(k);
+    if (rc == TG_OK && !dry && active && !p->upa_ready[k])      // once per plan, ahead of its first reader (as WZ / WA)
+      p->upa_ready[k] = (rc = tg_upconv_pack(lw.w, a, cin, cout, tg_conv3x3_pick_ocb(cout), st)) == TG_OK;
+    go(conv_single_kind(layer, cin, cout, 2 * sh, 2 * sw), 2.0 * cin * 9 * cout * 4 * spx,
+       4.0 * spx * (cin + 9 * cout) + 4.0 * 9 * cin * cout,
+       [&] { return tg_upconv_tap_gemm(x, (int64_t)cin * sh * sw, a, p->UPZ, zns, n, cin, cout, sh, sw, st); });
+    go(K_UPSAMPLE, 0, 4.0 * spx * cout * (9 + 4), [&] {
+      return tg_upconv_combine(p->UPZ, zns, lw.b, y, (int64_t)cout * 4 * sh * sw, n, cout, sh, sw, act, st);
+    });
+  }
+
   // ---- FNet (tecogan_nets.py:67-82), phase 1: (lr_curr, lr_prev) -> flow_buf, which it returns -------------------------
   float* fnet_stage(const float* lr_curr, const float* lr_prev, float* flow_buf) {
     begin_phase(1);
@@ -388,16 +437,25 @@ struct Emit {
     // A decoder block's x2 up-sampling can be folded into the staging of the conv that reads it (decoder2.0, decoder3.0,
     // flow.0) when that conv runs the Winograd form: the block then leaves its low-resolution result in `src` and
     // there is no K_UPSAMPLE launch.  tg::conv3x3_wino_folds_up2 says where (measured: nowhere unless the form is forced).
-    bool up2 = false;      // src is the low-resolution source of the (hh, ww) map
+    // Or the reader runs its matrix work on the low-resolution map itself (upconv above: a tap GEMM and a combine in the
+    // place of the up-sampling launch and the conv), where upconv_wanted says so.
+    bool up2 = false;      // src is the low-resolution source of the (hh, ww) map, folded into the Winograd staging
+    bool low = false;      // src is that source and the reader runs at the low resolution
+    // reader k of a decoder block: decoder2.0, decoder3.0, flow.0; (src, cin) -> A at (hh, ww)
+    auto read_block = [&](int layer, int k, int co) {
+      if (low) upconv(layer, k, src, cin, co, hh / 2, ww / 2, TG_ACT_LRELU02, A);
+      else conv(layer, src, (int64_t)cin * (up2 ? (hh / 2) * (ww / 2) : hh * ww), cin, nullptr, 0, cin, co, hh, ww,
+                TG_ACT_LRELU02, nullptr, 0, A, (int64_t)co * hh * ww, false, nullptr, up2);
+    };
     for (int d = 0; d < 3; ++d) {
       const int co = FNET_DEC[d];
-      conv(at.dec(d, 0), src, (int64_t)cin * (up2 ? (hh / 2) * (ww / 2) : hh * ww), cin, nullptr, 0, cin, co, hh, ww,
-           TG_ACT_LRELU02, nullptr, 0, A, (int64_t)co * hh * ww, false, nullptr, up2);
+      read_block(at.dec(d, 0), d - 1, co);      // (decoder1.0 reads the encoder: neither flag is set)
       conv(at.dec(d, 1), A, (int64_t)co * hh * ww, co, nullptr, 0, co, co, hh, ww, TG_ACT_LRELU02, nullptr, 0, B,
            (int64_t)co * hh * ww);
       const int reader = d < 2 ? at.dec(d + 1, 0) : at.flow(0), rco = d < 2 ? FNET_DEC[d + 1] : FNET_HEAD;
       up2 = p->L[reader].u && tg::conv3x3_wino_folds_up2(n, co, rco, 2 * hh, 2 * ww);
-      if (!up2) {
+      low = !up2 && upconv_wanted(reader, co, rco, hh, ww);
+      if (!up2 && !low) {
         go(K_UPSAMPLE, 0, 4.0 * n * co * hh * ww * 5.0,
            [&] { return tg_upsample_fwd(B, A, n * co, hh, ww, 2, TG_UP_BILINEAR, 1.0f, st); });
         float* t = A; A = B; B = t;
@@ -405,8 +463,7 @@ struct Emit {
       hh *= 2; ww *= 2; cin = co;
       src = B;
     }
-    conv(at.flow(0), src, (int64_t)cin * (up2 ? (hh / 2) * (ww / 2) : hh * ww), cin, nullptr, 0, cin, FNET_HEAD, hh, ww,
-         TG_ACT_LRELU02, nullptr, 0, A, (int64_t)FNET_HEAD * hh * ww, false, nullptr, up2);
+    read_block(at.flow(0), 2, FNET_HEAD);
     const tg_layer_weights lw = p->L[at.flow(1)];
     go(K_SMALL, 2.0 * FNET_HEAD * 9 * FNET_FLOW * n * hh * ww, 4.0 * n * hh * ww * (FNET_HEAD + FNET_FLOW), [&] {
       return tg_conv3x3_small_fwd(A, (int64_t)FNET_HEAD * hh * ww, lw.w, lw.b, nullptr, TG_UP_NONE, 1, flow_buf,
@@ -649,6 +706,7 @@ extern "C" int tg_frnet_plan_create(const tg_frnet_cfg* cfg, const tg_layer_weig
   p->U2 = cfg->scale == 4 ? region(R_U2) : nullptr; p->PART = region(R_PART);
   p->FA = region(R_FA); p->FB = region(R_FB); p->FPART = region(R_FPART); p->FLOW2 = region(R_FLOW2);
   p->WZ = region(R_WZ_WA); p->WA = p->WZ + 2048;
+  p->UPZ = region(R_UPZ); p->UPA = region(R_UPA);
   p->CHAINF = reinterpret_cast<int32_t*>(region(R_CHAINF)); p->RESWS = region(R_RESWS);
   if (!cfg->fnet_only) {
     void* hp = nullptr;

@@ -13,8 +13,8 @@
 // exist only in lab builds (TG_LAB_BUILD=1 OUT=<dir> bash build.sh, which sets -DTG_LAB=1).  The one compile-time lab
 // switch is WR_UASM=0 (tg_conv3x3_wino_res.hip: the cross-check form of the resident kernel's weight loads); the
 // row chain's per-layer time stamps (tg_conv3x3_chain.hip) are compiled in by TG_LAB itself.  The ablation and A/B
-// variants of rounds 1-6 are in EXPERIMENTS.md and in git history.  The shipped library reads exactly three variables,
-// all documented in INTEGRATION.md: TG_CONV_WINO, TG_WINO_CHAIN and TG_WINO_RES (kernel-form selection
+// variants of rounds 1-6 are in EXPERIMENTS.md and in git history.  The shipped library reads exactly four variables,
+// all documented in INTEGRATION.md: TG_CONV_WINO, TG_WINO_CHAIN, TG_WINO_RES and TG_UPCONV (kernel-form selection
 // for A/B runs; every setting produces reference-parity results).  The Python mirror has switches of its own
 // (TG_FNET_BATCH, TG_WINO_RES_CT, TG_CONV4_DIRECT, TECOGAN_COMM, TECOGAN_HIP_LIB): INTEGRATION.md.
 #ifndef TG_LAB

@@ -1763,6 +1763,55 @@ def conv3x3_wino(x, u_packed, bias, cin, cout, act=ACT_NONE, x2=None, res=None, 
     return y
 
 
+def pack_upconv(w, ocb=0, cin=None, cout=None):
+    """tg_upconv_pack: the tap-GEMM operand of conv3x3(bilinear_x2(.)).  ocb 0: w is the OIHW weight; 32 | 64: w is
+    pack_conv3x3's layout with that ocb (cin, cout then given)."""
+    _chk(w, 'w')
+    if ocb == 0:
+        cout, cin = w.shape[0], w.shape[1]
+    nflt = L.lib().tg_upconv_packed_floats(cin, cout)
+    if nflt == 0:
+        raise L.TecoganHipError(f'pack_upconv: cin={cin} cout={cout} is not a supported shape')
+    out = torch.empty(nflt, dtype=torch.float32, device=w.device)
+    L.check(L.lib().tg_upconv_pack(w.data_ptr(), out.data_ptr(), cin, cout, ocb, _stream()), 'tg_upconv_pack')
+    return out
+
+
+def upconv_tap_gemm(x, a_packed, cin, cout, z=None):
+    """z (n, 9 cout, h, w) = the nine taps' channel mixes of x (n, cin, h, w) at its own resolution."""
+    _chk(x, 'x'); _chk(a_packed, 'a_packed')
+    n, c, h, w = x.shape
+    assert c == cin
+    z = z if z is not None else torch.empty(n, 9 * cout, h, w, dtype=torch.float32, device=x.device)
+    L.check(L.lib().tg_upconv_tap_gemm(x.data_ptr(), x.stride(0), a_packed.data_ptr(), z.data_ptr(), z.stride(0), n, cin,
+                                       cout, h, w, _stream()), 'tg_upconv_tap_gemm')
+    return z
+
+
+def upconv_combine(z, bias, cout, act=ACT_NONE, out=None):
+    """y (n, cout, 2h, 2w) = act(bias + the nine shifted, bilinearly x2 up-sampled planes of z (n, 9 cout, h, w))."""
+    _chk(z, 'z')
+    n, c9, h, w = z.shape
+    assert c9 == 9 * cout
+    y = out if out is not None else torch.empty(n, cout, 2 * h, 2 * w, dtype=torch.float32, device=z.device)
+    L.check(L.lib().tg_upconv_combine(z.data_ptr(), z.stride(0), _ptr(bias), y.data_ptr(), y.stride(0), n, cout, h, w,
+                                      act, _stream()), 'tg_upconv_combine')
+    return y
+
+
+def upconv3x3(x, a_packed, bias, cin, cout, act=ACT_NONE, out=None):
+    """act(conv3x3(bilinear_x2(x)) + bias) with the matrix work at x's resolution (tg_upconv3x3_fwd: both launches)."""
+    _chk(x, 'x'); _chk(a_packed, 'a_packed')
+    n, c, h, w = x.shape
+    assert c == cin
+    z = torch.empty(n, 9 * cout, h, w, dtype=torch.float32, device=x.device)
+    y = out if out is not None else torch.empty(n, cout, 2 * h, 2 * w, dtype=torch.float32, device=x.device)
+    L.check(L.lib().tg_upconv3x3_fwd(x.data_ptr(), x.stride(0), a_packed.data_ptr(), _ptr(bias), z.data_ptr(),
+                                     z.stride(0), y.data_ptr(), y.stride(0), n, cin, cout, h, w, act, _stream()),
+            'tg_upconv3x3_fwd')
+    return y
+
+
 class RowChain:
     """tg_conv3x3_chain: dependent 3x3 layers of small frames in one persistent launch.  `layers` is a
     list of dicts (x, w (OIHW weight tensor), bias=None, act=ACT_NONE, x2=None, res=None, mask=None, y);

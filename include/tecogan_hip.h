@@ -661,6 +661,22 @@ int tg_rgb_f32_to_yuv_planar16(const float* rgb_chw, uint16_t* yuv, int n, int H
  *   f: the fp32 gains of the input direction's matrix step: ky = 1/ys, then rv, gu, gv, bu per sixteenth of a code */
 int tg_yuv_tables(int depth, int matrix, int full_range, int q[12], float f[5]);
 
+/* Semi-planar YUV: what hardware decoders and encoders exchange -- NV12 / NV16 / NV24 at 8 bits,
+ * P010 / P012, P210 / P212, P410 / P412 above.  A frame is the Y plane h*w, then ONE chroma plane of ceil(h/sy) rows of
+ * 2 * ceil(w/sx) samples, sample 2c of a row U[r, c] and sample 2c + 1 V[r, c], tightly packed: the sample count of the
+ * planar frame of the same chroma.  A sample is a byte at depth 8 and above it a 16-bit little-endian word that holds
+ * code << (16 - depth): read as word >> (16 - depth) (the low bits are ignored, so nothing exceeds 2^depth - 1), written
+ * with the low bits zero.  Everything else -- enums, tables, siting, taps, the one fp32 step on the way in, the exact
+ * integers on the way out -- is the planar functions': these three launch the same two kernel templates with the
+ * chroma layout switched, the samples equal those of the planar function on the relaid frame bit for bit, and the
+ * argument lists, shapes, refusals (TG_E_ARG without a launch) and alignment rules are the planar ones. */
+int tg_yuv_semiplanar_to_rgb_f32(const void* yuv, float* rgb_chw, int n, int h, int w, int chroma, int depth,
+                                 int matrix, int full_range, int siting, tg_stream_t stream);
+int tg_rgb_u8_to_yuv_semiplanar(const uint8_t* rgb_hwc, uint8_t* yuv, int n, int H, int W, int chroma, int matrix,
+                                int full_range, int siting, tg_stream_t stream);
+int tg_rgb_f32_to_yuv_semiplanar16(const float* rgb_chw, uint16_t* yuv, int n, int H, int W, int chroma, int depth,
+                                   int matrix, int full_range, int siting, tg_stream_t stream);
+
 /* Motion-adaptive deinterlacing of planar YUV (the reference has no counterpart): interlaced
  * frames in, progressive frames out, same layout and sample type as tg_yuv_planar_to_rgb_f32 takes.  The
  * specification is tests/deinterlace_ref.py and the samples are equal: an edge-directed line average over three

@@ -1,14 +1,20 @@
-// Planar YUV in and out of the stream (DESIGN.md sections 7e, 7k, 7l): what a decoder hands over and an encoder takes,
-// converted on the device so that fewer bytes cross PCIe than RGB would need.  These are the only yuv kernels: ONE
-// template per direction over (sample type T, SX, SY, VEC, LEFT), 20 instantiations each, behind seven entry points --
-// the three planar ones and the four 4:2:0 ones (tg_yuv420_to_rgb_f32, tg_rgb_u8_to_yuv420, tg_yuv420p16_to_rgb_f32,
-// tg_rgb_f32_to_yuv420p16), which keep their own argument checks (BT.601 / BT.709 only) and launch the (2,2) forms.
+// Planar and semi-planar YUV in and out of the stream (DESIGN.md sections 7e, 7k, 7l, 7p): what a decoder hands over
+// and an encoder takes, converted on the device so that fewer bytes cross PCIe than RGB would need.  These are the only
+// yuv kernels: ONE template per direction over (sample type T, SX, SY, VEC, LEFT, SEMI), 40 instantiations each, behind
+// ten entry points -- the three planar ones, the three semi-planar ones (SEMI) and the four 4:2:0 ones
+// (tg_yuv420_to_rgb_f32, tg_rgb_u8_to_yuv420, tg_yuv420p16_to_rgb_f32, tg_rgb_f32_to_yuv420p16), which keep their own
+// argument checks (BT.601 / BT.709 only) and launch the planar (2,2) forms.
 //
 // Format.  A frame is the Y plane H W, then U, then V, each ceil(H/SY) x ceil(W/SX), tightly packed; (SX, SY) is the
 // chroma sub-sampling, (2,2) 4:2:0 | (2,1) 4:2:2 | (1,1) 4:4:4.  A sample is a byte at depth 8 (T = uint8_t) and a
 // 16-bit little-endian word with d = 10 | 12 significant bits above it (T = uint16_t; one above 2^d - 1 is read as
 // 2^d - 1).  LEFT: a chroma sample sits on the left luma column of its pair, else in the centre (along x only; the
 // vertical rule of 4:2:0 is the centred one either way).
+// SEMI (NV12 / NV16 / NV24, P010 / P012 and their 4:2:2 and 4:4:4 siblings): behind the Y plane ONE chroma plane of
+// ceil(H/SY) rows of 2 ceil(W/SX) samples, sample 2c of a row U[r, c] and 2c + 1 V[r, c]; a 16-bit word holds
+// code << (16 - d).  It is read as word >> (16 - d) -- nothing exceeds 2^d - 1, the clamp above has nothing to do -- and
+// written with the low bits zero; the shift travels as a kernel argument (0 for bytes, not looked at without SEMI).
+// Nothing else differs: the values are the planar form's, relaid.
 //
 // Arithmetic.  Both tables come from (Kr, Kb) in fp64 on the host and travel as kernel arguments (forward_table,
 // inverse_table; tg_yuv_tables shows them to the host).
@@ -38,6 +44,14 @@
 //   Hence: Y runs of 4 samples and 4:4:4 chroma runs of 4 are aligned to 4 samples (a dword at 8 bit, 8 bytes at 16
 //   bit), chroma runs of 2 to 2 samples (a 16-bit word / a dword).  fp32 CHW: plane H W and row W are multiples of 4
 //   floats, so every float4 is 16-byte aligned; uint8 HWC: row 3W = 12m and 3 x0 = 12 tx, so the three dwords are.
+//   SEMI, same bases, W = 4 m.  The chroma plane starts H W = 4 H m samples behind the frame: a multiple of 4.  Its row
+//   is 2 cw samples: 4m for SX = 2 (cw = 2m), 8m for SX = 1.  A frame is H W + ch 2 cw: 4:2:0 (ch = ceil(H/2)) 4m (H +
+//   ch), 4:2:2 8 H m, 4:4:4 12 H m -- a multiple of 4, and at 4:4:4 with H m odd of nothing more.  A strip's run of
+//   2 NC samples starts at j 2 cw + 2 NC tx: 4 (j m + tx) for SX = 2, 8 (j m + tx) for SX = 1.
+//   Hence: for SX = 2 the run of 4 samples (u0 v0 u1 v1) is aligned to its own size, ONE store of 4 samples where the
+//   planar form has two of 2; for SX = 1 the run of 8 is aligned to 4 samples only (frame and Y plane are 4:4:4's
+//   12 H m and 4 H m), TWO stores of 4 samples.  On the way in the wide loads are the Y samples' (aligned as above: the
+//   frame is a multiple of 4 samples for odd h as well); the chroma loads are element-wide in both layouts.
 // Every other shape or placement (W = 2 mod 4, odd sizes, a base off its alignment) takes the element-wide form of
 // the same kernel.
 //
@@ -45,7 +59,8 @@
 // logical shift (the same value: a negative acc gives 0, one of (top + 1) << sh or more gives top).  With the clamp
 // AFTER the shift hipcc fuses two neighbours into one v_ashr_pk_u8_i32, whose 16-bit result it then packed into the Y
 // dword as if the upper half of the register were zero: bytes 2 and 3 of the store came out wrong on the MI355X.
-// shift_clip_u8 and shift_clip_top are the only places that clip, so no packed shift can be formed.
+// shift_clip_u8 and shift_clip_top are the only places that clip, so no packed shift can be formed -- in the SEMI form's
+// u0 | v0 << 8 | u1 << 16 | v1 << 24, the very pattern, neither: its four values leave those two functions clamped.
 #include "tg_common.h"
 
 namespace tg {
@@ -232,10 +247,11 @@ __device__ __forceinline__ void store_samples(uint16_t* dst, const unsigned v[N]
 
 // thread = rows SY*j .. SY*j + SY-1 x pixels 4*tx .. 4*tx+3 of frame k.  H is a multiple of SY and W one of SX (the
 // entry points test it), so a strip holds whole chroma samples: npx is 2 or 4 for SX = 2, 1 .. 4 for SX = 1.
-template <typename T, int SX, int SY, bool VEC, bool LEFT>
+// SEMI: the chroma samples of the strip go out as one interleaved run (u0 v0 u1 v1 ...), every sample shifted left by shl.
+template <typename T, int SX, int SY, bool VEC, bool LEFT, bool SEMI>
 __global__ __launch_bounds__(256) void rgb_to_yuv_planar_kernel(const typename yuv_out<T>::src_t* __restrict__ rgb,
                                                                 T* __restrict__ yuv, int H, int W, int strips,
-                                                                long long total, yuv_qp q) {
+                                                                long long total, yuv_qp q, int shl) {
   typedef yuv_out<T> O;
   typedef typename O::acc_t acc_t;
   static_assert((SX == 2 || SX == 1) && (SY == 2 || SY == 1) && SY <= SX, "4:2:0, 4:2:2 or 4:4:4");
@@ -261,7 +277,10 @@ __global__ __launch_bounds__(256) void rgb_to_yuv_planar_kernel(const typename y
   for (int rr = 0; rr < SY; ++rr) {
     unsigned yv[4];
 #pragma unroll
-    for (int x = 0; x < 4; ++x) yv[x] = O::clip(O::dot(q.y, p[rr][x]) + yround, O::BASE, q.top);
+    for (int x = 0; x < 4; ++x) {
+      yv[x] = O::clip(O::dot(q.y, p[rr][x]) + yround, O::BASE, q.top);
+      if (SEMI) yv[x] <<= shl;
+    }
     store_samples<VEC, 4>(yp + (long long)(SY * j + rr) * W + x0, yv, npx);
   }
   constexpr int NC = 4 / SX;                                      // chroma samples of the strip, per plane
@@ -295,18 +314,31 @@ __global__ __launch_bounds__(256) void rgb_to_yuv_planar_kernel(const typename y
   }
   const long long co = (long long)j * cw + NC * tx;
   const int ncs = npx / SX;                                       // chroma samples inside the frame
-  store_samples<VEC, NC>(up + co, uo, ncs);
-  store_samples<VEC, NC>(vp + co, vo, ncs);
+  if (SEMI) {                                                     // one run of 2 NC samples, 2 co behind the Y plane
+    unsigned cv[2 * NC];
+#pragma unroll
+    for (int c2 = 0; c2 < NC; ++c2) {
+      cv[2 * c2] = uo[c2] << shl;
+      cv[2 * c2 + 1] = vo[c2] << shl;
+    }
+    store_samples<VEC, 4>(up + 2 * co, cv, 2 * ncs);
+    if (NC == 4) store_samples<VEC, 4>(up + 2 * co + 4, cv + (NC == 4 ? 4 : 0), 2 * ncs - 4);
+  } else {
+    store_samples<VEC, NC>(up + co, uo, ncs);
+    store_samples<VEC, NC>(vp + co, vo, ncs);
+  }
 }
 
 // thread = row y x pixels 4*tx .. 4*tx+3 of frame k.  `top` = 2^d - 1 bounds every 16-bit
 // sample, `mid16` = 16 * mid.  Along a sub-sampled axis the taps are the ones above; along one that is not, the sample
 // of the pixel itself times 4.  Every chroma index is clamped into the plane, so the loads of the pixels past the
 // width are in bounds too.
-template <typename T, int SX, int SY, bool VEC, bool LEFT>
+// SEMI: U and V of chroma column c are samples 2c and 2c + 1 of the one chroma plane, and every sample is read as
+// word >> shr (element-wide chroma loads in either layout; the wide loads are the Y samples').
+template <typename T, int SX, int SY, bool VEC, bool LEFT, bool SEMI>
 __global__ __launch_bounds__(256) void yuv_planar_to_rgb_f32_kernel(const T* __restrict__ yuv, float* __restrict__ rgb,
                                                                     int h, int w, int strips, long long total, yuv_f f,
-                                                                    int top, int mid16) {
+                                                                    int top, int mid16, int shr) {
   static_assert((SX == 2 || SX == 1) && (SY == 2 || SY == 1) && SY <= SX, "4:2:0, 4:2:2 or 4:4:4");
   static_assert(SX == 2 || !LEFT, "the siting matters along a sub-sampled axis only");
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -318,9 +350,9 @@ __global__ __launch_bounds__(256) void yuv_planar_to_rgb_f32_kernel(const T* __r
   const int x0 = 4 * tx, ch = (h + SY - 1) / SY, cw = (w + SX - 1) / SX;
   const T* yp = yuv + k * ((long long)h * w + 2LL * ch * cw);
   const T* up = yp + (long long)h * w;
-  const T* vp = up + (long long)ch * cw;
-  auto sample = [top](const T* p, long long at) {
-    const int s = (int)p[at];
+  const T* vp = SEMI ? up + 1 : up + (long long)ch * cw;
+  auto sample = [top, shr](const T* p, long long at) {
+    const int s = SEMI ? (int)p[2 * at] >> shr : (int)p[at];
     return sizeof(T) == 1 ? s : (s > top ? top : s);
   };
   int r0, r1, w0, w1;                                             // two chroma rows and their weights, in quarters
@@ -372,6 +404,10 @@ __global__ __launch_bounds__(256) void yuv_planar_to_rgb_f32_kernel(const T* __r
 #pragma unroll
     for (int x = 0; x < 4; ++x) yy[x] = x0 + x < w ? (int)ysrc[x] : 0;
   }
+  if (SEMI) {
+#pragma unroll
+    for (int x = 0; x < 4; ++x) yy[x] >>= shr;
+  }
   float R[4], G[4], B[4];
 #pragma unroll
   for (int x = 0; x < 4; ++x) {
@@ -405,36 +441,37 @@ static bool yuv_planar_enums_ok(int chroma, int matrix, int full_range, int siti
          (full_range == 0 || full_range == 1) && (siting == TG_YUV_CENTER || siting == TG_YUV_LEFT);
 }
 
-template <typename T, int SX, int SY>
+template <typename T, int SX, int SY, bool SEMI>
 static void launch_planar_out(bool vec, bool left, dim3 grid, hipStream_t st, const typename yuv_out<T>::src_t* rgb,
-                              T* yuv, int H, int W, int strips, long long total, const yuv_qp& q) {
+                              T* yuv, int H, int W, int strips, long long total, const yuv_qp& q, int shl) {
   constexpr bool L = SX == 2;                                     // (4:4:4 has the one form: the siting is not looked at)
   const dim3 block(256);
   if (vec) {
-    if (left) hipLaunchKernelGGL((rgb_to_yuv_planar_kernel<T, SX, SY, true, L>), grid, block, 0, st, rgb, yuv, H, W, strips, total, q);
-    else hipLaunchKernelGGL((rgb_to_yuv_planar_kernel<T, SX, SY, true, false>), grid, block, 0, st, rgb, yuv, H, W, strips, total, q);
+    if (left) hipLaunchKernelGGL((rgb_to_yuv_planar_kernel<T, SX, SY, true, L, SEMI>), grid, block, 0, st, rgb, yuv, H, W, strips, total, q, shl);
+    else hipLaunchKernelGGL((rgb_to_yuv_planar_kernel<T, SX, SY, true, false, SEMI>), grid, block, 0, st, rgb, yuv, H, W, strips, total, q, shl);
   } else {
-    if (left) hipLaunchKernelGGL((rgb_to_yuv_planar_kernel<T, SX, SY, false, L>), grid, block, 0, st, rgb, yuv, H, W, strips, total, q);
-    else hipLaunchKernelGGL((rgb_to_yuv_planar_kernel<T, SX, SY, false, false>), grid, block, 0, st, rgb, yuv, H, W, strips, total, q);
+    if (left) hipLaunchKernelGGL((rgb_to_yuv_planar_kernel<T, SX, SY, false, L, SEMI>), grid, block, 0, st, rgb, yuv, H, W, strips, total, q, shl);
+    else hipLaunchKernelGGL((rgb_to_yuv_planar_kernel<T, SX, SY, false, false, SEMI>), grid, block, 0, st, rgb, yuv, H, W, strips, total, q, shl);
   }
 }
 
-template <typename T, int SX, int SY>
+template <typename T, int SX, int SY, bool SEMI>
 static void launch_planar_in(bool vec, bool left, dim3 grid, hipStream_t st, const T* yuv, float* rgb, int h, int w,
-                             int strips, long long total, const yuv_f& f, int top, int mid16) {
+                             int strips, long long total, const yuv_f& f, int top, int mid16, int shr) {
   constexpr bool L = SX == 2;
   const dim3 block(256);
   if (vec) {
-    if (left) hipLaunchKernelGGL((yuv_planar_to_rgb_f32_kernel<T, SX, SY, true, L>), grid, block, 0, st, yuv, rgb, h, w, strips, total, f, top, mid16);
-    else hipLaunchKernelGGL((yuv_planar_to_rgb_f32_kernel<T, SX, SY, true, false>), grid, block, 0, st, yuv, rgb, h, w, strips, total, f, top, mid16);
+    if (left) hipLaunchKernelGGL((yuv_planar_to_rgb_f32_kernel<T, SX, SY, true, L, SEMI>), grid, block, 0, st, yuv, rgb, h, w, strips, total, f, top, mid16, shr);
+    else hipLaunchKernelGGL((yuv_planar_to_rgb_f32_kernel<T, SX, SY, true, false, SEMI>), grid, block, 0, st, yuv, rgb, h, w, strips, total, f, top, mid16, shr);
   } else {
-    if (left) hipLaunchKernelGGL((yuv_planar_to_rgb_f32_kernel<T, SX, SY, false, L>), grid, block, 0, st, yuv, rgb, h, w, strips, total, f, top, mid16);
-    else hipLaunchKernelGGL((yuv_planar_to_rgb_f32_kernel<T, SX, SY, false, false>), grid, block, 0, st, yuv, rgb, h, w, strips, total, f, top, mid16);
+    if (left) hipLaunchKernelGGL((yuv_planar_to_rgb_f32_kernel<T, SX, SY, false, L, SEMI>), grid, block, 0, st, yuv, rgb, h, w, strips, total, f, top, mid16, shr);
+    else hipLaunchKernelGGL((yuv_planar_to_rgb_f32_kernel<T, SX, SY, false, false, SEMI>), grid, block, 0, st, yuv, rgb, h, w, strips, total, f, top, mid16, shr);
   }
 }
 
-// the checks and the launch of the output direction for one sample type; `base_ok` = the wide form's base alignments
-template <typename T>
+// the checks and the launch of the output direction for one sample type and chroma layout; `base_ok` = the wide form's
+// base alignments.  Semi-planar words carry their code in the top bits: shl = 16 - depth (0 for bytes).
+template <typename T, bool SEMI = false>
 static int rgb_to_yuv_planar(const char* name, const typename yuv_out<T>::src_t* rgb, T* yuv, int n, int H, int W,
                              int chroma, int depth, int matrix, int full_range, int siting, bool base_ok,
                              tg_stream_t stream) {
@@ -450,14 +487,15 @@ static int rgb_to_yuv_planar(const char* name, const typename yuv_out<T>::src_t*
   const yuv_qp q = forward_table(matrix, full_range, depth);
   const dim3 grid((unsigned)((total + 255) / 256));
   const hipStream_t st = (hipStream_t)stream;
-  if (chroma == TG_YUV_420) launch_planar_out<T, 2, 2>(vec, left, grid, st, rgb, yuv, H, W, strips, total, q);
-  else if (chroma == TG_YUV_422) launch_planar_out<T, 2, 1>(vec, left, grid, st, rgb, yuv, H, W, strips, total, q);
-  else launch_planar_out<T, 1, 1>(vec, left, grid, st, rgb, yuv, H, W, strips, total, q);
+  const int shl = SEMI && depth > 8 ? 16 - depth : 0;
+  if (chroma == TG_YUV_420) launch_planar_out<T, 2, 2, SEMI>(vec, left, grid, st, rgb, yuv, H, W, strips, total, q, shl);
+  else if (chroma == TG_YUV_422) launch_planar_out<T, 2, 1, SEMI>(vec, left, grid, st, rgb, yuv, H, W, strips, total, q, shl);
+  else launch_planar_out<T, 1, 1, SEMI>(vec, left, grid, st, rgb, yuv, H, W, strips, total, q, shl);
   return check_launch(name);
 }
 
 // the launch of the input direction for one sample type; the entry points have checked the arguments
-template <typename T>
+template <typename T, bool SEMI = false>
 static int yuv_planar_to_rgb(const char* name, const T* yuv, float* rgb, int n, int h, int w, int chroma, int depth,
                              int matrix, int full_range, int siting, bool base_ok, tg_stream_t stream) {
   const int sx = chroma == TG_YUV_444 ? 1 : 2;
@@ -469,47 +507,89 @@ static int yuv_planar_to_rgb(const char* name, const T* yuv, float* rgb, int n, 
   const int top = (1 << depth) - 1, mid16 = 16 << (depth - 1);
   const dim3 grid((unsigned)((total + 255) / 256));
   const hipStream_t st = (hipStream_t)stream;
-  if (chroma == TG_YUV_420) launch_planar_in<T, 2, 2>(vec, left, grid, st, yuv, rgb, h, w, strips, total, f, top, mid16);
-  else if (chroma == TG_YUV_422) launch_planar_in<T, 2, 1>(vec, left, grid, st, yuv, rgb, h, w, strips, total, f, top, mid16);
-  else launch_planar_in<T, 1, 1>(vec, left, grid, st, yuv, rgb, h, w, strips, total, f, top, mid16);
+  const int shr = SEMI && depth > 8 ? 16 - depth : 0;
+  if (chroma == TG_YUV_420) launch_planar_in<T, 2, 2, SEMI>(vec, left, grid, st, yuv, rgb, h, w, strips, total, f, top, mid16, shr);
+  else if (chroma == TG_YUV_422) launch_planar_in<T, 2, 1, SEMI>(vec, left, grid, st, yuv, rgb, h, w, strips, total, f, top, mid16, shr);
+  else launch_planar_in<T, 1, 1, SEMI>(vec, left, grid, st, yuv, rgb, h, w, strips, total, f, top, mid16, shr);
   return check_launch(name);
+}
+
+// the three entry points of a chroma layout: one body each, the planar and the semi-planar function differ in SEMI and
+// in the name their messages carry
+template <bool SEMI>
+static int yuv_to_rgb_f32_entry(const char* name, const void* yuv, float* rgb_chw, int n, int h, int w, int chroma,
+                                int depth, int matrix, int full_range, int siting, tg_stream_t stream) {
+  TG_REQUIRE(yuv && rgb_chw, TG_E_ARG, "%s: null pointer", name);
+  TG_REQUIRE(depth == 8 || depth == 10 || depth == 12, TG_E_ARG, "%s: depth=%d (8, 10 or 12)", name, depth);
+  TG_REQUIRE((depth == 8 || (uintptr_t)yuv % 2 == 0) && (uintptr_t)rgb_chw % 4 == 0, TG_E_ARG,
+             "%s: 16-bit samples are 2-byte aligned and rgb_chw 4-byte aligned", name);
+  TG_REQUIRE(n >= 1 && h >= 2 && w >= 2, TG_E_ARG, "%s: n=%d h=%d w=%d (n >= 1, h, w >= 2)", name, n, h, w);
+  TG_REQUIRE(yuv_planar_enums_ok(chroma, matrix, full_range, siting), TG_E_ARG,
+             "%s: chroma=%d matrix=%d full_range=%d siting=%d", name, chroma, matrix, full_range, siting);
+  const bool f16 = (uintptr_t)rgb_chw % 16 == 0;
+  if (depth == 8)
+    return yuv_planar_to_rgb<uint8_t, SEMI>(name, (const uint8_t*)yuv, rgb_chw, n, h, w, chroma, depth, matrix,
+                                            full_range, siting, f16 && (uintptr_t)yuv % 4 == 0, stream);
+  return yuv_planar_to_rgb<uint16_t, SEMI>(name, (const uint16_t*)yuv, rgb_chw, n, h, w, chroma, depth, matrix,
+                                           full_range, siting, f16 && (uintptr_t)yuv % 8 == 0, stream);
+}
+
+template <bool SEMI>
+static int rgb_u8_to_yuv_entry(const char* name, const uint8_t* rgb_hwc, uint8_t* yuv, int n, int H, int W, int chroma,
+                               int matrix, int full_range, int siting, tg_stream_t stream) {
+  TG_REQUIRE(rgb_hwc && yuv, TG_E_ARG, "%s: null pointer", name);
+  return rgb_to_yuv_planar<uint8_t, SEMI>(name, rgb_hwc, yuv, n, H, W, chroma, 8, matrix, full_range, siting,
+                                          (uintptr_t)rgb_hwc % 4 == 0 && (uintptr_t)yuv % 4 == 0, stream);
+}
+
+template <bool SEMI>
+static int rgb_f32_to_yuv16_entry(const char* name, const float* rgb_chw, uint16_t* yuv, int n, int H, int W,
+                                  int chroma, int depth, int matrix, int full_range, int siting, tg_stream_t stream) {
+  TG_REQUIRE(rgb_chw && yuv, TG_E_ARG, "%s: null pointer", name);
+  TG_REQUIRE((uintptr_t)yuv % 2 == 0 && (uintptr_t)rgb_chw % 4 == 0, TG_E_ARG,
+             "%s: yuv is 2-byte aligned and rgb_chw 4-byte aligned", name);
+  TG_REQUIRE(depth == 10 || depth == 12, TG_E_ARG, "%s: depth=%d (10 or 12)", name, depth);
+  return rgb_to_yuv_planar<uint16_t, SEMI>(name, rgb_chw, yuv, n, H, W, chroma, depth, matrix, full_range, siting,
+                                           (uintptr_t)rgb_chw % 16 == 0 && (uintptr_t)yuv % 8 == 0, stream);
 }
 
 }  // namespace tg
 
 extern "C" int tg_yuv_planar_to_rgb_f32(const void* yuv, float* rgb_chw, int n, int h, int w, int chroma, int depth,
                                         int matrix, int full_range, int siting, tg_stream_t stream) {
-  TG_REQUIRE(yuv && rgb_chw, TG_E_ARG, "yuv_planar_to_rgb_f32: null pointer");
-  TG_REQUIRE(depth == 8 || depth == 10 || depth == 12, TG_E_ARG, "yuv_planar_to_rgb_f32: depth=%d (8, 10 or 12)", depth);
-  TG_REQUIRE((depth == 8 || (uintptr_t)yuv % 2 == 0) && (uintptr_t)rgb_chw % 4 == 0, TG_E_ARG,
-             "yuv_planar_to_rgb_f32: 16-bit samples are 2-byte aligned and rgb_chw 4-byte aligned");
-  TG_REQUIRE(n >= 1 && h >= 2 && w >= 2, TG_E_ARG, "yuv_planar_to_rgb_f32: n=%d h=%d w=%d (n >= 1, h, w >= 2)", n, h, w);
-  TG_REQUIRE(tg::yuv_planar_enums_ok(chroma, matrix, full_range, siting), TG_E_ARG,
-             "yuv_planar_to_rgb_f32: chroma=%d matrix=%d full_range=%d siting=%d", chroma, matrix, full_range, siting);
-  const bool f16 = (uintptr_t)rgb_chw % 16 == 0;
-  if (depth == 8)
-    return tg::yuv_planar_to_rgb<uint8_t>("yuv_planar_to_rgb_f32", (const uint8_t*)yuv, rgb_chw, n, h, w, chroma, depth,
-                                          matrix, full_range, siting, f16 && (uintptr_t)yuv % 4 == 0, stream);
-  return tg::yuv_planar_to_rgb<uint16_t>("yuv_planar_to_rgb_f32", (const uint16_t*)yuv, rgb_chw, n, h, w, chroma, depth,
-                                         matrix, full_range, siting, f16 && (uintptr_t)yuv % 8 == 0, stream);
+  return tg::yuv_to_rgb_f32_entry<false>("yuv_planar_to_rgb_f32", yuv, rgb_chw, n, h, w, chroma, depth, matrix,
+                                         full_range, siting, stream);
 }
 
 extern "C" int tg_rgb_u8_to_yuv_planar(const uint8_t* rgb_hwc, uint8_t* yuv, int n, int H, int W, int chroma,
                                        int matrix, int full_range, int siting, tg_stream_t stream) {
-  TG_REQUIRE(rgb_hwc && yuv, TG_E_ARG, "rgb_u8_to_yuv_planar: null pointer");
-  return tg::rgb_to_yuv_planar<uint8_t>("rgb_u8_to_yuv_planar", rgb_hwc, yuv, n, H, W, chroma, 8, matrix, full_range,
-                                        siting, (uintptr_t)rgb_hwc % 4 == 0 && (uintptr_t)yuv % 4 == 0, stream);
+  return tg::rgb_u8_to_yuv_entry<false>("rgb_u8_to_yuv_planar", rgb_hwc, yuv, n, H, W, chroma, matrix, full_range,
+                                        siting, stream);
 }
 
 extern "C" int tg_rgb_f32_to_yuv_planar16(const float* rgb_chw, uint16_t* yuv, int n, int H, int W, int chroma,
                                           int depth, int matrix, int full_range, int siting, tg_stream_t stream) {
-  TG_REQUIRE(rgb_chw && yuv, TG_E_ARG, "rgb_f32_to_yuv_planar16: null pointer");
-  TG_REQUIRE((uintptr_t)yuv % 2 == 0 && (uintptr_t)rgb_chw % 4 == 0, TG_E_ARG,
-             "rgb_f32_to_yuv_planar16: yuv is 2-byte aligned and rgb_chw 4-byte aligned");
-  TG_REQUIRE(depth == 10 || depth == 12, TG_E_ARG, "rgb_f32_to_yuv_planar16: depth=%d (10 or 12)", depth);
-  return tg::rgb_to_yuv_planar<uint16_t>("rgb_f32_to_yuv_planar16", rgb_chw, yuv, n, H, W, chroma, depth, matrix,
-                                         full_range, siting, (uintptr_t)rgb_chw % 16 == 0 && (uintptr_t)yuv % 8 == 0,
-                                         stream);
+  return tg::rgb_f32_to_yuv16_entry<false>("rgb_f32_to_yuv_planar16", rgb_chw, yuv, n, H, W, chroma, depth, matrix,
+                                           full_range, siting, stream);
+}
+
+// ---- semi-planar: the same bodies with the chroma layout switched --------------------------------
+extern "C" int tg_yuv_semiplanar_to_rgb_f32(const void* yuv, float* rgb_chw, int n, int h, int w, int chroma, int depth,
+                                            int matrix, int full_range, int siting, tg_stream_t stream) {
+  return tg::yuv_to_rgb_f32_entry<true>("yuv_semiplanar_to_rgb_f32", yuv, rgb_chw, n, h, w, chroma, depth, matrix,
+                                        full_range, siting, stream);
+}
+
+extern "C" int tg_rgb_u8_to_yuv_semiplanar(const uint8_t* rgb_hwc, uint8_t* yuv, int n, int H, int W, int chroma,
+                                           int matrix, int full_range, int siting, tg_stream_t stream) {
+  return tg::rgb_u8_to_yuv_entry<true>("rgb_u8_to_yuv_semiplanar", rgb_hwc, yuv, n, H, W, chroma, matrix, full_range,
+                                       siting, stream);
+}
+
+extern "C" int tg_rgb_f32_to_yuv_semiplanar16(const float* rgb_chw, uint16_t* yuv, int n, int H, int W, int chroma,
+                                              int depth, int matrix, int full_range, int siting, tg_stream_t stream) {
+  return tg::rgb_f32_to_yuv16_entry<true>("rgb_f32_to_yuv_semiplanar16", rgb_chw, yuv, n, H, W, chroma, depth, matrix,
+                                          full_range, siting, stream);
 }
 
 // ---- the four 4:2:0 entry points: their own checks (BT.601 / BT.709 only), then the (2,2) forms above ------------------

@@ -29,6 +29,13 @@ the network computed -- and `--yuv-matrix bt2020` is the non-constant-luminance 
 GPU in front of the generator, at field rate (the header's `F` doubled) or with `--deinterlace-rate frame` at the
 input's; without it an interlaced header is refused.  The header written says `Ip`.
 
+`--raw-format nv12|nv16|nv24|p010|p012|p210|p212|p410|p412 --raw-size WxH [--raw-rate N:D]` takes
+the input (a file, or `-`) as headerless semi-planar raw video, what hardware decoders hand over and
+`ffmpeg -f rawvideo -pix_fmt nv12` writes; `--output-format raw|y4m` (default: raw for raw input, y4m for y4m input) says
+what is written -- raw is semi-planar at `--output-chroma` / `--output-depth`, its format name and size named on stderr:
+
+  ffmpeg -i in.mp4 -f rawvideo -pix_fmt nv12 - | python -m tecogan_pytorch_amd.main --mode infer --input - --raw-format nv12 --raw-size 320x134 --output - | ffmpeg -f rawvideo -pix_fmt nv12 -s 1280x536 -i - out.mp4
+
 `--scene-cut` (both forms of `infer`) restarts the recurrence at scene cuts, detected on the
 device; the cut frames are listed on stderr at the end, never on stdout.
 
@@ -59,6 +66,23 @@ def output_size_arg(text):
     if not m:
         raise argparse.ArgumentTypeError(f'{text!r}: the output size is WxH, two positive integers')
     return int(m.group(1)), int(m.group(2))
+
+
+def raw_rate_arg(text):
+    """`N:D` of --raw-rate -> (n, d)."""
+    m = re.fullmatch(r'([1-9][0-9]*):([1-9][0-9]*)', text.strip())
+    if not m:
+        raise argparse.ArgumentTypeError(f'{text!r}: the frame rate is N:D, two positive integers')
+    return int(m.group(1)), int(m.group(2))
+
+
+def raw_format_arg(text):
+    """A --raw-format name -> its table key (`p010le` is `p010`)."""
+    from .data.rawvideo import FORMAT_OF, RawVideoError, format_of
+    try:
+        return FORMAT_OF[format_of(text)]
+    except RawVideoError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
 
 
 def parse_args(argv=None):
@@ -132,7 +156,26 @@ def parse_args(argv=None):
     p.add_argument('--deinterlace-rate', dest='deinterlace_rate', type=str, default=None, choices=['field', 'frame'],
                    help='--deinterlace: field (default): two output frames per input frame and twice the frame rate in the '
                         "header; frame: the input's rate, the earlier field's frame only")
+    p.add_argument('--raw-format', dest='raw_format', type=raw_format_arg, default=None, metavar='FMT',
+                   help='--mode infer: the input (a file, or - for stdin) is headerless semi-planar raw video of this '
+                        'format instead of y4m (DESIGN.md section 7p): nv12 nv16 nv24 p010 p012 p210 p212 p410 p412, '
+                        "ffmpeg's -pix_fmt names; needs --raw-size")
+    p.add_argument('--raw-size', dest='raw_size', type=output_size_arg, default=None, metavar='WxH',
+                   help='--raw-format: the size of the frames')
+    p.add_argument('--raw-rate', dest='raw_rate', type=raw_rate_arg, default=None, metavar='N:D',
+                   help='--raw-format: frames per second, for the header of a y4m output (default 25:1)')
+    p.add_argument('--output-format', dest='output_format', type=str, default=None, choices=['raw', 'y4m'],
+                   help='y4m or raw input: what is written -- y4m (planar, with a header) or raw (headerless semi-planar '
+                        'frames at --output-chroma / --output-depth; the format name and the size are printed on '
+                        'stderr).  Default: raw for raw input, y4m for y4m input')
     args = p.parse_args(argv)
+    if args.raw_format is not None and args.raw_size is None:
+        p.error('--raw-format needs --raw-size WxH (headerless frames carry no size)')
+    if args.raw_format is None and (args.raw_size is not None or args.raw_rate is not None):
+        p.error('--raw-size and --raw-rate belong to --raw-format')
+    if args.raw_format is not None and args.deinterlace != 'off':
+        p.error('--deinterlace cannot be combined with --raw-format: interlaced semi-planar input is not supported '
+                '(DESIGN.md section 7p)')
     y4m_input = bool(args.mode == 'infer' and args.input and (args.input == '-' or os.path.isfile(args.input)))
     if args.deinterlace != 'off' and not y4m_input:
         p.error('--deinterlace belongs to --mode infer with y4m input (a y4m file, or - for stdin)')
@@ -150,6 +193,8 @@ def parse_args(argv=None):
         p.error('--output-size resizes the 8-bit frames; it cannot be combined with --output-depth above 8')
     if args.png_encoder == 'device' and args.input and (args.input == '-' or os.path.isfile(args.input)):
         p.error('--png-encoder device writes PNG folders; y4m input is written as y4m')
+    if (args.raw_format is not None or args.output_format is not None) and not y4m_input:
+        p.error('--raw-format and --output-format belong to --mode infer with a file or - as the input')
     if args.png_lz77 and args.png_encoder != 'device':
         p.error('--png-lz77 belongs to --png-encoder device')
     return args
@@ -522,7 +567,8 @@ def infer(opt, input_dir, output_dir, scene_cut=None, png_encoder='pillow', outp
 
 
 def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None, output_size=None, siting='left',
-              output_depth=None, output_chroma=None, deinterlace='off', deinterlace_rate=None):
+              output_depth=None, output_chroma=None, deinterlace='off', deinterlace_rate=None, raw=None,
+              output_format=None):
     """--mode infer on raw video: the y4m stream `src` (a binary file object) through VSRModel.infer_stream(yuv=...)
     into the y4m stream `dst`, in order.  The output header carries the scaled size and the input's F, A, C and X tags.
     Each chunk is written out of the ring slot before the generator is advanced; nothing is held beyond it.
@@ -536,20 +582,44 @@ def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None, out
     reader; 'auto' deinterlaces an It / Ib stream in the header's field order and leaves an Ip stream alone; 'tff' / 'bff'
     deinterlace in that order whatever the header says.  deinterlace_rate 'field' (None: the same) | 'frame': at field
     rate two frames are written per frame read and the header's F tag is doubled.  The header written says Ip.  Returns
-    the number of frames written."""
+    the number of frames written.
+    raw (format, w, h, (rate n, d) | None): `src` is headerless semi-planar raw video instead (DESIGN.md section 7p;
+    data/rawvideo.py), the range is `yuv_range` (None: limited) and the siting `siting`; not with deinterlace.
+    output_format 'raw' | 'y4m' | None (raw for raw input, y4m for y4m input): 'raw' writes headerless semi-planar frames
+    at output_chroma / output_depth and names their format and size on stderr; 'y4m' after raw input writes planar frames
+    behind a header made from the size and the rate (25:1 without one).  Either input goes with either output."""
     import sys
-    from .data.y4m import Y4MReader, Y4MWriter
+    from .data.rawvideo import FORMAT_OF, RawReader, RawWriter
+    from .data.y4m import TAG_OF_SITING, Y4MReader, Y4MWriter
     from .models.networks import Deinterlace, Yuv, Yuv420
     if deinterlace not in ('off', 'auto', 'tff', 'bff'):
         raise ValueError(f'deinterlace is off, auto, tff or bff, got {deinterlace!r}')
-    reader = Y4MReader(src, depths=(8, 10, 12), chromas=('420', '422', '444'), interlaced=deinterlace != 'off')
+    if output_format not in (None, 'raw', 'y4m'):
+        raise ValueError(f'output_format is raw, y4m or None, got {output_format!r}')
+    raw_out = (raw is not None) if output_format is None else output_format == 'raw'
+    if raw is not None:
+        if deinterlace != 'off':
+            raise ValueError('deinterlace cannot be combined with raw input: interlaced semi-planar input is not supported')
+        fmt, rw, rh, rate = raw
+        reader = RawReader(src, fmt, rw, rh)
+        reader.siting, reader.full_range, reader.interlace = siting, None, 'p'
+        tags = ['F%d:%d' % (rate or (25, 1)), 'C' + TAG_OF_SITING[siting]]
+        if yuv_range is not None:                   # (a y4m written from it says what the command line said)
+            tags.append('XCOLORRANGE=' + yuv_range.upper())
+        reader.header = {'tags': tags, 'depth': reader.depth, 'chroma': reader.chroma}
+    else:
+        reader = Y4MReader(src, depths=(8, 10, 12), chromas=('420', '422', '444'), interlaced=deinterlace != 'off')
     order = {'t': 'tff', 'b': 'bff', 'p': None}[reader.interlace] if deinterlace == 'auto' else \
         None if deinterlace == 'off' else deinterlace
     deint = None if order is None else Deinterlace(tff=order == 'tff', rate=deinterlace_rate or 'field')
     full = reader.full_range if yuv_range is None else yuv_range == 'full'
     common = dict(matrix=matrix, full_range=bool(full), siting=reader.siting if reader.siting is not None else siting,
                   depth=reader.depth, out_depth=output_depth)
-    if reader.chroma == '420' and output_chroma in (None, '420') and matrix != 'bt2020':
+    if raw is not None or raw_out:
+        spec = Yuv(reader.h, reader.w, chroma=reader.chroma, out_chroma=output_chroma, **common,
+                   layout='planar' if raw is None else 'semi', out_layout='semi' if raw_out else 'planar')
+        oc = spec.oc
+    elif reader.chroma == '420' and output_chroma in (None, '420') and matrix != 'bt2020':
         spec, oc = Yuv420(reader.h, reader.w, **common), '420'
     else:
         spec = Yuv(reader.h, reader.w, chroma=reader.chroma, out_chroma=output_chroma, **common)
@@ -573,8 +643,13 @@ def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None, out
         if oh * W != ow * H:                        # the shape changes: every pixel becomes this much wider for its height
             aspect = (W * oh, H * ow)
         W, H = ow, oh
-    writer = Y4MWriter(dst, W, H, reader.header, aspect_scale=aspect, depth=spec.od, siting=spec.siting, chroma=oc,
-                       rate_scale=(2, 1) if deint is not None and deint.rate == 'field' else None)
+    if raw_out:
+        writer = RawWriter(dst, spec.out_size_bytes(H, W))
+        print(f'raw: writing {FORMAT_OF[(oc, spec.od)]} {W}x{H} (ffmpeg -f rawvideo -pix_fmt {FORMAT_OF[(oc, spec.od)]}'
+              f'{"le" if spec.od > 8 else ""} -s {W}x{H})', file=sys.stderr, flush=True)
+    else:
+        writer = Y4MWriter(dst, W, H, reader.header, aspect_scale=aspect, depth=spec.od, siting=spec.siting, chroma=oc,
+                           rate_scale=(2, 1) if deint is not None and deint.rate == 'field' else None)
     t0, k = time.time(), 0
     for chunk in model.infer_stream(reader, yuv=spec, **kw):
         for frame in chunk:
@@ -585,7 +660,7 @@ def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None, out
     if scene_cut is not None:
         log_scene_cuts('y4m', scene_cut)
     dt = time.time() - t0
-    print(f'y4m: {k} frames {reader.w}x{reader.h} -> {W}x{H} '
+    print(f'{"y4m" if raw is None else raw[0]}: {k} frames {reader.w}x{reader.h} -> {W}x{H} '
           f'({k / max(dt, 1e-9):.1f} frames/s, {spec.matrix} {"full" if spec.full_range else "limited"} range, '
           f'{spec.siting} siting, {spec.depth} -> {spec.od} bits, {reader.chroma} -> {oc})', flush=True)
     if deinterlace != 'off':
@@ -596,7 +671,8 @@ def infer_y4m(opt, src, dst, matrix='bt709', yuv_range=None, scene_cut=None, out
 
 
 def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range, scene_cut=None, output_size=None, siting='left',
-                  output_depth=None, output_chroma=None, deinterlace='off', deinterlace_rate=None):
+                  output_depth=None, output_chroma=None, deinterlace='off', deinterlace_rate=None, raw=None,
+                  output_format=None):
     """Opens the two ends of infer_y4m.  With `--output -` the y4m bytes are the ONLY thing on stdout: the descriptor
     is set aside for them and, for the length of the run, descriptor 1 and sys.stdout lead to stderr, so that neither
     a print nor a library's message can land in the stream."""
@@ -606,7 +682,7 @@ def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range, scene_cut=Non
         if output_path != '-':
             with open(output_path, 'wb') as dst:
                 return infer_y4m(opt, src, dst, matrix, yuv_range, scene_cut, output_size, siting, output_depth,
-                                 output_chroma, deinterlace, deinterlace_rate)
+                                 output_chroma, deinterlace, deinterlace_rate, raw, output_format)
         sys.stdout.flush()
         keep = os.dup(1)
         py_stdout = sys.stdout
@@ -615,7 +691,7 @@ def infer_y4m_cli(opt, input_path, output_path, matrix, yuv_range, scene_cut=Non
         try:
             with os.fdopen(os.dup(keep), 'wb') as dst:
                 return infer_y4m(opt, src, dst, matrix, yuv_range, scene_cut, output_size, siting, output_depth,
-                                 output_chroma, deinterlace, deinterlace_rate)
+                                 output_chroma, deinterlace, deinterlace_rate, raw, output_format)
         finally:
             sys.stdout = py_stdout
             os.dup2(keep, 1)
@@ -702,7 +778,9 @@ def main(argv=None):
         if args.input == '-' or os.path.isfile(args.input):
             infer_y4m_cli(opt, args.input, args.output, args.yuv_matrix, args.yuv_range, scene_cut_option(args),
                           args.output_size, args.yuv_siting, args.output_depth, args.output_chroma, args.deinterlace,
-                          args.deinterlace_rate)
+                          args.deinterlace_rate,
+                          None if args.raw_format is None else (args.raw_format, *args.raw_size, args.raw_rate),
+                          args.output_format)
         else:
             infer(opt, args.input, args.output, scene_cut_option(args), args.png_encoder, args.output_size, args.png_lz77)
     elif args.mode == 'profile':

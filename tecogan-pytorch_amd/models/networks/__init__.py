@@ -1,5 +1,6 @@
 from .tecogan_nets import (FRNet, FNet, SRNet, SpatioTemporalDiscriminator,
-                           SpatialDiscriminator, Deinterlace, Png, Resize, SceneCut, Yuv420, yuv420_planes, Yuv, yuv_planes)
+                           SpatialDiscriminator, Deinterlace, Png, Resize, SceneCut, Yuv420, yuv420_planes, Yuv, yuv_planes,
+                           yuv_semiplanes)
 
 
 def define_generator(opt):

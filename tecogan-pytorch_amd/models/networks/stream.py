@@ -185,6 +185,7 @@ class StreamRing:
 
 
 YUV_DEPTHS = (8, 10, 12)
+YUV_LAYOUTS = ('planar', 'semi')                 # U and V planes | one plane of interleaved U,V pairs
 
 
 class _YuvSpec:
@@ -215,6 +216,10 @@ class _YuvSpec:
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v not in YUV_DEPTHS:
                 raise ValueError(f'{who}: {name} is one of {YUV_DEPTHS}, got {v!r}')
             object.__setattr__(self, name, int(v))
+        for name in ('layout', 'out_layout'):
+            v = getattr(self, name)
+            if not (name == 'out_layout' and v is None) and (not isinstance(v, str) or v not in YUV_LAYOUTS):
+                raise ValueError(f'{who}: {name} is one of {sorted(YUV_LAYOUTS)}, got {v!r}')
 
     @property
     def od(self):
@@ -261,6 +266,7 @@ class Yuv420(_YuvSpec):
     depth: int = 8
     out_depth: Optional[int] = None
     MATRICES, chroma, out_chroma = L.YUV_MATRIX, '420', None         # (no fields: the one layout, BT.601 / BT.709 only)
+    layout, out_layout = 'planar', None
 
     def out_frame_bytes(self, scale):
         """Bytes of a super-resolved frame (s*h and s*w are even: the scale is 2 or 4)."""
@@ -288,7 +294,12 @@ class Yuv(_YuvSpec):
     (non-constant luminance), full_range (bool), siting 'center' | 'left': where a chroma sample sits along a
     sub-sampled horizontal axis (not looked at for 4:4:4).  depth and out_depth as Yuv420's.  Samples pass through as
     code values whatever their transfer function (PQ and HLG included).  A Yuv always takes the planar launches
-    (tg_yuv_planar_to_rgb_f32, tg_rgb_u8_to_yuv_planar, tg_rgb_f32_to_yuv_planar16), at '420' as well.  Frozen."""
+    (tg_yuv_planar_to_rgb_f32, tg_rgb_u8_to_yuv_planar, tg_rgb_f32_to_yuv_planar16), at '420' as well.
+    layout 'planar' | 'semi': the input's chroma as U and V planes, or as ONE plane of interleaved U,V pairs with the
+    code in the top bits of a 16-bit word (NV12 / NV16 / NV24, P010 / P012, P210 / P212, P410 /
+    P412); out_layout the same | None (the input's), independent of it.  A frame has the same bytes either way, and a
+    semi-planar side takes the semi-planar launch in place of the planar one (tg_yuv_semiplanar_to_rgb_f32,
+    tg_rgb_u8_to_yuv_semiplanar, tg_rgb_f32_to_yuv_semiplanar16).  Frozen."""
     h: int
     w: int
     chroma: str = '420'
@@ -298,7 +309,14 @@ class Yuv(_YuvSpec):
     siting: str = 'left'
     depth: int = 8
     out_depth: Optional[int] = None
+    layout: str = 'planar'
+    out_layout: Optional[str] = None
     MATRICES = L.YUV_PLANAR_MATRIX
+
+    @property
+    def ol(self):
+        """Chroma layout of the output: out_layout, or the input's."""
+        return self.layout if self.out_layout is None else self.out_layout
 
     def out_frame_bytes(self, scale):
         """Bytes of a super-resolved frame."""
@@ -307,13 +325,16 @@ class Yuv(_YuvSpec):
         return self.out_size_bytes(scale * self.h, scale * self.w)
 
     def input_launch(self):
-        return 'tg_yuv_planar_to_rgb_f32', (self.h, self.w, L.YUV_CHROMA[self.chroma], self.depth, *self.codes())
+        name = 'tg_yuv_semiplanar_to_rgb_f32' if self.layout == 'semi' else 'tg_yuv_planar_to_rgb_f32'
+        return name, (self.h, self.w, L.YUV_CHROMA[self.chroma], self.depth, *self.codes())
 
     def out_launch(self, H, W):
-        return 'tg_rgb_u8_to_yuv_planar', (H, W, L.YUV_CHROMA[self.oc], *self.codes())
+        name = 'tg_rgb_u8_to_yuv_semiplanar' if self.ol == 'semi' else 'tg_rgb_u8_to_yuv_planar'
+        return name, (H, W, L.YUV_CHROMA[self.oc], *self.codes())
 
     def deep_launch(self, H, W):
-        return 'tg_rgb_f32_to_yuv_planar16', (H, W, L.YUV_CHROMA[self.oc], self.od, *self.codes())
+        name = 'tg_rgb_f32_to_yuv_semiplanar16' if self.ol == 'semi' else 'tg_rgb_f32_to_yuv_planar16'
+        return name, (H, W, L.YUV_CHROMA[self.oc], self.od, *self.codes())
 
 
 @dataclass(frozen=True)
@@ -394,7 +415,13 @@ class Deinterlace:
         return 2 if self.rate == 'field' else 1
 
     def check_source(self, yuv):
-        """ValueError unless every plane of the spec's frames has both row parities: an even h, h % 4 == 0 at 4:2:0."""
+        """ValueError unless every plane of the spec's frames has both row parities: an even h, h % 4 == 0 at 4:2:0.
+        Semi-planar input is refused: the edge directions step one sample sideways, which on interleaved chroma would
+        mix U with V."""
+        if getattr(yuv, 'layout', 'planar') != 'planar':
+            raise ValueError("Deinterlace: interlaced semi-planar input (layout='semi') is not supported: the edge "
+                             'directions of the deinterlacer step one sample sideways, which on interleaved chroma '
+                             'would mix U with V; repack to planar')
         need = 4 if yuv.chroma == '420' else 2
         if yuv.h % need or yuv.h < 4:
             raise ValueError(f'Deinterlace: a 4:{yuv.chroma[1]}:{yuv.chroma[2]} frame needs a height that is a multiple of '
@@ -519,6 +546,18 @@ def yuv_planes(chunk, H, W, chroma='420', depth=8, who='yuv_planes'):
     return (chunk[..., :H * W].reshape(lead + (H, W)),
             chunk[..., H * W:H * W + ch * cw].reshape(lead + (ch, cw)),
             chunk[..., H * W + ch * cw:].reshape(lead + (ch, cw)))
+
+
+def yuv_semiplanes(chunk, H, W, chroma='420', depth=8, who='yuv_semiplanes'):
+    """(Y, UV) views of semi-planar frames: Y of H x W and UV of (ch, cw, 2) with ch x cw =
+    ceil(H/sy) x ceil(W/sx), UV[..., 0] U and UV[..., 1] V.  chunk (m, frame_bytes) or a single frame (frame_bytes,),
+    numpy or torch; nothing is copied.  depth above 8: the chunk holds 2-byte words (uint8 as the stream yields it, or
+    uint16 already), the views are uint16 and the words are as stored, the code in the top bits (code << (16 - depth))."""
+    y, u, v = yuv_planes(chunk, H, W, chroma, depth, who=who)       # (the checks, and the sizes: U and V have ch x cw each)
+    ch, cw = u.shape[-2:]
+    if chunk.shape[-1] != H * W + 2 * ch * cw:                      # bytes of 2-byte words, as the stream yields them
+        chunk = chunk.view(np.uint16 if isinstance(chunk, np.ndarray) else torch.uint16)
+    return y, chunk[..., H * W:].reshape(tuple(y.shape[:-2]) + (ch, cw, 2))
 
 
 # -- the forms of a stream: each object owns its buffers and is the only place that knows their layout.  alloc(eng) runs

@@ -22,7 +22,7 @@ from ...utils.net_utils import get_upsampling_func
 from .frnet_infer import (FNET_FIRST_PASS_FRAMES, _SIDE_STREAMS, _StepPlan, _norm_device, clip_batches,  # noqa: F401
                           enqueue_batch, side_stream, stream_batch_sizes)
 from .stream import (STREAM_SLOTS, Deinterlace, Png, Resize, SceneCut, StreamFormat, StreamRing, Yuv420, _StreamEngine, stream_frames,  # noqa: F401
-                     stream_frames_yuv, stream_parts, stream_rebatch, yuv420_planes, Yuv, yuv_planes)
+                     stream_frames_yuv, stream_parts, stream_rebatch, yuv420_planes, Yuv, yuv_planes, yuv_semiplanes)
 
 
 class _Conv(nn.Module):
@@ -475,6 +475,11 @@ class FRNet(nn.Module):
         depth) splits a chunk.  The layouts and depths of the two sides combine freely: a 4:2:0 clip can leave as 4:4:4,
         which keeps the chroma the network computed.  `resize` with an 8-bit 4:2:2 output needs an even width, with
         4:2:0 even sides, with 4:4:4 nothing; with an output above 8 bits it stays a ValueError.
+        Yuv(..., layout='semi') / out_layout='semi'  is the semi-planar form of either side --
+        NV12 / NV16 / NV24, P010 ... P412: one plane of interleaved U,V pairs, the code in the top bits of a 16-bit word
+        -- with the same frame bytes, taken by tg_yuv_semiplanar_to_rgb_f32 / tg_rgb_u8_to_yuv_semiplanar /
+        tg_rgb_f32_to_yuv_semiplanar16 in the planar launches' places; yuv_semiplanes(chunk, H, W, chroma, depth) splits
+        a chunk.  Not with `deinterlace`.
 
         scene_cut: a SceneCut(mad, hist, detect, at, keep_scores) restarts the recurrence at scene cuts, decided on the
         device; without one the stream enqueues exactly what it always did.  For every batch

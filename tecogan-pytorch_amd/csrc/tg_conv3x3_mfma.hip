@@ -23,6 +23,11 @@
 // pixels and channel tails get an out-of-range offset and read as 0), four
 // channel planes of one pixel per thread -> one ds_write_b128.
 //
+// Kernels of this file: conv3x3_mfma_kernel<WM, WN, NT, DUAL, KS> (the scheme above; phase-restricted taps, split-K
+// partial sums + splitk_finalize_kernel), conv3x3_oneshot_kernel<STRIDE, DUAL> (the training frames: whole K range in
+// flight, stride 1 and the stride-2 data gradient of the transposed conv as one body), pack3x3_kernel.  All of them
+// share one epilogue (ep_act / ep_elem / ep_store4).
+//
 // Reference ops replaced: nn.Conv2d(.,.,3,1,1)+bias+act(+residual) at
 // codes/models/networks/tecogan_nets.py:23-65, 92-98, 111-113, 367-369 and the
 // torch.cat at :71 / :141 (two-source input).
@@ -53,8 +58,7 @@ struct Conv3x3Args {
   float* part;
   long long part_ss;
   int vec_ok;   // w % 4 == 0 and 16-byte aligned y / res planes: float4 epilogue allowed
-  long long* dbg;   // lab instrumentation (ABL & 16): 8 cycle stamps per workgroup
-  int nblocks;      // > 0: XCD-banded block order over nblocks tiles (grid = 8 * ceil(nblocks / 8))
+  int nblocks;     // > 0: XCD-banded block order over nblocks tiles (grid = 8 * ceil(nblocks / 8))
   // optional ReLU-backward mask applied last: y = mask > 0 ? y : 0  (same layout as y).  Lets the
   // data-gradient conv of a layer deliver dZ of the PREVIOUS layer directly (no act_bwd pass).
   const float* mask;
@@ -113,7 +117,7 @@ __device__ __forceinline__ void chunk_taps(const float* si, const float* sw, f32
   f32x4 bq[2], aq[2][NT];
   auto fetch = [&](int i, int slot) {
     const int ky = Y0 + i / NX, kx = X0 + i % NX;
-    bq[slot] = *reinterpret_cast<const f32x4*>(si + (ky * 2 * 34 + kx) * 4);      // RS = 34
+    bq[slot] = *reinterpret_cast<const f32x4*>(si + (ky * 2 * RS + kx) * 4);
 #pragma unroll
     for (int t = 0; t < NT; ++t)
       aq[slot][t] = *reinterpret_cast<const f32x4*>(sw + (ky * 3 + kx) * (2 * OCB * 4) + t * 128);
@@ -150,16 +154,42 @@ __device__ __forceinline__ void chunk_taps_sel(int ry, int rx, const float* si, 
   }
 }
 
-// ABL: ablation bits for tools/conv_lab.hip only (0 in the product):
-//   1 = no re-staging inside the chunk loop, 2 = no barrier in the loop,
-//   4 = no epilogue stores, 8 = no LDS operand reads.
+// ---- the epilogue of every form: q = act(acc + bias) + residual, then the ReLU-backward mask ------------------------
+// The activation is a select on a wave-uniform slope (act_slope): no branch per element.  The `+ 0.f` makes the ReLU
+// (slope 0) of a negative value +0, not -0.
+__device__ __forceinline__ float ep_act(float q, float slope) { return q >= 0.f ? q : q * slope + 0.f; }
+
+// The two mask predicates are NOT the same function: the element form zeroes q where mask <= 0 (a NaN mask keeps q), the
+// f32x4 form keeps q where mask > 0 (a NaN mask gives 0).  Masks are ReLU outputs, for which both agree; each site keeps
+// the predicate it always had, so that no result changes.
+__device__ __forceinline__ bool ep_dead(float mask) { return mask <= 0.f; }
+__device__ __forceinline__ float ep_elem(float v, float bias, float slope, float res, bool dead) {
+  const float q = ep_act(v + bias, slope) + res;
+  return dead ? 0.f : q;
+}
+// f32x4 form: v = four consecutive pixels of channel oc, `off` their float offset in one (cout, h, w) item of y / res /
+// mask (16-byte aligned: a.vec_ok); loads, epilogue and one 16-byte store.
+__device__ __forceinline__ void ep_store4(const Conv3x3Args& a, int n, int oc, long long off, float slope, f32x4 v) {
+  const float bb = a.bias ? a.bias[oc] : 0.f;
+  f32x4 rr = {0.f, 0.f, 0.f, 0.f};
+  if (a.res) rr = *reinterpret_cast<const f32x4*>(a.res + (long long)n * a.res_ns + off);
+  f32x4 mm = {1.f, 1.f, 1.f, 1.f};
+  if (a.mask) mm = *reinterpret_cast<const f32x4*>(a.mask + (long long)n * a.mask_ns + off);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float q = ep_act(v[e] + bb, slope) + rr[e];
+    v[e] = mm[e] > 0.f ? q : 0.f;
+  }
+  *reinterpret_cast<f32x4*>(a.y + (long long)n * a.y_ns + off) = v;
+}
+
 // The weight chunks are staged by LDS-DMA (global_load_lds) and, where a.vec_ok, the epilogue goes through LDS
 // with 16-byte stores: together measured +2 % on the frame against staging through registers + 4-byte stores.
 // KS = 2: the workgroup's waves are also split over K -- wave group wk takes every KS-th
 // channel chunk (both chunks of a pair are staged together), the partial accumulators are
 // added through LDS in a fixed order.  For problems with fewer 32x32 tiles than SIMDs
 // (training: 2 x 64 x 64 LR frames) this doubles the busy SIMDs without a second launch.
-template <int WM, int WN, int NT, bool DUAL, int ABL = 0, int KS = 1>
+template <int WM, int WN, int NT, bool DUAL, int KS = 1>
 __global__ __launch_bounds__(WM* WN* KS * 64) void conv3x3_mfma_kernel(Conv3x3Args a) {
   static_assert(KS == 1 || KS == 2, "wave groups over K: one or two");
   constexpr int NTHREADS = WM * WN * KS * 64;
@@ -226,7 +256,6 @@ __global__ __launch_bounds__(WM* WN* KS * 64) void conv3x3_mfma_kernel(Conv3x3Ar
   f32x4 rin[KS][I_PER_T];
 
   auto load_chunk = [&](int ch) {
-    if (!((ABL & 32) && ch != ch_begin))      // lab: skip input re-staging
 #pragma unroll
     for (int k = 0; k < KS; ++k) {
       const unsigned cbase = (unsigned)((ch + k) * CK) * plane;
@@ -243,7 +272,6 @@ __global__ __launch_bounds__(WM* WN* KS * 64) void conv3x3_mfma_kernel(Conv3x3Ar
         }
       }
     }
-    if ((ABL & 64) && ch != ch_begin) return;   // lab: skip weight re-staging
     // LDS-DMA: each wave instruction moves 1 KiB (64 lanes x 16 B) of the packed chunk
     // straight into the other weight buffer; no VGPR round trip, no ds_write.
     constexpr int PIECES = W_FLOATS * 4 / 1024;
@@ -283,70 +311,28 @@ __global__ __launch_bounds__(WM* WN* KS * 64) void conv3x3_mfma_kernel(Conv3x3Ar
   const int b_off = ((wm * 2 + lh) * RS + ll) * 4;
   const int a_off = (lh * OCB + wn * (NT * 32) + ll) * 4;
 
-  long long tk0 = 0, tk1 = 0, t_mfma = 0, t_sync = 0, t_issue = 0;
-  if constexpr (ABL & 16) tk0 = clock64();
   load_chunk(ch_begin);
   store_chunk(bufof(ch_begin));
   __syncthreads();
-  if constexpr (ABL & 16) tk1 = clock64();
 
   for (int ch = ch_begin; ch < ch_end; ch += KS) {
-    long long ta = 0, tb = 0, tc = 0;
-    if constexpr (ABL & 16) ta = clock64();
     const int buf = bufof(ch);
-    const bool more = (ch + KS < ch_end) && !(ABL & 1);
+    const bool more = ch + KS < ch_end;
     if (more) load_chunk(ch + KS);
 
-    if constexpr (ABL & 16) tb = clock64();
     const float* si = s_in + (buf * KS + wk) * IN_FLOATS + b_off;
     const float* sw = s_w + (buf * KS + wk) * W_FLOATS + a_off;
     if (KS == 1 || ch + wk < ch_end) {       // odd chunk count: the last pair has one member
-    if (a.tapsel) {
-      // phase of this chunk's input channels (1) or of this block's output channels (2)
-      const int ph = a.tapsel == 1 ? ((ch + wk) * CK) / a.cphase : (ocg * OCB) / a.cphase;
-      chunk_taps_sel<NT, OCB>(a.rowsets[(ph >> 1) & 1], a.rowsets[ph & 1], si, sw, acc);
-    } else {
-    f32x4 bq[2], aq[2][NT];
-    bq[0] = *reinterpret_cast<const f32x4*>(si);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) aq[0][t] = *reinterpret_cast<const f32x4*>(sw + t * 128);
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      const int cur = tap & 1, nxt = cur ^ 1;
-      if (tap + 1 < 9 && !(ABL & 8)) {
-        const int ky = (tap + 1) / 3, kx = (tap + 1) % 3;
-        bq[nxt] = *reinterpret_cast<const f32x4*>(si + (ky * 2 * RS + kx) * 4);
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-          aq[nxt][t] = *reinterpret_cast<const f32x4*>(sw + (tap + 1) * (2 * OCB * 4) + t * 128);
+      if (a.tapsel) {
+        // phase of this chunk's input channels (1) or of this block's output channels (2)
+        const int ph = a.tapsel == 1 ? ((ch + wk) * CK) / a.cphase : (ocg * OCB) / a.cphase;
+        chunk_taps_sel<NT, OCB>(a.rowsets[(ph >> 1) & 1], a.rowsets[ph & 1], si, sw, acc);
+      } else {
+        chunk_taps<NT, OCB, TAPS_ALL, TAPS_ALL>(si, sw, acc);
       }
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[cur][t][kk], bq[cur][kk], acc[t], 0, 0, 0);
-      }
-    }
-    }
-    }
-    if constexpr (ABL & 16) {
-      // wait for the accumulator (i.e. for the last MFMA) before stamping
-      asm volatile("s_nop 0" ::"v"(acc[0][0]));
-      tc = clock64();
     }
     if (more) store_chunk(buf ^ 1);
-    if (!(ABL & 2)) __syncthreads();
-    if constexpr (ABL & 16) {
-      long long td = clock64();
-      t_issue += tb - ta; t_mfma += tc - tb; t_sync += td - tc;
-    }
-  }
-  if constexpr (ABL & 16) {
-    if (a.dbg && tid == 0) {
-      long long* d = a.dbg + (long long)blockIdx.x * 8;
-      d[0] = tk0; d[1] = tk1 - tk0; d[2] = t_issue; d[3] = t_mfma; d[4] = t_sync; d[5] = clock64();
-      d[6] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | ((4 - 1) << 11));   // HW_REG_XCC_ID[3:0]
-    }
+    __syncthreads();
   }
 
   if constexpr (KS == 2) {
@@ -413,22 +399,9 @@ __global__ __launch_bounds__(WM* WN* KS * 64) void conv3x3_mfma_kernel(Conv3x3Ar
         int ol = idx4 >> 3, p4 = (idx4 & 7) * 4;
         int oc = ocw + ol;
         int gx = x0 + p4;
-        if (oc < a.cout && gx < a.w) {
-          f32x4 v = *reinterpret_cast<const f32x4*>(ep + ol * ES + p4);
-          float bb = a.bias ? a.bias[oc] : 0.f;
-          long long off = (long long)oc * hw + (long long)py * a.w + gx;
-          f32x4 rr = {0.f, 0.f, 0.f, 0.f};
-          if (a.res) rr = *reinterpret_cast<const f32x4*>(a.res + (long long)n * a.res_ns + off);
-          f32x4 mm = {1.f, 1.f, 1.f, 1.f};
-          if (a.mask) mm = *reinterpret_cast<const f32x4*>(a.mask + (long long)n * a.mask_ns + off);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            float q = v[e] + bb;
-            q = (q >= 0.f ? q : q * slope + 0.f) + rr[e];
-            v[e] = mm[e] > 0.f ? q : 0.f;
-          }
-          *reinterpret_cast<f32x4*>(a.y + (long long)n * a.y_ns + off) = v;
-        }
+        if (oc < a.cout && gx < a.w)
+          ep_store4(a, n, oc, (long long)oc * hw + (long long)py * a.w + gx, slope,
+                    *reinterpret_cast<const f32x4*>(ep + ol * ES + p4));
       }
     }
     return;
@@ -446,7 +419,7 @@ __global__ __launch_bounds__(WM* WN* KS * 64) void conv3x3_mfma_kernel(Conv3x3Ar
       int occ = oc < a.cout ? oc : a.cout - 1;
       bv[t][r] = a.bias ? a.bias[occ] : 0.f;
       rv[t][r] = (a.res && inimg) ? a.res[(long long)n * a.res_ns + opix + (long long)occ * hw] : 0.f;
-      if (a.mask && inimg && a.mask[(long long)n * a.mask_ns + opix + (long long)occ * hw] <= 0.f)
+      if (a.mask && inimg && ep_dead(a.mask[(long long)n * a.mask_ns + opix + (long long)occ * hw]))
         dead[t] |= 1u << r;
     }
   if (inimg) {
@@ -456,10 +429,8 @@ __global__ __launch_bounds__(WM* WN* KS * 64) void conv3x3_mfma_kernel(Conv3x3Ar
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         int oc = ocb0 + t * 32 + (r & 3) + 8 * (r >> 2);
-        float v = acc[t][r] + bv[t][r];
-        v = (v >= 0.f ? v : v * slope + 0.f) + rv[t][r];
-        if (dead[t] & (1u << r)) v = 0.f;
-        if (oc < a.cout && (!(ABL & 4) || v == 12345.678f)) yb[(long long)oc * hw] = v;
+        if (oc < a.cout)
+          yb[(long long)oc * hw] = ep_elem(acc[t][r], bv[t][r], slope, rv[t][r], dead[t] & (1u << r));
       }
   }
 }
@@ -478,11 +449,25 @@ __global__ __launch_bounds__(WM* WN* KS * 64) void conv3x3_mfma_kernel(Conv3x3Ar
 //   * K groups 1..3 hand their accumulators to group 0 through LDS (fixed order: deterministic),
 //     the result is transposed through LDS and leaves as one 16-byte store per thread with
 //     bias / activation / residual / ReLU-mask applied -- three barriers per launch in all.
-template <bool DUAL>
+//
+// STRIDE = 2 is the same scheme for y(oy, ox) = sum_k w[k] x(2 oy - 1 + ky, 2 ox - 1 + kx) (zero outside; a.h x a.w
+// is the OUTPUT, x is 2 a.h x 2 a.w) -- the data gradient of ConvTranspose2d(k3, s2, p1, op1) (tecogan_nets.py:119-126)
+// on the training frames.  Through its space-to-depth embedding that gradient is a 256-channel phased conv walking 32
+// channel chunks (27 us per launch for 2 x 32 x 32 outputs); directly it is a K = 576 contraction like any body layer.
+// Against STRIDE = 1 the patch row is 66 columns instead of 34, the patch starts at (2 y0 - 1, 2 x0 - 1) and the B
+// operand of output pixel ox and tap kx sits at column 2 ox + kx; one source and the element-wide epilogue only.
+constexpr int oneshot_patch_row(int stride) { return stride * TW + 2; }   // columns fetched = LDS row stride (slots)
+constexpr size_t oneshot_lds_bytes(int stride) {   // 8 chunk patches of 3 rows x 2 halves, then [2][3][16][64] partial sums
+  return (size_t)(8 * 3 * 2 * oneshot_patch_row(stride) * 4 + 2 * 3 * 16 * 64) * sizeof(float);
+}
+
+template <int STRIDE, bool DUAL>
 __global__ __launch_bounds__(512) void conv3x3_oneshot_kernel(Conv3x3Args a) {
+  static_assert(STRIDE == 1 || (STRIDE == 2 && !DUAL), "the stride-2 form has one source");
   constexpr int OCB = 64, KG = 4, MAXCH = 8;
-  constexpr int IN_FLOATS = 3 * 2 * RS * 4;            // one chunk's patch: 3 rows x 2 halves x 34 slots
-  constexpr int ITEMS_PER_CH = 3 * 2 * PW;             // 204 16-byte items
+  constexpr int PR = oneshot_patch_row(STRIDE);
+  constexpr int IN_FLOATS = 3 * 2 * PR * 4;            // one chunk's patch: 3 rows x 2 halves x PR slots
+  constexpr int ITEMS_PER_CH = 3 * 2 * PR;             // 204 / 396 16-byte items
   constexpr int W_VEC4 = 9 * CK * OCB / 4;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* s_in = smem;                                  // [MAXCH][IN_FLOATS]; later the epilogue stage [64][36]
@@ -496,12 +481,13 @@ __global__ __launch_bounds__(512) void conv3x3_oneshot_kernel(Conv3x3Args a) {
   const int ty = b % a.tiles_y;
   const int n = b / a.tiles_y;
   const int x0 = tx * TW, y0 = ty;
-  const int hw = a.h * a.w;
-  const unsigned plane = (unsigned)hw * 4u;
+  const int hw = a.h * a.w;                            // output plane
+  const int ih = STRIDE * a.h, iw = STRIDE * a.w, ihw = ih * iw;   // input plane
+  const unsigned plane = (unsigned)ihw * 4u;
   const int nchunk = a.nchunk;
-  const __amdgpu_buffer_rsrc_t rs1 = TG_BUF_RSRC(a.x + (long long)n * a.x_ns, a.c1 * hw * 4);
+  const __amdgpu_buffer_rsrc_t rs1 = TG_BUF_RSRC(a.x + (long long)n * a.x_ns, a.c1 * ihw * 4);
   const __amdgpu_buffer_rsrc_t rs2 = TG_BUF_RSRC(
-      DUAL ? a.x2 + (long long)n * a.x2_ns : a.x, DUAL ? (a.cin - a.c1) * hw * 4 : 0);
+      DUAL ? a.x2 + (long long)n * a.x2_ns : a.x, DUAL ? (a.cin - a.c1) * ihw * 4 : 0);
 
   // ---- weights of this wave's chunks -> registers (issued first: longest latency)
   const int cpw = (nchunk + KG - 1) / KG;              // chunks per K group (<= 2)
@@ -523,21 +509,27 @@ __global__ __launch_bounds__(512) void conv3x3_oneshot_kernel(Conv3x3Args a) {
   const int total = nchunk * ITEMS_PER_CH;
   // two items per thread in flight: all their loads are issued before the first LDS store (a loop of
   // load -> store iterations pays the memory latency once per iteration)
-  constexpr int MAXQ = (MAXCH * ITEMS_PER_CH + 511) / 512;     // 4
+  constexpr int MAXQ = (MAXCH * ITEMS_PER_CH + 511) / 512;     // 4 / 7 (odd: the last pair has one member)
+  struct Item { int ch, r, hf, col; bool on; };
+  auto item = [&](int k) {                              // staging item k of this thread: (chunk, row, half, column)
+    const int q = tid + k * 512;
+    const int ch = q / ITEMS_PER_CH, rem = q - ch * ITEMS_PER_CH;
+    const int r = rem / (2 * PR), rem2 = rem - r * (2 * PR);
+    const int hf = rem2 / PR;
+    return Item{ch, r, hf, rem2 - hf * PR, k < MAXQ && q < total};
+  };
 #pragma unroll
   for (int k0 = 0; k0 < MAXQ; k0 += 2) {
     f32x4 v[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-      const int q = tid + (k0 + k) * 512;
-      const int ch = q / ITEMS_PER_CH, rem = q - ch * ITEMS_PER_CH;
-      const int r = rem / (2 * PW), rem2 = rem - r * (2 * PW);
-      const int hf = rem2 / PW, col = rem2 - hf * PW;
-      const int gy = y0 - 1 + r, gx = x0 - 1 + col;
-      const bool ok = q < total && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w;
-      const unsigned base = ok ? (unsigned)(((ch * CK + 4 * hf) * hw + gy * a.w + gx) * 4) : BUF_OOB;
+      const Item it = item(k0 + k);
+      const int gy = STRIDE * y0 - 1 + it.r, gx = STRIDE * x0 - 1 + it.col;
+      const bool ok = it.on && gy >= 0 && gy < ih && gx >= 0 && gx < iw;
+      const unsigned base = ok ? (unsigned)(((it.ch * CK + 4 * it.hf) * ihw + gy * iw + gx) * 4) : BUF_OOB;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
+        // beyond c1 the offset is past num_records and the load returns 0; the second source then supplies it
         const unsigned o1 = base + (unsigned)j * plane;
         float t = buf_ld<float>(rs1, o1);
         if (DUAL) t += buf_ld<float>(rs2, o1 - (unsigned)a.c1 * plane);
@@ -546,11 +538,8 @@ __global__ __launch_bounds__(512) void conv3x3_oneshot_kernel(Conv3x3Args a) {
     }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-      const int q = tid + (k0 + k) * 512;
-      const int ch = q / ITEMS_PER_CH, rem = q - ch * ITEMS_PER_CH;
-      const int r = rem / (2 * PW), rem2 = rem - r * (2 * PW);
-      const int hf = rem2 / PW, col = rem2 - hf * PW;
-      if (q < total) *reinterpret_cast<f32x4*>(s_in + ch * IN_FLOATS + ((r * 2 + hf) * RS + col) * 4) = v[k];
+      const Item it = item(k0 + k);
+      if (it.on) *reinterpret_cast<f32x4*>(s_in + it.ch * IN_FLOATS + ((it.r * 2 + it.hf) * PR + it.col) * 4) = v[k];
     }
   }
   __syncthreads();
@@ -563,11 +552,11 @@ __global__ __launch_bounds__(512) void conv3x3_oneshot_kernel(Conv3x3Args a) {
   for (int ci = 0; ci < 2; ++ci) {
     const int c = c0 + ci;
     if (ci < cpw && c < nchunk) {
-      const float* si = s_in + c * IN_FLOATS + (lh * RS + ll) * 4;
+      const float* si = s_in + c * IN_FLOATS + (lh * PR + STRIDE * ll) * 4;
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap) {
         const int ky = tap / 3, kx = tap % 3;
-        const f32x4 bq = *reinterpret_cast<const f32x4*>(si + (ky * 2 * RS + kx) * 4);
+        const f32x4 bq = *reinterpret_cast<const f32x4*>(si + (ky * 2 * PR + kx) * 4);
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk)
           acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[ci][tap][kk], bq[kk], acc, 0, 0, 0);
@@ -592,160 +581,25 @@ __global__ __launch_bounds__(512) void conv3x3_oneshot_kernel(Conv3x3Args a) {
   }
   __syncthreads();
   const float slope = act_slope(a.act);
-  const int py = y0;
-  if (a.vec_ok) {
+  if (STRIDE == 1 && a.vec_ok) {
     const int oc = tid >> 3, p4 = (tid & 7) * 4;
     const int gx = x0 + p4;
-    if (oc < a.cout && gx < a.w) {
-      f32x4 v = *reinterpret_cast<const f32x4*>(ep + oc * ES + p4);
-      const float bb = a.bias ? a.bias[oc] : 0.f;
-      const long long off = (long long)oc * hw + (long long)py * a.w + gx;
-      f32x4 rr = {0.f, 0.f, 0.f, 0.f};
-      if (a.res) rr = *reinterpret_cast<const f32x4*>(a.res + (long long)n * a.res_ns + off);
-      f32x4 mm = {1.f, 1.f, 1.f, 1.f};
-      if (a.mask) mm = *reinterpret_cast<const f32x4*>(a.mask + (long long)n * a.mask_ns + off);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float q = v[e] + bb;
-        q = (q >= 0.f ? q : q * slope + 0.f) + rr[e];
-        v[e] = mm[e] > 0.f ? q : 0.f;
-      }
-      *reinterpret_cast<f32x4*>(a.y + (long long)n * a.y_ns + off) = v;
-    }
+    if (oc < a.cout && gx < a.w)
+      ep_store4(a, n, oc, (long long)oc * hw + (long long)y0 * a.w + gx, slope,
+                *reinterpret_cast<const f32x4*>(ep + oc * ES + p4));
   } else {
     for (int i = tid; i < 64 * TW; i += 512) {
       const int oc = i >> 5, p = i & 31;
       const int gx = x0 + p;
       if (oc < a.cout && gx < a.w) {
-        const long long off = (long long)oc * hw + (long long)py * a.w + gx;
-        float q = ep[oc * ES + p] + (a.bias ? a.bias[oc] : 0.f);
-        q = (q >= 0.f ? q : q * slope + 0.f) + (a.res ? a.res[(long long)n * a.res_ns + off] : 0.f);
-        if (a.mask && a.mask[(long long)n * a.mask_ns + off] <= 0.f) q = 0.f;
-        a.y[(long long)n * a.y_ns + off] = q;
+        const long long off = (long long)oc * hw + (long long)y0 * a.w + gx;
+        a.y[(long long)n * a.y_ns + off] =
+            ep_elem(ep[oc * ES + p], a.bias ? a.bias[oc] : 0.f, slope, a.res ? a.res[(long long)n * a.res_ns + off] : 0.f,
+                    a.mask && ep_dead(a.mask[(long long)n * a.mask_ns + off]));
       }
     }
   }
 }
-
-// ---------------------------------------------------------------------------------------
-// The one-shot scheme for a STRIDE-2 3x3 conv: y(oy, ox) = sum_k w[k] x(2 oy - 1 + ky, 2 ox - 1 + kx)
-// (zero outside) -- the data gradient of ConvTranspose2d(k3, s2, p1, op1) (tecogan_nets.py:119-126)
-// on the training frames.  Through its space-to-depth embedding that gradient is a 256-channel
-// phased conv walking 32 channel chunks (27 us per launch for 2 x 32 x 32 outputs); directly it is a
-// K = 576 contraction like any body layer: the patch is 3 input rows x 66 input columns per
-// 8-channel chunk, the B operand of output pixel ox and tap kx sits at column 2 ox + kx.
-constexpr int RS2 = 2 * TW + 2;                        // 66 patch columns
-__global__ __launch_bounds__(512) void conv3x3s2_oneshot_kernel(Conv3x3Args a) {
-  constexpr int OCB = 64, KG = 4, MAXCH = 8;
-  constexpr int IN_FLOATS = 3 * 2 * RS2 * 4;           // one chunk's patch
-  constexpr int ITEMS_PER_CH = 3 * 2 * RS2;            // 396 16-byte items
-  constexpr int W_VEC4 = 9 * CK * OCB / 4;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* s_in = smem;                                  // [MAXCH][IN_FLOATS]; later the epilogue stage [64][36]
-  float* red = smem + MAXCH * IN_FLOATS;               // [2][KG-1][16][64]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wn = wave & 1, wk = wave >> 1;
-  const int lh = lane >> 5, ll = lane & 31;
-  int b = blockIdx.x;
-  const int tx = b % a.tiles_x; b /= a.tiles_x;
-  const int ty = b % a.tiles_y;
-  const int n = b / a.tiles_y;
-  const int x0 = tx * TW, y0 = ty;
-  const int hw = a.h * a.w;                            // OUTPUT plane
-  const int ih = 2 * a.h, iw = 2 * a.w, ihw = ih * iw; // input plane
-  const unsigned plane = (unsigned)ihw * 4u;
-  const int nchunk = a.nchunk;
-  const __amdgpu_buffer_rsrc_t rs1 = TG_BUF_RSRC(a.x + (long long)n * a.x_ns, a.cin * ihw * 4);
-  const int cpw = (nchunk + KG - 1) / KG;
-  const int c0 = wk * cpw;
-  const f32x4* wlane = reinterpret_cast<const f32x4*>(a.wpk) + (lh * OCB + wn * 32 + ll);
-  f32x4 aw[2][9];
-#pragma unroll
-  for (int ci = 0; ci < 2; ++ci) {
-    const int c = c0 + ci;
-    const bool on = ci < cpw && c < nchunk;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (on) v = wlane[(size_t)c * W_VEC4 + tap * (2 * OCB)];
-      aw[ci][tap] = v;
-    }
-  }
-  const int total = nchunk * ITEMS_PER_CH;
-  constexpr int MAXQ = (MAXCH * ITEMS_PER_CH + 511) / 512;     // 7
-#pragma unroll
-  for (int k0 = 0; k0 < MAXQ; k0 += 2) {
-    f32x4 v[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int q = tid + (k0 + k) * 512;
-      const int ch = q / ITEMS_PER_CH, rem = q - ch * ITEMS_PER_CH;
-      const int r = rem / (2 * RS2), rem2 = rem - r * (2 * RS2);
-      const int hf = rem2 / RS2, col = rem2 - hf * RS2;
-      const int gy = 2 * y0 - 1 + r, gx = 2 * x0 - 1 + col;
-      const bool ok = (k0 + k) < MAXQ && q < total && gy >= 0 && gy < ih && gx >= 0 && gx < iw;
-      const unsigned base = ok ? (unsigned)(((ch * CK + 4 * hf) * ihw + gy * iw + gx) * 4) : BUF_OOB;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[k][j] = buf_ld<float>(rs1, base + (unsigned)j * plane);
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int q = tid + (k0 + k) * 512;
-      const int ch = q / ITEMS_PER_CH, rem = q - ch * ITEMS_PER_CH;
-      const int r = rem / (2 * RS2), rem2 = rem - r * (2 * RS2);
-      const int hf = rem2 / RS2, col = rem2 - hf * RS2;
-      if ((k0 + k) < MAXQ && q < total) *reinterpret_cast<f32x4*>(s_in + ch * IN_FLOATS + ((r * 2 + hf) * RS2 + col) * 4) = v[k];
-    }
-  }
-  __syncthreads();
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-  for (int ci = 0; ci < 2; ++ci) {
-    const int c = c0 + ci;
-    if (ci < cpw && c < nchunk) {
-      const float* si = s_in + c * IN_FLOATS + (lh * RS2 + 2 * ll) * 4;
-#pragma unroll
-      for (int tap = 0; tap < 9; ++tap) {
-        const int ky = tap / 3, kx = tap % 3;
-        const f32x4 bq = *reinterpret_cast<const f32x4*>(si + (ky * 2 * RS2 + kx) * 4);
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[ci][tap][kk], bq[kk], acc, 0, 0, 0);
-      }
-    }
-  }
-  if (wk > 0) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[((wn * (KG - 1) + wk - 1) * 16 + r) * 64 + lane] = acc[r];
-  }
-  __syncthreads();
-  constexpr int ES = 36;
-  float* ep = smem;
-  if (wk == 0) {
-#pragma unroll
-    for (int g = 0; g < KG - 1; ++g)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] += red[((wn * (KG - 1) + g) * 16 + r) * 64 + lane];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) ep[(wn * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * ES + ll] = acc[r];
-  }
-  __syncthreads();
-  const float slope = act_slope(a.act);
-  for (int i = tid; i < 64 * TW; i += 512) {
-    const int oc = i >> 5, p = i & 31;
-    const int gx = x0 + p;
-    if (oc < a.cout && gx < a.w) {
-      const long long off = (long long)oc * hw + (long long)y0 * a.w + gx;
-      float q = ep[oc * ES + p] + (a.bias ? a.bias[oc] : 0.f);
-      q = (q >= 0.f ? q : q * slope + 0.f) + (a.res ? a.res[(long long)n * a.res_ns + off] : 0.f);
-      if (a.mask && a.mask[(long long)n * a.mask_ns + off] <= 0.f) q = 0.f;
-      a.y[(long long)n * a.y_ns + off] = q;
-    }
-  }
-}
-
 
 // w % 4 == 0 and 16-byte aligned y / res / mask planes: the float4 epilogue is allowed
 static int conv3x3_vec_ok(const Conv3x3Args& a) {
@@ -767,8 +621,8 @@ static int launch_conv(const Conv3x3Args& a0, int n, hipStream_t stream) {
   if (a.ksplit < 1) a.ksplit = 1;
   TG_REQUIRE(KS == 1 || a.ksplit == 1, TG_E_ARG, "conv3x3: in-workgroup K split excludes ksplit");
   if (KS > 1) {
-    const int rc = a.x2 ? ensure_dynamic_lds<conv3x3_mfma_kernel<WM, WN, NT, true, 0, KS>>(lds, "conv3x3_mfma")
-                        : ensure_dynamic_lds<conv3x3_mfma_kernel<WM, WN, NT, false, 0, KS>>(lds, "conv3x3_mfma");
+    const int rc = a.x2 ? ensure_dynamic_lds<conv3x3_mfma_kernel<WM, WN, NT, true, KS>>(lds, "conv3x3_mfma")
+                        : ensure_dynamic_lds<conv3x3_mfma_kernel<WM, WN, NT, false, KS>>(lds, "conv3x3_mfma");
     if (rc != TG_OK) return rc;
   }
   long long blocks = (long long)a.tiles_x * a.tiles_y * a.nocg * n * a.ksplit;
@@ -779,12 +633,30 @@ static int launch_conv(const Conv3x3Args& a0, int n, hipStream_t stream) {
   a.nblocks = xcd ? (int)blocks : 0;
   const unsigned grid = xcd ? (unsigned)(8 * ((blocks + 7) / 8)) : (unsigned)blocks;
   if (a.x2)
-    hipLaunchKernelGGL((conv3x3_mfma_kernel<WM, WN, NT, true, 0, KS>),
+    hipLaunchKernelGGL((conv3x3_mfma_kernel<WM, WN, NT, true, KS>),
                        dim3(grid), dim3(WM * WN * KS * 64), lds, stream, a);
   else
-    hipLaunchKernelGGL((conv3x3_mfma_kernel<WM, WN, NT, false, 0, KS>),
+    hipLaunchKernelGGL((conv3x3_mfma_kernel<WM, WN, NT, false, KS>),
                        dim3(grid), dim3(WM * WN * KS * 64), lds, stream, a);
   return check_launch("conv3x3_mfma");
+}
+
+// The one-shot forms: one-row tiles, one 64-channel block, every chunk in flight (a.h x a.w is the output).
+template <auto Kernel>
+static int launch_oneshot_kernel(const Conv3x3Args& a, int n, size_t lds, hipStream_t stream, const char* name) {
+  if (const int rc = ensure_dynamic_lds<Kernel>(lds, name)) return rc;
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)(a.tiles_x * a.tiles_y * n)), dim3(512), lds, stream, a);
+  return check_launch(name);
+}
+template <int STRIDE>
+static int launch_oneshot(Conv3x3Args a, int n, hipStream_t stream) {
+  constexpr const char* name = STRIDE == 1 ? "conv3x3_oneshot" : "conv3x3s2_oneshot";
+  constexpr size_t lds = oneshot_lds_bytes(STRIDE);    // 50.7 KB / 75.3 KB
+  a.vec_ok = conv3x3_vec_ok(a);
+  a.tiles_x = cdiv(a.w, TW); a.tiles_y = a.h; a.nocg = 1; a.nchunk = cdiv(a.cin, CK);
+  if constexpr (STRIDE == 1)
+    if (a.x2) return launch_oneshot_kernel<conv3x3_oneshot_kernel<1, true>>(a, n, lds, stream, name);
+  return launch_oneshot_kernel<conv3x3_oneshot_kernel<STRIDE, false>>(a, n, lds, stream, name);
 }
 
 // out = act(sum_s part[s] + bias), optionally followed by MaxPool2d(2,2) (floor).
@@ -805,8 +677,7 @@ __global__ void splitk_finalize_kernel(const float* __restrict__ part, int S, lo
       const float* p = part + plane + (long long)yy * w + xx;
       float v = 0.f;
       for (int s = 0; s < S; ++s) v += p[(long long)s * part_ss];
-      v += b;
-      return v >= 0.f ? v : v * slope + 0.f;
+      return ep_act(v + b, slope);
     };
     float v;
     if (pool) {
@@ -853,13 +724,6 @@ extern "C" int tg_conv3x3_pick_ksplit(int n, int cin, int cout, int h, int w) {
   // the one-shot kernel already has the whole K range in flight inside ONE launch: 10.8 us against
   // 9.0 + 4.2 us for a 4-way split + finalize on the 2 x 32 x 32 training frames (rocprofv3, round 3)
   if (conv3x3_uses_oneshot(n, cin, cout, h, w)) return 1;
-  static const int legacy = TG_LAB_ENV("TG_KSPLIT_LEGACY", 0);
-  if (legacy) {   // lab: the round-1 rule (fill ~640 workgroup slots)
-    if (wgs >= 400 || nchunk < 4) return 1;
-    int ks = 1;
-    while (ks < 8 && wgs * ks < 640 && nchunk / (ks * 2) >= 2) ks *= 2;
-    return ks;
-  }
   auto cost = [&](int ks) {
     double share = wgs * ks / 256.0;
     return 4.0 + 1.15 * ((double)nchunk / ks) * (share > 1.0 ? share : 1.0) + (ks > 1 ? 4.5 : 0.0);
@@ -937,18 +801,7 @@ static int conv3x3_impl(const float* x, int64_t x_nstride, int c1, const float* 
   if (conv3x3_rows_per_wg(ocb, (long long)n * h * w) == 4) return launch_conv<4, 1, 2>(a, n, s);
   // At most half as many 2-row tiles as CUs (e.g. a training batch of 2 x 64 x 64): 1-row tiles
   // with the channel chunks split over two wave groups keep every SIMD busy in ONE launch.
-  if (a.ksplit <= 1 && !tapsel && conv3x3_uses_oneshot(n, cin, cout, h, w)) {
-    a.vec_ok = conv3x3_vec_ok(a);
-    a.tiles_x = cdiv(a.w, TW); a.tiles_y = a.h; a.nocg = 1; a.nchunk = cdiv(a.cin, CK);
-    const size_t lds = (size_t)(8 * 3 * 2 * RS * 4 + 2 * 3 * 16 * 64) * sizeof(float);    // 50.7 KB
-    const int rc = a.x2 ? ensure_dynamic_lds<conv3x3_oneshot_kernel<true>>(lds, "conv3x3_oneshot")
-                        : ensure_dynamic_lds<conv3x3_oneshot_kernel<false>>(lds, "conv3x3_oneshot");
-    if (rc != TG_OK) return rc;
-    const unsigned grid = (unsigned)(a.tiles_x * a.tiles_y * n);
-    if (a.x2) hipLaunchKernelGGL(conv3x3_oneshot_kernel<true>, dim3(grid), dim3(512), lds, s, a);
-    else hipLaunchKernelGGL(conv3x3_oneshot_kernel<false>, dim3(grid), dim3(512), lds, s, a);
-    return check_launch("conv3x3_oneshot");
-  }
+  if (a.ksplit <= 1 && !tapsel && conv3x3_uses_oneshot(n, cin, cout, h, w)) return launch_oneshot<1>(a, n, s);
   if (a.ksplit <= 1 && conv3x3_uses_wg_ksplit(n, cin, cout, h, w)) return launch_conv<1, 2, 1, 2>(a, n, s);
   return launch_conv<2, 2, 1>(a, n, s);
 }
@@ -1036,12 +889,7 @@ extern "C" int tg_conv3x3s2_fwd(const float* x, int64_t x_nstride, const float* 
   a.x = x; a.wpk = w_packed; a.bias = bias; a.y = y; a.x_ns = x_nstride; a.y_ns = y_nstride;
   a.mask = relu_mask; a.mask_ns = mask_nstride;
   a.c1 = cin; a.cin = cin; a.cout = cout; a.h = h_out; a.w = w_out; a.act = act;
-  a.tiles_x = cdiv(w_out, TW); a.tiles_y = h_out; a.nocg = 1; a.nchunk = cdiv(cin, CK);
-  const size_t lds = (size_t)(8 * 3 * 2 * RS2 * 4 + 2 * 3 * 16 * 64) * sizeof(float);
-  if (const int rc = ensure_dynamic_lds<conv3x3s2_oneshot_kernel>(lds, "conv3x3s2_oneshot")) return rc;
-  hipLaunchKernelGGL(conv3x3s2_oneshot_kernel, dim3((unsigned)(a.tiles_x * a.tiles_y * n)), dim3(512), lds,
-                     (hipStream_t)stream, a);
-  return check_launch("conv3x3s2_oneshot");
+  return launch_oneshot<2>(a, n, (hipStream_t)stream);
 }
 
 extern "C" int tg_conv3x3_fwd_masked(const float* x, int64_t x_nstride, int c1, const float* x2,

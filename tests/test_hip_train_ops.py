@@ -632,6 +632,54 @@ def test_convt_data_gradient_as_stride2_conv(ops, n, ci, co, h, w):
     assert not ops.conv3x3s2_supported(8, 64, 64, 256, 256)
 
 
+# x (n, cin, h, w) and cout: 8 chunks, one full tile, the float4 stride-1 epilogue | 6 chunks (K group 3 idles), a
+# partial 64-channel block, a partial last tile in both forms, w % 4 != 0 (the element-wide stride-1 epilogue), n > 1
+ONE_BODY_SHAPES = [(1, 64, 64, 16, 32), (2, 48, 40, 6, 70)]
+
+
+def _one_body_inputs(ops, n, cin, cout, h, w):
+    x = dev(rs(1, (n, cin, h, w)))
+    wpk = ops.pack_conv3x3(dev(rs(2, (cout, cin, 3, 3)) / (3.0 * cin ** 0.5)), ocb=64)[0]
+    return x, wpk, dev(torch.relu(rs(3, (n, cout, h, w))))
+
+
+@pytest.mark.parametrize('masked', [False, True])
+@pytest.mark.parametrize('n,cin,cout,h,w', ONE_BODY_SHAPES)
+def test_stride2_oneshot_is_the_stride1_oneshot_at_the_even_pixels(ops, n, cin, cout, h, w, masked):
+    """The two one-shot convs are one body: y2(oy, ox) = sum_k w[k] x(2 oy - 1 + ky, 2 ox - 1 + kx) is the stride-1
+    result at (2 oy, 2 ox), and both forms issue the same MFMAs per output pixel, add the K groups in the same order and
+    apply the same epilogue arithmetic -- equal bit for bit, with the same packed weights.
+    The launchers' rules that put both shapes on the one-shot forms (tg_conv3x3_mfma.hip, restated):
+      stride 1 (conv3x3_uses_oneshot): ocb 64 (cout > 32), cout <= 64, 6 <= ceil(cin / 8) <= 8, n h w < 200000 and
+        ceil(w / 32) ceil(h / 2) n <= 128 two-row tiles; ksplit = 1, no phased taps;
+      stride 2 (tg_conv3x3s2_supported): cin, cout <= 64 and n h_out ceil(w_out / 32) <= 1024 one-row tiles."""
+    assert cout > 32 and cout <= 64 and 6 <= -(-cin // 8) <= 8 and n * h * w < 200000
+    assert -(-w // 32) * -(-h // 2) * n <= 128 and ops.conv3x3s2_supported(n, cin, cout, h // 2, w // 2)
+    x, wpk, mask = _one_body_inputs(ops, n, cin, cout, h, w)
+    y1 = ops.conv3x3(x, wpk, None, cin, cout, 64, ksplit=1, relu_mask=mask if masked else None)
+    y2 = ops.conv3x3s2(x, wpk, cin, cout, relu_mask=mask[:, :, ::2, ::2].contiguous() if masked else None)
+    assert torch.equal(y2, y1[:, :, ::2, ::2])
+
+
+@pytest.mark.parametrize('n,cin,cout,h,w', ONE_BODY_SHAPES)
+def test_stride2_oneshot_epilogue_is_the_stride1_epilogue(ops, n, cin, cout, h, w):
+    """The same identity with a bias and LeakyReLU(0.2), which only the C entry points give the stride-2 form."""
+    from tecogan_pytorch_amd import _lib
+    lib = _lib.lib()
+    x, wpk, _ = _one_body_inputs(ops, n, cin, cout, h, w)
+    b = dev(rs(4, (cout,), -0.5, 0.5))
+    y1 = torch.empty(n, cout, h, w, device='cuda')
+    y2 = torch.empty(n, cout, h // 2, w // 2, device='cuda')
+    torch.cuda.synchronize()
+    _lib.check(lib.tg_conv3x3_fwd(x.data_ptr(), cin * h * w, cin, None, 0, wpk.data_ptr(), 64, b.data_ptr(), None, 0,
+                                  y1.data_ptr(), cout * h * w, n, cin, cout, h, w, ops.ACT_LRELU02, None), 'tg_conv3x3_fwd')
+    _lib.check(lib.tg_conv3x3s2_fwd(x.data_ptr(), cin * h * w, wpk.data_ptr(), b.data_ptr(), None, 0, y2.data_ptr(),
+                                    cout * (h // 2) * (w // 2), n, cin, cout, h // 2, w // 2, ops.ACT_LRELU02, None),
+               'tg_conv3x3s2_fwd')
+    torch.cuda.synchronize()
+    assert (y1 < 0).any() and torch.equal(y2, y1[:, :, ::2, ::2])
+
+
 @pytest.mark.parametrize('n,h,w', [(2, 32, 32), (2, 64, 64), (3, 9, 70), (1, 20, 37)])
 def test_row_chain_with_reused_buffers_equals_layer_launches(ops, n, h, w):
     """tg_conv3x3_chain in SRNet's INFERENCE buffer pattern -- two ping-pong tensors and in-place

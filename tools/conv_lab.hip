@@ -1,4 +1,4 @@
-// Stand-alone ablation / tile-shape lab for the conv3x3 MFMA kernel (no torch).
+// Stand-alone timing / tile-shape lab for the shipped conv3x3 MFMA kernel (no torch): time per tile shape, occupancy probe.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/conv_lab.hip -o tools/conv_lab
 #include "../tecogan-pytorch_amd/csrc/tg_conv3x3_mfma.hip"
 #include <vector>
@@ -7,7 +7,7 @@
 namespace tg { void set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fputc('\n', stderr);} }
 using namespace tg;
 
-template <int WM, int WN, int NT, int ABL>
+template <int WM, int WN, int NT>
 static float run(const char* name, Conv3x3Args a, int n, int reps, double gflop) {
   a.vec_ok = (a.w % 4 == 0);
   a.ksplit = 1;
@@ -17,10 +17,10 @@ static float run(const char* name, Conv3x3Args a, int n, int reps, double gflop)
   unsigned blocks = a.tiles_x * a.tiles_y * a.nocg * n;
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   for (int i = 0; i < 3; ++i)
-    hipLaunchKernelGGL((conv3x3_mfma_kernel<WM, WN, NT, false, ABL>), dim3(blocks), dim3(WM * WN * 64), lds, 0, a);
+    hipLaunchKernelGGL((conv3x3_mfma_kernel<WM, WN, NT, false>), dim3(blocks), dim3(WM * WN * 64), lds, 0, a);
   hipEventRecord(e0, 0);
   for (int i = 0; i < reps; ++i)
-    hipLaunchKernelGGL((conv3x3_mfma_kernel<WM, WN, NT, false, ABL>), dim3(blocks), dim3(WM * WN * 64), lds, 0, a);
+    hipLaunchKernelGGL((conv3x3_mfma_kernel<WM, WN, NT, false>), dim3(blocks), dim3(WM * WN * 64), lds, 0, a);
   hipEventRecord(e1, 0); hipEventSynchronize(e1);
   float ms; hipEventElapsedTime(&ms, e0, e1);
   float us = 1e3f * ms / reps;
@@ -54,66 +54,30 @@ int main(int argc, char** argv) {
   {
     int nb = 0;
     size_t lds = 2 * (size_t)((2 + 2) * 2 * RS * 4 + 9 * CK * 64) * sizeof(float);
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)conv3x3_mfma_kernel<2, 2, 1, false, 0>, 256, lds);
-    hipFuncAttributes fa; hipFuncGetAttributes(&fa, (const void*)conv3x3_mfma_kernel<2, 2, 1, false, 0>);
+    hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)conv3x3_mfma_kernel<2, 2, 1, false>, 256, lds);
+    hipFuncAttributes fa; hipFuncGetAttributes(&fa, (const void*)conv3x3_mfma_kernel<2, 2, 1, false>);
     printf("occupancy API: %d blocks/CU for <2,2,1> (dyn LDS %zu B, numRegs %d, static LDS %zu)\n", nb, lds, fa.numRegs, (size_t)fa.sharedSizeBytes);
     for (size_t l = 16384; l <= 65536; l += 8192) {
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)conv3x3_mfma_kernel<2, 2, 1, false, 0>, 256, l);
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)conv3x3_mfma_kernel<2, 2, 1, false>, 256, l);
       printf("   dyn LDS %6zu -> %d blocks/CU\n", l, nb);
     }
   }
   const int R = 50;
-  run<2, 2, 1, 0>("<2,2,1>", a, n, R, gflop);
-  {   // anatomy of a workgroup (ABL 16: clock stamps)
-    long long* dbg; unsigned nb = 670;
-    hipMalloc(&dbg, nb * 8 * sizeof(long long)); hipMemset(dbg, 0, nb * 8 * sizeof(long long));
-    Conv3x3Args ad = a; ad.dbg = dbg;
-    run<2, 2, 1, 16>("<2,2,1> instrumented", ad, n, 5, gflop);
-    std::vector<long long> h(nb * 8);
-    hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost);
-    double pro = 0, iss = 0, mf = 0, sy = 0, life = 0;
-    for (unsigned i = 0; i < nb; ++i) { pro += h[i*8+1]; iss += h[i*8+2]; mf += h[i*8+3]; sy += h[i*8+4]; life += h[i*8+5] - h[i*8]; }
-    printf("  cycles/WG avg: prologue %.0f | load-issue %.0f  mfma-block %.0f  store+barrier %.0f | lifetime %.0f (ideal mfma 8x36x64 = 18432)\n",
-           pro / nb, iss / nb, mf / nb, sy / nb, life / nb);
-    // per-XCD view (s_memtime is only comparable inside one XCD)
-    for (int x = 0; x < 8; ++x) {
-      long long lo = -1, hi = 0; double lf = 0; int cnt = 0; long long first_end = -1;
-      for (unsigned i = 0; i < nb; ++i) if ((h[i*8+6] & 15) == x) {
-        if (lo < 0 || h[i*8] < lo) lo = h[i*8];
-        if (h[i*8+5] > hi) hi = h[i*8+5];
-        if (first_end < 0 || h[i*8+5] < first_end) first_end = h[i*8+5];
-        lf += h[i*8+5] - h[i*8]; ++cnt;
-      }
-      long long last_start = 0; for (unsigned i = 0; i < nb; ++i) if ((h[i*8+6] & 15) == x && h[i*8] > last_start) last_start = h[i*8];
-      if (cnt) printf("   XCD %d: %3d WGs  span %6lld  avg lifetime %6.0f  last start +%lld  first end +%lld\n", x, cnt, hi - lo, lf / cnt, last_start - lo, first_end - lo);
-    }
-    hipFree(dbg);
-  }
+  run<2, 2, 1>("<2,2,1>", a, n, R, gflop);
   // tile shapes (each twice: the first run of a shape also pays its code load)
   for (int rep = 0; rep < 2; ++rep) {
-    run<2, 2, 1, 0>("<2,2,1>", a, n, R, gflop);
-    run<3, 2, 1, 0>("<3,2,1> (6 waves)", a, n, R, gflop);
-    run<5, 2, 1, 0>("<5,2,1> (10 waves)", a, n, R, gflop);
-    run<4, 1, 2, 0>("<4,1,2>", a, n, R, gflop);
-    run<4, 2, 1, 0>("<4,2,1> (8 waves)", a, n, R, gflop);
-    run<2, 1, 2, 0>("<2,1,2> (2 waves)", a, n, R, gflop);
-    run<1, 2, 1, 0>("<1,2,1> (2 waves)", a, n, R, gflop);
-    run<1, 1, 2, 0>("<1,1,2> (1 wave)", a, n, R, gflop);
+    run<2, 2, 1>("<2,2,1>", a, n, R, gflop);
+    run<3, 2, 1>("<3,2,1> (6 waves)", a, n, R, gflop);
+    run<5, 2, 1>("<5,2,1> (10 waves)", a, n, R, gflop);
+    run<4, 1, 2>("<4,1,2>", a, n, R, gflop);
+    run<4, 2, 1>("<4,2,1> (8 waves)", a, n, R, gflop);
+    run<2, 1, 2>("<2,1,2> (2 waves)", a, n, R, gflop);
+    run<1, 2, 1>("<1,2,1> (2 waves)", a, n, R, gflop);
+    run<1, 1, 2>("<1,1,2> (1 wave)", a, n, R, gflop);
   }
-  // ablations (wrong results, timing only)
-  run<2, 2, 1, 32>("<2,2,1> no input restage", a, n, R, gflop);
-  run<2, 2, 1, 64>("<2,2,1> no weight restage", a, n, R, gflop);
-  run<2, 2, 1, 96>("<2,2,1> neither", a, n, R, gflop);
-  run<2, 2, 1, 1>("<2,2,1> no-restage", a, n, R, gflop);
-  run<2, 2, 1, 3>("<2,2,1> no-restage no-bar", a, n, R, gflop);
-  run<2, 2, 1, 4>("<2,2,1> no-epilogue-store", a, n, R, gflop);
-  run<2, 2, 1, 7>("<2,2,1> mfma+lds only", a, n, R, gflop);
-  run<2, 2, 1, 15>("<2,2,1> mfma only", a, n, R, gflop);
-  run<4, 1, 2, 7>("<4,1,2> mfma+lds only", a, n, R, gflop);
-  run<4, 2, 1, 7>("<4,2,1> mfma+lds only", a, n, R, gflop);
-  run<2, 2, 1, 0>("<2,2,1> again", a, n, R, gflop);
+  run<2, 2, 1>("<2,2,1> again", a, n, R, gflop);
   a.wpk = wp32;
-  run<4, 1, 1, 0>("<4,1,1> ocb32", a, n, R, gflop);
-  run<2, 1, 1, 0>("<2,1,1> ocb32 (2 waves)", a, n, R, gflop);
+  run<4, 1, 1>("<4,1,1> ocb32", a, n, R, gflop);
+  run<2, 1, 1>("<2,1,1> ocb32 (2 waves)", a, n, R, gflop);
   return 0;
 }

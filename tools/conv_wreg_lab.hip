@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256, 1) void conv_wreg_kernel(WArgs a) {
       int hf = rem / PW, col = rem - hf * PW;
       int gy = y0 - 1 + r, gx = x0 - 1 + col;
       bool ok = q < IN_ITEMS && gy >= 0 && gy < a.h && gx >= 0 && gx < a.w;
-      voff[i] = ok ? (unsigned)((4 * hf * hw + gy * a.w + gx) * 4) : OOB;
+      voff[i] = ok ? (unsigned)((4 * hf * hw + gy * a.w + gx) * 4) : BUF_OOB;
       lds_item[i] = q < IN_ITEMS ? ((r * 2 + hf) * RS + col) * 4 : -1;
     }
     f32x4 rin[I_PER_T];
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256, 1) void conv_wreg_kernel(WArgs a) {
 #pragma unroll
       for (int i = 0; i < I_PER_T; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) rin[i][j] = buf_load(rs, voff[i] + cbase + (unsigned)j * plane);
+        for (int j = 0; j < 4; ++j) rin[i][j] = buf_ld<float>(rs, voff[i] + cbase + (unsigned)j * plane);
     };
     auto store_chunk = [&](int buf) {
 #pragma unroll
